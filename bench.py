@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 16-frame 224x224 RGB crop-clips/s through I3D extract -> MIL score.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" = one pass of the hot path over one batch of synthetic input already resident in HBM:
@@ -9,6 +9,12 @@ every rank runs the I3D-ResNet50 backbone (53 fused fp32-MFMA conv launches + po
 crop-clips, the 2048-d rows are all-gathered (RCCL; no-op at N=1), and every video (32 clips x 10
 crops = 320 crop-clips) whose last crop-clip arrived is scored by its owner rank with the MGFN
 scorer (eval).  Weak scaling: per-GPU work is fixed.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the other records at N=1: the
+sustained leg, the MGFN training step, the PCIe-inclusive legs and the CPU baseline (each still has its --no-* switch).
+`--dump-outputs DIR` writes, on rank 0, what the timed steps computed (inputs are seeded: same arguments, same inputs):
+  DIR/features.npy      (global_batch, 2048) float32, the gathered feature rows of the last timed step
+  DIR/video_scores.npy  (n_clips,) float32, the scores of the last video the timed steps scored (absent if none was)
 """
 from __future__ import annotations
 
@@ -93,6 +99,16 @@ def stream_start(clips, ncrops: int, global_batch: int, warmup: int, steps: int)
         if end >= mid:
             return (end - mid) // global_batch * global_batch
         v += 1
+
+
+def dump_outputs(out_dir: str, features, scores) -> None:
+    """`--dump-outputs`: what a caller of the timed path receives, as float32 .npy files (a few hundred KB)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "features.npy"), features.detach().float().cpu().numpy())
+    if scores is not None:
+        np.save(os.path.join(out_dir, "video_scores.npy"), scores.detach().float().cpu().numpy())
 
 
 def launch_ranks(n: int, argv) -> int:
@@ -277,7 +293,12 @@ def main():
                     "in the middle of the timed steps); 0 in the PMC passes of tools/profile_bench.sh: no video completes in their few steps, so the "
                     "conv-kernel counters are the backbone's alone (the scorer's GEMMs run on the same kernels)")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous only (gloo, no GPU): checks the rank launch + result relay")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the sustained leg, the MGFN training step, the PCIe-inclusive "
+                    "legs and the CPU baseline (N=1); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.h2d:  # the full set of PCIe-inclusive legs is one of the --full records
+        args.full = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # plain `python bench.py --gpus N`: be our own launcher
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -327,7 +348,8 @@ def main():
     stream = ExtractScoreStream(backbone, scorer, clips_per_video=clips, ncrops=10, local_batch=args.batch, world=world, rank=rank)
     pos0 = stream_start(clips, 10, args.batch * world, args.warmup, args.steps) if args.stream_start < 0 else args.stream_start
     stream.seek(pos0)
-    stream.ring.uniform_(0.0, 3.0)  # (the rows of the picked-up video that lie before the stream's start: plausible features, not zeros)
+    # (the rows of the picked-up video that lie before the stream's start: plausible features, not zeros; seeded like the input)
+    stream.ring.uniform_(0.0, 3.0, generator=torch.Generator(device=dev).manual_seed(4321 + rank))
 
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     x = torch.randn((args.batch, 3, 16, 224, 224), device=dev, generator=gen)
@@ -353,15 +375,18 @@ def main():
     backbone.forward = lambda b: backbone.forward_single(b, events=events)
     videos_before = stream.videos_scored
     log_before = len(stream.scored_log)
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        stream.step_async(x)
+        last = stream.step_async(x)
     stream.drain()
     barrier()
     elapsed = time.perf_counter() - t0
     videos_timed = stream.videos_scored - videos_before  # (the counter keeps running through the sustained / PCIe legs below)
     clips_timed = [n for _v, n in stream.scored_log[log_before:]]
     backbone.forward = orig_forward
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last.result()[0], stream.last_scores if videos_timed else None)
     rank_elapsed = [elapsed]
     backend_observed, world_observed = "none (single process)", 1
     if world > 1:
@@ -396,7 +421,7 @@ def main():
     # clock than the chip sustains; this record shows the difference instead of hiding it).  Same step count on
     # every rank (derived from the max-reduced time), same barrier / synchronize bracket.
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         n_sus = max(args.steps, int(args.sustain_s / (elapsed / args.steps)) + 1)
         barrier()
         t1 = time.perf_counter()
@@ -417,7 +442,7 @@ def main():
     # BASELINE config 4: one MGFN training step (32,10,32,2049): forward + 4 losses + backward + Adam, rank 0 at N=1 --
     # the step the runner's Trainer executes: captured once as a HIP graph (train_graph.GraphedTrainStep), replayed per batch
     mgfn_train = None
-    if world == 1 and not args.no_mgfn_train:
+    if args.full and world == 1 and not args.no_mgfn_train:
         from anomaly_detection_on_video_amd.train_graph import GraphedTrainStep
 
         scorer.train()
@@ -469,7 +494,7 @@ def main():
 
     h2d = h2d_u8 = h2d_frames = None
     pcie = None
-    if world == 1 and not args.no_pcie and not args.h2d:
+    if args.full and world == 1 and not args.no_pcie and not args.h2d:
         # SURVEY 8(d) cfg 1-2: the end-to-end rate INCLUDING the host -> device copy, labelled separately (never `value`).
         # Pinned host buffers every step; the copy runs on its own stream ahead of the step that consumes it; 3 + K steps each.
         from anomaly_detection_on_video_amd.pipeline import FrameCrops
@@ -623,7 +648,7 @@ def main():
                               "ratio": round(frames40 / res40, 4),
                               "two_pass_clips_per_s": round(frames40_2pass, 2),  # TenCrop + normalise as its own HIP pass (round-2 mid form)
                               "two_pass_b32_clips_per_s": round(h2d_frames_2pass, 2)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

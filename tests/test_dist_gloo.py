@@ -156,7 +156,9 @@ def test_bench_launches_eight_ranks_dry():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    # (the two variables bench.launch_ranks defaults are unset here: a value exported by the calling shell would win)
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY", "NCCL_DEBUG")}
     env["OMP_NUM_THREADS"] = "1"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--dry-run"],
                        env=env, capture_output=True, text=True, timeout=600)

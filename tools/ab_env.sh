@@ -6,7 +6,7 @@ mkdir -p $OUT
 for round in 1 2; do
 for spec in "$@"; do
   name=${spec%%:*}; vars=${spec#*:}
-  env $vars python bench.py --no-cpu-baseline --no-pcie --no-mgfn-train --sustain-s 2 $BENCH_ARGS > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err || exit 1
+  env $vars python bench.py --full --no-cpu-baseline --no-pcie --no-mgfn-train --sustain-s 2 $BENCH_ARGS > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err || exit 1
   python -c "import json; d=json.load(open('$OUT/bench_${name}_$round.json')); print('$name', $round, d['value'], d['roofline']['frac'], d['sustained']['clips_per_s'])" | tee -a $OUT/summary.txt
 done
 done

@@ -8,7 +8,7 @@ for round in 1 2; do
 for spec in "$@"; do
   name=${spec%%=*}; path=${spec#*=}
   if [ "$path" = "base" ]; then cp /tmp/base.so $SO; else cp $path $SO; fi
-  python bench.py --no-cpu-baseline --no-pcie --sustain-s 2 > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err || exit 1
+  python bench.py --full --no-cpu-baseline --no-pcie --sustain-s 2 > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err || exit 1
   python -c "import json; d=json.load(open('$OUT/bench_${name}_$round.json')); print('$name', $round, d['value'], d['roofline']['frac'], d['sustained']['clips_per_s'], d['mgfn_train_step']['ms_per_step'])" | tee -a $OUT/summary.txt
 done
 done

@@ -3,7 +3,7 @@
 # (is the fp32-MFMA peak of 157.3 TFLOP/s -- 2.4 GHz x 256 CUs x 256 FLOP/clk -- the clock the stream actually runs at?)
 OUT=$1; SECS=${2:-12}
 mkdir -p $OUT
-python bench.py --no-cpu-baseline --no-pcie --no-mgfn-train --steps 40 --warmup 6 --sustain-s $SECS > $OUT/bench.json 2> $OUT/bench.err &
+python bench.py --full --no-cpu-baseline --no-pcie --no-mgfn-train --steps 40 --warmup 6 --sustain-s $SECS > $OUT/bench.json 2> $OUT/bench.err &
 BP=$!
 sleep 2
 for i in $(seq 1 $((SECS * 4 + 40))); do
