@@ -192,6 +192,7 @@ SIGNATURES = {
     "advhip_tencrop_normalize_planes_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _L, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_normalize_permute_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
+    "advhip_resize_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

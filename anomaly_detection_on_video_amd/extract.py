@@ -19,6 +19,7 @@ import torch
 
 from . import dist as adist
 from . import mil_ops
+from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
 
 FRAMES_PER_CLIP = 16
@@ -138,12 +139,16 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
-                         clips_per_step: int = 3, **kw) -> np.ndarray:
+                         clips_per_step: int = 3, resize=None, resample="bilinear", **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
     reference's DataLoader ships per clip, src/dataset.py:175-195, extract_features.py:79-86).  `clips_per_step` clips
-    (x 10 crops) are pre-processed and run per step."""
+    (x 10 crops) are pre-processed and run per step.
+
+    With `resize` (e.g. 256), `frames` are the decoded frames at their native size, on the host or the device, and each
+    step's frames are resized on the device first: `GroupResize(resize, resample)` of src/gtransforms.py:9-18, PIL's bytes
+    (resize.resize_u8).  Only the decoded uint8 frames cross PCIe then."""
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
     dev = next(model.parameters()).device
@@ -153,7 +158,13 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     direct = hasattr(model, "forward_frames") and hasattr(model, "frames_fused") and model.frames_fused()
     for f0 in range(0, frames.shape[0], step):
         fr = frames[f0 : f0 + step]
-        if direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
+        if resize is not None:  # decoded frames -> GroupResize on the device, into a buffer with the stem's spare bytes
+            fr = fr.to(dev, non_blocking=True).contiguous()
+            oh, ow = resize_mod.output_size(fr.shape[1], fr.shape[2], resize)
+            n = fr.shape[0] * oh * ow * fr.shape[3]
+            buf = torch.empty((n + 16,), device=dev, dtype=torch.uint8)
+            fr = resize_mod.resize_u8(fr, resize, resample, out=buf[:n].view(fr.shape[0], oh, ow, fr.shape[3]))
+        elif direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
             buf = torch.empty((fr.numel() + 16,), device=dev, dtype=torch.uint8)
             buf[: fr.numel()].copy_(fr.reshape(-1), non_blocking=True)
             fr = buf[: fr.numel()].view(fr.shape)
@@ -193,7 +204,8 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     """The reference's treatment of videos too large to hold in RAM (extract_features.py:116-148): the video is cut into
     segments of `seg_len` frames (a multiple of 16, so only the last clip of the video is LoopPad-ed), each segment's
     (n_clips, 10, 2048) features are cached as `<outpath>/<name>/<name>_<seg>.npy` and re-used on a later run, and the
-    segments are stacked.  `read_frames(start, stop)` returns the resized uint8 frames [start, stop) as (F, H, W, 3)."""
+    segments are stacked.  `read_frames(start, stop)` returns the resized uint8 frames [start, stop) as (F, H, W, 3) (the decoded
+    ones with `resize=...` in `kw`, see extract_video_frames)."""
     seg_folder = os.path.join(outpath, name)
     os.makedirs(seg_folder, exist_ok=True)
     segments = []

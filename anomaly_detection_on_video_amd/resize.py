@@ -1,0 +1,200 @@
+"""GroupResize on the device: the reference's `GroupResize(256, Image.BILINEAR)` (src/gtransforms.py:9-18, applied in
+src/dataset.py:175-183) on decoded uint8 frames, bit-exact with Pillow.
+
+Host side (this module): torchvision's `Resize(int)` output-size rule and Pillow's fixed-point resampling tables
+(Resample.c: `precompute_coeffs` + `normalize_coeffs_8bpc`), restated in double precision with Pillow's order of operations.
+Device side (csrc/resize.hip, `advhip_resize_u8`): Pillow's two passes, horizontal into a uint8 workspace then vertical,
+each `clamp((2**21 + sum(pixel * coef)) >> 22, 0, 255)` in int32.  NEAREST and HAMMING are not supported.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, NamedTuple, Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import HipExtensionError, check, ptr, require_gpu, stream
+
+PRECISION_BITS = 22  # Pillow: 32 - 8 - 2
+
+
+def _box(x: float) -> float:
+    return 1.0 if -0.5 < x <= 0.5 else 0.0
+
+
+def _bilinear(x: float) -> float:
+    x = -x if x < 0.0 else x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic(x: float) -> float:  # a = -0.5
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * -0.5
+    return 0.0
+
+
+def _sinc(x: float) -> float:
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x: float) -> float:
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+# name -> (support, filter)
+FILTERS = {"box": (0.5, _box), "bilinear": (1.0, _bilinear), "bicubic": (2.0, _bicubic), "lanczos": (3.0, _lanczos)}
+PIL_CODES = {1: "lanczos", 2: "bilinear", 3: "bicubic", 4: "box"}  # PIL.Image.Resampling values
+_REFUSED = {0: "nearest", 5: "hamming"}
+
+
+def filter_name(resample: Union[int, str]) -> str:
+    """A PIL resampling code (LANCZOS 1, BILINEAR 2, BICUBIC 3, BOX 4) or a lowercase name -> the filter's name."""
+    if isinstance(resample, str):
+        if resample in FILTERS:
+            return resample
+    elif isinstance(resample, (int, np.integer)) and not isinstance(resample, bool):
+        if int(resample) in PIL_CODES:
+            return PIL_CODES[int(resample)]
+        if int(resample) in _REFUSED:
+            resample = _REFUSED[int(resample)]
+    raise ValueError(f"resize: resampling filter {resample!r} is not supported (box, bilinear, bicubic, lanczos or PIL codes 1-4)")
+
+
+def output_size(h: int, w: int, size: Union[int, Tuple[int, int]]) -> Tuple[int, int]:
+    """(out_h, out_w) of torchvision's `Resize(size)` for an (h, w) frame: an int sets the short side and scales the long
+    side to int(size * long / short) (a frame already at that size stays as it is); an (h, w) pair is used as given."""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError(f"resize: size must be an int or (h, w), got {size!r}")
+        oh, ow = int(size[0]), int(size[1])
+    else:
+        size = int(size)
+        short, long = (w, h) if w <= h else (h, w)
+        if short == size:
+            return h, w
+        new_short, new_long = size, int(size * long / short)
+        ow, oh = (new_short, new_long) if w <= h else (new_long, new_short)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"resize: output size ({oh}, {ow}) must be at least 1 x 1")
+    return oh, ow
+
+
+def coefficients(in_size: int, out_size: int, resample: Union[int, str] = "bilinear") -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's tables for one axis: bounds int32 (out, 2) = (first source index, tap count) and the 2**22 fixed-point
+    coefficients int32 (out, ksize), zero past each output's tap count."""
+    support0, filt = FILTERS[filter_name(resample)]
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resize: sizes must be >= 1 (in {in_size}, out {out_size})")
+    scale = float(in_size) / out_size
+    fs = max(scale, 1.0)
+    support = support0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    coef = np.zeros((out_size, ksize), dtype=np.int32)
+    one = float(1 << PRECISION_BITS)
+    for i in range(out_size):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - xmin
+        w = [filt((j + xmin - center + 0.5) * ss) for j in range(n)]
+        total = 0.0
+        for v in w:
+            total += v
+        if total != 0.0:
+            w = [v / total for v in w]
+        bounds[i] = (xmin, n)
+        coef[i, :n] = [int(v * one + 0.5) if v >= 0 else int(v * one - 0.5) for v in w]
+    return bounds, coef
+
+
+class Plan(NamedTuple):
+    """Host tables of one resize (in_h, in_w) -> (out_h, out_w): which passes run, and each axis' tables.  The horizontal
+    pass computes source rows [row0, row0 + rows) only (the rows the vertical pass reads)."""
+    out_h: int
+    out_w: int
+    horizontal: bool
+    vertical: bool
+    xbounds: np.ndarray
+    xcoef: np.ndarray
+    ybounds: np.ndarray
+    ycoef: np.ndarray
+    row0: int
+    rows: int
+
+
+def plan(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, str] = "bilinear") -> Plan:
+    xb, xk = coefficients(in_w, out_w, resample)
+    yb, yk = coefficients(in_h, out_h, resample)
+    row0 = int(yb[0, 0])
+    rows = int(yb[-1, 0] + yb[-1, 1]) - row0
+    return Plan(out_h, out_w, out_w != in_w, out_h != in_h, xb, xk, yb, yk, row0, rows)
+
+
+class _Tables(NamedTuple):
+    plan: Plan
+    buf: torch.Tensor  # int32 [xbounds | xcoef | ybounds | ycoef] on the device
+    offsets: Tuple[int, int, int, int]
+
+
+_TABLES: Dict[tuple, _Tables] = {}
+
+
+def tables(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, str], device: torch.device) -> _Tables:
+    """The device tables of one resize, built on the current stream on first use and cached per
+    (in_h, in_w, out_h, out_w, filter, device) (like the conv gather tables: a caller about to fork streams builds them first)."""
+    key = (in_h, in_w, out_h, out_w, filter_name(resample), torch.device(device))
+    t = _TABLES.get(key)
+    if t is None:
+        p = plan(in_h, in_w, out_h, out_w, resample)
+        parts = [p.xbounds, p.xcoef, p.ybounds, p.ycoef]
+        offsets = tuple(int(o) for o in np.cumsum([0] + [a.size for a in parts[:-1]]))
+        host = torch.from_numpy(np.concatenate([a.reshape(-1) for a in parts]))
+        if host.device.type == "cpu" and torch.cuda.is_available():
+            host = host.pin_memory()  # an asynchronous copy on the current stream (the pinned block outlives it)
+        buf = host.to(device, non_blocking=True)
+        t = _TABLES[key] = _Tables(p, buf, offsets)
+    return t
+
+
+def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, resample: Union[int, str] = "bilinear",
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 (F, H, W, 3) frames on the GPU -> (F, OH, OW, 3), what `GroupResize(size, resample)` gives frame by frame (PIL
+    `Image.resize`, bit for bit), on the current stream with no host synchronisation.  `out` places the result in a
+    caller-owned contiguous (F, OH, OW, 3) uint8 tensor (e.g. a view of a larger buffer).  Without `out`, frames already at
+    the output size are returned as they are (torchvision returns the image itself)."""
+    require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise HipExtensionError(f"resize_u8 wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
+    F, H, W, _ = frames.shape
+    name = filter_name(resample)
+    oh, ow = output_size(H, W, size)
+    if out is None:
+        if (oh, ow) == (H, W):
+            return frames
+        out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
+    else:
+        require_gpu(frames, out)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (F, oh, ow, 3):
+            raise HipExtensionError(f"resize_u8: out must be uint8 {(F, oh, ow, 3)}, got {out.dtype} {tuple(out.shape)}")
+        a0, a1 = frames.data_ptr(), frames.data_ptr() + frames.numel()
+        if out.data_ptr() < a1 and a0 < out.data_ptr() + out.numel():
+            raise HipExtensionError("resize_u8: out overlaps the input frames")
+    t = tables(H, W, oh, ow, name, frames.device)
+    p, b, (o_xb, o_xk, o_yb, o_yk) = t.plan, t.buf, t.offsets
+    ws = None
+    if p.horizontal and p.vertical:
+        ws = torch.empty((F * p.rows * ow * 3,), device=frames.device, dtype=torch.uint8)
+    check(_lib.load().advhip_resize_u8(ptr(frames), ptr(out), ptr(ws), F, H, W, 3, oh, ow,
+                                       ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
+                                       ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
+          "resize_u8")
+    return out

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
 tensors of the same layout; plug a real decoder in by passing (name, loader) pairs to
-`anomaly_detection_on_video_amd.extract.extract`.
+`anomaly_detection_on_video_amd.extract.extract`.  With `--frame-size HxW` the source is synthetic DECODED uint8 frames of
+that size instead, resized (GroupResize(256)), ten-cropped and normalised on the device: `extract_frames(..., resize=256)`,
+the entry point for a real decoder's (name, n_frames, read_frames) triples.
 """
 import argparse
 import os
@@ -17,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from anomaly_detection_on_video_amd.extract import extract, load_feature_extraction_model, segment  # noqa: E402,F401
+from anomaly_detection_on_video_amd.extract import extract, extract_frames, load_feature_extraction_model, segment  # noqa: E402,F401
 
 
 def synthetic_sources(n_videos: int, seed: int = 0):
@@ -28,15 +30,42 @@ def synthetic_sources(n_videos: int, seed: int = 0):
         yield name, (lambda n=n_clips, s=seed + i: torch.randn((n, 10, 16, 3, 224, 224), generator=torch.Generator().manual_seed(s)))
 
 
+def synthetic_frame_sources(n_videos: int, frame_size, seed: int = 0):
+    """(name, n_frames, read_frames) of synthetic decoded uint8 (F, H, W, 3) videos of 2-5 clips plus a few frames."""
+    g = torch.Generator().manual_seed(seed)
+    h, w = frame_size
+    for i in range(n_videos):
+        n_frames = int(torch.randint(2 * 16, 6 * 16, (1,), generator=g))
+        name = ("Normal_Videos_%03d_x264" if i % 2 == 0 else "Abuse%03d_x264") % i
+
+        def read_frames(lo, hi, n=n_frames, s=seed + i):  # the same video on every call (a decoder reads a range of it)
+            return torch.randint(0, 256, (n, h, w, 3), generator=torch.Generator().manual_seed(s), dtype=torch.uint8)[lo:hi]
+
+        yield name, n_frames, read_frames
+
+
+def parse_frame_size(text: str):
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--frame-size wants HxW, e.g. 240x320; got {text!r}")
+    if h < 1 or w < 1:
+        raise argparse.ArgumentTypeError(f"--frame-size {text!r}: sizes must be >= 1")
+    return h, w
+
+
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
-         model_name: str = "i3d_8x8_r50"):
+         model_name: str = "i3d_8x8_r50", frame_size=None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
     outpath = os.path.join(outdir, "anomaly_features", "train")
-    extract(synthetic_sources(videos), model, outpath)
+    if frame_size is None:
+        extract(synthetic_sources(videos), model, outpath)
+    else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
+        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -49,5 +78,7 @@ if __name__ == "__main__":
     ap.add_argument("--synthetic-weights", action="store_true")
     ap.add_argument("--model-name", default="i3d_8x8_r50", choices=["i3d_8x8_r50", "tushar-n-baseline"],
                     help="the reference's default is i3d_8x8_r50 (parity-unpinned here); tushar-n-baseline = the pinned in-repo I3Res50")
+    ap.add_argument("--frame-size", type=parse_frame_size, default=None, metavar="HxW",
+                    help="feed synthetic decoded uint8 frames of this size, resized to 256 on the device (default: ten-cropped clip tensors)")
     a = ap.parse_args()
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name)
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size)

@@ -619,6 +619,18 @@ int advhip_normalize_permute_u8(const uint8_t* x, float* y, int64_t N, int32_t T
 int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                 int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream);
 
+/* The resize in front of all that: GroupResize(256, Image.BILINEAR) (src/gtransforms.py:9-18, applied in src/dataset.py:175-183),
+ * i.e. PIL Image.resize of every decoded frame, byte for byte (Pillow's 8-bit two-pass resampler).
+ *   src: uint8 (F, H, W, C) decoded frames, C == 3;  dst: uint8 (F, OH, OW, C).
+ *   xbounds int32 (OW, 2) = (first source column, tap count), xcoef int32 (OW, xksize): the horizontal table; ybounds / ycoef /
+ *   yksize: the vertical one (source rows as Pillow computes them); coefficients are 2^22 fixed point (resize.py builds them).
+ *   The horizontal pass runs iff OW != W and computes source rows [row0, row0 + rows) into ws (uint8 (F, rows, OW, C)), or all
+ *   H rows straight into dst when OH == H; the vertical pass runs iff OH != H, from ws (or src).  Neither: dst = a copy of src.
+ * Two launches on `stream` at most; every argument is checked before the first. */
+int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F, int32_t H, int32_t W, int32_t C, int32_t OH,
+                     int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds,
+                     const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
