@@ -127,6 +127,7 @@ struct ConvArgs {
   // crop-clip u8_first + b = (clip, crop) of torchvision's TenCrop order (4 corners, centre, then the same five mirrored);
   // T / H / W above are the clip-local extents (frames per clip, crop size) the tap masks are taken against
   int u8_first, u8_FH, u8_FW;
+  int u8_cstride;           // frames between the starts of consecutive clips: T (back to back) or less (overlapping windows)
   int u8_ctop, u8_cleft;    // top / left of the centre crop (round-half-to-even, as torchvision)
   float in_std;             // conv of (pixel - mean) / in_std: the mean through pad_corr, 1 / in_std through the BN scale
   const int2* ktab_u8;      // [2][Kpad] {byte offset, tap bits}: as stored, and mirrored along w
@@ -1323,7 +1324,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
       const int FWC = a.u8_FW * a.Cin, FHWC = a.u8_FH * FWC;
       // (mirrored crops are five_crop(hflip(frame)): column c of such a crop is source column FW - 1 - (left + c))
       const int col = u8_flip ? a.u8_FW - 1 - left - iw0 - (a.kw_ - 1) : left + iw0;
-      vbase = (unsigned)((clip * a.T + it0) * FHWC + (top + ih0) * FWC + col * a.Cin + a.pad_off);
+      vbase = (unsigned)((clip * a.u8_cstride + it0) * FHWC + (top + ih0) * FWC + col * a.Cin + a.pad_off);
     } else {
       vbase = (unsigned)(pb * a.x_bstride + it0 * a.HW + ih0 * a.W + iw0 + a.pad_off) * 4u;
     }
@@ -2057,7 +2058,7 @@ void stem_u8_tap_kernel(const ConvArgs a) {
     const int it0 = pot * a.st - a.pt, ih0 = poh * a.sh - a.ph, iw0 = pow_ * a.sw - a.pw;
     const int top = j5 == 4 ? a.u8_ctop : ((j5 >> 1) ? a.u8_FH - a.H : 0), left = j5 == 4 ? a.u8_cleft : ((j5 & 1) ? a.u8_FW - a.W : 0);
     const int col = flip ? a.u8_FW - 1 - left - iw0 - (a.kw_ - 1) : left + iw0;  // (mirrored crops: see the byte form)
-    vbase = (unsigned)((((clip * a.T + it0) * a.u8_FH + top + ih0) * a.u8_FW + col) * 3 + a.pad_off);
+    vbase = (unsigned)((((clip * a.u8_cstride + it0) * a.u8_FH + top + ih0) * a.u8_FW + col) * 3 + a.pad_off);
     vmask = tap_bits(it0, a.kt_, a.T) | (tap_bits(ih0, a.kh_, a.H) << 10) | (tap_bits(iw0, a.kw_, a.W) << 20);
   }
   U8Corr u8c{};
@@ -3597,8 +3598,13 @@ extern "C" int advhip_conv3d_s2w_bn_relu_maxpool233_f32(const advhip_conv3d_desc
 
 // ---- stem + maxpool1 straight from resized uint8 frames (TenCrop, float conversion and normalisation in the load stage) ----
 namespace advhip {
-static int u8_check_frames(const advhip_conv3d_desc* d, int64_t F, int FH, int FW) {
-  ADVHIP_REQUIRE(F > 0 && F % d->T == 0, "conv3d u8: %lld frames are not whole clips of %d", (long long)F, d->T);
+// the frames buffer of the fused stems holds whole windows: F = (n - 1) * clip_stride + T for n >= 1 windows (clip_stride = T:
+// whole back-to-back clips).  *n_clips receives n.
+static int u8_check_frames(const advhip_conv3d_desc* d, int64_t F, int FH, int FW, int clip_stride, int64_t* n_clips = nullptr) {
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= d->T, "conv3d u8: clip stride %d outside [1, %d]", clip_stride, d->T);
+  ADVHIP_REQUIRE(F >= d->T && (F - d->T) % clip_stride == 0, "conv3d u8: %lld frames are not whole clips of %d at stride %d", (long long)F, d->T,
+                 clip_stride);
+  if (n_clips) *n_clips = (F - d->T) / clip_stride + 1;
   ADVHIP_REQUIRE(FH >= d->H && FW >= d->W, "conv3d u8: frames (%d x %d) smaller than the %d x %d crop", FH, FW, d->H, d->W);
   ADVHIP_REQUIRE(d->kt <= 10 && d->kh <= 10 && d->kw <= 10, "conv3d u8: kernel extents above 10");
   ADVHIP_REQUIRE(F * FH * FW * d->Cin < (1ll << 31) - (1 << 24), "conv3d u8: frames tensor above 2 GiB");
@@ -3618,7 +3624,7 @@ extern "C" int advhip_conv3d_u8_build_tables(const advhip_conv3d_desc* d, int32_
                                              int32_t* ktab_u8, float* corr, void* stream) {
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_u8 && corr, "conv3d u8 tables: null pointer");
-  if (int rc = u8_check_frames(d, d->T, FH, FW)) return rc;
+  if (int rc = u8_check_frames(d, d->T, FH, FW, d->T)) return rc;
   const Geometry g = geometry(d);
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
@@ -3638,13 +3644,25 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(const advhip_conv
                                                                int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                void* stream) {
   if (int rc = validate(d)) return rc;
+  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(d, frames, F, FH, FW, d->T, first_crop_clip, w_packed, ktab_u8, corr, scale, shift,
+                                                                 stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                       int32_t FW, int32_t clip_stride, int64_t first_crop_clip,
+                                                                       const float* w_packed, const int32_t* ktab_u8, const float* corr,
+                                                                       const float* scale, const float* shift, float stdv, float* y,
+                                                                       int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                                       void* stream) {
+  if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(frames && w_packed && ktab_u8 && corr && scale && shift && y, "conv3d u8+pool233: null pointer");
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8+pool233: padding not smaller than the kernel");
   ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8+pool233: std must be non-zero");
-  if (int rc = u8_check_frames(d, F, FH, FW)) return rc;
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= F / d->T * 10,
+  int64_t n_clips = 0;
+  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, &n_clips)) return rc;
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * 10,
                  "conv3d u8+pool233: crop-clips [%lld, %lld) outside the %lld clips x 10 crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)(F / d->T));
+                 (long long)first_crop_clip + d->B, (long long)n_clips);
   const Geometry g = geometry(d);
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
@@ -3656,7 +3674,7 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(const advhip_conv
   ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_packed, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW;
+  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
   // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
@@ -3705,7 +3723,7 @@ extern "C" int advhip_conv3d_u8_taps_build_tables(const advhip_conv3d_desc* d, i
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_taps && corr && w_taps, "conv3d u8 taps tables: null pointer");
   ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
-  if (int rc = u8_check_frames(d, d->T, FH, FW)) return rc;
+  if (int rc = u8_check_frames(d, d->T, FH, FW, d->T)) return rc;
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
   ADVHIP_REQUIRE(total < (1ll << 28), "conv3d u8 taps tables: padding (%d,%d,%d) too large", d->pt, d->ph, d->pw);
@@ -3727,17 +3745,30 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(const advhip
                                                                     int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                     void* stream) {
   if (int rc = validate(d)) return rc;
+  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(d, frames, F, FH, FW, d->T, readable_bytes, first_crop_clip, w_taps, ktab_taps,
+                                                                      corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes,
+                                                                      stream);
+}
+
+extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F,
+                                                                            int32_t FH, int32_t FW, int32_t clip_stride, int64_t readable_bytes,
+                                                                            int64_t first_crop_clip, const float* w_taps,
+                                                                            const int32_t* ktab_taps, const float* corr, const float* scale,
+                                                                            const float* shift, float stdv, float* y, int64_t y_batch_stride,
+                                                                            void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(frames && w_taps && ktab_taps && corr && scale && shift && y, "conv3d u8 taps+pool233: null pointer");
   ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps+pool233: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8 taps+pool233: padding not smaller than the kernel");
   ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8 taps+pool233: std must be non-zero");
-  if (int rc = u8_check_frames(d, F, FH, FW)) return rc;
+  int64_t n_clips = 0;
+  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, &n_clips)) return rc;
   const int64_t fbytes = F * FH * FW * 3;
   ADVHIP_REQUIRE(readable_bytes >= fbytes + 1, "conv3d u8 taps+pool233: the frames allocation must extend one byte past the last pixel "
                  "(pixels are fetched as 4-byte pieces): %lld readable, %lld needed", (long long)readable_bytes, (long long)fbytes + 1);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= F / d->T * 10,
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * 10,
                  "conv3d u8 taps+pool233: crop-clips [%lld, %lld) outside the %lld clips x 10 crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)(F / d->T));
+                 (long long)first_crop_clip + d->B, (long long)n_clips);
   const Geometry g = geometry(d);
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8 taps+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
@@ -3749,7 +3780,7 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(const advhip
   ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8 taps+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_taps, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW;
+  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
   a.in_std = stdv;

@@ -84,14 +84,15 @@ __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float
 // input (n_clips * 10, C, fpc, cs, cs) fp32.  Crop j < 5 of a frame = its (top_j, left_j) window: top-left, top-right,
 // bottom-left, bottom-right, centre (torchvision five_crop order; centre offsets are Python-rounded halves, computed by the
 // caller); crops 5..9 = the same five windows of the horizontally flipped frame: pixel (y, x) = frame[top + y][W - 1 - (left + x)].
-// Frame t of clip c = frames[c * fpc + t % len_c], len_c = min(fpc, F - c * fpc) (LoopPad: a short last clip repeats itself).
+// Frame t of clip c = frames[c * cstride + t % len_c], len_c = min(fpc, F - c * cstride) (LoopPad: a short last clip repeats
+// itself); cstride = the distance between clip starts, fpc for the reference's back-to-back clips, less for overlapping windows.
 // One wave per output row (clip, crop, c, t, y): the row decode (five divisions) happens once per 224 outputs, the lanes run
 // along x with 16-byte stores (the first form decoded every float4 separately and indexed a by-value crop table: 165 us for
 // 40 crop-clips, VALU-bound at 2.3 TB/s).
 template <int VW>
 __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int F, int H, int W,
-                                                                   int C, int fpc, int cs, int ctop, int cleft, float mean, float stdv,
-                                                                   long long rows) {
+                                                                   int C, int fpc, int cstride, int cs, int ctop, int cleft, float mean,
+                                                                   float stdv, long long rows) {
   const int lane = threadIdx.x & 63;
   const int csv = cs / VW;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
@@ -104,8 +105,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
     r /= C;
     const int crop = (int)(r % 10);
     const int clip = (int)(r / 10);
-    const int len = min(fpc, F - clip * fpc);
-    const int f = clip * fpc + t % len;
+    const int len = min(fpc, F - clip * cstride);
+    const int f = clip * cstride + t % len;
     const int j = crop % 5;
     const int top = j == 4 ? ctop : ((j >> 1) ? H - cs : 0), left = j == 4 ? cleft : ((j & 1) ? W - cs : 0);
     const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
@@ -128,8 +129,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
 // [first, first + count), xs[(clip-crop, c, t, y)][par][2 + j] = normalised pixel of crop column 2 j + par, zero in the
 // padding columns.  One wave per (row, both planes); the arithmetic per pixel is the pass above's, so the values are its values.
 __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, int F, int H,
-                                                                          int W, int C, int fpc, int cs, int ctop, int cleft, float mean,
-                                                                          float stdv, long long first, long long rows, int WP) {
+                                                                          int W, int C, int fpc, int cstride, int cs, int ctop, int cleft,
+                                                                          float mean, float stdv, long long first, long long rows, int WP) {
   const int lane = threadIdx.x & 63;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
     long long r = r0;  // (clip-crop - first, c, t, y)
@@ -141,8 +142,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const 
     r = r / C + first;
     const int crop = (int)(r % 10);
     const int clip = (int)(r / 10);
-    const int len = min(fpc, F - clip * fpc);
-    const int f = clip * fpc + t % len;
+    const int len = min(fpc, F - clip * cstride);
+    const int f = clip * cstride + t % len;
     const int j5 = crop % 5;
     const int top = j5 == 4 ? ctop : ((j5 >> 1) ? H - cs : 0), left = j5 == 4 ? cleft : ((j5 & 1) ? W - cs : 0);
     const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
@@ -159,17 +160,36 @@ __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const 
   }
 }
 
+// Per-window scores (n,) -> per-frame scores: window w covers frames [w * cstride, w * cstride + fpc); the score of a frame is
+// the mean of the scores of the windows covering it, added in ascending window order, one division by their count (cstride =
+// fpc: one window per frame, np.repeat(scores, fpc) of runner.py:66-76).  One thread per frame, at most ceil(fpc / cstride) adds.
+__global__ __launch_bounds__(256) void frame_scores_kernel(const float* __restrict__ scores, float* __restrict__ out, int n, int fpc, int cstride,
+                                                           int n_frames) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= n_frames) return;
+  const int lo = f < fpc ? 0 : (f - fpc) / cstride + 1;  // first w with w * cstride + fpc > f
+  const int hi = min(n - 1, f / cstride);                // last w with w * cstride <= f
+  float acc = scores[lo];
+  for (int w = lo + 1; w <= hi; ++w) acc += scores[w];
+  out[f] = acc / (float)(hi - lo + 1);
+}
+
 }  // namespace advhip
 
 using namespace advhip;
 
-extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                  int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
-                                                  float stdv, void* stream) {
+// windows of a video of F frames: window w starts at frame w * clip_stride, the last one may be short (LoopPad)
+static long long window_count(long long F, int fpc, int clip_stride) { return 1 + (F > fpc ? (F - fpc + clip_stride - 1) / clip_stride : 0); }
+
+extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
+                                                          int64_t count, float mean, float stdv, void* stream) {
   ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0 && crop % 2 == 0, "tencrop_normalize_planes_u8: bad arguments");
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_planes_u8: clip stride %d outside [1, %d]", clip_stride,
+                 frames_per_clip);
   ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_planes_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
   ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_planes_u8: std must be non-zero");
-  const long long n_clips = (F + frames_per_clip - 1) / frames_per_clip;
+  const long long n_clips = window_count(F, frames_per_clip, clip_stride);
   ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * 10,
                  "tencrop_normalize_planes_u8: crop-clips [%lld, %lld) outside the video's %lld", (long long)first_crop_clip,
                  (long long)(first_crop_clip + count), n_clips * 10);
@@ -178,27 +198,56 @@ extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* 
   const long long rows = (long long)count * C * frames_per_clip * crop;
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, frames_per_clip,
-                     crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4);
+                     clip_stride, crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4);
   return check_launch("tencrop_normalize_planes_u8");
 }
 
-extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                           int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream) {
+extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                  int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
+                                                  float stdv, void* stream) {
+  return advhip_tencrop_normalize_planes_u8_strided(frames, xs, F, H, W, C, frames_per_clip, frames_per_clip, crop, first_crop_clip, count, mean,
+                                                    stdv, stream);
+}
+
+extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
+                                                   void* stream) {
   ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0, "tencrop_normalize_u8: bad arguments");
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_u8: clip stride %d outside [1, %d]", clip_stride,
+                 frames_per_clip);
   ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
   ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_u8: std must be non-zero");
   // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
   auto half_even = [](int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); };
   const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const long long n_clips = (F + frames_per_clip - 1) / frames_per_clip;
+  const long long n_clips = window_count(F, frames_per_clip, clip_stride);
   const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
   const long long rows = n_clips * 10 * C * frames_per_clip * (long long)crop;
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                              frames_per_clip, crop, ctop, cleft, mean, stdv, rows);
+                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows);
   else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                          frames_per_clip, crop, ctop, cleft, mean, stdv, rows);
+                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows);
   return check_launch("tencrop_normalize_u8");
+}
+
+extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                           int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream) {
+  return advhip_tencrop_normalize_u8_strided(frames, y, F, H, W, C, frames_per_clip, frames_per_clip, crop, mean, stdv, stream);
+}
+
+extern "C" int advhip_frame_scores_f32(const float* scores, float* out, int64_t n_windows, int32_t frames_per_clip, int32_t clip_stride,
+                                       int64_t n_frames, void* stream) {
+  ADVHIP_REQUIRE(scores && out && n_windows > 0 && frames_per_clip > 0, "frame_scores: bad arguments");
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "frame_scores: clip stride %d outside [1, %d]", clip_stride, frames_per_clip);
+  const long long covered = (long long)(n_windows - 1) * clip_stride + frames_per_clip;
+  ADVHIP_REQUIRE(n_frames > 0 && n_frames <= covered, "frame_scores: %lld frames, but %lld windows of %d at stride %d cover %lld",
+                 (long long)n_frames, (long long)n_windows, frames_per_clip, clip_stride, covered);
+  ADVHIP_REQUIRE(covered < (1ll << 31), "frame_scores: more than 2^31 frames");
+  const unsigned grid = (unsigned)((n_frames + 255) / 256);
+  hipLaunchKernelGGL(frame_scores_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, scores, out, (int)n_windows, frames_per_clip, clip_stride,
+                     (int)n_frames);
+  return check_launch("frame_scores");
 }
 
 extern "C" int advhip_normalize_permute_u8(const uint8_t* x, float* y, int64_t N, int32_t T, int32_t C, int32_t H,

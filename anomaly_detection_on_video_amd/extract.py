@@ -21,6 +21,7 @@ from . import dist as adist
 from . import mil_ops
 from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
+from .ops import n_windows, pad_windows_u8, resolve_clip_stride  # noqa: F401  (n_windows is part of this module's interface)
 
 FRAMES_PER_CLIP = 16
 NCROPS = 10
@@ -139,7 +140,7 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
-                         clips_per_step: int = 3, resize=None, resample="bilinear", **kw) -> np.ndarray:
+                         clips_per_step: int = 3, resize=None, resample="bilinear", clip_stride: Optional[int] = None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -148,16 +149,24 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
 
     With `resize` (e.g. 256), `frames` are the decoded frames at their native size, on the host or the device, and each
     step's frames are resized on the device first: `GroupResize(resize, resample)` of src/gtransforms.py:9-18, PIL's bytes
-    (resize.resize_u8).  Only the decoded uint8 frames cross PCIe then."""
+    (resize.resize_u8).  Only the decoded uint8 frames cross PCIe then.
+
+    `clip_stride` (default frames_per_clip, the reference's back-to-back clips): clip w is the window of frames_per_clip
+    frames that starts at frame w * clip_stride, n_clips = n_windows(F, frames_per_clip, clip_stride), only the last window is
+    LoopPad-ed.  The windows are addressed in place by the kernels: a step reads frames [w0 * s, (w0 + clips_per_step - 1) * s +
+    frames_per_clip), host frames are copied per step with that overlap (with `resize`, the overlap is resized again: PIL's
+    bytes either way), frames already on the device are not copied at all."""
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
     dev = next(model.parameters()).device
     rows = []
-    step = clips_per_step * frames_per_clip
+    n_total = n_windows(frames.shape[0], frames_per_clip, s)
     max_cc = kw.get("max_crop_clips", 32)
     direct = hasattr(model, "forward_frames") and hasattr(model, "frames_fused") and model.frames_fused()
-    for f0 in range(0, frames.shape[0], step):
-        fr = frames[f0 : f0 + step]
+    for w0 in range(0, n_total, clips_per_step):
+        w1 = min(w0 + clips_per_step, n_total)
+        fr = frames[w0 * s : (w1 - 1) * s + frames_per_clip]  # (the slice ends with the video: a short last window)
         if resize is not None:  # decoded frames -> GroupResize on the device, into a buffer with the stem's spare bytes
             fr = fr.to(dev, non_blocking=True).contiguous()
             oh, ow = resize_mod.output_size(fr.shape[1], fr.shape[2], resize)
@@ -171,23 +180,18 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         else:
             fr = fr.to(dev, non_blocking=True)
         if not direct:
-            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop)
+            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=s)
             rows.append(run_chunks_on_lanes(model, [x[i : i + max_cc] for i in range(0, x.shape[0], max_cc)]))
             continue
         # the stem kernel reads the uint8 pixels itself (TenCrop + float + normalise in its load stage): only LoopPad is left,
-        # and only for a last clip shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
-        short = fr.shape[0] % frames_per_clip
-        if short:
-            whole = fr.shape[0] - short
-            idx = torch.arange(frames_per_clip, device=dev) % short + whole
-            fr = torch.cat([fr[:whole], fr[idx]], dim=0)
-        fr = fr.contiguous()
-        n = fr.shape[0] // frames_per_clip * NCROPS
+        # and only for a last window shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
+        fr = pad_windows_u8(fr, frames_per_clip, s).contiguous()
+        n = (w1 - w0) * NCROPS
         ranges = [(i, min(max_cc, n - i)) for i in range(0, n, max_cc)]
 
         def run_range(r, fr=fr):
             fr.record_stream(torch.cuda.current_stream(dev))  # (read on a lane stream, allocated on the caller's)
-            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop)
+            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=s)
 
         rows.append(run_chunks_on_lanes(
             model, ranges, fn=run_range,
@@ -199,21 +203,44 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
 SEGMENT_FRAMES = 16 * 188  # 3008: extract_features.py:121
 
 
+def segment_windows(n_frames: int, seg_len: int = SEGMENT_FRAMES, frames_per_clip: int = FRAMES_PER_CLIP,
+                    clip_stride: Optional[int] = None):
+    """How a long video's windows are shared out between its segments: [(segment, first window, end window, first frame, end
+    frame)] over the reference's segments 0 .. n_frames // seg_len (extract_features.py:116-148), those that own no window left out.
+    Segment k owns the windows that START in [k * seg_len, (k + 1) * seg_len) and therefore reads frames up to frames_per_clip -
+    clip_stride past its end: frames [k * seg_len, min((k + 1) * seg_len + frames_per_clip - clip_stride, n_frames)), which taken
+    as a video of their own have exactly the owned windows -- and only the video's last window can be short.  seg_len must be a
+    multiple of clip_stride (window starts would drift against the segments otherwise)."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    if seg_len < 1 or seg_len % s:
+        raise ValueError(f"seg_len {seg_len} is not a positive multiple of clip_stride {s}")
+    n, per_seg = n_windows(n_frames, frames_per_clip, s), seg_len // s
+    out = []
+    for seg in range(n_frames // seg_len + 1):
+        w0, w1 = seg * per_seg, min((seg + 1) * per_seg, n)
+        if w0 >= w1:  # nothing starts here: n_frames a multiple of seg_len, or a tail the previous segment's last window covers
+            continue
+        out.append((seg, w0, w1, seg * seg_len, min((seg + 1) * seg_len + frames_per_clip - s, n_frames)))
+    return out
+
+
 def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Callable[[int, int], torch.Tensor], outpath: str,
                               seg_len: int = SEGMENT_FRAMES, **kw) -> np.ndarray:
     """The reference's treatment of videos too large to hold in RAM (extract_features.py:116-148): the video is cut into
     segments of `seg_len` frames (a multiple of 16, so only the last clip of the video is LoopPad-ed), each segment's
     (n_clips, 10, 2048) features are cached as `<outpath>/<name>/<name>_<seg>.npy` and re-used on a later run, and the
     segments are stacked.  `read_frames(start, stop)` returns the resized uint8 frames [start, stop) as (F, H, W, 3) (the decoded
-    ones with `resize=...` in `kw`, see extract_video_frames)."""
+    ones with `resize=...` in `kw`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
+    in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another."""
+    fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
+    s = resolve_clip_stride(fpc, kw.get("clip_stride"))
+    tag = "" if s == fpc else f"_s{s}"
     seg_folder = os.path.join(outpath, name)
+    plan = segment_windows(n_frames, seg_len, fpc, s)  # (refuses a seg_len the stride does not divide before anything is written)
     os.makedirs(seg_folder, exist_ok=True)
     segments = []
-    for seg in range(n_frames // seg_len + 1):
-        lo, hi = seg * seg_len, min((seg + 1) * seg_len, n_frames)
-        if lo >= hi:  # n_frames a multiple of seg_len: the reference's last segment is empty
-            continue
-        seg_path = os.path.join(seg_folder, f"{name}_{seg}.npy")
+    for seg, _w0, _w1, lo, hi in plan:
+        seg_path = os.path.join(seg_folder, f"{name}{tag}_{seg}.npy")
         if os.path.exists(seg_path):
             out = np.load(seg_path)
         else:
@@ -226,11 +253,15 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
 def extract_frames(sources: Iterable[Tuple[str, int, Callable[[int, int], torch.Tensor]]], model, outpath: str,
                    long_video_frames: int = SEGMENT_FRAMES, seg_len: int = SEGMENT_FRAMES, **kw) -> Dict[str, str]:
     """Per-video driver for frame sources (name, n_frames, read_frames): `<name>_i3d.npy` per video with the reference's
-    skip-if-exists rule (:106-110); videos longer than `long_video_frames` go through the per-segment cache."""
+    skip-if-exists rule (:106-110); videos longer than `long_video_frames` go through the per-segment cache.  With
+    `clip_stride` (below frames_per_clip) the files are `<name>_i3d_s<stride>.npy`."""
     os.makedirs(outpath, exist_ok=True)
+    fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
+    s = resolve_clip_stride(fpc, kw.get("clip_stride"))
+    suffix = "_i3d.npy" if s == fpc else f"_i3d_s{s}.npy"
     written = {}
     for name, n_frames, read_frames in sources:
-        savepath = os.path.join(outpath, name + "_i3d.npy")
+        savepath = os.path.join(outpath, name + suffix)
         if os.path.exists(savepath):
             continue
         if n_frames > long_video_frames:

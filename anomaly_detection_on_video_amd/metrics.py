@@ -2,7 +2,7 @@
 restated in numpy (sklearn is optional; pinned against sklearn known-answers in the tests)."""
 from __future__ import annotations
 
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -37,9 +37,45 @@ def pr_auc(labels: Sequence[float], preds: Sequence[float]) -> float:
     return -_area(recall, precision)
 
 
-def frame_level_auc(preds_per_video, labels_per_video, frames_per_clip: int = 16) -> Tuple[float, float]:
-    """np.repeat(clip scores, 16) vs the frame-level ground truth (runner.py:66-76)."""
-    preds = np.repeat(np.concatenate([np.asarray(p).ravel() for p in preds_per_video]), frames_per_clip)
+def frame_scores(scores, frames_per_clip: int = 16, clip_stride: Optional[int] = None, n_frames: Optional[int] = None) -> np.ndarray:
+    """Per-window scores (n,) -> per-frame scores, fp32 (what mil_ops.frame_scores computes on the device).  Window w covers
+    frames [w * clip_stride, w * clip_stride + frames_per_clip); a frame's score is the mean of the scores of the windows
+    covering it: added in ascending window order, one division by the count.  Length n_frames, default (n - 1) * clip_stride +
+    frames_per_clip; clip_stride = frames_per_clip (the default) is np.repeat(scores, frames_per_clip) bit for bit."""
+    s = frames_per_clip if clip_stride is None else int(clip_stride)
+    if not 1 <= s <= frames_per_clip:
+        raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip = {frames_per_clip}]")
+    x = np.asarray(scores, dtype=np.float32).ravel()
+    if x.size == 0:
+        raise ValueError("frame_scores: no window scores")
+    n = x.size
+    covered = (n - 1) * s + frames_per_clip
+    nf = covered if n_frames is None else int(n_frames)
+    if not 0 < nf <= covered:
+        raise ValueError(f"frame_scores: {nf} frames, but {n} windows of {frames_per_clip} at stride {s} cover {covered}")
+    f = np.arange(nf)
+    lo = np.where(f < frames_per_clip, 0, (f - frames_per_clip) // s + 1)  # first window that reaches frame f
+    hi = np.minimum(n - 1, f // s)                                        # last window that starts at or before it
+    acc = x[lo].copy()
+    for k in range(1, -(-frames_per_clip // s)):  # the k-th further window of every frame that has one
+        more = lo + k <= hi
+        acc[more] += x[(lo + k)[more]]
+    return acc / (hi - lo + 1).astype(np.float32)
+
+
+def frame_level_auc(preds_per_video, labels_per_video, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> Tuple[float, float]:
+    """np.repeat(clip scores, 16) vs the frame-level ground truth (runner.py:66-76).  With `clip_stride` < frames_per_clip the
+    predictions are scores of overlapping windows, assembled per video by frame_scores; a video whose labels end inside its last
+    window (the video's own length rather than the padded one) is cut there."""
+    if clip_stride is None or int(clip_stride) == frames_per_clip:
+        preds = np.repeat(np.concatenate([np.asarray(p).ravel() for p in preds_per_video]), frames_per_clip)
+    else:
+        per_video = []
+        for p, l in zip(preds_per_video, labels_per_video):
+            n, nl = np.asarray(p).size, np.asarray(l).size
+            inside = n > 0 and (n - 1) * int(clip_stride) < nl <= (n - 1) * int(clip_stride) + frames_per_clip
+            per_video.append(frame_scores(p, frames_per_clip, clip_stride, nl if inside else None))
+        preds = np.concatenate(per_video)
     labels = np.concatenate([np.asarray(l).ravel() for l in labels_per_video])
     if preds.shape != labels.shape:
         raise ValueError(f"{preds.shape[0]} repeated predictions vs {labels.shape[0]} frame labels")

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
+from .ops import n_windows, resolve_clip_stride
 
 
 class _MilMagnitude(torch.autograd.Function):
@@ -249,10 +250,12 @@ def normalize_permute_u8(frames: torch.Tensor, mean: float = PIXEL_MEAN, std: fl
 
 
 def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
-                         std: float = PIXEL_STD) -> torch.Tensor:
+                         std: float = PIXEL_STD, clip_stride: Optional[int] = None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) of one video -> the backbone's input (n_clips * 10, C, frames_per_clip, crop, crop)
     fp32: TenCrop, float, normalise, LoopPad and the layout permutes of TenCropVideoFrameDataset / _extract
-    (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop."""
+    (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop.
+    `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = ops.n_windows(F, ...)."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
@@ -260,8 +263,29 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
     f, h, w, c = frames.shape
     if h < crop or w < crop:
         raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
-    n_clips = -(-f // frames_per_clip)
+    n_clips = n_windows(f, frames_per_clip, s)
     out = torch.empty((n_clips * 10, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_u8(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, crop, C_float(mean), C_float(std),
-                                                  stream()), "tencrop_normalize_u8")
+    check(_lib.load().advhip_tencrop_normalize_u8_strided(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, C_float(mean),
+                                                          C_float(std), stream()), "tencrop_normalize_u8")
+    return out
+
+
+def frame_scores(scores: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
+                 n_frames: Optional[int] = None) -> torch.Tensor:
+    """Per-window scores (n,) -> per-frame scores (n_frames,) on the device.  Window w covers frames [w * clip_stride,
+    w * clip_stride + frames_per_clip); a frame's score is the mean of the scores of the windows covering it (fp32, ascending
+    window order, one division by the count).  n_frames defaults to (n - 1) * clip_stride + frames_per_clip; clip_stride =
+    frames_per_clip gives np.repeat(scores, frames_per_clip) (src/runner.py:66-76) bit for bit."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    scores = scores.contiguous()
+    require_gpu(scores)
+    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() == 0:
+        raise ValueError(f"frame_scores: expected a non-empty fp32 (n_windows,) tensor, got {scores.dtype} {tuple(scores.shape)}")
+    n = scores.shape[0]
+    covered = (n - 1) * s + frames_per_clip
+    nf = covered if n_frames is None else int(n_frames)
+    if not 0 < nf <= covered:
+        raise ValueError(f"frame_scores: {nf} frames, but {n} windows of {frames_per_clip} at stride {s} cover {covered}")
+    out = torch.empty((nf,), device=scores.device, dtype=torch.float32)
+    check(_lib.load().advhip_frame_scores_f32(ptr(scores), ptr(out), n, frames_per_clip, s, nf, stream()), "frame_scores")
     return out

@@ -327,23 +327,44 @@ def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optiona
     return y
 
 
+def resolve_clip_stride(frames_per_clip: int, clip_stride: Optional[int]) -> int:
+    """The distance between window starts: None = frames_per_clip (the reference's back-to-back clips); 1 <= s <= frames_per_clip
+    (a larger stride would leave frames unseen)."""
+    s = frames_per_clip if clip_stride is None else int(clip_stride)
+    if not 1 <= s <= frames_per_clip:
+        raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip = {frames_per_clip}]")
+    return s
+
+
+def n_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> int:
+    """Windows of a video of `n_frames`: window w starts at frame w * clip_stride, and the last one is the first to reach the
+    video's end (it may be short: LoopPad).  clip_stride = frames_per_clip: (F - 1) // fpc + 1, the reference's clip count
+    (src/dataset.py)."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    if n_frames < 1:
+        raise ValueError(f"n_windows: {n_frames} frames")
+    return 1 + max(0, -(-(n_frames - frames_per_clip) // s))
+
+
 def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = 114.75,
-                      std: float = 57.375) -> torch.Tensor:
+                      std: float = 57.375, clip_stride: Optional[int] = None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) -> column-parity planes (count, C, frames_per_clip, crop, 2, crop/2 + 4) of crop-clips
     [first, first + count) (row = clip * 10 + crop): TenCrop, float, normalise, LoopPad and the layout permutes of
     TenCropVideoFrameDataset / _extract (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass,
-    written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's."""
+    written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's.  `clip_stride` (default
+    frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
     f, h, w, c = frames.shape
-    n = -(-f // frames_per_clip) * 10
+    n = n_windows(f, frames_per_clip, s) * 10
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_planes_u8(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, crop, first, count, C.c_float(mean),
-                                                         C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
+    check(_lib.load().advhip_tencrop_normalize_planes_u8_strided(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, first, count,
+                                                                 C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
     return xs
 
 
@@ -405,6 +426,21 @@ def with_slack(frames: torch.Tensor, slack: int = 4) -> torch.Tensor:
     return buf[: frames.numel()].view(frames.shape)
 
 
+def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> torch.Tensor:
+    """`frames` (F, H, W, C) on the device as WHOLE windows, (n - 1) * clip_stride + frames_per_clip frames: a short last window's
+    LoopPad frames (src/gtransforms.py:119-132: frame (n - 1) * s + t % len for t in [len, frames_per_clip)) appended behind
+    frame F - 1 -- a uint8 gather of < frames_per_clip frames; only the last window reads them.  Whole already: `frames`
+    itself, no copy."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    F = frames.shape[0]
+    start = (n_windows(F, frames_per_clip, s) - 1) * s
+    length = F - start
+    if length == frames_per_clip:
+        return frames
+    idx = torch.arange(length, frames_per_clip, device=frames.device) % length + start
+    return torch.cat([frames, frames[idx]], dim=0)
+
+
 def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN):
     key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean))
     cache = pc.__dict__.setdefault("_u8_tables", {})
@@ -446,19 +482,23 @@ def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tupl
 
 def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv", first: int, count: int, frames_per_clip: int = 16,
                                          crop: int = 224, out: Optional[torch.Tensor] = None, mean: float = PIXEL_MEAN,
-                                         std: float = PIXEL_STD) -> torch.Tensor:
+                                         std: float = PIXEL_STD, clip_stride: Optional[int] = None) -> torch.Tensor:
     """The stem (conv1 + bn1 + relu + maxpool1, src/i3d.py:303-306) of crop-clips [first, first + count) of a video given as
     resized uint8 frames (F, FH, FW, 3): row = clip * 10 + crop (TenCrop order).  TenCrop, float conversion and
-    (x - mean) / std happen in the conv's load stage (src/gtransforms.py:29-38,57-73, extract_features.py:83-89)."""
+    (x - mean) / std happen in the conv's load stage (src/gtransforms.py:29-38,57-73, extract_features.py:83-89).
+    `clip_stride` (default frames_per_clip): clip w = frames [w * clip_stride, w * clip_stride + frames_per_clip); the frames
+    are whole windows, F = (n - 1) * clip_stride + frames_per_clip (pad_windows_u8 appends a short last window's LoopPad frames)."""
     require_gpu(frames)
     require_gpu(out, contiguous=False)
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != pc.cin:
         raise ValueError(f"{pc.name}: expected uint8 (F,H,W,{pc.cin}) frames, got {frames.dtype} {tuple(frames.shape)}")
     F, FH, FW, _ = frames.shape
-    if F % frames_per_clip or FH < crop or FW < crop:
-        raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips of at least {crop}x{crop}")
-    if count <= 0 or first < 0 or first + count > F // frames_per_clip * 10:
-        raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {F // frames_per_clip * 10}")
+    if F < frames_per_clip or (F - frames_per_clip) % s or FH < crop or FW < crop:
+        raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips (stride {s}) of at least {crop}x{crop}")
+    n = ((F - frames_per_clip) // s + 1) * 10
+    if count <= 0 or first < 0 or first + count > n:
+        raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {n}")
     d = pc.desc(count, frames_per_clip, crop, crop, True, 0, 1)
     lib = _lib.load()
     tp, hp, wp = C.c_int32(), C.c_int32(), C.c_int32()
@@ -476,15 +516,15 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     if U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64:
         frames = with_slack(frames)
         ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
-        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(C.byref(d), ptr(frames), F, FH, FW, readable_bytes(frames), first, ptr(wt),
-                                                                       ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift), C.c_float(std),
-                                                                       ptr(y), batch_stride(y), ptr(ws), need, stream()),
+        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(C.byref(d), ptr(frames), F, FH, FW, s, readable_bytes(frames), first,
+                                                                               ptr(wt), ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
+                                                                               C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
               f"conv3d_u8_taps+pool233[{pc.name}]")
         return y
     ktab, corr = ensure_u8_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
-    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(C.byref(d), ptr(frames), F, FH, FW, first, ptr(pc.w_packed), ptr(ktab),
-                                                              ptr(corr), ptr(pc.scale), ptr(pc.shift),
-                                                              C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
+    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(C.byref(d), ptr(frames), F, FH, FW, s, first, ptr(pc.w_packed), ptr(ktab),
+                                                                      ptr(corr), ptr(pc.scale), ptr(pc.shift),
+                                                                      C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
           f"conv3d_u8+pool233[{pc.name}]")
     return y
 

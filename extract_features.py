@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
 tensors of the same layout; plug a real decoder in by passing (name, loader) pairs to
 `anomaly_detection_on_video_amd.extract.extract`.  With `--frame-size HxW` the source is synthetic DECODED uint8 frames of
 that size instead, resized (GroupResize(256)), ten-cropped and normalised on the device: `extract_frames(..., resize=256)`,
-the entry point for a real decoder's (name, n_frames, read_frames) triples.
+the entry point for a real decoder's (name, n_frames, read_frames) triples.  `--clip-stride N` (with `--frame-size`) extracts a
+16-frame window every N frames instead of every 16 (`<name>_i3d_s<N>.npy`); the windows overlap in place on the device.
 """
 import argparse
 import os
@@ -55,9 +56,13 @@ def parse_frame_size(text: str):
 
 
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
-         model_name: str = "i3d_8x8_r50", frame_size=None):
+         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
+    if clip_stride is not None and frame_size is None:
+        raise ValueError("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
+    if clip_stride is not None and not 1 <= clip_stride <= 16:
+        raise ValueError(f"--clip-stride {clip_stride} outside [1, 16]")
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
@@ -65,7 +70,7 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
     if frame_size is None:
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
-        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256)
+        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -80,5 +85,11 @@ if __name__ == "__main__":
                     help="the reference's default is i3d_8x8_r50 (parity-unpinned here); tushar-n-baseline = the pinned in-repo I3Res50")
     ap.add_argument("--frame-size", type=parse_frame_size, default=None, metavar="HxW",
                     help="feed synthetic decoded uint8 frames of this size, resized to 256 on the device (default: ten-cropped clip tensors)")
+    ap.add_argument("--clip-stride", type=int, default=None, metavar="N",
+                    help="with --frame-size: a 16-frame window every N frames (1..16; default 16, the reference's back-to-back clips)")
     a = ap.parse_args()
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size)
+    if a.clip_stride is not None and a.frame_size is None:
+        ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
+    if a.clip_stride is not None and not 1 <= a.clip_stride <= 16:
+        ap.error(f"--clip-stride {a.clip_stride} outside [1, 16]")
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride)

@@ -228,6 +228,11 @@ int advhip_conv3d_s2w_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const 
 int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                        int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
                                        float stdv, void* stream);
+/* ... for windows that start every `clip_stride` frames (advhip_tencrop_normalize_u8_strided below); the call above is
+ * clip_stride = frames_per_clip. */
+int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                               int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
+                                               int64_t count, float mean, float stdv, void* stream);
 
 /* --- the same stem, fed by resized uint8 frames (src/gtransforms.py:29-38,57-73 + extract_features.py:83-89 in the load stage)
  * frames: uint8 (F, FH, FW, Cin) -- what the decoder + GroupResize hand over -- F a whole number of clips of d->T frames.
@@ -251,6 +256,15 @@ int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d,
                                                     const float* scale, const float* shift, float stdv, float* y,
                                                     int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                     void* stream);
+/* Overlapping windows: clip w = frames [w * clip_stride, w * clip_stride + d->T), 1 <= clip_stride <= d->T, and the buffer holds
+ * whole windows, F = (n - 1) * clip_stride + d->T (the caller appends the LoopPad frames of a short last window).  The stride is
+ * one launch argument of the same kernel (the gather tables depend on the geometry only); clip_stride = d->T is the call above. */
+int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                            int32_t FW, int32_t clip_stride, int64_t first_crop_clip,
+                                                            const float* w_packed, const int32_t* ktab_u8, const float* corr,
+                                                            const float* scale, const float* shift, float stdv, float* y,
+                                                            int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                            void* stream);
 
 /* The same stem from WHOLE PIXELS: K runs tap-major (k' = tap * 3 + c), one 4-byte LDS-DMA per (tap, position) fetches the
  * pixel's three channel bytes at the pixel's byte address (a third of the gather instructions of the byte form for the same
@@ -266,6 +280,13 @@ int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(const advhip_conv3d_des
                                                          const float* scale, const float* shift, float stdv, float* y,
                                                          int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                          void* stream);
+/* ... over windows every `clip_stride` frames, as advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32. */
+int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                 int32_t FW, int32_t clip_stride, int64_t readable_bytes,
+                                                                 int64_t first_crop_clip, const float* w_taps, const int32_t* ktab_taps,
+                                                                 const float* corr, const float* scale, const float* shift, float stdv,
+                                                                 float* y, int64_t y_batch_stride, void* workspace,
+                                                                 int64_t workspace_bytes, void* stream);
 
 /* y = MaxPool3d(k=(2,1,1), s=(2,1,1))( act( conv3d(x, w) * scale + shift (+ residual) ) ) for a 1x1x1 stride-1 conv
  * (Cin a multiple of 32) in ONE launch: the last Bottleneck of layer1 followed by maxpool2 (src/i3d.py:111-121, 309).
@@ -618,6 +639,22 @@ int advhip_normalize_permute_u8(const uint8_t* x, float* y, int64_t N, int32_t T
  *   row = clip * 10 + crop index.  Only the resized uint8 frames cross PCIe: 1/23 of the fp32 ten-crop bytes. */
 int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                 int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream);
+/* Dense extraction: the same pass over overlapping windows.  Window w = frames [w * clip_stride, w * clip_stride +
+ * frames_per_clip), 1 <= clip_stride <= frames_per_clip; n = 1 + max(0, ceil((F - frames_per_clip) / clip_stride)) windows; only
+ * the last can be short (len = F - (n - 1) * clip_stride frames) and reads frame (n - 1) * clip_stride + t % len (LoopPad).
+ * y: fp32 (n * 10, C, fpc, crop, crop).  No frame is duplicated in memory: the stride is part of the index arithmetic.
+ * clip_stride = frames_per_clip is the call above. */
+int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
+                                        void* stream);
+
+/* Per-window scores (n_windows,) -> per-frame scores (n_frames,): window w covers frames [w * clip_stride, w * clip_stride +
+ * frames_per_clip); the score of a frame is the mean of the scores of the windows covering it (fp32, added in ascending window
+ * order, one division by their count).  0 < n_frames <= (n_windows - 1) * clip_stride + frames_per_clip.  clip_stride =
+ * frames_per_clip gives np.repeat(scores, frames_per_clip) (src/runner.py:66-76) bit for bit.  Every argument is checked before
+ * the launch. */
+int advhip_frame_scores_f32(const float* scores, float* out, int64_t n_windows, int32_t frames_per_clip, int32_t clip_stride,
+                            int64_t n_frames, void* stream);
 
 /* The resize in front of all that: GroupResize(256, Image.BILINEAR) (src/gtransforms.py:9-18, applied in src/dataset.py:175-183),
  * i.e. PIL Image.resize of every decoded frame, byte for byte (Pillow's 8-bit two-pass resampler).
