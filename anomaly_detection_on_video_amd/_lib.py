@@ -39,12 +39,20 @@ ALGO_DMA2_BASE = 160  # + tile id: LDS-DMA kernel, 2-deep ring (less LDS, more r
 DMA2_ALGOS = tuple(ALGO_DMA2_BASE + a for a in (1, 2, 3, 4, 6, 7, 8, 9))
 ALGO_TSPAN_128x64 = 192  # (kt,1,1) convs: 128x64 tile of 2 or 4 frames x flattened spatial positions
 ALGO_MIXED_128x64 = 200  # unsplit 1x1x1 stride-1 convs: 128x64 tiles + 64x64 tiles for the last, partial round of workgroups
+ALGO_TFOLD_BASE = 208  # + tile id of the 2-deep LDS-DMA family: (kt,1,1) convs on T <= kt//2 + 1 frames as the dense 1x1x1 conv (B, Cin*T, 1, H, W) -> Cout*T
+TFOLD_ALGOS = tuple(ALGO_TFOLD_BASE + a for a in (1, 2, 3, 4, 6, 7, 8, 9))
 ALGO_PERSIST_BASE = 224  # + tile id (2: 128x64, 3: 64x64) + 8 * (workgroups per CU - 1), 1..3: persistent wave-specialised kernel (opt-in), unsplit 1x1x1 stride-1 convs, K >= 64
 PERSIST_ALGOS = tuple(ALGO_PERSIST_BASE + t + 8 * (w - 1) for w in (1, 2, 3) for t in (2, 3))
 
 
+def is_tfold(algo: int) -> bool:
+    return ALGO_TFOLD_BASE <= algo < ALGO_TFOLD_BASE + 16
+
+
 def algo_tile(algo: int):
     """(BM, BN, BK) of an implicit-GEMM algorithm id."""
+    if is_tfold(algo):  # the folded launch is the 2-deep LDS-DMA kernel of the same tile id
+        algo += ALGO_DMA2_BASE - ALGO_TFOLD_BASE
     if algo in (ALGO_TSPAN_128x64, ALGO_MIXED_128x64):
         return (128, 64, 16)
     if ALGO_PERSIST_BASE <= algo < ALGO_PERSIST_BASE + 32:
@@ -114,6 +122,9 @@ SIGNATURES = {
     "advhip_conv3d_pack_weight_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
     "advhip_conv3d_pack_weight_bf16x3": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
     "advhip_conv3d_build_ktab": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),
+    "advhip_conv3d_tfold_desc": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
+    "advhip_conv3d_pack_weight_tfold_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
+    "advhip_conv3d_tfold_scale_shift_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "advhip_bn_fold_f32": (C.c_int, [_P, _P, _P, _P, C.c_float, _I, _P, _P, _P]),
     "advhip_conv3d_workspace_bytes": (_L, [C.POINTER(ConvDesc)]),
     "advhip_conv3d_bn_act_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),

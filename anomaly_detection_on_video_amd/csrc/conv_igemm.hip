@@ -3038,14 +3038,36 @@ struct SplitLayout {
   int64_t cnt_bytes, part_bytes;
   int64_t total() const { return cnt_bytes + part_bytes; }
 };
-static SplitLayout split_layout(const advhip_conv3d_desc* d, const Geometry& g, const Choice& c) {
+// `Mv`: rows of the launch's M index space -- g.M, or the virtually padded count (padded_rows below) that its m-tiles cover.
+static SplitLayout split_layout(const advhip_conv3d_desc* d, const Geometry& g, const Choice& c, long long Mv) {
   if (c.splits <= 1) return {0, 0};
   if (!reduces_in_kernel(c.algo)) return {0, (int64_t)c.splits * g.M * d->Cout * (int64_t)sizeof(float)};
   int BM, BN, BK;
   tile_of(c.algo, &BM, &BN, &BK);
-  const int64_t tiles = ((g.M + BM - 1) / BM) * (d->Cout / BN);
+  const int64_t tiles = ((Mv + BM - 1) / BM) * (d->Cout / BN);
   return {(tiles * 4 + 255) / 256 * 256, tiles * c.splits * BM * BN * (int64_t)sizeof(float)};
 }
+
+// every tap of every output position inside the input: no validity mask needed
+static bool is_nocheck(const advhip_conv3d_desc* d, const Geometry& g) {
+  return d->kt == 1 && d->kh == 1 && d->kw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 && g.K == g.Kpad;
+}
+
+// 1x1x1 stride-1 conv whose rows are not a multiple of 4 positions long (layer 4: 2 x 7 x 7 = 98; the folded temporal convs: 55 x 55,
+// 7 x 7), 2-deep LDS-DMA ring, plain epilogue: the launcher pads every sample's rows to a multiple of 4 IN THE M INDEX SPACE ONLY
+// (ConvArgs::MP), so that the A tile can go to LDS as 16-byte pieces.  Returns the padded M when the descriptor and the choice allow
+// that (the launcher also needs a 16-byte aligned x and none of the MGFN epilogue operands), 0 otherwise.  Split launches of these
+// families reduce inside the kernel, tile by tile, so their partial-tile workspace is sized from the padded M.
+static long long padded_rows(const advhip_conv3d_desc* d, const Geometry& g, const Choice& c) {
+  const long long thw = (long long)g.To * g.Ho * g.Wo;
+  if (!(is_nocheck(d, g) && d->st == 1 && d->sh == 1 && d->sw == 1 && thw % 4 != 0)) return 0;
+  if (!((c.algo > ADVHIP_ALGO_DMA2_BASE && c.algo <= ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_256x64) || c.algo == ADVHIP_ALGO_MIXED_128x64 || is_persist(c.algo))) return 0;
+  const long long Mv = (long long)d->B * ((thw + 3) / 4 * 4);
+  return Mv < (1ll << 31) ? Mv : 0;
+}
+
+// ADVHIP_ALGO_TFOLD_BASE + tile id: the launch is the folded descriptor's (conv_tfold.hip: advhip_conv3d_tfold_desc)
+static bool is_tfold(int algo) { return algo >= ADVHIP_ALGO_TFOLD_BASE && algo < ADVHIP_ALGO_TFOLD_BASE + 16; }
 }  // namespace advhip
 
 namespace advhip {
@@ -3079,13 +3101,19 @@ static void launch_dma2(bool nocheck, bool s16, dim3 grid, hipStream_t st, const
 
 extern "C" int64_t advhip_conv3d_workspace_bytes(const advhip_conv3d_desc* d) {
   if (validate(d)) return -1;
+  if (is_tfold(d->algo)) {
+    advhip_conv3d_desc f;
+    return advhip_conv3d_tfold_desc(d, &f) ? -1 : advhip_conv3d_workspace_bytes(&f);
+  }
   const Geometry g = geometry(d);
   const Choice c = choose(d, g.M, g.Kpad);
   if (!instantiated(c.algo)) {
     set_error("conv3d: algo %d is not instantiated in this library", c.algo);
     return -1;
   }
-  return split_layout(d, g, c).total();
+  // (whether the rows are padded also depends on the pointers of the launch: the larger of the two sizes)
+  const long long Mp = padded_rows(d, g, c);
+  return split_layout(d, g, c, Mp > g.M ? Mp : g.M).total();
 }
 
 extern "C" int advhip_conv3d_bn_act_f32(const advhip_conv3d_desc* d, const float* x, const float* w_packed,
@@ -3110,6 +3138,16 @@ extern "C" int advhip_conv3d_bn_act_ex_f32(const advhip_conv3d_desc* d, const fl
                                            const advhip_conv3d_epilogue* ep, void* workspace, int64_t workspace_bytes,
                                            void* stream) {
   if (int rc = validate(d)) return rc;
+  if (is_tfold(d->algo)) {
+    // the temporal fold: the same memory as a dense 1x1x1 conv (B, Cin*T, 1, H, W) -> Cout*T; w_packed / ktab / scale / shift are
+    // the folded operands, everything else passes through
+    advhip_conv3d_desc f;
+    if (int rc = advhip_conv3d_tfold_desc(d, &f)) return rc;
+    ADVHIP_REQUIRE(!ep || (ep->ln_u == nullptr && ep->avgpool_out == nullptr),
+                   "conv3d: ADVHIP_ALGO_TFOLD takes neither the LayerNorm fold nor avgpool_out (both are per position of the unfolded conv)");
+    return advhip_conv3d_bn_act_ex_f32(&f, x, x_batch_stride, w_packed, ktab, scale, shift, residual, y, y_batch_stride, ep, workspace,
+                                       workspace_bytes, stream);
+  }
   float* y_preact = ep ? ep->y_preact : nullptr;
   const float* dact_z = ep ? ep->dact_z : nullptr;
   float* avg_out = ep ? ep->avgpool_out : nullptr;
@@ -3192,7 +3230,20 @@ extern "C" int advhip_conv3d_bn_act_ex_f32(const advhip_conv3d_desc* d, const fl
   ADVHIP_REQUIRE(c.splits >= 1 && c.splits <= nk && c.splits <= 64, "conv3d: bad split count %d (k-tiles %d)", c.splits, nk);
   a.part = nullptr; a.cnt = nullptr; a.part_bytes = 0;
   a.mix_big = a.mix_small = a.mix_mbase = 0;
-  const SplitLayout lay = split_layout(d, g, c);
+  const bool nocheck = is_nocheck(d, g);
+  // rows padded to a multiple of 4 in the M index space (padded_rows): a group of 4 positions never straddles two samples; the last
+  // group of a row reads on into the next channel's row -- or past the tensor, where the buffer range check returns zeros -- for
+  // positions nobody stores.  Split launches too: the partial tiles and the arrival counters are per tile of the padded M.
+  long long Mv = M;
+  bool a16pad = false;
+  if (const long long Mp = padded_rows(d, g, c); Mp > 0 && ((uintptr_t)x & 15) == 0 && !ln && y_preact == nullptr && dact_z == nullptr) {
+    a.MP = (a.THWo + 3) / 4 * 4;
+    Mv = Mp;
+    a16pad = true;
+    a.M = (int)Mv;
+    a.dTHWo = FastDiv::make((unsigned)a.MP);
+  }
+  const SplitLayout lay = split_layout(d, g, c, Mv);
   if (c.splits > 1) {
     ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= lay.total(),
                    "conv3d: split-K needs a %lld-byte workspace (got %lld); query advhip_conv3d_workspace_bytes",
@@ -3205,27 +3256,6 @@ extern "C" int advhip_conv3d_bn_act_ex_f32(const advhip_conv3d_desc* d, const fl
       a.part_bytes = (unsigned)lay.part_bytes;
     } else {
       a.y = reinterpret_cast<float*>(workspace);
-    }
-  }
-  // every tap of every output position inside the input: no validity mask needed
-  const bool nocheck = d->kt == 1 && d->kh == 1 && d->kw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 && g.K == g.Kpad;
-  // 1x1x1 stride-1 conv whose rows are not a multiple of 4 positions long (layer 4: 2 x 7 x 7 = 98), 2-deep LDS-DMA ring, unsplit,
-  // plain epilogue: pad every sample's rows to a multiple of 4 IN THE M INDEX SPACE ONLY (ConvArgs::MP), so that the A tile
-  // can go to LDS as 16-byte pieces (a group of 4 positions never straddles two samples; the last group of a row reads
-  // on into the next channel's row -- or past the tensor, where the buffer range check returns zeros -- for positions nobody stores)
-  long long Mv = M;
-  bool a16pad = false;
-  if (nocheck && d->st == 1 && d->sh == 1 && d->sw == 1 && a.THW % 4 != 0 && ((uintptr_t)x & 15) == 0 && c.splits == 1 &&
-      ((c.algo > ADVHIP_ALGO_DMA2_BASE && c.algo <= ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_256x64) || c.algo == ADVHIP_ALGO_MIXED_128x64 || is_persist(c.algo)) && !ln && y_preact == nullptr && dact_z == nullptr) {
-    a.MP = (a.THWo + 3) / 4 * 4;
-    Mv = (long long)d->B * a.MP;
-    if (Mv < (1ll << 31)) {
-      a16pad = true;
-      a.M = (int)Mv;
-      a.dTHWo = FastDiv::make((unsigned)a.MP);
-    } else {
-      a.MP = a.THWo;
-      Mv = M;
     }
   }
   if (avg_out != nullptr) {  // (the same virtual padding, to the whole tile: the last groups of a sample read on into rows nobody adds up)

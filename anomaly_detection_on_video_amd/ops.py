@@ -48,6 +48,10 @@ class PackedConv:
     splits: int = 0  # 0 = library heuristic
     weight: Optional[torch.Tensor] = None   # the torch-layout fp32 weights (a reference, not a copy)
     w_split: Optional[torch.Tensor] = None  # bf16 hi/lo images for the opt-in split-bf16 kernels, packed on first use
+    # operands of the temporal fold (ADVHIP_ALGO_TFOLD_BASE), built on first use: T -> (w_folded [Kpad', Cout*T], scale, shift of
+    # Cout*T entries); (T,H,W) -> the folded 1x1x1 conv's gather table
+    tfold_w: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = field(default_factory=dict)
+    tfold_ktabs: Dict[Tuple[int, int, int], torch.Tensor] = field(default_factory=dict)
     # (B,T,H,W) -> (algo, splits) resolved from the measured table (tuned.py)
     choices: Dict[Tuple[int, int, int, int], Tuple[int, int]] = field(default_factory=dict)
 
@@ -109,10 +113,46 @@ def split_weight(pc: PackedConv) -> torch.Tensor:
     return pc.w_split
 
 
+def tfold_desc(d: ConvDesc) -> ConvDesc:
+    """The dense 1x1x1 conv (B, Cin*T, 1, H, W) -> Cout*T that the (kt,1,1) conv `d` on T <= kt//2 + 1 frames is
+    (include/advhip.h: advhip_conv3d_tfold_desc); raises HipExtensionError where the fold does not apply."""
+    f = ConvDesc()
+    check(_lib.load().advhip_conv3d_tfold_desc(C.byref(d), C.byref(f)), "conv3d_tfold_desc")
+    return f
+
+
+def tfold_operands(pc: PackedConv, thw: Tuple[int, int, int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(w_folded, ktab, scale, shift) of `pc` for the ADVHIP_ALGO_TFOLD_* launch on (T,H,W) inputs, built on the current
+    stream on first use (the weights and the BN pair once per T, the table once per (T,H,W))."""
+    T = thw[0]
+    d = pc.desc(1, *thw, relu=False, algo=0, splits=1)
+    ops_t = pc.tfold_w.get(T)
+    ktab = pc.tfold_ktabs.get(thw)
+    if ops_t is not None and ktab is not None:
+        return ops_t[0], ktab, ops_t[1], ops_t[2]
+    if pc.weight is None:
+        raise _lib.HipExtensionError(f"{pc.name}: the temporal fold packs its operand from the torch-layout weights, which this conv does not keep")
+    f = tfold_desc(d)
+    lib = _lib.load()
+    dev = pc.w_packed.device
+    if ops_t is None:
+        wf = torch.empty((_packed_rows(f), f.Cout), device=dev, dtype=torch.float32)
+        check(lib.advhip_conv3d_pack_weight_tfold_f32(C.byref(d), ptr(pc.weight), ptr(wf), stream()), f"pack_weight_tfold[{pc.name}]")
+        sc, sh = torch.empty((f.Cout,), device=dev, dtype=torch.float32), torch.empty((f.Cout,), device=dev, dtype=torch.float32)
+        check(lib.advhip_conv3d_tfold_scale_shift_f32(C.byref(d), ptr(pc.scale), ptr(pc.shift), ptr(sc), ptr(sh), stream()), f"tfold_scale_shift[{pc.name}]")
+        ops_t = pc.tfold_w[T] = (wf, sc, sh)
+    if ktab is None:
+        ktab = torch.empty((_packed_rows(f) * 6,), device=dev, dtype=torch.int32)
+        check(lib.advhip_conv3d_build_ktab(C.byref(f), ptr(ktab), stream()), f"build_ktab_tfold[{pc.name}]")
+        pc.tfold_ktabs[thw] = ktab
+    return ops_t[0], ktab, ops_t[1], ops_t[2]
+
+
 def ensure_ktab(pc: PackedConv, thw: Tuple[int, int, int], batch: Optional[int] = None) -> torch.Tensor:
     """The gather table of `pc` for input dims (T,H,W), built on the current stream on first use.  With `batch`, also
-    every other lazily built operand the launch for (batch, T, H, W) will read -- today the bf16 hi/lo weight images
-    of the opt-in split-bf16 kernels -- so that a caller about to fork streams has ALL of them behind one event."""
+    every other lazily built operand the launch for (batch, T, H, W) will read -- the bf16 hi/lo weight images of the
+    opt-in split-bf16 kernels, the folded operands of the temporal fold -- so that a caller about to fork streams has
+    ALL of them behind one event."""
     ktab = pc.ktabs.get(thw)
     if ktab is None:
         ktab = pc.ktabs[thw] = _build_ktab(pc, thw)
@@ -120,6 +160,8 @@ def ensure_ktab(pc: PackedConv, thw: Tuple[int, int, int], batch: Optional[int] 
         d = pc.desc(batch, *thw, relu=False)
         if _lib.ALGO_BF16X3_BASE <= d.algo < _lib.ALGO_DMA2_BASE:
             split_weight(pc)
+        if _lib.is_tfold(d.algo):
+            tfold_operands(pc, thw)
     return ktab
 
 
@@ -240,15 +282,17 @@ def conv3d_bn_act(x: torch.Tensor, pc: PackedConv, relu: bool = True, residual: 
     if need < 0:
         check(int(need), f"conv3d_workspace_bytes[{pc.name}]")
     ws = workspace(x.device, need)
-    w = pc.w_packed
+    w, scale, shift = pc.w_packed, pc.scale, pc.shift
     if _lib.ALGO_BF16X3_BASE <= d.algo < _lib.ALGO_DMA2_BASE:
         w = split_weight(pc)
+    if _lib.is_tfold(d.algo):  # the same memory as a dense 1x1x1 conv over Cin*T channels: only the operands differ
+        w, ktab, scale, shift = tfold_operands(pc, (T, H, W))
     xbs, ybs = batch_stride(x), batch_stride(y)  # (x and / or y may be a channel slice of a wider tensor)
     ep = None
     if need > 0:  # split-K: this stream's self-resetting arrival counters instead of a memset ahead of every launch
         cnt = splitk_counters(x.device)
         ep = C.byref(_lib.ConvEpilogue(None, None, None, None, None, ptr(cnt), cnt.numel() * 4))
-    check(lib.advhip_conv3d_bn_act_ex_f32(C.byref(d), ptr(x), xbs, ptr(w), ptr(ktab), ptr(pc.scale), ptr(pc.shift), ptr(residual), ptr(y), ybs,
+    check(lib.advhip_conv3d_bn_act_ex_f32(C.byref(d), ptr(x), xbs, ptr(w), ptr(ktab), ptr(scale), ptr(shift), ptr(residual), ptr(y), ybs,
                                           ep, ptr(ws), need, stream()), f"conv3d[{pc.name}]")
     return y
 

@@ -66,6 +66,17 @@ extern "C" {
  * unit): every workgroup of the last, partial round is then a short one.  Same K order per output as the plain tiles: bit-identical
  * results.  Launches below one round / on a round boundary are the plain 128x64 launch. */
 #define ADVHIP_ALGO_MIXED_128x64 200
+/* + tile id 1..4, 6..9 (those of ADVHIP_ALGO_DMA2_BASE): the TEMPORAL FOLD.  A (kt,1,1) stride-1 conv with padding pt = kt/2 on
+ * T <= pt + 1 frames joins every (output frame t, input frame ti) pair by exactly one tap, dt = ti - t + pt, so it IS the dense
+ * 1x1x1 conv (B, Cin*T, 1, H, W) -> Cout*T on the same memory (channel ci*T + ti in, n*T + t out) with the weights
+ * W'[n*T + t][ci*T + ti] = W[n][ci][ti - t + pt]: T*T MACs per position instead of kt*T, none of them on the zero padding, the
+ * input read once instead of once per tap, no gather mask.  The launch is ADVHIP_ALGO_DMA2_BASE + tile id on the descriptor of
+ * advhip_conv3d_tfold_desc with the same `splits`; x, y, residual and the batch strides are the caller's own (a channel slice of
+ * a wider buffer is still dense within a sample under the folded view); w_packed, ktab, scale and shift are the FOLDED operands
+ * (advhip_conv3d_pack_weight_tfold_f32, advhip_conv3d_build_ktab on the folded descriptor, advhip_conv3d_tfold_scale_shift_f32).
+ * Same non-zero terms per output in the same order (ci major, dt ascending).  No LayerNorm fold, no avgpool_out.  Never chosen
+ * by ADVHIP_ALGO_AUTO. */
+#define ADVHIP_ALGO_TFOLD_BASE 208
 /* + tile id (ADVHIP_ALGO_IGEMM_128x64 or _64x64) + 8 * (W - 1), W = 1..3 workgroups per compute unit: a PERSISTENT, wave-specialised
  * kernel for unsplit 1x1x1 stride-1 convs on 16-byte aligned rows with K >= 64 (the `conv3` + residual launches,
  * src/i3d.py:85-89, 108-121): eight-wave workgroups that stay for the whole launch and walk a share of the output tiles; four waves
@@ -181,6 +192,21 @@ int advhip_conv3d_bn_act_ex_f32(const advhip_conv3d_desc* d, const float* x, int
                                 const int32_t* ktab, const float* scale, const float* shift, const float* residual, float* y,
                                 int64_t y_batch_stride, const advhip_conv3d_epilogue* ep, void* workspace,
                                 int64_t workspace_bytes, void* stream);
+
+/* --- the temporal fold (ADVHIP_ALGO_TFOLD_BASE) ---------------------------------------------------------------------------------
+ * advhip_conv3d_tfold_desc: the one statement of the rule.  ADVHIP_EINVAL (the message names the rule broken) unless d is a
+ * (kt,1,1) conv, strides 1, ph = pw = 0, 2 pt + 1 = kt, T <= pt + 1 (the Bottleneck conv1s with a temporal kernel of layers
+ * 2-4, src/i3d.py:71-75, 144-146, whose inputs have T = 2 after maxpool2); otherwise *folded = d with Cin*T input channels,
+ * Cout*T output channels, T = 1, kt = 1, pt = 0, and algo ADVHIP_ALGO_DMA2_BASE + tile for a TFOLD id (any other algo value is
+ * copied).  Host arithmetic only.  Callers size and build w_packed rows and the gather table from `folded`
+ * (advhip_conv3d_packed_rows / advhip_conv3d_build_ktab).
+ * advhip_conv3d_pack_weight_tfold_f32: torch-layout weights w[Cout][Cin][kt][1][1] of d -> the folded conv's packed operand
+ * w_folded[Kpad'][Cout*T], row ci*T + ti, column n*T + t = w[n][ci][ti - t + pt], zero rows above Cin*T.  Once per (weights, T).
+ * advhip_conv3d_tfold_scale_shift_f32: scale_folded[n*T + t] = scale[n], likewise shift (Cout*T entries each). */
+int advhip_conv3d_tfold_desc(const advhip_conv3d_desc* d, advhip_conv3d_desc* folded);
+int advhip_conv3d_pack_weight_tfold_f32(const advhip_conv3d_desc* d, const float* w, float* w_folded, void* stream);
+int advhip_conv3d_tfold_scale_shift_f32(const advhip_conv3d_desc* d, const float* scale, const float* shift, float* scale_folded,
+                                        float* shift_folded, void* stream);
 
 /* mu[n] = mean over channels of x[c, n], rs[n] = 1 / (sqrt(biased variance over channels) + eps) for a (C, N) activation:
  * the statistics of MGFNLayerNorm (modeling_mgfn.py:43-46: division by std + eps, not sqrt(var + eps)). */

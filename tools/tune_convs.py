@@ -39,6 +39,8 @@ def main():
     ap.add_argument("--quick", action="store_true", help="skip the generic-gather variants")
     ap.add_argument("--algos", default="", help="comma-separated algo ids: time only these (e.g. 162,169 for a tile A/B)")
     ap.add_argument("--max-splits", type=int, default=16)
+    ap.add_argument("--fold-only", action="store_true",
+                    help="time only the convs the temporal fold applies to (the fold ids against the table's current entry); every other entry stays as it is")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     os.environ["ADV_NO_TUNED"] = "1"
@@ -64,6 +66,14 @@ def main():
         y = ops.conv3d_bn_act(xin, pc, relu=relu, residual=res, algo=3, splits=1)
         macs = y.numel() * pc.cin * pc.kernel[0] * pc.kernel[1] * pc.kernel[2]
         tot_flop += 2 * macs
+        try:  # the temporal fold (ADVHIP_ALGO_TFOLD_*): its launch is a 1x1x1 conv over Cin*T -> Cout*T channels on H*W positions
+            fd = ops.tfold_desc(pc.desc(B, T, H, W, relu, 0, 1)) if pc.kernel[0] > 1 else None
+        except _lib.HipExtensionError:
+            fd = None
+        if args.fold_only and fd is None:
+            a, sp = table.get(key, (3, 1))
+            total_best += time_fn(lambda: ops.conv3d_bn_act(xin, pc, relu=relu, residual=res, algo=a, splits=sp, out=y), args.reps)
+            return y
         if key in seen:
             best = seen[key]
         else:
@@ -71,19 +81,32 @@ def main():
             cands = []
             taps = pc.kernel[0] * pc.kernel[1] * pc.kernel[2]
             pool = ((3,) if args.quick else _lib.IGEMM_ALGOS) + ((35,) if args.quick else _lib.FAST_ALGOS) + _lib.DMA_ALGOS + _lib.DMA4_ALGOS + _lib.DMA2_ALGOS
+            if fd is not None:
+                pool = pool + _lib.TFOLD_ALGOS
             if args.algos:
                 pool = tuple(int(a) for a in args.algos.split(","))
+            if args.fold_only:
+                pool = _lib.TFOLD_ALGOS
+                if key in table:
+                    cands.append((int(table[key][0]), int(table[key][1])))
             for algo in pool:
                 bm, bn, bk = _lib.algo_tile(algo)
-                if pc.cout % bn:
+                if _lib.is_tfold(algo):  # tiles and k-tiles of the FOLDED GEMM: B*H*W rows, Cout*T columns, K = Cin*T
+                    if fd is None:
+                        continue
+                    n_cols, k_rows = fd.Cout, -(-fd.Cin // 32) * 32
+                else:
+                    n_cols, k_rows = pc.cout, kpad
+                if n_cols % bn:
                     continue
-                tiles = -(-(y.numel() // pc.cout) // bm) * (pc.cout // bn)
+                tiles = -(-(y.numel() // n_cols) // bm) * (n_cols // bn)
                 for sp in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16):
                     if sp > args.max_splits:
                         continue
-                    if sp > 1 and (tiles * sp > 4096 or kpad // bk < 2 * sp):
+                    if sp > 1 and (tiles * sp > 4096 or k_rows // bk < 2 * sp):
                         continue
-                    cands.append((algo, sp))
+                    if (algo, sp) not in cands:
+                        cands.append((algo, sp))
             res_t = []
             for algo, sp in cands:
                 try:
