@@ -34,6 +34,24 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+// A crop subset of TenCrop as the kernels take it: `ncrops` 4-bit indices, entry j in bits [4 j, 4 j + 4) (row clip * ncrops + j
+// holds crop entry j).  All ten in order = the identity set.
+constexpr unsigned long long TENCROP_ALL = 0x9876543210ull;
+
+// null = well formed: 1 <= ncrops <= 10, every index < 10, strictly ascending (TenCrop's own order), unused nibbles zero
+inline const char* crops_packed_error(int ncrops, unsigned long long packed) {
+  if (ncrops < 1 || ncrops > 10) return "ncrops outside [1, 10]";
+  int prev = -1;
+  for (int j = 0; j < ncrops; ++j) {
+    const int c = (int)((packed >> (4 * j)) & 15);
+    if (c > 9) return "crop index above 9";
+    if (c <= prev) return "crop indices not strictly ascending";
+    prev = c;
+  }
+  if (packed >> (4 * ncrops)) return "bits set above the last crop index";
+  return nullptr;
+}
+
 }  // namespace advhip
 
 #define ADVHIP_REQUIRE(cond, ...)        \

@@ -128,6 +128,10 @@ struct ConvArgs {
   // T / H / W above are the clip-local extents (frames per clip, crop size) the tap masks are taken against
   int u8_first, u8_FH, u8_FW;
   int u8_cstride;           // frames between the starts of consecutive clips: T (back to back) or less (overlapping windows)
+  // crop subset: crop-clip g = (clip g / u8_nc, crop (u8_crops >> 4 (g % u8_nc)) & 15); all ten in order = {10, TENCROP_ALL}
+  int u8_nc;
+  FastDiv u8_dnc;
+  unsigned long long u8_crops;
   int u8_ctop, u8_cleft;    // top / left of the centre crop (round-half-to-even, as torchvision)
   float in_std;             // conv of (pixel - mean) / in_std: the mean through pad_corr, 1 / in_std through the BN scale
   const int2* ktab_u8;      // [2][Kpad] {byte offset, tap bits}: as stored, and mirrored along w
@@ -1312,14 +1316,19 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     pow_ = bk_w * BRICK_W + ml % BRICK_W;
     pvalid = pot < a.To && poh < a.Ho && pow_ < a.Wo;
   }
-  int u8_flip = 0;
+  int u8_flip = 0, u8_clip = 0, u8_crop = 0;
+  if constexpr (U8) {  // the brick's (clip, crop): one per workgroup, kept scalar
+    const int bg = __builtin_amdgcn_readfirstlane(a.u8_first + bk_b);
+    u8_clip = (int)a.u8_dnc.div((unsigned)bg);
+    u8_crop = (int)(a.u8_crops >> (4 * (bg - u8_clip * a.u8_nc))) & 15;
+    u8_flip = u8_crop >= 5;
+  }
   if (pvalid) {
     const int it0 = pot * a.st - a.pt, ih0 = poh * a.sh - a.ph, iw0 = pow_ * a.sw - a.pw;
     if constexpr (U8) {
       // byte offset of the window origin in the frames tensor (F, FH, FW, C): the crop's corner, then the clip-local
       // coordinates; a mirrored crop walks its source columns backwards (its table holds (kw-1-dw) * C, see build_ktab_u8)
-      const int bg = a.u8_first + bk_b, clip = bg / 10, crop = bg - clip * 10, j = crop >= 5 ? crop - 5 : crop;
-      u8_flip = crop >= 5;
+      const int clip = u8_clip, j = u8_flip ? u8_crop - 5 : u8_crop;
       const int top = j == 4 ? a.u8_ctop : ((j >> 1) ? a.u8_FH - a.H : 0), left = j == 4 ? a.u8_cleft : ((j & 1) ? a.u8_FW - a.W : 0);
       const int FWC = a.u8_FW * a.Cin, FHWC = a.u8_FH * FWC;
       // (mirrored crops are five_crop(hflip(frame)): column c of such a crop is source column FW - 1 - (left + c))
@@ -1384,7 +1393,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x) - a.pad_off, 0, a.x_bytes, 0x00020000);
   const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, a.w_bytes, 0x00020000);
   // (the brick's crop, hence the table, is the same for the whole workgroup: keep the pointer scalar for the s_loads)
-  const int2* __restrict__ ktab2 = U8 ? a.ktab_u8 + (size_t)__builtin_amdgcn_readfirstlane((bk_b + a.u8_first) % 10 >= 5 ? a.Kpad : 0)
+  const int2* __restrict__ ktab2 = U8 ? a.ktab_u8 + (size_t)__builtin_amdgcn_readfirstlane(u8_flip ? a.Kpad : 0)
                                       : reinterpret_cast<const int2*>(a.ktab + a.Kpad);
   constexpr int A_BYTES = U8 ? 1 : 4;  // uint8 input: `buffer_load_ubyte ... lds` puts the zero-extended byte in the lane's LDS dword
   // B rows: a wave's 64 lanes x 16 B cover RPW consecutive k-rows of the [BK][BN] tile
@@ -2051,7 +2060,9 @@ void stem_u8_tap_kernel(const ConvArgs a) {
   const int bk_h = (int)a.dNbw.div((unsigned)r2);
   const int bk_w = r2 - bk_h * a.nbw;
   const int pot = bk_t * 2 + ml / (BRICK_H * BRICK_W), poh = bk_h * BRICK_H + (ml / BRICK_W) % BRICK_H, pow_ = bk_w * BRICK_W + ml % BRICK_W;
-  const int bg = a.u8_first + bk_b, clip = bg / 10, crop = bg - clip * 10, j5 = crop >= 5 ? crop - 5 : crop;
+  // the brick's (clip, crop) of the crop subset: one per workgroup, kept scalar
+  const int bg = __builtin_amdgcn_readfirstlane(a.u8_first + bk_b), clip = (int)a.u8_dnc.div((unsigned)bg);
+  const int crop = (int)(a.u8_crops >> (4 * (bg - clip * a.u8_nc))) & 15, j5 = crop >= 5 ? crop - 5 : crop;
   const int flip = __builtin_amdgcn_readfirstlane(crop >= 5);
   unsigned vbase = OOB, vmask = 0;
   if (pot < a.To && poh < a.Ho && pow_ < a.Wo) {
@@ -3684,15 +3695,28 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const adv
                                                                        const float* scale, const float* shift, float stdv, float* y,
                                                                        int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                        void* stream) {
+  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(d, frames, F, FH, FW, clip_stride, 10, TENCROP_ALL, first_crop_clip, w_packed,
+                                                               ktab_u8, corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes,
+                                                               stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                     int32_t FW, int32_t clip_stride, int32_t ncrops, uint64_t crops_packed,
+                                                                     int64_t first_crop_clip, const float* w_packed, const int32_t* ktab_u8,
+                                                                     const float* corr, const float* scale, const float* shift, float stdv,
+                                                                     float* y, int64_t y_batch_stride, void* workspace,
+                                                                     int64_t workspace_bytes, void* stream) {
   if (int rc = validate(d)) return rc;
+  if (const char* why = crops_packed_error(ncrops, crops_packed))
+    ADVHIP_REQUIRE(false, "conv3d u8+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && w_packed && ktab_u8 && corr && scale && shift && y, "conv3d u8+pool233: null pointer");
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8+pool233: padding not smaller than the kernel");
   ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8+pool233: std must be non-zero");
   int64_t n_clips = 0;
   if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, &n_clips)) return rc;
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * 10,
-                 "conv3d u8+pool233: crop-clips [%lld, %lld) outside the %lld clips x 10 crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)n_clips);
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
+                 "conv3d u8+pool233: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", (long long)first_crop_clip,
+                 (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
   const Geometry g = geometry(d);
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
@@ -3705,6 +3729,7 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const adv
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_packed, nullptr, scale, shift, false)) return rc;
   a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
+  a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
   // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
@@ -3786,7 +3811,21 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(cons
                                                                             const int32_t* ktab_taps, const float* corr, const float* scale,
                                                                             const float* shift, float stdv, float* y, int64_t y_batch_stride,
                                                                             void* workspace, int64_t workspace_bytes, void* stream) {
+  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(d, frames, F, FH, FW, clip_stride, 10, TENCROP_ALL, readable_bytes,
+                                                                    first_crop_clip, w_taps, ktab_taps, corr, scale, shift, stdv, y,
+                                                                    y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                          int32_t FW, int32_t clip_stride, int32_t ncrops,
+                                                                          uint64_t crops_packed, int64_t readable_bytes, int64_t first_crop_clip,
+                                                                          const float* w_taps, const int32_t* ktab_taps, const float* corr,
+                                                                          const float* scale, const float* shift, float stdv, float* y,
+                                                                          int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                                          void* stream) {
   if (int rc = validate(d)) return rc;
+  if (const char* why = crops_packed_error(ncrops, crops_packed))
+    ADVHIP_REQUIRE(false, "conv3d u8 taps+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && w_taps && ktab_taps && corr && scale && shift && y, "conv3d u8 taps+pool233: null pointer");
   ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps+pool233: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8 taps+pool233: padding not smaller than the kernel");
@@ -3796,9 +3835,9 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(cons
   const int64_t fbytes = F * FH * FW * 3;
   ADVHIP_REQUIRE(readable_bytes >= fbytes + 1, "conv3d u8 taps+pool233: the frames allocation must extend one byte past the last pixel "
                  "(pixels are fetched as 4-byte pieces): %lld readable, %lld needed", (long long)readable_bytes, (long long)fbytes + 1);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * 10,
-                 "conv3d u8 taps+pool233: crop-clips [%lld, %lld) outside the %lld clips x 10 crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)n_clips);
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
+                 "conv3d u8 taps+pool233: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", (long long)first_crop_clip,
+                 (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
   const Geometry g = geometry(d);
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8 taps+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
@@ -3811,6 +3850,7 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(cons
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_taps, nullptr, scale, shift, false)) return rc;
   a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
+  a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
   a.in_std = stdv;

@@ -86,13 +86,15 @@ __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float
 // caller); crops 5..9 = the same five windows of the horizontally flipped frame: pixel (y, x) = frame[top + y][W - 1 - (left + x)].
 // Frame t of clip c = frames[c * cstride + t % len_c], len_c = min(fpc, F - c * cstride) (LoopPad: a short last clip repeats
 // itself); cstride = the distance between clip starts, fpc for the reference's back-to-back clips, less for overlapping windows.
+// A crop SUBSET (nc of the ten, ascending, 4-bit indices packed into `crops`): output row clip * nc + j holds crop
+// (crops >> 4 j) & 15 of that clip -- the same arithmetic per pixel, so the row is the ten-crop pass's row clip * 10 + that crop.
 // One wave per output row (clip, crop, c, t, y): the row decode (five divisions) happens once per 224 outputs, the lanes run
 // along x with 16-byte stores (the first form decoded every float4 separately and indexed a by-value crop table: 165 us for
 // 40 crop-clips, VALU-bound at 2.3 TB/s).
 template <int VW>
 __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int F, int H, int W,
                                                                    int C, int fpc, int cstride, int cs, int ctop, int cleft, float mean,
-                                                                   float stdv, long long rows) {
+                                                                   float stdv, long long rows, int nc, unsigned long long crops) {
   const int lane = threadIdx.x & 63;
   const int csv = cs / VW;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
@@ -103,8 +105,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
     r /= fpc;
     const int c = (int)(r % C);
     r /= C;
-    const int crop = (int)(r % 10);
-    const int clip = (int)(r / 10);
+    const int clip = (int)(r / nc);
+    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;  // (the subset's j-th crop: a nibble of the argument)
     const int len = min(fpc, F - clip * cstride);
     const int f = clip * cstride + t % len;
     const int j = crop % 5;
@@ -130,7 +132,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
 // padding columns.  One wave per (row, both planes); the arithmetic per pixel is the pass above's, so the values are its values.
 __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, int F, int H,
                                                                           int W, int C, int fpc, int cstride, int cs, int ctop, int cleft,
-                                                                          float mean, float stdv, long long first, long long rows, int WP) {
+                                                                          float mean, float stdv, long long first, long long rows, int WP,
+                                                                          int nc, unsigned long long crops) {
   const int lane = threadIdx.x & 63;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
     long long r = r0;  // (clip-crop - first, c, t, y)
@@ -140,8 +143,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const 
     r /= fpc;
     const int c = (int)(r % C);
     r = r / C + first;
-    const int crop = (int)(r % 10);
-    const int clip = (int)(r / 10);
+    const int clip = (int)(r / nc);
+    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;
     const int len = min(fpc, F - clip * cstride);
     const int f = clip * cstride + t % len;
     const int j5 = crop % 5;
@@ -181,25 +184,36 @@ using namespace advhip;
 // windows of a video of F frames: window w starts at frame w * clip_stride, the last one may be short (LoopPad)
 static long long window_count(long long F, int fpc, int clip_stride) { return 1 + (F > fpc ? (F - fpc + clip_stride - 1) / clip_stride : 0); }
 
-extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
-                                                          int64_t count, float mean, float stdv, void* stream) {
+extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                        uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
+                                                        float stdv, void* stream) {
+  if (const char* why = crops_packed_error(ncrops, crops_packed))
+    ADVHIP_REQUIRE(false, "tencrop_normalize_planes_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0 && crop % 2 == 0, "tencrop_normalize_planes_u8: bad arguments");
   ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_planes_u8: clip stride %d outside [1, %d]", clip_stride,
                  frames_per_clip);
   ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_planes_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
   ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_planes_u8: std must be non-zero");
   const long long n_clips = window_count(F, frames_per_clip, clip_stride);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * 10,
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * ncrops,
                  "tencrop_normalize_planes_u8: crop-clips [%lld, %lld) outside the video's %lld", (long long)first_crop_clip,
-                 (long long)(first_crop_clip + count), n_clips * 10);
+                 (long long)(first_crop_clip + count), n_clips * ncrops);
   auto half_even = [](int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); };
   const int ctop = half_even(H - crop), cleft = half_even(W - crop);
   const long long rows = (long long)count * C * frames_per_clip * crop;
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, frames_per_clip,
-                     clip_stride, crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4);
+                     clip_stride, crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4, ncrops,
+                     (unsigned long long)crops_packed);
   return check_launch("tencrop_normalize_planes_u8");
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
+                                                          int64_t count, float mean, float stdv, void* stream) {
+  return advhip_tencrop_normalize_planes_u8_crops(frames, xs, F, H, W, C, frames_per_clip, clip_stride, crop, 10, TENCROP_ALL, first_crop_clip,
+                                                  count, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
@@ -209,9 +223,11 @@ extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* 
                                                     stdv, stream);
 }
 
-extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
-                                                   void* stream) {
+extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                 int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                 uint64_t crops_packed, float mean, float stdv, void* stream) {
+  if (const char* why = crops_packed_error(ncrops, crops_packed))
+    ADVHIP_REQUIRE(false, "tencrop_normalize_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0, "tencrop_normalize_u8: bad arguments");
   ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_u8: clip stride %d outside [1, %d]", clip_stride,
                  frames_per_clip);
@@ -222,13 +238,19 @@ extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float*
   const int ctop = half_even(H - crop), cleft = half_even(W - crop);
   const long long n_clips = window_count(F, frames_per_clip, clip_stride);
   const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
-  const long long rows = n_clips * 10 * C * frames_per_clip * (long long)crop;
+  const long long rows = n_clips * ncrops * C * frames_per_clip * (long long)crop;
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows);
+                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed);
   else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows);
+                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed);
   return check_launch("tencrop_normalize_u8");
+}
+
+extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
+                                                   void* stream) {
+  return advhip_tencrop_normalize_u8_crops(frames, y, F, H, W, C, frames_per_clip, clip_stride, crop, 10, TENCROP_ALL, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,

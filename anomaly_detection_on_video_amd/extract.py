@@ -21,7 +21,7 @@ from . import dist as adist
 from . import mil_ops
 from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
-from .ops import n_windows, pad_windows_u8, resolve_clip_stride  # noqa: F401  (n_windows is part of this module's interface)
+from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_crops  # noqa: F401  (n_windows is part of this module's interface)
 
 FRAMES_PER_CLIP = 16
 NCROPS = 10
@@ -140,7 +140,8 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
-                         clips_per_step: int = 3, resize=None, resample="bilinear", clip_stride: Optional[int] = None, **kw) -> np.ndarray:
+                         clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
+                         crops=None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -155,7 +156,18 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     frames that starts at frame w * clip_stride, n_clips = n_windows(F, frames_per_clip, clip_stride), only the last window is
     LoopPad-ed.  The windows are addressed in place by the kernels: a step reads frames [w0 * s, (w0 + clips_per_step - 1) * s +
     frames_per_clip), host frames are copied per step with that overlap (with `resize`, the overlap is resized again: PIL's
-    bytes either way), frames already on the device are not copied at all."""
+    bytes either way), frames already on the device are not copied at all.
+
+    `crops` (ops.resolve_crops: "ten", "five", "center" / "centre", "center_flip" or a strictly ascending tuple of TenCrop
+    indices; default None = all ten): only those crops are extracted, (n_clips, len(crops), 2048) -- a subset is never squeezed -- and row
+    [q, j] is bit for bit row [q, crops[j]] of the ten-crop features at the same step cuts: 10 / len(crops) times less backbone
+    work per clip.  `clips_per_step` defaults to 3; with a crop subset and no explicit value to max(1, 30 // len(crops)), so a
+    step still launches about 30 crop-clips."""
+    crops = resolve_crops(crops)
+    nc = len(crops)
+    subset = nc != 10  # ("ten" and (0, ..., 9) are None in every respect, the squeeze included)
+    if clips_per_step is None:
+        clips_per_step = max(1, 30 // nc) if subset else 3
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
     s = resolve_clip_stride(frames_per_clip, clip_stride)
@@ -180,24 +192,24 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         else:
             fr = fr.to(dev, non_blocking=True)
         if not direct:
-            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=s)
+            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=s, crops=crops)
             rows.append(run_chunks_on_lanes(model, [x[i : i + max_cc] for i in range(0, x.shape[0], max_cc)]))
             continue
         # the stem kernel reads the uint8 pixels itself (TenCrop + float + normalise in its load stage): only LoopPad is left,
         # and only for a last window shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
         fr = pad_windows_u8(fr, frames_per_clip, s).contiguous()
-        n = (w1 - w0) * NCROPS
+        n = (w1 - w0) * nc
         ranges = [(i, min(max_cc, n - i)) for i in range(0, n, max_cc)]
 
         def run_range(r, fr=fr):
             fr.record_stream(torch.cuda.current_stream(dev))  # (read on a lane stream, allocated on the caller's)
-            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=s)
+            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=s, crops=crops)
 
         rows.append(run_chunks_on_lanes(
             model, ranges, fn=run_range,
             prepare=lambda fr=fr: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b) for b in sorted({r[1] for r in ranges})]))
-    out = torch.cat(rows, dim=0).reshape(-1, NCROPS, 2048).cpu().numpy()
-    return np.squeeze(out)
+    out = torch.cat(rows, dim=0).reshape(-1, nc, 2048).cpu().numpy()
+    return out if subset else np.squeeze(out)  # (the reference's np.squeeze quirk belongs to its own ten-crop call only)
 
 
 SEGMENT_FRAMES = 16 * 188  # 3008: extract_features.py:121
@@ -224,6 +236,14 @@ def segment_windows(n_frames: int, seg_len: int = SEGMENT_FRAMES, frames_per_cli
     return out
 
 
+def feature_tag(frames_per_clip: int = FRAMES_PER_CLIP, clip_stride: Optional[int] = None, crops=None) -> str:
+    """What a feature file's name says about how it was extracted: "" for the reference's own (back-to-back clips, ten crops),
+    "_s<stride>" for overlapping windows, then "_c<digits>" for a crop subset ("_s8_c4", "_c01234").  Files made one way are
+    never read another way."""
+    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    return ("" if s == frames_per_clip else f"_s{s}") + crops_tag(crops)
+
+
 def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Callable[[int, int], torch.Tensor], outpath: str,
                               seg_len: int = SEGMENT_FRAMES, **kw) -> np.ndarray:
     """The reference's treatment of videos too large to hold in RAM (extract_features.py:116-148): the video is cut into
@@ -231,10 +251,13 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     (n_clips, 10, 2048) features are cached as `<outpath>/<name>/<name>_<seg>.npy` and re-used on a later run, and the
     segments are stacked.  `read_frames(start, stop)` returns the resized uint8 frames [start, stop) as (F, H, W, 3) (the decoded
     ones with `resize=...` in `kw`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
-    in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another."""
+    in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another.
+    With `crops` in `kw` the features are (n_clips, len(crops), 2048) and the files carry the set too, behind the stride:
+    `<name>_s8_c4_<seg>.npy`."""
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
     s = resolve_clip_stride(fpc, kw.get("clip_stride"))
-    tag = "" if s == fpc else f"_s{s}"
+    nc = len(resolve_crops(kw.get("crops")))
+    tag = feature_tag(fpc, s, kw.get("crops"))
     seg_folder = os.path.join(outpath, name)
     plan = segment_windows(n_frames, seg_len, fpc, s)  # (refuses a seg_len the stride does not divide before anything is written)
     os.makedirs(seg_folder, exist_ok=True)
@@ -246,7 +269,7 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
         else:
             out = extract_video_frames(model, read_frames(lo, hi), **kw)
             np.save(seg_path, out)
-        segments.append(out.reshape(-1, NCROPS, 2048))
+        segments.append(out.reshape(-1, nc, 2048))
     return np.vstack(segments)
 
 
@@ -254,11 +277,12 @@ def extract_frames(sources: Iterable[Tuple[str, int, Callable[[int, int], torch.
                    long_video_frames: int = SEGMENT_FRAMES, seg_len: int = SEGMENT_FRAMES, **kw) -> Dict[str, str]:
     """Per-video driver for frame sources (name, n_frames, read_frames): `<name>_i3d.npy` per video with the reference's
     skip-if-exists rule (:106-110); videos longer than `long_video_frames` go through the per-segment cache.  With
-    `clip_stride` (below frames_per_clip) the files are `<name>_i3d_s<stride>.npy`."""
+    `clip_stride` (below frames_per_clip) the files are `<name>_i3d_s<stride>.npy`, with a crop subset
+    `<name>_i3d[_s<stride>]_c<digits>.npy` (feature_tag)."""
     os.makedirs(outpath, exist_ok=True)
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
     s = resolve_clip_stride(fpc, kw.get("clip_stride"))
-    suffix = "_i3d.npy" if s == fpc else f"_i3d_s{s}.npy"
+    suffix = "_i3d" + feature_tag(fpc, s, kw.get("crops")) + ".npy"
     written = {}
     for name, n_frames, read_frames in sources:
         savepath = os.path.join(outpath, name + suffix)

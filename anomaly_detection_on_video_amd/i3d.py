@@ -345,21 +345,24 @@ class I3Res50(nn.Module):
         return ops.U8_STEM_FORM == "planes" and ops.s2w_ok(self._plan[0].convs[0], crop)
 
     def forward_frames(self, frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224,
-                       clip_stride: Optional[int] = None) -> torch.Tensor:
+                       clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
         """Features (count, 2048, 1, 1, 1) of crop-clips [first, first + count) of a video given as resized uint8 frames
         (F, FH, FW, 3), F whole clips; row = clip * 10 + crop in TenCrop order.  What the reference does on the host per clip
         -- GroupTenCrop, ToTensor, GroupNormalize, the (T,C)->(C,T) permute (src/dataset.py:175-195, src/gtransforms.py:29-38,
         57-73, extract_features.py:83-89) -- happens in the load stage of the stem kernel: the fp32 ten-crop tensor never exists.
         `clip_stride` (default frames_per_clip): clip w = frames [w * clip_stride, w * clip_stride + frames_per_clip), F whole
-        windows (ops.pad_windows_u8); overlapping windows are addressed in place, no frame is duplicated."""
+        windows (ops.pad_windows_u8); overlapping windows are addressed in place, no frame is duplicated.
+        `crops` (ops.resolve_crops: "center", "center_flip", "five", a tuple of TenCrop indices; default all ten): row =
+        clip * len(crops) + j holds crop crops[j] -- the ten-crop row of that (clip, crop) bit for bit, at 1 / 10 .. 1 of the work."""
         s = ops.resolve_clip_stride(frames_per_clip, clip_stride)
+        crops = ops.resolve_crops(crops)
         if self.training:
             raise _lib.HipExtensionError("I3Res50 HIP path implements eval-mode BatchNorm only; call .eval()")
         if self.in_channels != 3:
             raise _lib.HipExtensionError("forward_frames takes RGB frames: the backbone was built with in_channels != 3")
         if frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_cuda:
             raise _lib.HipExtensionError(f"forward_frames wants uint8 (F,H,W,3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
-        n = ops.n_windows(frames.shape[0], frames_per_clip, s) * 10
+        n = ops.n_windows(frames.shape[0], frames_per_clip, s) * len(crops)
         if count <= 0 or first < 0 or first + count > n:
             raise ValueError(f"forward_frames: crop-clips [{first}, {first + count}) outside the video's {n}")
         self.prepare()
@@ -367,16 +370,16 @@ class I3Res50(nn.Module):
             if not self.frames_fused():  # other stems / ADV_I3D_FUSE_POOL=0: TenCrop + normalise as its own HIP pass
                 from . import mil_ops
 
-                return self.forward_single(mil_ops.tencrop_normalize_u8(frames, frames_per_clip, crop, clip_stride=s)[first : first + count])
+                return self.forward_single(mil_ops.tencrop_normalize_u8(frames, frames_per_clip, crop, clip_stride=s, crops=crops)[first : first + count])
             stem, pu = self._plan[0], self._plan[0].pool_unit
             if self._frames_planes(crop):
                 # one pass: TenCrop + float + normalise + permutes, written as column-parity planes; then the stem with 16-byte
                 # gather pieces.  Same arithmetic per pixel as the fp32 pipeline: the features equal model(tencrop_normalize_u8(..)).
-                xs = ops.tencrop_planes_u8(frames, first, count, frames_per_clip, crop, clip_stride=s)
+                xs = ops.tencrop_planes_u8(frames, first, count, frames_per_clip, crop, clip_stride=s, crops=crops)
                 stem_fn = lambda out=None: ops.conv3d_s2w_bn_relu_maxpool233(xs, stem.convs[0], out=out)
             else:
                 stem_fn = lambda out=None: ops.conv3d_u8_tencrop_bn_relu_maxpool233(frames, stem.convs[0], first, count, frames_per_clip, crop, out=out,
-                                                                                   clip_stride=s)
+                                                                                   clip_stride=s, crops=crops)
             if pu.cat_channels:  # straight into the [x ; h] buffer of layer1.0, like _Unit.run
                 d = ops.conv_pool_out_dims((frames_per_clip, crop, crop), stem.convs[0], pu.kernel, pu.stride)
                 x = torch.empty((count, stem.convs[0].cout + pu.cat_channels) + d, device=frames.device, dtype=torch.float32)

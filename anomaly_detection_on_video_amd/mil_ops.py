@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
-from .ops import n_windows, resolve_clip_stride
+from .ops import n_windows, pack_crops, resolve_clip_stride
 
 
 class _MilMagnitude(torch.autograd.Function):
@@ -250,12 +250,14 @@ def normalize_permute_u8(frames: torch.Tensor, mean: float = PIXEL_MEAN, std: fl
 
 
 def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
-                         std: float = PIXEL_STD, clip_stride: Optional[int] = None) -> torch.Tensor:
+                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) of one video -> the backbone's input (n_clips * 10, C, frames_per_clip, crop, crop)
     fp32: TenCrop, float, normalise, LoopPad and the layout permutes of TenCropVideoFrameDataset / _extract
     (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop.
-    `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = ops.n_windows(F, ...)."""
+    `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = ops.n_windows(F, ...).
+    `crops` (ops.resolve_crops; default all ten): (n_clips * len(crops), ...), row = clip * len(crops) + j holds crop crops[j]."""
     s = resolve_clip_stride(frames_per_clip, clip_stride)
+    nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
@@ -264,9 +266,9 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
     if h < crop or w < crop:
         raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
     n_clips = n_windows(f, frames_per_clip, s)
-    out = torch.empty((n_clips * 10, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_u8_strided(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, C_float(mean),
-                                                          C_float(std), stream()), "tencrop_normalize_u8")
+    out = torch.empty((n_clips * nc, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
+    check(_lib.load().advhip_tencrop_normalize_u8_crops(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, nc, packed, C_float(mean),
+                                                        C_float(std), stream()), "tencrop_normalize_u8")
     return out
 
 

@@ -8,6 +8,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
+import numbers
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -390,25 +391,72 @@ def n_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[in
     return 1 + max(0, -(-(n_frames - frames_per_clip) // s))
 
 
+CROP_SETS = {"ten": tuple(range(10)), "five": (0, 1, 2, 3, 4), "center": (4,), "centre": (4,), "center_flip": (4, 9)}
+
+
+def resolve_crops(crops) -> Tuple[int, ...]:
+    """A crop subset of TenCrop as a strictly ascending tuple of indices 0..9: 0-3 top-left, top-right, bottom-left,
+    bottom-right, 4 centre, 5-9 the same five windows of the horizontally flipped frame.  None / "ten" = all ten, "five" =
+    (0..4), "center" / "centre" = (4,), "center_flip" = (4, 9), or 1 to 10 indices.  Ascending order keeps the crop order
+    TenCrop's own; duplicates, descending or out-of-range indices and an empty set raise ValueError."""
+    if crops is None:
+        return CROP_SETS["ten"]
+    if isinstance(crops, str):
+        if crops not in CROP_SETS:
+            raise ValueError(f"crops {crops!r}: not one of {sorted(CROP_SETS)} or a tuple of TenCrop indices")
+        return CROP_SETS[crops]
+    try:
+        idx = tuple(crops)
+    except TypeError:
+        raise ValueError(f"crops {crops!r}: a name or a tuple of TenCrop indices") from None
+    if not 1 <= len(idx) <= 10:
+        raise ValueError(f"crops {crops!r}: 1 to 10 indices")
+    for c in idx:
+        if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= int(c) <= 9:
+            raise ValueError(f"crops {crops!r}: indices are integers in 0..9")
+    idx = tuple(int(c) for c in idx)
+    if any(b <= a for a, b in zip(idx, idx[1:])):
+        raise ValueError(f"crops {crops!r}: indices must be strictly ascending (TenCrop order, no duplicates)")
+    return idx
+
+
+def pack_crops(crops) -> Tuple[int, int]:
+    """(ncrops, packed) as the kernels take a crop set: index j in bits [4 j, 4 j + 4) of one 64-bit launch argument."""
+    idx = resolve_crops(crops)
+    return len(idx), sum(c << (4 * j) for j, c in enumerate(idx))
+
+
+def unpack_crops(ncrops: int, packed: int) -> Tuple[int, ...]:
+    return tuple((packed >> (4 * j)) & 15 for j in range(ncrops))
+
+
+def crops_tag(crops) -> str:
+    """The file-name tag of a crop subset: "" for all ten, else "_c<digits>" ("_c4", "_c01234")."""
+    idx = resolve_crops(crops)
+    return "" if len(idx) == 10 else "_c" + "".join(str(c) for c in idx)
+
+
 def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = 114.75,
-                      std: float = 57.375, clip_stride: Optional[int] = None) -> torch.Tensor:
+                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) -> column-parity planes (count, C, frames_per_clip, crop, 2, crop/2 + 4) of crop-clips
     [first, first + count) (row = clip * 10 + crop): TenCrop, float, normalise, LoopPad and the layout permutes of
     TenCropVideoFrameDataset / _extract (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass,
     written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's.  `clip_stride` (default
-    frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride."""
+    frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride.  `crops`
+    (resolve_crops): row = clip * len(crops) + j holds crop crops[j]."""
     s = resolve_clip_stride(frames_per_clip, clip_stride)
+    nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
     f, h, w, c = frames.shape
-    n = n_windows(f, frames_per_clip, s) * 10
+    n = n_windows(f, frames_per_clip, s) * nc
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_planes_u8_strided(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, first, count,
-                                                                 C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
+    check(_lib.load().advhip_tencrop_normalize_planes_u8_crops(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, nc, packed, first, count,
+                                                               C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
     return xs
 
 
@@ -526,21 +574,24 @@ def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tupl
 
 def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv", first: int, count: int, frames_per_clip: int = 16,
                                          crop: int = 224, out: Optional[torch.Tensor] = None, mean: float = PIXEL_MEAN,
-                                         std: float = PIXEL_STD, clip_stride: Optional[int] = None) -> torch.Tensor:
+                                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
     """The stem (conv1 + bn1 + relu + maxpool1, src/i3d.py:303-306) of crop-clips [first, first + count) of a video given as
     resized uint8 frames (F, FH, FW, 3): row = clip * 10 + crop (TenCrop order).  TenCrop, float conversion and
     (x - mean) / std happen in the conv's load stage (src/gtransforms.py:29-38,57-73, extract_features.py:83-89).
     `clip_stride` (default frames_per_clip): clip w = frames [w * clip_stride, w * clip_stride + frames_per_clip); the frames
-    are whole windows, F = (n - 1) * clip_stride + frames_per_clip (pad_windows_u8 appends a short last window's LoopPad frames)."""
+    are whole windows, F = (n - 1) * clip_stride + frames_per_clip (pad_windows_u8 appends a short last window's LoopPad frames).
+    `crops` (resolve_crops; default all ten): row = clip * len(crops) + j holds crop crops[j], bit for bit the ten-crop row of
+    that (clip, crop); the set is a by-value argument of the same kernel."""
     require_gpu(frames)
     require_gpu(out, contiguous=False)
     s = resolve_clip_stride(frames_per_clip, clip_stride)
+    nc, packed = pack_crops(crops)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != pc.cin:
         raise ValueError(f"{pc.name}: expected uint8 (F,H,W,{pc.cin}) frames, got {frames.dtype} {tuple(frames.shape)}")
     F, FH, FW, _ = frames.shape
     if F < frames_per_clip or (F - frames_per_clip) % s or FH < crop or FW < crop:
         raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips (stride {s}) of at least {crop}x{crop}")
-    n = ((F - frames_per_clip) // s + 1) * 10
+    n = ((F - frames_per_clip) // s + 1) * nc
     if count <= 0 or first < 0 or first + count > n:
         raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {n}")
     d = pc.desc(count, frames_per_clip, crop, crop, True, 0, 1)
@@ -560,15 +611,16 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     if U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64:
         frames = with_slack(frames)
         ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
-        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(C.byref(d), ptr(frames), F, FH, FW, s, readable_bytes(frames), first,
-                                                                               ptr(wt), ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
-                                                                               C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
+        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed,
+                                                                             readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
+                                                                             ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
+                                                                             batch_stride(y), ptr(ws), need, stream()),
               f"conv3d_u8_taps+pool233[{pc.name}]")
         return y
     ktab, corr = ensure_u8_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
-    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(C.byref(d), ptr(frames), F, FH, FW, s, first, ptr(pc.w_packed), ptr(ktab),
-                                                                      ptr(corr), ptr(pc.scale), ptr(pc.shift),
-                                                                      C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
+    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed, first, ptr(pc.w_packed),
+                                                                    ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
+                                                                    C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
           f"conv3d_u8+pool233[{pc.name}]")
     return y
 

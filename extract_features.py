@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N]]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--crops SET]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
@@ -10,6 +10,8 @@ tensors of the same layout; plug a real decoder in by passing (name, loader) pai
 that size instead, resized (GroupResize(256)), ten-cropped and normalised on the device: `extract_frames(..., resize=256)`,
 the entry point for a real decoder's (name, n_frames, read_frames) triples.  `--clip-stride N` (with `--frame-size`) extracts a
 16-frame window every N frames instead of every 16 (`<name>_i3d_s<N>.npy`); the windows overlap in place on the device.
+`--crops ten|five|center|center_flip|0,4,9` (with `--frame-size`) extracts only those of TenCrop's ten crops
+(`<name>_i3d[_s<N>]_c<digits>.npy`, features (n_clips, len(SET), 2048)): a tenth to all of the backbone work per clip.
 """
 import argparse
 import os
@@ -55,14 +57,26 @@ def parse_frame_size(text: str):
     return h, w
 
 
+def parse_crops(text: str):
+    """--crops: a name of ops.CROP_SETS or comma-separated TenCrop indices, e.g. 0,4,9 -> the validated tuple."""
+    from anomaly_detection_on_video_amd.ops import CROP_SETS, resolve_crops
+
+    try:
+        return resolve_crops(text if text in CROP_SETS else tuple(int(v) for v in text.split(",")))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--crops {text!r}: {e}")
+
+
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
-         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None):
+         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if clip_stride is not None and frame_size is None:
         raise ValueError("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
     if clip_stride is not None and not 1 <= clip_stride <= 16:
         raise ValueError(f"--clip-stride {clip_stride} outside [1, 16]")
+    if crops is not None and frame_size is None:
+        raise ValueError("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
@@ -70,7 +84,7 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
     if frame_size is None:
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
-        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride)
+        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -87,9 +101,13 @@ if __name__ == "__main__":
                     help="feed synthetic decoded uint8 frames of this size, resized to 256 on the device (default: ten-cropped clip tensors)")
     ap.add_argument("--clip-stride", type=int, default=None, metavar="N",
                     help="with --frame-size: a 16-frame window every N frames (1..16; default 16, the reference's back-to-back clips)")
+    ap.add_argument("--crops", type=parse_crops, default=None, metavar="SET",
+                    help="with --frame-size: ten (default), five, center, center_flip, or ascending TenCrop indices such as 0,4,9")
     a = ap.parse_args()
     if a.clip_stride is not None and a.frame_size is None:
         ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
     if a.clip_stride is not None and not 1 <= a.clip_stride <= 16:
         ap.error(f"--clip-stride {a.clip_stride} outside [1, 16]")
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride)
+    if a.crops is not None and a.frame_size is None:
+        ap.error("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops)

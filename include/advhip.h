@@ -259,6 +259,12 @@ int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t
 int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                                int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
                                                int64_t count, float mean, float stdv, void* stream);
+/* ... for a crop subset (advhip_tencrop_normalize_u8_crops below): crop-clip = clip * ncrops + j, [first, first + count) within
+ * windows * ncrops; the call above is the identity set. */
+int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                             int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                             uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean, float stdv,
+                                             void* stream);
 
 /* --- the same stem, fed by resized uint8 frames (src/gtransforms.py:29-38,57-73 + extract_features.py:83-89 in the load stage)
  * frames: uint8 (F, FH, FW, Cin) -- what the decoder + GroupResize hand over -- F a whole number of clips of d->T frames.
@@ -291,6 +297,16 @@ int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_
                                                             const float* scale, const float* shift, float stdv, float* y,
                                                             int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                             void* stream);
+/* A crop SUBSET of the ten: `ncrops` (1..10) strictly ascending TenCrop indices (0-3 corners, 4 centre, 5-9 the same of the
+ * mirrored frame), entry j in bits [4 j, 4 j + 4) of `crops_packed`, the bits above zero.  Sample b of the launch is crop-clip
+ * first_crop_clip + b = (clip g / ncrops, crop entry g % ncrops); first_crop_clip + d->B <= windows * ncrops.  The set is one
+ * by-value launch argument of the same kernel (no table in memory); every row is bit for bit the row the ten-crop call gives
+ * for that (clip, crop).  (10, 0x9876543210) is the call above.  A malformed set is refused (ADVHIP_EINVAL) before any launch. */
+int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                          int32_t FW, int32_t clip_stride, int32_t ncrops, uint64_t crops_packed,
+                                                          int64_t first_crop_clip, const float* w_packed, const int32_t* ktab_u8,
+                                                          const float* corr, const float* scale, const float* shift, float stdv, float* y,
+                                                          int64_t y_batch_stride, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The same stem from WHOLE PIXELS: K runs tap-major (k' = tap * 3 + c), one 4-byte LDS-DMA per (tap, position) fetches the
  * pixel's three channel bytes at the pixel's byte address (a third of the gather instructions of the byte form for the same
@@ -313,6 +329,13 @@ int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(const advhip_co
                                                                  const float* corr, const float* scale, const float* shift, float stdv,
                                                                  float* y, int64_t y_batch_stride, void* workspace,
                                                                  int64_t workspace_bytes, void* stream);
+/* ... for a crop subset, as advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32. */
+int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                               int32_t FW, int32_t clip_stride, int32_t ncrops, uint64_t crops_packed,
+                                                               int64_t readable_bytes, int64_t first_crop_clip, const float* w_taps,
+                                                               const int32_t* ktab_taps, const float* corr, const float* scale,
+                                                               const float* shift, float stdv, float* y, int64_t y_batch_stride,
+                                                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* y = MaxPool3d(k=(2,1,1), s=(2,1,1))( act( conv3d(x, w) * scale + shift (+ residual) ) ) for a 1x1x1 stride-1 conv
  * (Cin a multiple of 32) in ONE launch: the last Bottleneck of layer1 followed by maxpool2 (src/i3d.py:111-121, 309).
@@ -673,6 +696,12 @@ int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int3
 int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                         int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
                                         void* stream);
+/* The same pass for a crop SUBSET: `ncrops` (1..10) strictly ascending TenCrop indices, entry j in bits [4 j, 4 j + 4) of
+ * `crops_packed`, the bits above zero (10, 0x9876543210 = the call above).  y: fp32 (n * ncrops, C, fpc, crop, crop), row
+ * clip * ncrops + j = row clip * 10 + entry j of the ten-crop pass, bit for bit.  A malformed set is refused before the launch. */
+int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                      int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops, uint64_t crops_packed,
+                                      float mean, float stdv, void* stream);
 
 /* Per-window scores (n_windows,) -> per-frame scores (n_frames,): window w covers frames [w * clip_stride, w * clip_stride +
  * frames_per_clip); the score of a frame is the mean of the scores of the windows covering it (fp32, added in ascending window
