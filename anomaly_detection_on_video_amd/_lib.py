@@ -152,6 +152,12 @@ SIGNATURES = {
                                                                         _P, C.c_float, _P, _L, _P, _L, _P]),
     "advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P,
                                                                           C.c_float, _P, _L, _P, _L, _P]),
+    "advhip_conv3d_u8_build_tables_sampled": (C.c_int, [C.POINTER(ConvDesc), _I, _I, _I, _P, C.c_float, _P, _P, _P]),
+    "advhip_conv3d_u8_taps_build_tables_sampled": (C.c_int, [C.POINTER(ConvDesc), _I, _I, _I, _P, C.c_float, _P, _P, _P, _P]),
+    "advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _I, _I, _I, _I, _I, C.c_uint64, _L, _L, _P, _P,
+                                                                               _P, _P, _P, C.c_float, _P, _L, _P, _L, _P]),
+    "advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _I, _I, _I, _I, _I, C.c_uint64, _L, _P, _P, _P,
+                                                                          _P, _P, C.c_float, _P, _L, _P, _L, _P]),
     "advhip_conv3d_bn_act_maxpool211_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
     "advhip_bgemm_f32": (C.c_int, [C.POINTER(GemmDesc), _P, _P, _P, _P]),
     "advhip_gemm_nt_f32": (C.c_int, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _L, _P]),
@@ -214,9 +220,12 @@ SIGNATURES = {
     "advhip_tencrop_normalize_u8_strided": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_planes_u8_crops": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _L, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_u8_crops": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, C.c_float, C.c_float, _P]),
+    "advhip_tencrop_normalize_planes_u8_sampled": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _L, C.c_float, C.c_float, _P]),
+    "advhip_tencrop_normalize_u8_sampled": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, C.c_float, C.c_float, _P]),
     "advhip_frame_scores_f32": (C.c_int, [_P, _P, _L, _I, _I, _L, _P]),
     "advhip_normalize_permute_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_resize_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "advhip_resize_u8_sampled": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

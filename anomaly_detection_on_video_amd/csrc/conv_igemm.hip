@@ -127,7 +127,8 @@ struct ConvArgs {
   // crop-clip u8_first + b = (clip, crop) of torchvision's TenCrop order (4 corners, centre, then the same five mirrored);
   // T / H / W above are the clip-local extents (frames per clip, crop size) the tap masks are taken against
   int u8_first, u8_FH, u8_FW;
-  int u8_cstride;           // frames between the starts of consecutive clips: T (back to back) or less (overlapping windows)
+  int u8_cstride;           // frames between the starts of consecutive clips: T * u8_fstep (back to back) or less (overlapping windows)
+  int u8_fstep;             // temporal sampling: clip frame t is source frame clip * u8_cstride + t * u8_fstep (1: consecutive frames)
   // crop subset: crop-clip g = (clip g / u8_nc, crop (u8_crops >> 4 (g % u8_nc)) & 15); all ten in order = {10, TENCROP_ALL}
   int u8_nc;
   FastDiv u8_dnc;
@@ -1333,7 +1334,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
       const int FWC = a.u8_FW * a.Cin, FHWC = a.u8_FH * FWC;
       // (mirrored crops are five_crop(hflip(frame)): column c of such a crop is source column FW - 1 - (left + c))
       const int col = u8_flip ? a.u8_FW - 1 - left - iw0 - (a.kw_ - 1) : left + iw0;
-      vbase = (unsigned)((clip * a.u8_cstride + it0) * FHWC + (top + ih0) * FWC + col * a.Cin + a.pad_off);
+      vbase = (unsigned)((clip * a.u8_cstride + it0 * a.u8_fstep) * FHWC + (top + ih0) * FWC + col * a.Cin + a.pad_off);
     } else {
       vbase = (unsigned)(pb * a.x_bstride + it0 * a.HW + ih0 * a.W + iw0 + a.pad_off) * 4u;
     }
@@ -2069,7 +2070,7 @@ void stem_u8_tap_kernel(const ConvArgs a) {
     const int it0 = pot * a.st - a.pt, ih0 = poh * a.sh - a.ph, iw0 = pow_ * a.sw - a.pw;
     const int top = j5 == 4 ? a.u8_ctop : ((j5 >> 1) ? a.u8_FH - a.H : 0), left = j5 == 4 ? a.u8_cleft : ((j5 & 1) ? a.u8_FW - a.W : 0);
     const int col = flip ? a.u8_FW - 1 - left - iw0 - (a.kw_ - 1) : left + iw0;  // (mirrored crops: see the byte form)
-    vbase = (unsigned)((((clip * a.u8_cstride + it0) * a.u8_FH + top + ih0) * a.u8_FW + col) * 3 + a.pad_off);
+    vbase = (unsigned)((((clip * a.u8_cstride + it0 * a.u8_fstep) * a.u8_FH + top + ih0) * a.u8_FW + col) * 3 + a.pad_off);
     vmask = tap_bits(it0, a.kt_, a.T) | (tap_bits(ih0, a.kh_, a.H) << 10) | (tap_bits(iw0, a.kw_, a.W) << 20);
   }
   U8Corr u8c{};
@@ -2780,8 +2781,9 @@ __global__ void build_ktab_s2w_kernel(int2* __restrict__ tab, int kt, int kh, in
 
 // ---- tables of the uint8-frame stem (conv3d_igemm_dma_kernel<..., U8 = true>) ---------------------------------------------
 // {byte offset, tap bits} per k-row for frames stored (F, FH, FW, C): table 0 as stored, table 1 for the mirrored crops
-// (tap dw of a mirrored crop is source column -dw; the kernel moves its window origin (kw-1) columns left to keep offsets >= 0)
-__global__ void build_ktab_u8_kernel(int2* __restrict__ tab, int kt, int kh, int kw, int C, int K, int Kpad, int FWC, int FHWC) {
+// (tap dw of a mirrored crop is source column -dw; the kernel moves its window origin (kw-1) columns left to keep offsets >= 0).
+// tpitch: bytes between consecutive frames of a clip, frame_step * FH * FW * C (temporal sampling: tap dt is frame_step frames on)
+__global__ void build_ktab_u8_kernel(int2* __restrict__ tab, int kt, int kh, int kw, int C, int K, int Kpad, int FWC, int tpitch) {
   const int taps = kt * kh * kw;
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < Kpad; k += gridDim.x * blockDim.x) {
     int2 f = make_int2(0, (int)(1u << 30)), g = f;  // padding rows: never inside
@@ -2790,8 +2792,8 @@ __global__ void build_ktab_u8_kernel(int2* __restrict__ tab, int kt, int kh, int
       const int dt = tap / (kh * kw), r = tap % (kh * kw);
       const int dh = r / kw, dw = r % kw;
       const int bits = (int)((1u << dt) | (1u << (10 + dh)) | (1u << (20 + dw)));
-      f = make_int2(ci + dt * FHWC + dh * FWC + dw * C, bits);
-      g = make_int2(ci + dt * FHWC + dh * FWC + (kw - 1 - dw) * C, bits);
+      f = make_int2(ci + dt * tpitch + dh * FWC + dw * C, bits);
+      g = make_int2(ci + dt * tpitch + dh * FWC + (kw - 1 - dw) * C, bits);
     }
     tab[k] = f;
     tab[Kpad + k] = g;
@@ -2800,7 +2802,8 @@ __global__ void build_ktab_u8_kernel(int2* __restrict__ tab, int kt, int kh, int
 
 // tables of stem_u8_tap_kernel: {byte offset of the tap's pixel, tap bits} for [2][taps_pad] (as stored, mirrored), and the weights
 // re-ordered tap-major: wt[(tap * C + c)][n] = wp[(c * taps + tap)][n], zero rows for the padding taps
-__global__ void build_ktab_u8_taps_kernel(int2* __restrict__ tab, int kt, int kh, int kw, int C, int taps_pad, int FW, int FHW) {
+// (tpitch: pixels between consecutive frames of a clip, frame_step * FH * FW)
+__global__ void build_ktab_u8_taps_kernel(int2* __restrict__ tab, int kt, int kh, int kw, int C, int taps_pad, int FW, int tpitch) {
   const int taps = kt * kh * kw;
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < taps_pad; t += gridDim.x * blockDim.x) {
     int2 f = make_int2(0, (int)(1u << 30)), g = f;
@@ -2808,8 +2811,8 @@ __global__ void build_ktab_u8_taps_kernel(int2* __restrict__ tab, int kt, int kh
       const int dt = t / (kh * kw), r = t % (kh * kw);
       const int dh = r / kw, dw = r % kw;
       const int bits = (int)((1u << dt) | (1u << (10 + dh)) | (1u << (20 + dw)));
-      f = make_int2((dt * FHW + dh * FW + dw) * C, bits);
-      g = make_int2((dt * FHW + dh * FW + (kw - 1 - dw)) * C, bits);
+      f = make_int2((dt * tpitch + dh * FW + dw) * C, bits);
+      g = make_int2((dt * tpitch + dh * FW + (kw - 1 - dw)) * C, bits);
     }
     tab[t] = f;
     tab[taps_pad + t] = g;
@@ -3639,16 +3642,28 @@ extern "C" int advhip_conv3d_s2w_bn_relu_maxpool233_f32(const advhip_conv3d_desc
 
 // ---- stem + maxpool1 straight from resized uint8 frames (TenCrop, float conversion and normalisation in the load stage) ----
 namespace advhip {
-// the frames buffer of the fused stems holds whole windows: F = (n - 1) * clip_stride + T for n >= 1 windows (clip_stride = T:
-// whole back-to-back clips).  *n_clips receives n.
-static int u8_check_frames(const advhip_conv3d_desc* d, int64_t F, int FH, int FW, int clip_stride, int64_t* n_clips = nullptr) {
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= d->T, "conv3d u8: clip stride %d outside [1, %d]", clip_stride, d->T);
-  ADVHIP_REQUIRE(F >= d->T && (F - d->T) % clip_stride == 0, "conv3d u8: %lld frames are not whole clips of %d at stride %d", (long long)F, d->T,
-                 clip_stride);
-  if (n_clips) *n_clips = (F - d->T) / clip_stride + 1;
+// the frames buffer of the fused stems holds whole windows: window w samples frames w * clip_stride + t * frame_step, t in [0, T),
+// so F = (n - 1) * clip_stride + (T - 1) * frame_step + 1 for n >= 1 windows (frame_step = 1, clip_stride = T: whole back-to-back
+// clips).  *n_clips receives n.
+static int u8_check_frames(const advhip_conv3d_desc* d, int64_t F, int FH, int FW, int clip_stride, int frame_step = 1, int64_t* n_clips = nullptr) {
+  ADVHIP_REQUIRE(frame_step >= 1 && (long long)d->T * frame_step < (1ll << 24), "conv3d u8: frame step %d", frame_step);
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= d->T * frame_step, "conv3d u8: clip stride %d outside [1, %d]", clip_stride,
+                 d->T * frame_step);
+  const int64_t reach = (int64_t)(d->T - 1) * frame_step + 1;  // frames from a window's first sampled frame to its last
+  ADVHIP_REQUIRE(frame_step > 1 || (F >= reach && (F - reach) % clip_stride == 0), "conv3d u8: %lld frames are not whole clips of %d at stride %d",
+                 (long long)F, d->T, clip_stride);
+  ADVHIP_REQUIRE(F >= reach && (F - reach) % clip_stride == 0, "conv3d u8: %lld frames are not whole clips of %d, one frame in %d, at stride %d",
+                 (long long)F, d->T, frame_step, clip_stride);
+  if (n_clips) *n_clips = (F - reach) / clip_stride + 1;
   ADVHIP_REQUIRE(FH >= d->H && FW >= d->W, "conv3d u8: frames (%d x %d) smaller than the %d x %d crop", FH, FW, d->H, d->W);
   ADVHIP_REQUIRE(d->kt <= 10 && d->kh <= 10 && d->kw <= 10, "conv3d u8: kernel extents above 10");
   ADVHIP_REQUIRE(F * FH * FW * d->Cin < (1ll << 31) - (1 << 24), "conv3d u8: frames tensor above 2 GiB");
+  // (the window origin of a border output lies pt * frame_step frames before the clip: pad_off, part of the 32-bit buffer range
+  // beside the frames; the largest table offset, (kt - 1) * frame_step frames, stays an int32 too.  frame_step = 1: the 16 MiB
+  // kept free above cover both)
+  ADVHIP_REQUIRE(frame_step == 1 ||
+                     ((int64_t)(d->pt + d->kt) * frame_step + 1) * FH * FW * d->Cin < (1ll << 31) - (1ll << 24) - F * FH * FW * d->Cin,
+                 "conv3d u8: frame step %d reaches past the 2 GiB the gather can address", frame_step);
   return ADVHIP_OK;
 }
 }  // namespace advhip
@@ -3663,16 +3678,22 @@ extern "C" int advhip_conv3d_u8_table_sizes(const advhip_conv3d_desc* d, int64_t
 
 extern "C" int advhip_conv3d_u8_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
                                              int32_t* ktab_u8, float* corr, void* stream) {
+  return advhip_conv3d_u8_build_tables_sampled(d, FH, FW, 1, w_packed, mean, ktab_u8, corr, stream);
+}
+
+extern "C" int advhip_conv3d_u8_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
+                                                     const float* w_packed, float mean, int32_t* ktab_u8, float* corr, void* stream) {
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_u8 && corr, "conv3d u8 tables: null pointer");
-  if (int rc = u8_check_frames(d, d->T, FH, FW, d->T)) return rc;
+  ADVHIP_REQUIRE(frame_step >= 1, "conv3d u8 tables: frame step %d", frame_step);
+  if (int rc = u8_check_frames(d, (int64_t)(d->T - 1) * frame_step + 1, FH, FW, d->T * frame_step, frame_step)) return rc;
   const Geometry g = geometry(d);
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
   ADVHIP_REQUIRE(total < (1ll << 28), "conv3d u8 tables: padding (%d,%d,%d) too large", d->pt, d->ph, d->pw);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(build_ktab_u8_kernel, dim3((g.Kpad + 255) / 256), dim3(256), 0, st, reinterpret_cast<int2*>(ktab_u8), d->kt, d->kh,
-                     d->kw, d->Cin, g.K, g.Kpad, FW * d->Cin, FH * FW * d->Cin);
+                     d->kw, d->Cin, g.K, g.Kpad, FW * d->Cin, frame_step * FH * FW * d->Cin);
   hipLaunchKernelGGL(u8_pad_corr_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, st, w_packed, corr,
                      (int)total, d->Cin, d->kt, d->kh, d->kw, d->pt, d->ph, d->pw, d->Cout, mean);
   return check_launch("conv3d_u8_build_tables");
@@ -3706,6 +3727,17 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhi
                                                                      const float* corr, const float* scale, const float* shift, float stdv,
                                                                      float* y, int64_t y_batch_stride, void* workspace,
                                                                      int64_t workspace_bytes, void* stream) {
+  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, first_crop_clip,
+                                                                 w_packed, ktab_u8, corr, scale, shift, stdv, y, y_batch_stride, workspace,
+                                                                 workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                       int32_t FW, int32_t clip_stride, int32_t frame_step, int32_t ncrops,
+                                                                       uint64_t crops_packed, int64_t first_crop_clip, const float* w_packed,
+                                                                       const int32_t* ktab_u8, const float* corr, const float* scale,
+                                                                       const float* shift, float stdv, float* y, int64_t y_batch_stride,
+                                                                       void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = validate(d)) return rc;
   if (const char* why = crops_packed_error(ncrops, crops_packed))
     ADVHIP_REQUIRE(false, "conv3d u8+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
@@ -3713,7 +3745,7 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhi
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8+pool233: padding not smaller than the kernel");
   ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8+pool233: std must be non-zero");
   int64_t n_clips = 0;
-  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, &n_clips)) return rc;
+  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, frame_step, &n_clips)) return rc;
   ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
                  "conv3d u8+pool233: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", (long long)first_crop_clip,
                  (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
@@ -3728,15 +3760,15 @@ extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhi
   ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_packed, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
+  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride; a.u8_fstep = frame_step;
   a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
   // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
   a.in_std = stdv;  // (the mean went into `corr` when the tables were built)
   a.ktab_u8 = reinterpret_cast<const int2*>(ktab_u8); a.pad_corr = corr;
-  // byte offsets: the window origin of a border output lies up to (pt, ph, pw + kw - 1) before the crop's corner
-  a.pad_off = (d->pt * FH * FW + d->ph * FW + d->pw + d->kw) * d->Cin;
+  // byte offsets: the window origin of a border output lies up to (pt sampled frames, ph, pw + kw - 1) before the crop's corner
+  a.pad_off = (d->pt * frame_step * FH * FW + d->ph * FW + d->pw + d->kw) * d->Cin;
   a.x_bytes = (unsigned)(F * FH * FW * d->Cin + a.pad_off);
   a.y = reinterpret_cast<float*>(workspace);
   a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
@@ -3775,17 +3807,24 @@ extern "C" int advhip_conv3d_u8_taps_table_sizes(const advhip_conv3d_desc* d, in
 
 extern "C" int advhip_conv3d_u8_taps_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
                                                   int32_t* ktab_taps, float* corr, float* w_taps, void* stream) {
+  return advhip_conv3d_u8_taps_build_tables_sampled(d, FH, FW, 1, w_packed, mean, ktab_taps, corr, w_taps, stream);
+}
+
+extern "C" int advhip_conv3d_u8_taps_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
+                                                          const float* w_packed, float mean, int32_t* ktab_taps, float* corr, float* w_taps,
+                                                          void* stream) {
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_taps && corr && w_taps, "conv3d u8 taps tables: null pointer");
   ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
-  if (int rc = u8_check_frames(d, d->T, FH, FW, d->T)) return rc;
+  ADVHIP_REQUIRE(frame_step >= 1, "conv3d u8 taps tables: frame step %d", frame_step);
+  if (int rc = u8_check_frames(d, (int64_t)(d->T - 1) * frame_step + 1, FH, FW, d->T * frame_step, frame_step)) return rc;
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
   ADVHIP_REQUIRE(total < (1ll << 28), "conv3d u8 taps tables: padding (%d,%d,%d) too large", d->pt, d->ph, d->pw);
   const int taps = d->kt * d->kh * d->kw, tp = u8_taps_pad(d);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(build_ktab_u8_taps_kernel, dim3((tp + 255) / 256), dim3(256), 0, st, reinterpret_cast<int2*>(ktab_taps), d->kt, d->kh, d->kw,
-                     d->Cin, tp, FW, FH * FW);
+                     d->Cin, tp, FW, frame_step * FH * FW);
   hipLaunchKernelGGL(pack_weight_taps_kernel, dim3((unsigned)(((long long)tp * d->Cin * d->Cout + 255) / 256)), dim3(256), 0, st, w_packed, w_taps,
                      d->Cout, d->Cin, taps, tp);
   hipLaunchKernelGGL(u8_pad_corr_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, st, w_packed, corr,
@@ -3823,6 +3862,18 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const 
                                                                           const float* scale, const float* shift, float stdv, float* y,
                                                                           int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                           void* stream) {
+  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, readable_bytes,
+                                                                      first_crop_clip, w_taps, ktab_taps, corr, scale, shift, stdv, y,
+                                                                      y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F,
+                                                                            int32_t FH, int32_t FW, int32_t clip_stride, int32_t frame_step,
+                                                                            int32_t ncrops, uint64_t crops_packed, int64_t readable_bytes,
+                                                                            int64_t first_crop_clip, const float* w_taps,
+                                                                            const int32_t* ktab_taps, const float* corr, const float* scale,
+                                                                            const float* shift, float stdv, float* y, int64_t y_batch_stride,
+                                                                            void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = validate(d)) return rc;
   if (const char* why = crops_packed_error(ncrops, crops_packed))
     ADVHIP_REQUIRE(false, "conv3d u8 taps+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
@@ -3831,7 +3882,7 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const 
   ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8 taps+pool233: padding not smaller than the kernel");
   ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8 taps+pool233: std must be non-zero");
   int64_t n_clips = 0;
-  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, &n_clips)) return rc;
+  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, frame_step, &n_clips)) return rc;
   const int64_t fbytes = F * FH * FW * 3;
   ADVHIP_REQUIRE(readable_bytes >= fbytes + 1, "conv3d u8 taps+pool233: the frames allocation must extend one byte past the last pixel "
                  "(pixels are fetched as 4-byte pieces): %lld readable, %lld needed", (long long)readable_bytes, (long long)fbytes + 1);
@@ -3849,7 +3900,7 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const 
   ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8 taps+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
   ConvArgs a;
   if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_taps, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride;
+  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride; a.u8_fstep = frame_step;
   a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
   auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
   a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
@@ -3858,7 +3909,7 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const 
   const int tp = u8_taps_pad(d);
   a.Kpad = 3 * tp;
   a.w_bytes = (unsigned)((long long)a.Kpad * d->Cout * 4);
-  a.pad_off = (d->pt * FH * FW + d->ph * FW + d->pw + d->kw) * 3;
+  a.pad_off = (d->pt * frame_step * FH * FW + d->ph * FW + d->pw + d->kw) * 3;
   a.x_bytes = (unsigned)(std::min<int64_t>(readable_bytes, fbytes + 4) + a.pad_off);
   a.y = reinterpret_cast<float*>(workspace);
   a.y_bstride = 0; a.Tp = Tp; a.relu = 1;

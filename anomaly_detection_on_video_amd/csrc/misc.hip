@@ -84,8 +84,9 @@ __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float
 // input (n_clips * 10, C, fpc, cs, cs) fp32.  Crop j < 5 of a frame = its (top_j, left_j) window: top-left, top-right,
 // bottom-left, bottom-right, centre (torchvision five_crop order; centre offsets are Python-rounded halves, computed by the
 // caller); crops 5..9 = the same five windows of the horizontally flipped frame: pixel (y, x) = frame[top + y][W - 1 - (left + x)].
-// Frame t of clip c = frames[c * cstride + t % len_c], len_c = min(fpc, F - c * cstride) (LoopPad: a short last clip repeats
-// itself); cstride = the distance between clip starts, fpc for the reference's back-to-back clips, less for overlapping windows.
+// Frame t of clip c = frames[c * cstride + (t % len_c) * fstep], len_c = min(fpc, ceil((F - c * cstride) / fstep)) (LoopPad: a short
+// last clip repeats itself); cstride = the distance between clip starts, fpc * fstep for back-to-back clips, less for overlapping
+// windows; fstep = the temporal sampling step (1: consecutive frames, the reference's clips; d: every d-th frame).
 // A crop SUBSET (nc of the ten, ascending, 4-bit indices packed into `crops`): output row clip * nc + j holds crop
 // (crops >> 4 j) & 15 of that clip -- the same arithmetic per pixel, so the row is the ten-crop pass's row clip * 10 + that crop.
 // One wave per output row (clip, crop, c, t, y): the row decode (five divisions) happens once per 224 outputs, the lanes run
@@ -94,7 +95,7 @@ __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float
 template <int VW>
 __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int F, int H, int W,
                                                                    int C, int fpc, int cstride, int cs, int ctop, int cleft, float mean,
-                                                                   float stdv, long long rows, int nc, unsigned long long crops) {
+                                                                   float stdv, long long rows, int nc, unsigned long long crops, int fstep) {
   const int lane = threadIdx.x & 63;
   const int csv = cs / VW;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
@@ -107,8 +108,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
     r /= C;
     const int clip = (int)(r / nc);
     const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;  // (the subset's j-th crop: a nibble of the argument)
-    const int len = min(fpc, F - clip * cstride);
-    const int f = clip * cstride + t % len;
+    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
+    const int f = clip * cstride + (t % len) * fstep;
     const int j = crop % 5;
     const int top = j == 4 ? ctop : ((j >> 1) ? H - cs : 0), left = j == 4 ? cleft : ((j & 1) ? W - cs : 0);
     const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t
 __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, int F, int H,
                                                                           int W, int C, int fpc, int cstride, int cs, int ctop, int cleft,
                                                                           float mean, float stdv, long long first, long long rows, int WP,
-                                                                          int nc, unsigned long long crops) {
+                                                                          int nc, unsigned long long crops, int fstep) {
   const int lane = threadIdx.x & 63;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
     long long r = r0;  // (clip-crop - first, c, t, y)
@@ -145,8 +146,8 @@ __global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const 
     r = r / C + first;
     const int clip = (int)(r / nc);
     const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;
-    const int len = min(fpc, F - clip * cstride);
-    const int f = clip * cstride + t % len;
+    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
+    const int f = clip * cstride + (t % len) * fstep;
     const int j5 = crop % 5;
     const int top = j5 == 4 ? ctop : ((j5 >> 1) ? H - cs : 0), left = j5 == 4 ? cleft : ((j5 & 1) ? W - cs : 0);
     const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
@@ -181,21 +182,26 @@ __global__ __launch_bounds__(256) void frame_scores_kernel(const float* __restri
 
 using namespace advhip;
 
-// windows of a video of F frames: window w starts at frame w * clip_stride, the last one may be short (LoopPad)
-static long long window_count(long long F, int fpc, int clip_stride) { return 1 + (F > fpc ? (F - fpc + clip_stride - 1) / clip_stride : 0); }
+// windows of a video of F frames: window w starts at frame w * clip_stride and spans fpc * frame_step frames (one sampled every
+// frame_step), the last one may be short (LoopPad)
+static long long window_count(long long F, int fpc, int clip_stride, int frame_step = 1) {
+  const long long span = (long long)fpc * frame_step;
+  return 1 + (F > span ? (F - span + clip_stride - 1) / clip_stride : 0);
+}
 
-extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
-                                                        uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
-                                                        float stdv, void* stream) {
+extern "C" int advhip_tencrop_normalize_planes_u8_sampled(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                                          int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
+                                                          float mean, float stdv, void* stream) {
   if (const char* why = crops_packed_error(ncrops, crops_packed))
     ADVHIP_REQUIRE(false, "tencrop_normalize_planes_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0 && crop % 2 == 0, "tencrop_normalize_planes_u8: bad arguments");
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_planes_u8: clip stride %d outside [1, %d]", clip_stride,
-                 frames_per_clip);
+  ADVHIP_REQUIRE(frame_step >= 1 && (long long)frames_per_clip * frame_step < (1ll << 31), "tencrop_normalize_planes_u8: frame step %d", frame_step);
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip * frame_step, "tencrop_normalize_planes_u8: clip stride %d outside [1, %d]",
+                 clip_stride, frames_per_clip * frame_step);
   ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_planes_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
   ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_planes_u8: std must be non-zero");
-  const long long n_clips = window_count(F, frames_per_clip, clip_stride);
+  const long long n_clips = window_count(F, frames_per_clip, clip_stride, frame_step);
   ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * ncrops,
                  "tencrop_normalize_planes_u8: crop-clips [%lld, %lld) outside the video's %lld", (long long)first_crop_clip,
                  (long long)(first_crop_clip + count), n_clips * ncrops);
@@ -205,8 +211,16 @@ extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, f
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, frames_per_clip,
                      clip_stride, crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4, ncrops,
-                     (unsigned long long)crops_packed);
+                     (unsigned long long)crops_packed, frame_step);
   return check_launch("tencrop_normalize_planes_u8");
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                        uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
+                                                        float stdv, void* stream) {
+  return advhip_tencrop_normalize_planes_u8_sampled(frames, xs, F, H, W, C, frames_per_clip, clip_stride, 1, crop, ncrops, crops_packed,
+                                                    first_crop_clip, count, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
@@ -223,28 +237,36 @@ extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* 
                                                     stdv, stream);
 }
 
-extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                 int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
-                                                 uint64_t crops_packed, float mean, float stdv, void* stream) {
+extern "C" int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                                   int32_t ncrops, uint64_t crops_packed, float mean, float stdv, void* stream) {
   if (const char* why = crops_packed_error(ncrops, crops_packed))
     ADVHIP_REQUIRE(false, "tencrop_normalize_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
   ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0, "tencrop_normalize_u8: bad arguments");
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip, "tencrop_normalize_u8: clip stride %d outside [1, %d]", clip_stride,
-                 frames_per_clip);
+  ADVHIP_REQUIRE(frame_step >= 1 && (long long)frames_per_clip * frame_step < (1ll << 31), "tencrop_normalize_u8: frame step %d", frame_step);
+  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip * frame_step, "tencrop_normalize_u8: clip stride %d outside [1, %d]", clip_stride,
+                 frames_per_clip * frame_step);
   ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
   ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_u8: std must be non-zero");
   // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
   auto half_even = [](int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); };
   const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const long long n_clips = window_count(F, frames_per_clip, clip_stride);
+  const long long n_clips = window_count(F, frames_per_clip, clip_stride, frame_step);
   const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
   const long long rows = n_clips * ncrops * C * frames_per_clip * (long long)crop;
   const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
   if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed);
+                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed, frame_step);
   else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed);
+                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed, frame_step);
   return check_launch("tencrop_normalize_u8");
+}
+
+extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                 int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                 uint64_t crops_packed, float mean, float stdv, void* stream) {
+  return advhip_tencrop_normalize_u8_sampled(frames, y, F, H, W, C, frames_per_clip, clip_stride, 1, crop, ncrops, crops_packed, mean, stdv,
+                                             stream);
 }
 
 extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,

@@ -17,15 +17,16 @@ __device__ __forceinline__ uint8_t clip8(int s) {
 }
 
 // Horizontal pass: dst row r = (f, y) of `rows` rows per frame <- src row (f, row0 + y); one wave per output row, a lane per
-// output pixel (three channels).  Bounds and coefficients of a pixel are read once for its three channels.
-__global__ __launch_bounds__(256) void resize_h_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W,
+// output pixel (three channels).  Bounds and coefficients of a pixel are read once for its three channels.  Output frame f reads
+// the source frame at byte f * fpitch: H * W * 3 for every frame, frame_step times that for every frame_step-th one.
+__global__ __launch_bounds__(256) void resize_h_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int W,
                                                          int OW, int row0, int rows, const int* __restrict__ xb,
                                                          const int* __restrict__ xk, int ksize, long long nrows) {
   const int lane = threadIdx.x & 63;
   for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
     const long long f = r / rows;
     const int y = (int)(r - f * rows);
-    const uint8_t* in = src + (f * H + row0 + y) * (long long)W * 3;
+    const uint8_t* in = src + f * fpitch + (row0 + y) * (long long)W * 3;
     uint8_t* out = dst + r * OW * 3;
     for (int x = lane; x < OW; x += 64) {
       const int x0 = xb[2 * x];
@@ -48,8 +49,8 @@ __global__ __launch_bounds__(256) void resize_h_u8_kernel(const uint8_t* __restr
 }
 
 // Vertical pass: dst row (f, oy) <- rows [yb[oy].first - ybase, + count) of the IH-row source frame f; one wave per output row,
-// a lane per output byte (the row's coefficients are the same for every lane).
-__global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int IH, int OH,
+// a lane per output byte (the row's coefficients are the same for every lane).  Source frame f starts at byte f * fpitch.
+__global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int IH, int OH,
                                                          int rowbytes, int ybase, const int* __restrict__ yb,
                                                          const int* __restrict__ yk, int ksize, long long nrows) {
   const int lane = threadIdx.x & 63;
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restr
     int n = min(yb[2 * oy + 1], ksize);
     if (y0 < 0 || y0 + n > IH) n = 0;  // (as above)
     const int* k = yk + (long long)oy * ksize;
-    const uint8_t* in = src + (f * IH + y0) * (long long)rowbytes;
+    const uint8_t* in = src + f * fpitch + y0 * (long long)rowbytes;
     uint8_t* out = dst + r * rowbytes;
     for (int q = lane; q < rowbytes; q += 64) {
       int s = 1 << (RESIZE_BITS - 1);
@@ -82,13 +83,24 @@ static bool mul_ok(long long a, long long b, long long c, long long d, long long
 extern "C" int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F, int32_t H, int32_t W, int32_t C, int32_t OH,
                                 int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds,
                                 const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream) {
+  return advhip_resize_u8_sampled(src, dst, ws, F, 1, H, W, C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, row0, rows, stream);
+}
+
+extern "C" int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
+                                        int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                                        const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows,
+                                        void* stream) {
   ADVHIP_REQUIRE(src && dst, "resize_u8: null frames or output");
+  ADVHIP_REQUIRE(frame_step >= 1, "resize_u8: frame step %d", frame_step);
+  // source frames 0, frame_step, 2 frame_step, ... -> a compact output (F_src < 1 is refused below)
+  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
   ADVHIP_REQUIRE(F >= 1 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1, "resize_u8: sizes must be >= 1 (F=%lld, %d x %d -> %d x %d)",
                  (long long)F, H, W, OH, OW);
   ADVHIP_REQUIRE(C == 3, "resize_u8: frames must have 3 channels (RGB), got C=%d", C);
   const bool horiz = OW != W, vert = OH != H;
   long long in_bytes, out_bytes, ws_bytes = 0;
-  ADVHIP_REQUIRE(mul_ok(F, H, W, C, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes), "resize_u8: frame sizes overflow int64");
+  ADVHIP_REQUIRE(mul_ok(F_src, H, W, C, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes), "resize_u8: frame sizes overflow int64");
+  const long long frame_bytes = (long long)H * W * C, src_pitch = F > 1 ? frame_bytes * frame_step : frame_bytes;  // (F > 1: inside in_bytes)
   ADVHIP_REQUIRE((long long)W * C <= INT32_MAX && (long long)OW * C <= INT32_MAX, "resize_u8: rows of %d / %d pixels are too long", W, OW);
   if (horiz) {
     ADVHIP_REQUIRE(xbounds && xcoef, "resize_u8: null horizontal tables");
@@ -105,7 +117,9 @@ extern "C" int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, i
   }
   hipStream_t s = (hipStream_t)stream;
   if (!horiz && !vert) {  // Pillow returns a copy
-    const hipError_t e = src == dst ? hipSuccess : hipMemcpyAsync(dst, src, (size_t)in_bytes, hipMemcpyDeviceToDevice, s);
+    hipError_t e = hipSuccess;
+    if (frame_step > 1) e = hipMemcpy2DAsync(dst, (size_t)frame_bytes, src, (size_t)src_pitch, (size_t)frame_bytes, (size_t)F, hipMemcpyDeviceToDevice, s);
+    else if (src != dst) e = hipMemcpyAsync(dst, src, (size_t)in_bytes, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) {
       set_error("resize_u8 copy: %s", hipGetErrorString(e));
       return ADVHIP_ELAUNCH;
@@ -115,7 +129,7 @@ extern "C" int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, i
   if (horiz) {
     const long long nrows = F * rows;
     const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid), dim3(256), 0, s, src, vert ? ws : dst, H, W, OW, row0, rows, xbounds, xcoef, xksize,
+    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid), dim3(256), 0, s, src, vert ? ws : dst, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
                        nrows);
     const int rc = check_launch("resize_u8 horizontal pass");
     if (rc != ADVHIP_OK) return rc;
@@ -123,7 +137,8 @@ extern "C" int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, i
   if (vert) {
     const long long nrows = F * OH;
     const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid), dim3(256), 0, s, horiz ? (const uint8_t*)ws : src, dst, horiz ? rows : H, OH, OW * C,
+    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid), dim3(256), 0, s, horiz ? (const uint8_t*)ws : src, dst,
+                       horiz ? (long long)rows * OW * C : src_pitch, horiz ? rows : H, OH, OW * C,
                        horiz ? row0 : 0, ybounds, ycoef, yksize, nrows);
     return check_launch("resize_u8 vertical pass");
   }

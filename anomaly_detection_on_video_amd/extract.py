@@ -21,7 +21,7 @@ from . import dist as adist
 from . import mil_ops
 from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
-from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_crops  # noqa: F401  (n_windows is part of this module's interface)
+from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_crops, resolve_frame_step  # noqa: F401  (n_windows is part of this module's interface)
 
 FRAMES_PER_CLIP = 16
 NCROPS = 10
@@ -141,7 +141,7 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
                          clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
-                         crops=None, **kw) -> np.ndarray:
+                         crops=None, frame_step: Optional[int] = None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -162,7 +162,17 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     indices; default None = all ten): only those crops are extracted, (n_clips, len(crops), 2048) -- a subset is never squeezed -- and row
     [q, j] is bit for bit row [q, crops[j]] of the ten-crop features at the same step cuts: 10 / len(crops) times less backbone
     work per clip.  `clips_per_step` defaults to 3; with a crop subset and no explicit value to max(1, 30 // len(crops)), so a
-    step still launches about 30 crop-clips."""
+    step still launches about 30 crop-clips.
+
+    `frame_step` d (default None = 1): temporal sampling -- sampled frame t of clip w is frames[w * clip_stride + t * d], a clip spans
+    frames_per_clip * d frames, clip_stride defaults to that span (1 <= clip_stride <= span) and n_clips = n_windows(F,
+    frames_per_clip, clip_stride, d); a short last clip LoopPads its ceil((F - w * s) / d) sampled frames.  Nothing is decimated
+    on the host into a second tensor.  Where d divides clip_stride a step's sampled frames form one lattice: of host frames only
+    that lattice is copied (and resized); decoded frames already on the device are resized straight from the lattice
+    (resize_u8(frame_step=d)), and the step then runs at (clip_stride // d, 1) -- the result is extract_video_frames(frames[::d],
+    clip_stride=clip_stride // d) bit for bit.  Resized frames already on the device, and any stride d does not divide, are
+    addressed in place by the kernels with d as a launch argument."""
+    fstep = resolve_frame_step(frame_step)
     crops = resolve_crops(crops)
     nc = len(crops)
     subset = nc != 10  # ("ten" and (0, ..., 9) are None in every respect, the squeeze included)
@@ -170,44 +180,65 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         clips_per_step = max(1, 30 // nc) if subset else 3
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, fstep)
     dev = next(model.parameters()).device
     rows = []
-    n_total = n_windows(frames.shape[0], frames_per_clip, s)
+    n_total = n_windows(frames.shape[0], frames_per_clip, s, fstep)
+    lattice = fstep != 1 and s % fstep == 0  # the sampled frames of a step: frames w0 * s + k * fstep, one arithmetic progression
     max_cc = kw.get("max_crop_clips", 32)
     direct = hasattr(model, "forward_frames") and hasattr(model, "frames_fused") and model.frames_fused()
     for w0 in range(0, n_total, clips_per_step):
         w1 = min(w0 + clips_per_step, n_total)
-        fr = frames[w0 * s : (w1 - 1) * s + frames_per_clip]  # (the slice ends with the video: a short last window)
+        fr = frames[w0 * s : (w1 - 1) * s + frames_per_clip * fstep]  # (the slice ends with the video: a short last window)
+        ss, dd, rstep = s, fstep, None  # how the kernels address `fr`; the step of the resize
+        if lattice:
+            if fr.is_cuda and resize is None:
+                pass  # resized frames on the device: read in place, every fstep-th frame
+            else:
+                ss, dd = s // fstep, 1  # downstream sees the lattice as a video of its own
+                if fr.is_cuda:
+                    rstep = fstep  # decoded frames on the device: the resize reads the lattice in place
+                else:
+                    fr = fr[::fstep]  # host frames: only the lattice crosses PCIe
         if resize is not None:  # decoded frames -> GroupResize on the device, into a buffer with the stem's spare bytes
             fr = fr.to(dev, non_blocking=True).contiguous()
             oh, ow = resize_mod.output_size(fr.shape[1], fr.shape[2], resize)
-            n = fr.shape[0] * oh * ow * fr.shape[3]
+            nf = fr.shape[0] if rstep is None else -(-fr.shape[0] // rstep)
+            n = nf * oh * ow * fr.shape[3]
             buf = torch.empty((n + 16,), device=dev, dtype=torch.uint8)
-            fr = resize_mod.resize_u8(fr, resize, resample, out=buf[:n].view(fr.shape[0], oh, ow, fr.shape[3]))
+            fr = resize_mod.resize_u8(fr, resize, resample, out=buf[:n].view(nf, oh, ow, fr.shape[3]), frame_step=rstep)
         elif direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
             buf = torch.empty((fr.numel() + 16,), device=dev, dtype=torch.uint8)
-            buf[: fr.numel()].copy_(fr.reshape(-1), non_blocking=True)
+            if fr.is_contiguous():
+                buf[: fr.numel()].copy_(fr.reshape(-1), non_blocking=True)
+            else:  # (the lattice of a sampled step: a strided host view, copied frame by frame into the compact buffer)
+                buf[: fr.numel()].view(fr.shape).copy_(fr, non_blocking=True)
             fr = buf[: fr.numel()].view(fr.shape)
         else:
             fr = fr.to(dev, non_blocking=True)
         if not direct:
-            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=s, crops=crops)
+            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=None if dd == 1 else dd)
             rows.append(run_chunks_on_lanes(model, [x[i : i + max_cc] for i in range(0, x.shape[0], max_cc)]))
             continue
         # the stem kernel reads the uint8 pixels itself (TenCrop + float + normalise in its load stage): only LoopPad is left,
         # and only for a last window shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
-        fr = pad_windows_u8(fr, frames_per_clip, s).contiguous()
+        if dd == 1:
+            fr = pad_windows_u8(fr, frames_per_clip, ss).contiguous()
+        elif not hasattr(model, "frames_need_whole_windows") or model.frames_need_whole_windows(crop):
+            fr = pad_windows_u8(fr, frames_per_clip, ss, dd).contiguous()  # (else: a TenCrop pass runs first and LoopPads itself)
         n = (w1 - w0) * nc
         ranges = [(i, min(max_cc, n - i)) for i in range(0, n, max_cc)]
 
-        def run_range(r, fr=fr):
+        def run_range(r, fr=fr, ss=ss, dd=dd):
             fr.record_stream(torch.cuda.current_stream(dev))  # (read on a lane stream, allocated on the caller's)
-            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=s, crops=crops)
+            if dd == 1:
+                return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops)
+            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd)
 
         rows.append(run_chunks_on_lanes(
             model, ranges, fn=run_range,
-            prepare=lambda fr=fr: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b) for b in sorted({r[1] for r in ranges})]))
+            prepare=lambda fr=fr, dd=dd: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b, **({} if dd == 1 else {"frame_step": dd}))
+                                          for b in sorted({r[1] for r in ranges})]))
     out = torch.cat(rows, dim=0).reshape(-1, nc, 2048).cpu().numpy()
     return out if subset else np.squeeze(out)  # (the reference's np.squeeze quirk belongs to its own ten-crop call only)
 
@@ -216,32 +247,36 @@ SEGMENT_FRAMES = 16 * 188  # 3008: extract_features.py:121
 
 
 def segment_windows(n_frames: int, seg_len: int = SEGMENT_FRAMES, frames_per_clip: int = FRAMES_PER_CLIP,
-                    clip_stride: Optional[int] = None):
+                    clip_stride: Optional[int] = None, frame_step: Optional[int] = None):
     """How a long video's windows are shared out between its segments: [(segment, first window, end window, first frame, end
     frame)] over the reference's segments 0 .. n_frames // seg_len (extract_features.py:116-148), those that own no window left out.
     Segment k owns the windows that START in [k * seg_len, (k + 1) * seg_len) and therefore reads frames up to frames_per_clip -
     clip_stride past its end: frames [k * seg_len, min((k + 1) * seg_len + frames_per_clip - clip_stride, n_frames)), which taken
     as a video of their own have exactly the owned windows -- and only the video's last window can be short.  seg_len must be a
-    multiple of clip_stride (window starts would drift against the segments otherwise)."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    multiple of clip_stride (window starts would drift against the segments otherwise).  With `frame_step` d a window spans
+    frames_per_clip * d frames: the same with that span, a segment reads up to frames_per_clip * d - clip_stride past its end."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     if seg_len < 1 or seg_len % s:
         raise ValueError(f"seg_len {seg_len} is not a positive multiple of clip_stride {s}")
-    n, per_seg = n_windows(n_frames, frames_per_clip, s), seg_len // s
+    n, per_seg = n_windows(n_frames, frames_per_clip, s, d), seg_len // s
     out = []
     for seg in range(n_frames // seg_len + 1):
         w0, w1 = seg * per_seg, min((seg + 1) * per_seg, n)
         if w0 >= w1:  # nothing starts here: n_frames a multiple of seg_len, or a tail the previous segment's last window covers
             continue
-        out.append((seg, w0, w1, seg * seg_len, min((seg + 1) * seg_len + frames_per_clip - s, n_frames)))
+        out.append((seg, w0, w1, seg * seg_len, min((seg + 1) * seg_len + frames_per_clip * d - s, n_frames)))
     return out
 
 
-def feature_tag(frames_per_clip: int = FRAMES_PER_CLIP, clip_stride: Optional[int] = None, crops=None) -> str:
+def feature_tag(frames_per_clip: int = FRAMES_PER_CLIP, clip_stride: Optional[int] = None, crops=None,
+                frame_step: Optional[int] = None) -> str:
     """What a feature file's name says about how it was extracted: "" for the reference's own (back-to-back clips, ten crops),
-    "_s<stride>" for overlapping windows, then "_c<digits>" for a crop subset ("_s8_c4", "_c01234").  Files made one way are
-    never read another way."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
-    return ("" if s == frames_per_clip else f"_s{s}") + crops_tag(crops)
+    "_d<step>" for temporal sampling, "_s<stride>" for a stride other than the window span (frames_per_clip * frame_step), then
+    "_c<digits>" for a crop subset ("_s8_c4", "_c01234", "_d2", "_d2_s8_c4").  Files made one way are never read another way."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    return ("" if d == 1 else f"_d{d}") + ("" if s == frames_per_clip * d else f"_s{s}") + crops_tag(crops)
 
 
 def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Callable[[int, int], torch.Tensor], outpath: str,
@@ -253,13 +288,14 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     ones with `resize=...` in `kw`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
     in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another.
     With `crops` in `kw` the features are (n_clips, len(crops), 2048) and the files carry the set too, behind the stride:
-    `<name>_s8_c4_<seg>.npy`."""
+    `<name>_s8_c4_<seg>.npy`.  With `frame_step` in `kw` the step comes first: `<name>_d2_<seg>.npy`, `<name>_d2_s8_c4_<seg>.npy`."""
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
-    s = resolve_clip_stride(fpc, kw.get("clip_stride"))
+    d = resolve_frame_step(kw.get("frame_step"))
+    s = resolve_clip_stride(fpc, kw.get("clip_stride"), d)
     nc = len(resolve_crops(kw.get("crops")))
-    tag = feature_tag(fpc, s, kw.get("crops"))
+    tag = feature_tag(fpc, s, kw.get("crops"), d)
     seg_folder = os.path.join(outpath, name)
-    plan = segment_windows(n_frames, seg_len, fpc, s)  # (refuses a seg_len the stride does not divide before anything is written)
+    plan = segment_windows(n_frames, seg_len, fpc, s, d)  # (refuses a seg_len the stride does not divide before anything is written)
     os.makedirs(seg_folder, exist_ok=True)
     segments = []
     for seg, _w0, _w1, lo, hi in plan:
@@ -278,11 +314,12 @@ def extract_frames(sources: Iterable[Tuple[str, int, Callable[[int, int], torch.
     """Per-video driver for frame sources (name, n_frames, read_frames): `<name>_i3d.npy` per video with the reference's
     skip-if-exists rule (:106-110); videos longer than `long_video_frames` go through the per-segment cache.  With
     `clip_stride` (below frames_per_clip) the files are `<name>_i3d_s<stride>.npy`, with a crop subset
-    `<name>_i3d[_s<stride>]_c<digits>.npy` (feature_tag)."""
+    `<name>_i3d[_s<stride>]_c<digits>.npy`, with `frame_step` `<name>_i3d_d<step>[_s<stride>][_c<digits>].npy` (feature_tag)."""
     os.makedirs(outpath, exist_ok=True)
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
-    s = resolve_clip_stride(fpc, kw.get("clip_stride"))
-    suffix = "_i3d" + feature_tag(fpc, s, kw.get("crops")) + ".npy"
+    d = resolve_frame_step(kw.get("frame_step"))
+    s = resolve_clip_stride(fpc, kw.get("clip_stride"), d)
+    suffix = "_i3d" + feature_tag(fpc, s, kw.get("crops"), d) + ".npy"
     written = {}
     for name, n_frames, read_frames in sources:
         savepath = os.path.join(outpath, name + suffix)

@@ -37,11 +37,25 @@ def pr_auc(labels: Sequence[float], preds: Sequence[float]) -> float:
     return -_area(recall, precision)
 
 
-def frame_scores(scores, frames_per_clip: int = 16, clip_stride: Optional[int] = None, n_frames: Optional[int] = None) -> np.ndarray:
+def _frame_step(frame_step) -> int:
+    d = 1 if frame_step is None else int(frame_step)
+    if d < 1:
+        raise ValueError(f"frame_step {frame_step!r}: an integer >= 1")
+    return d
+
+
+def frame_scores(scores, frames_per_clip: int = 16, clip_stride: Optional[int] = None, n_frames: Optional[int] = None,
+                 frame_step: Optional[int] = None) -> np.ndarray:
     """Per-window scores (n,) -> per-frame scores, fp32 (what mil_ops.frame_scores computes on the device).  Window w covers
     frames [w * clip_stride, w * clip_stride + frames_per_clip); a frame's score is the mean of the scores of the windows
     covering it: added in ascending window order, one division by the count.  Length n_frames, default (n - 1) * clip_stride +
-    frames_per_clip; clip_stride = frames_per_clip (the default) is np.repeat(scores, frames_per_clip) bit for bit."""
+    frames_per_clip; clip_stride = frames_per_clip (the default) is np.repeat(scores, frames_per_clip) bit for bit.
+    `frame_step` d (temporal sampling: a window's frames_per_clip sampled frames stand for a span of frames_per_clip * d frames):
+    the same rule on spans -- window w covers [w * clip_stride, w * clip_stride + frames_per_clip * d), clip_stride defaults to
+    the span and may be up to it; the default stride is np.repeat(scores, frames_per_clip * d)."""
+    d = _frame_step(frame_step)
+    if d != 1:
+        return frame_scores(scores, frames_per_clip * d, frames_per_clip * d if clip_stride is None else clip_stride, n_frames)
     s = frames_per_clip if clip_stride is None else int(clip_stride)
     if not 1 <= s <= frames_per_clip:
         raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip = {frames_per_clip}]")
@@ -63,10 +77,13 @@ def frame_scores(scores, frames_per_clip: int = 16, clip_stride: Optional[int] =
     return acc / (hi - lo + 1).astype(np.float32)
 
 
-def frame_level_auc(preds_per_video, labels_per_video, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> Tuple[float, float]:
+def frame_level_auc(preds_per_video, labels_per_video, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
+                    frame_step: Optional[int] = None) -> Tuple[float, float]:
     """np.repeat(clip scores, 16) vs the frame-level ground truth (runner.py:66-76).  With `clip_stride` < frames_per_clip the
     predictions are scores of overlapping windows, assembled per video by frame_scores; a video whose labels end inside its last
-    window (the video's own length rather than the padded one) is cut there."""
+    window (the video's own length rather than the padded one) is cut there.  With `frame_step` d the windows are spans of
+    frames_per_clip * d frames (frame_scores): the same, at that span."""
+    frames_per_clip = frames_per_clip * _frame_step(frame_step)
     if clip_stride is None or int(clip_stride) == frames_per_clip:
         preds = np.repeat(np.concatenate([np.asarray(p).ravel() for p in preds_per_video]), frames_per_clip)
     else:

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
-from .ops import n_windows, pack_crops, resolve_clip_stride
+from .ops import n_windows, pack_crops, resolve_clip_stride, resolve_frame_step
 
 
 class _MilMagnitude(torch.autograd.Function):
@@ -250,13 +250,19 @@ def normalize_permute_u8(frames: torch.Tensor, mean: float = PIXEL_MEAN, std: fl
 
 
 def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
-                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
+                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None,
+                         frame_step: Optional[int] = None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) of one video -> the backbone's input (n_clips * 10, C, frames_per_clip, crop, crop)
     fp32: TenCrop, float, normalise, LoopPad and the layout permutes of TenCropVideoFrameDataset / _extract
     (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop.
     `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = ops.n_windows(F, ...).
-    `crops` (ops.resolve_crops; default all ten): (n_clips * len(crops), ...), row = clip * len(crops) + j holds crop crops[j]."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    `crops` (ops.resolve_crops; default all ten): (n_clips * len(crops), ...), row = clip * len(crops) + j holds crop crops[j].
+    `frame_step` d (default 1): sampled frame t of clip w is frames[w * clip_stride + t * d]; a clip spans frames_per_clip * d
+    frames, clip_stride defaults to that span (1 <= clip_stride <= span), and a short last clip of L = ceil((F - w * s) / d)
+    sampled frames repeats them (LoopPad): frame t >= L is frames[w * s + (t % L) * d].  Row w is the row of the call without
+    `frame_step` on those frames as a one-clip video, bit for bit; nothing is gathered."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
@@ -265,20 +271,29 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
     f, h, w, c = frames.shape
     if h < crop or w < crop:
         raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
-    n_clips = n_windows(f, frames_per_clip, s)
+    n_clips = n_windows(f, frames_per_clip, s, d)
     out = torch.empty((n_clips * nc, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_u8_crops(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, nc, packed, C_float(mean),
-                                                        C_float(std), stream()), "tencrop_normalize_u8")
+    if d == 1:
+        check(_lib.load().advhip_tencrop_normalize_u8_crops(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, nc, packed, C_float(mean),
+                                                            C_float(std), stream()), "tencrop_normalize_u8")
+    else:
+        check(_lib.load().advhip_tencrop_normalize_u8_sampled(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
+                                                              C_float(mean), C_float(std), stream()), "tencrop_normalize_u8")
     return out
 
 
 def frame_scores(scores: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
-                 n_frames: Optional[int] = None) -> torch.Tensor:
+                 n_frames: Optional[int] = None, frame_step: Optional[int] = None) -> torch.Tensor:
     """Per-window scores (n,) -> per-frame scores (n_frames,) on the device.  Window w covers frames [w * clip_stride,
     w * clip_stride + frames_per_clip); a frame's score is the mean of the scores of the windows covering it (fp32, ascending
     window order, one division by the count).  n_frames defaults to (n - 1) * clip_stride + frames_per_clip; clip_stride =
-    frames_per_clip gives np.repeat(scores, frames_per_clip) (src/runner.py:66-76) bit for bit."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    frames_per_clip gives np.repeat(scores, frames_per_clip) (src/runner.py:66-76) bit for bit.
+    `frame_step` d: the windows are spans of frames_per_clip * d frames -- window w covers [w * clip_stride, w * clip_stride +
+    frames_per_clip * d), clip_stride defaults to the span: the same kernel at that clip length; the default stride gives
+    np.repeat(scores, frames_per_clip * d)."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    frames_per_clip = frames_per_clip * d
     scores = scores.contiguous()
     require_gpu(scores)
     if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() == 0:

@@ -372,23 +372,50 @@ def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optiona
     return y
 
 
-def resolve_clip_stride(frames_per_clip: int, clip_stride: Optional[int]) -> int:
-    """The distance between window starts: None = frames_per_clip (the reference's back-to-back clips); 1 <= s <= frames_per_clip
-    (a larger stride would leave frames unseen)."""
-    s = frames_per_clip if clip_stride is None else int(clip_stride)
-    if not 1 <= s <= frames_per_clip:
-        raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip = {frames_per_clip}]")
+def resolve_frame_step(frame_step: Optional[int]) -> int:
+    """The temporal sampling step d: sampled frame t of a window is source frame start + t * d.  None = 1 (consecutive frames, the
+    reference's clips); an integer >= 1."""
+    if frame_step is None:
+        return 1
+    if isinstance(frame_step, bool) or not isinstance(frame_step, numbers.Integral) or int(frame_step) < 1:
+        raise ValueError(f"frame_step {frame_step!r}: an integer >= 1")
+    return int(frame_step)
+
+
+def resolve_clip_stride(frames_per_clip: int, clip_stride: Optional[int], frame_step: Optional[int] = None) -> int:
+    """The distance between window starts.  A window spans frames_per_clip * frame_step frames: None = that span (back-to-back
+    spans; frame_step 1: the reference's back-to-back clips); 1 <= s <= span (a larger stride would leave frames in no span)."""
+    d = resolve_frame_step(frame_step)
+    span = frames_per_clip * d
+    s = span if clip_stride is None else int(clip_stride)
+    if not 1 <= s <= span:
+        if d == 1:
+            raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip = {frames_per_clip}]")
+        raise ValueError(f"clip_stride {clip_stride} outside [1, frames_per_clip * frame_step = {span}]")
     return s
 
 
-def n_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> int:
-    """Windows of a video of `n_frames`: window w starts at frame w * clip_stride, and the last one is the first to reach the
-    video's end (it may be short: LoopPad).  clip_stride = frames_per_clip: (F - 1) // fpc + 1, the reference's clip count
-    (src/dataset.py)."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+def n_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None, frame_step: Optional[int] = None) -> int:
+    """Windows of a video of `n_frames`: window w starts at frame w * clip_stride and spans frames_per_clip * frame_step frames,
+    and the last one is the first whose span reaches the video's end (it may be short: LoopPad).  frame_step 1, clip_stride =
+    frames_per_clip: (F - 1) // fpc + 1, the reference's clip count (src/dataset.py)."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     if n_frames < 1:
         raise ValueError(f"n_windows: {n_frames} frames")
-    return 1 + max(0, -(-(n_frames - frames_per_clip) // s))
+    return 1 + max(0, -(-(n_frames - frames_per_clip * d) // s))
+
+
+def window_frame_indices(n_frames: int, w: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
+                         frame_step: Optional[int] = None) -> Tuple[int, ...]:
+    """The frames_per_clip source frames window `w` of a video of `n_frames` is made of, LoopPad included: w * s + (t % L) * d with
+    L = min(frames_per_clip, ceil((n_frames - w * s) / d)) -- what the kernels address."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    if not 0 <= w < n_windows(n_frames, frames_per_clip, s, d):
+        raise ValueError(f"window {w} of a video of {n_frames} frames")
+    length = min(frames_per_clip, -(-(n_frames - w * s) // d))
+    return tuple(w * s + (t % length) * d for t in range(frames_per_clip))
 
 
 CROP_SETS = {"ten": tuple(range(10)), "five": (0, 1, 2, 3, 4), "center": (4,), "centre": (4,), "center_flip": (4, 9)}
@@ -437,26 +464,33 @@ def crops_tag(crops) -> str:
 
 
 def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = 114.75,
-                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
+                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) -> column-parity planes (count, C, frames_per_clip, crop, 2, crop/2 + 4) of crop-clips
     [first, first + count) (row = clip * 10 + crop): TenCrop, float, normalise, LoopPad and the layout permutes of
     TenCropVideoFrameDataset / _extract (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass,
     written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's.  `clip_stride` (default
     frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride.  `crops`
-    (resolve_crops): row = clip * len(crops) + j holds crop crops[j]."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    (resolve_crops): row = clip * len(crops) + j holds crop crops[j].  `frame_step` (default 1): clip w = frames w * clip_stride +
+    t * frame_step, t in [0, frames_per_clip); clip_stride then defaults to frames_per_clip * frame_step."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
     f, h, w, c = frames.shape
-    n = n_windows(f, frames_per_clip, s) * nc
+    n = n_windows(f, frames_per_clip, s, d) * nc
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_tencrop_normalize_planes_u8_crops(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, nc, packed, first, count,
-                                                               C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
+    lib = _lib.load()
+    if d == 1:
+        check(lib.advhip_tencrop_normalize_planes_u8_crops(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, nc, packed, first, count,
+                                                           C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
+    else:
+        check(lib.advhip_tencrop_normalize_planes_u8_sampled(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, first, count,
+                                                             C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
     return xs
 
 
@@ -518,23 +552,41 @@ def with_slack(frames: torch.Tensor, slack: int = 4) -> torch.Tensor:
     return buf[: frames.numel()].view(frames.shape)
 
 
-def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None) -> torch.Tensor:
+def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
+                   frame_step: Optional[int] = None) -> torch.Tensor:
     """`frames` (F, H, W, C) on the device as WHOLE windows, (n - 1) * clip_stride + frames_per_clip frames: a short last window's
     LoopPad frames (src/gtransforms.py:119-132: frame (n - 1) * s + t % len for t in [len, frames_per_clip)) appended behind
     frame F - 1 -- a uint8 gather of < frames_per_clip frames; only the last window reads them.  Whole already: `frames`
-    itself, no copy."""
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    itself, no copy.
+    With `frame_step` d > 1 window w samples frames w * s + t * d: the whole-window buffer has (n - 1) * s + (frames_per_clip - 1) *
+    d + 1 frames, and of the frames behind F - 1 only the slots start + t * d, t >= len = ceil((F - start) / d), are written (with
+    frame start + (t % len) * d); the slots between them are never read.  A last window whose sampled frames all exist (its span
+    may still overrun the video) is whole: `frames[:that many]`, a view."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     F = frames.shape[0]
-    start = (n_windows(F, frames_per_clip, s) - 1) * s
-    length = F - start
+    start = (n_windows(F, frames_per_clip, s, d) - 1) * s
+    if d == 1:
+        length = F - start
+        if length == frames_per_clip:
+            return frames
+        idx = torch.arange(length, frames_per_clip, device=frames.device) % length + start
+        return torch.cat([frames, frames[idx]], dim=0)
+    whole = start + (frames_per_clip - 1) * d + 1
+    length = min(frames_per_clip, -(-(F - start) // d))
     if length == frames_per_clip:
-        return frames
-    idx = torch.arange(length, frames_per_clip, device=frames.device) % length + start
-    return torch.cat([frames, frames[idx]], dim=0)
+        return frames[:whole]
+    out = torch.empty((whole,) + tuple(frames.shape[1:]), device=frames.device, dtype=frames.dtype)
+    out[:F].copy_(frames)
+    t = torch.arange(length, frames_per_clip, device=frames.device)
+    out[start + t * d] = frames[start + (t % length) * d]
+    return out
 
 
-def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN):
-    key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean))
+def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
+                          frame_step: int = 1):
+    """(`frame_step`: the temporal term of the gather table is frame_step frames per tap -- part of the cache key.)"""
+    key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean)) + ((int(frame_step),) if frame_step != 1 else ())
     cache = pc.__dict__.setdefault("_u8_tables", {})
     tabs = cache.get(key)
     if tabs is None:
@@ -546,16 +598,23 @@ def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw:
         ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
         corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
         wt = torch.empty((nw.value,), device=dev, dtype=torch.float32)
-        check(lib.advhip_conv3d_u8_taps_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
-                                                     ptr(corr), ptr(wt), stream(dev)), f"conv3d_u8_taps_build_tables[{pc.name}]")
+        if frame_step == 1:
+            check(lib.advhip_conv3d_u8_taps_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
+                                                         ptr(corr), ptr(wt), stream(dev)), f"conv3d_u8_taps_build_tables[{pc.name}]")
+        else:
+            check(lib.advhip_conv3d_u8_taps_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
+                                                                 C.c_float(mean), ptr(ktab), ptr(corr), ptr(wt), stream(dev)),
+                  f"conv3d_u8_taps_build_tables[{pc.name}]")
         tabs = cache[key] = (ktab, corr, wt)
     return tabs
 
 
-def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN):
+def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
+                     frame_step: int = 1):
     """Gather / border tables of the uint8-frame stem for frames of (FH, FW) and clips of (T, crop, crop); cached on the conv
-    (built on the current stream: callers that fork streams build them first, like the other lazily built tables)."""
-    key = (tuple(frame_hw), tuple(clip_thw), float(mean))
+    (built on the current stream: callers that fork streams build them first, like the other lazily built tables).  `frame_step`:
+    the temporal term of the gather table is frame_step frames per tap -- part of the cache key."""
+    key = (tuple(frame_hw), tuple(clip_thw), float(mean)) + ((int(frame_step),) if frame_step != 1 else ())
     cache = pc.__dict__.setdefault("_u8_tables", {})
     tabs = cache.get(key)
     if tabs is None:
@@ -566,32 +625,44 @@ def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tupl
         dev = pc.w_packed.device
         ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
         corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
-        check(lib.advhip_conv3d_u8_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
-                                                ptr(corr), stream(dev)), f"conv3d_u8_build_tables[{pc.name}]")
+        if frame_step == 1:
+            check(lib.advhip_conv3d_u8_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
+                                                    ptr(corr), stream(dev)), f"conv3d_u8_build_tables[{pc.name}]")
+        else:
+            check(lib.advhip_conv3d_u8_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
+                                                            C.c_float(mean), ptr(ktab), ptr(corr), stream(dev)),
+                  f"conv3d_u8_build_tables[{pc.name}]")
         tabs = cache[key] = (ktab, corr)
     return tabs
 
 
 def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv", first: int, count: int, frames_per_clip: int = 16,
                                          crop: int = 224, out: Optional[torch.Tensor] = None, mean: float = PIXEL_MEAN,
-                                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None) -> torch.Tensor:
+                                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None,
+                                         frame_step: Optional[int] = None) -> torch.Tensor:
     """The stem (conv1 + bn1 + relu + maxpool1, src/i3d.py:303-306) of crop-clips [first, first + count) of a video given as
     resized uint8 frames (F, FH, FW, 3): row = clip * 10 + crop (TenCrop order).  TenCrop, float conversion and
     (x - mean) / std happen in the conv's load stage (src/gtransforms.py:29-38,57-73, extract_features.py:83-89).
     `clip_stride` (default frames_per_clip): clip w = frames [w * clip_stride, w * clip_stride + frames_per_clip); the frames
     are whole windows, F = (n - 1) * clip_stride + frames_per_clip (pad_windows_u8 appends a short last window's LoopPad frames).
     `crops` (resolve_crops; default all ten): row = clip * len(crops) + j holds crop crops[j], bit for bit the ten-crop row of
-    that (clip, crop); the set is a by-value argument of the same kernel."""
+    that (clip, crop); the set is a by-value argument of the same kernel.
+    `frame_step` d (default 1): clip w = frames w * clip_stride + t * d, t in [0, frames_per_clip); clip_stride defaults to
+    frames_per_clip * d, and the whole-window buffer has F = (n - 1) * clip_stride + (frames_per_clip - 1) * d + 1 frames
+    (pad_windows_u8 with the same arguments).  Scalar set-up of the same kernel plus gather tables built for d."""
     require_gpu(frames)
     require_gpu(out, contiguous=False)
-    s = resolve_clip_stride(frames_per_clip, clip_stride)
+    fstep = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, fstep)
+    reach = (frames_per_clip - 1) * fstep + 1
     nc, packed = pack_crops(crops)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != pc.cin:
         raise ValueError(f"{pc.name}: expected uint8 (F,H,W,{pc.cin}) frames, got {frames.dtype} {tuple(frames.shape)}")
     F, FH, FW, _ = frames.shape
-    if F < frames_per_clip or (F - frames_per_clip) % s or FH < crop or FW < crop:
-        raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips (stride {s}) of at least {crop}x{crop}")
-    n = ((F - frames_per_clip) // s + 1) * nc
+    if F < reach or (F - reach) % s or FH < crop or FW < crop:
+        raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips (stride {s}"
+                         + (f", frame step {fstep}" if fstep != 1 else "") + f") of at least {crop}x{crop}")
+    n = ((F - reach) // s + 1) * nc
     if count <= 0 or first < 0 or first + count > n:
         raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {n}")
     d = pc.desc(count, frames_per_clip, crop, crop, True, 0, 1)
@@ -610,14 +681,27 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     ws = workspace(frames.device, need)
     if U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64:
         frames = with_slack(frames)
-        ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
+        ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean, fstep)
+        if fstep != 1:
+            check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed,
+                                                                                   readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
+                                                                                   ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
+                                                                                   batch_stride(y), ptr(ws), need, stream()),
+                  f"conv3d_u8_taps+pool233[{pc.name}]")
+            return y
         check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed,
                                                                              readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
                                                                              ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
                                                                              batch_stride(y), ptr(ws), need, stream()),
               f"conv3d_u8_taps+pool233[{pc.name}]")
         return y
-    ktab, corr = ensure_u8_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean)
+    ktab, corr = ensure_u8_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean, fstep)
+    if fstep != 1:
+        check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed, first,
+                                                                          ptr(pc.w_packed), ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
+                                                                          C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
+              f"conv3d_u8+pool233[{pc.name}]")
+        return y
     check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed, first, ptr(pc.w_packed),
                                                                     ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
                                                                     C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),

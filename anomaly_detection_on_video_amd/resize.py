@@ -166,20 +166,27 @@ def tables(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, st
 
 
 def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, resample: Union[int, str] = "bilinear",
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None) -> torch.Tensor:
     """uint8 (F, H, W, 3) frames on the GPU -> (F, OH, OW, 3), what `GroupResize(size, resample)` gives frame by frame (PIL
     `Image.resize`, bit for bit), on the current stream with no host synchronisation.  `out` places the result in a
     caller-owned contiguous (F, OH, OW, 3) uint8 tensor (e.g. a view of a larger buffer).  Without `out`, frames already at
-    the output size are returned as they are (torchvision returns the image itself)."""
+    the output size are returned as they are (torchvision returns the image itself).
+    `frame_step` d (default 1): only source frames 0, d, 2 d, ... are resized, into a compact (ceil(F / d), OH, OW, 3) result --
+    resize_u8(frames[::d].contiguous()) byte for byte, read in place (a source frame pitch in the kernels; the workspace holds
+    the sampled frames only).  Frames already at the output size come back as the view frames[::d] (without `out`)."""
+    d = 1 if frame_step is None else int(frame_step)
+    if d < 1:
+        raise ValueError(f"resize_u8: frame_step {frame_step!r} must be an integer >= 1")
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise HipExtensionError(f"resize_u8 wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
-    F, H, W, _ = frames.shape
+    F_src, H, W, _ = frames.shape
+    F = -(-F_src // d)
     name = filter_name(resample)
     oh, ow = output_size(H, W, size)
     if out is None:
         if (oh, ow) == (H, W):
-            return frames
+            return frames if d == 1 else frames[::d]
         out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
     else:
         require_gpu(frames, out)
@@ -193,8 +200,14 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     ws = None
     if p.horizontal and p.vertical:
         ws = torch.empty((F * p.rows * ow * 3,), device=frames.device, dtype=torch.uint8)
-    check(_lib.load().advhip_resize_u8(ptr(frames), ptr(out), ptr(ws), F, H, W, 3, oh, ow,
-                                       ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
-                                       ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
-          "resize_u8")
+    if d == 1:
+        check(_lib.load().advhip_resize_u8(ptr(frames), ptr(out), ptr(ws), F, H, W, 3, oh, ow,
+                                           ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
+                                           ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
+              "resize_u8")
+    else:
+        check(_lib.load().advhip_resize_u8_sampled(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, 3, oh, ow,
+                                                   ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
+                                                   ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
+              "resize_u8")
     return out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--crops SET]]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
@@ -12,6 +12,8 @@ the entry point for a real decoder's (name, n_frames, read_frames) triples.  `--
 16-frame window every N frames instead of every 16 (`<name>_i3d_s<N>.npy`); the windows overlap in place on the device.
 `--crops ten|five|center|center_flip|0,4,9` (with `--frame-size`) extracts only those of TenCrop's ten crops
 (`<name>_i3d[_s<N>]_c<digits>.npy`, features (n_clips, len(SET), 2048)): a tenth to all of the backbone work per clip.
+`--frame-step N` (with `--frame-size`) samples every N-th frame: a window is 16 frames out of a span of 16 x N, windows start
+every `--clip-stride` frames (1 .. 16 x N, default the span), files are `<name>_i3d_d<N>[_s<stride>][_c<digits>].npy`.
 """
 import argparse
 import os
@@ -68,13 +70,18 @@ def parse_crops(text: str):
 
 
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
-         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None):
+         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None, frame_step: int = None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if clip_stride is not None and frame_size is None:
         raise ValueError("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
-    if clip_stride is not None and not 1 <= clip_stride <= 16:
-        raise ValueError(f"--clip-stride {clip_stride} outside [1, 16]")
+    if frame_step is not None and frame_size is None:
+        raise ValueError("--frame-step needs --frame-size: the clip-tensor source has no frames to sample")
+    if frame_step is not None and frame_step < 1:
+        raise ValueError(f"--frame-step {frame_step} must be at least 1")
+    span = 16 * (frame_step or 1)
+    if clip_stride is not None and not 1 <= clip_stride <= span:
+        raise ValueError(f"--clip-stride {clip_stride} outside [1, {span}]")
     if crops is not None and frame_size is None:
         raise ValueError("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
     if synthetic_weights:
@@ -84,7 +91,8 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
     if frame_size is None:
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
-        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops)
+        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops,
+                       **({} if frame_step is None else {"frame_step": frame_step}))
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -100,14 +108,20 @@ if __name__ == "__main__":
     ap.add_argument("--frame-size", type=parse_frame_size, default=None, metavar="HxW",
                     help="feed synthetic decoded uint8 frames of this size, resized to 256 on the device (default: ten-cropped clip tensors)")
     ap.add_argument("--clip-stride", type=int, default=None, metavar="N",
-                    help="with --frame-size: a 16-frame window every N frames (1..16; default 16, the reference's back-to-back clips)")
+                    help="with --frame-size: a 16-frame window every N frames (1..16 x frame step; default: that span, back-to-back windows)")
+    ap.add_argument("--frame-step", type=int, default=None, metavar="N",
+                    help="with --frame-size: temporal sampling, a window is every N-th frame of a span of 16 x N frames (default 1)")
     ap.add_argument("--crops", type=parse_crops, default=None, metavar="SET",
                     help="with --frame-size: ten (default), five, center, center_flip, or ascending TenCrop indices such as 0,4,9")
     a = ap.parse_args()
     if a.clip_stride is not None and a.frame_size is None:
         ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
-    if a.clip_stride is not None and not 1 <= a.clip_stride <= 16:
-        ap.error(f"--clip-stride {a.clip_stride} outside [1, 16]")
+    if a.frame_step is not None and a.frame_size is None:
+        ap.error("--frame-step needs --frame-size: the clip-tensor source has no frames to sample")
+    if a.frame_step is not None and a.frame_step < 1:
+        ap.error(f"--frame-step {a.frame_step} must be at least 1")
+    if a.clip_stride is not None and not 1 <= a.clip_stride <= 16 * (a.frame_step or 1):
+        ap.error(f"--clip-stride {a.clip_stride} outside [1, {16 * (a.frame_step or 1)}]")
     if a.crops is not None and a.frame_size is None:
         ap.error("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops)
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step)

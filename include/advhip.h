@@ -265,6 +265,11 @@ int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, i
                                              int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
                                              uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean, float stdv,
                                              void* stream);
+/* ... sampling every `frame_step`-th frame (advhip_tencrop_normalize_u8_sampled below); the call above is frame_step = 1. */
+int advhip_tencrop_normalize_planes_u8_sampled(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                               int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                               int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
+                                               float stdv, void* stream);
 
 /* --- the same stem, fed by resized uint8 frames (src/gtransforms.py:29-38,57-73 + extract_features.py:83-89 in the load stage)
  * frames: uint8 (F, FH, FW, Cin) -- what the decoder + GroupResize hand over -- F a whole number of clips of d->T frames.
@@ -307,6 +312,21 @@ int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_de
                                                           int64_t first_crop_clip, const float* w_packed, const int32_t* ktab_u8,
                                                           const float* corr, const float* scale, const float* shift, float stdv, float* y,
                                                           int64_t y_batch_stride, void* workspace, int64_t workspace_bytes, void* stream);
+/* Temporal sampling: clip w = frames w * clip_stride + t * frame_step, t in [0, d->T) -- every frame_step-th frame of a span of
+ * d->T * frame_step frames.  frame_step >= 1, 1 <= clip_stride <= d->T * frame_step, and the buffer holds whole windows: F >=
+ * (d->T - 1) * frame_step + 1 with (F - ((d->T - 1) * frame_step + 1)) % clip_stride == 0 (the caller puts a short last window's
+ * LoopPad frames into the slots that window samples).  The step is scalar set-up of the same kernel (window origin and the
+ * temporal term of the gather table, which advhip_conv3d_u8_build_tables_sampled builds for that frame_step: a table built for
+ * one step must not be used with another); rows are bit for bit what the call above gives for the sampled frames as a video
+ * of their own.  frame_step = 1 is the call above.  Refused (ADVHIP_EINVAL) before any launch. */
+int advhip_conv3d_u8_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step, const float* w_packed,
+                                          float mean, int32_t* ktab_u8, float* corr, void* stream);
+int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                            int32_t FW, int32_t clip_stride, int32_t frame_step, int32_t ncrops,
+                                                            uint64_t crops_packed, int64_t first_crop_clip, const float* w_packed,
+                                                            const int32_t* ktab_u8, const float* corr, const float* scale, const float* shift,
+                                                            float stdv, float* y, int64_t y_batch_stride, void* workspace,
+                                                            int64_t workspace_bytes, void* stream);
 
 /* The same stem from WHOLE PIXELS: K runs tap-major (k' = tap * 3 + c), one 4-byte LDS-DMA per (tap, position) fetches the
  * pixel's three channel bytes at the pixel's byte address (a third of the gather instructions of the byte form for the same
@@ -336,6 +356,17 @@ int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv
                                                                const int32_t* ktab_taps, const float* corr, const float* scale,
                                                                const float* shift, float stdv, float* y, int64_t y_batch_stride,
                                                                void* workspace, int64_t workspace_bytes, void* stream);
+/* ... sampling every `frame_step`-th frame, as advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32 (tables for that step). */
+int advhip_conv3d_u8_taps_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
+                                               const float* w_packed, float mean, int32_t* ktab_taps, float* corr, float* w_taps,
+                                               void* stream);
+int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                 int32_t FW, int32_t clip_stride, int32_t frame_step, int32_t ncrops,
+                                                                 uint64_t crops_packed, int64_t readable_bytes, int64_t first_crop_clip,
+                                                                 const float* w_taps, const int32_t* ktab_taps, const float* corr,
+                                                                 const float* scale, const float* shift, float stdv, float* y,
+                                                                 int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                                 void* stream);
 
 /* y = MaxPool3d(k=(2,1,1), s=(2,1,1))( act( conv3d(x, w) * scale + shift (+ residual) ) ) for a 1x1x1 stride-1 conv
  * (Cin a multiple of 32) in ONE launch: the last Bottleneck of layer1 followed by maxpool2 (src/i3d.py:111-121, 309).
@@ -702,6 +733,15 @@ int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t
 int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                       int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops, uint64_t crops_packed,
                                       float mean, float stdv, void* stream);
+/* Temporal sampling: frame t of window w is frames[w * clip_stride + t * frame_step] -- every frame_step-th frame of a span of
+ * frames_per_clip * frame_step frames.  frame_step >= 1, 1 <= clip_stride <= frames_per_clip * frame_step (above it frames would
+ * lie in no span); n = 1 + max(0, ceil((F - frames_per_clip * frame_step) / clip_stride)) windows; only the last can be short:
+ * len = min(frames_per_clip, ceil((F - (n - 1) * clip_stride) / frame_step)) sampled frames, and frame t >= len is
+ * frames[(n - 1) * clip_stride + (t % len) * frame_step] (LoopPad).  Row w = the row of the call above for those sampled frames
+ * as a one-clip video, bit for bit; frame_step = 1 is the call above.  Refused (ADVHIP_EINVAL) before the launch. */
+int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                        int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop, int32_t ncrops,
+                                        uint64_t crops_packed, float mean, float stdv, void* stream);
 
 /* Per-window scores (n_windows,) -> per-frame scores (n_frames,): window w covers frames [w * clip_stride, w * clip_stride +
  * frames_per_clip); the score of a frame is the mean of the scores of the windows covering it (fp32, added in ascending window
@@ -722,6 +762,13 @@ int advhip_frame_scores_f32(const float* scores, float* out, int64_t n_windows, 
 int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F, int32_t H, int32_t W, int32_t C, int32_t OH,
                      int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds,
                      const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream);
+/* The same for every frame_step-th frame: source frames 0, frame_step, 2 frame_step, ... of src (F_src, H, W, C) into a compact
+ * dst (ceil(F_src / frame_step), OH, OW, C) -- a source frame pitch in both passes; ws: uint8 (ceil(F_src / frame_step), rows, OW,
+ * C), the sampled frames only.  Each output frame is byte for byte the call above's for that source frame; frame_step = 1 is
+ * the call above. */
+int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
+                             int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                             const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream);
 
 #ifdef __cplusplus
 }
