@@ -6,6 +6,14 @@
 
 #include "../../include/advhip.h"
 
+#define ADVHIP_REQUIRE(cond, ...)        \
+  do {                                   \
+    if (!(cond)) {                       \
+      advhip::set_error(__VA_ARGS__);    \
+      return ADVHIP_EINVAL;              \
+    }                                    \
+  } while (0)
+
 namespace advhip {
 
 void set_error(const char* fmt, ...);
@@ -52,12 +60,43 @@ inline const char* crops_packed_error(int ncrops, unsigned long long packed) {
   return nullptr;
 }
 
-}  // namespace advhip
+// The clip-sampling rule of the uint8-frame ops, host side.  Window w of a video samples frames w * clip_stride + t * frame_step,
+// t in [0, fpc); row w * ncrops + j of an op's output holds crop (crops >> 4 j) & 15 of window w.  The kernels restate the frame
+// index on the device; every count and every check of the five numbers is here.
+struct ClipSampling {
+  int fpc, clip_stride, frame_step, ncrops;
+  unsigned long long crops;
 
-#define ADVHIP_REQUIRE(cond, ...)        \
-  do {                                   \
-    if (!(cond)) {                       \
-      advhip::set_error(__VA_ARGS__);    \
-      return ADVHIP_EINVAL;              \
-    }                                    \
-  } while (0)
+  int check_crops(const char* who) const {
+    const char* why = crops_packed_error(ncrops, crops);
+    ADVHIP_REQUIRE(!why, "%s: crop set (%d, 0x%llx): %s", who, ncrops, crops, why);
+    return ADVHIP_OK;
+  }
+  // `span_limit`: the op's own bound on fpc * frame_step (what its kernel's index arithmetic holds)
+  int check_windows(const char* who, long long span_limit) const {
+    ADVHIP_REQUIRE(frame_step >= 1 && (long long)fpc * frame_step < span_limit, "%s: frame step %d", who, frame_step);
+    ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= fpc * frame_step, "%s: clip stride %d outside [1, %d]", who, clip_stride,
+                   fpc * frame_step);
+    return ADVHIP_OK;
+  }
+  // windows of a video of F frames; the last one may be short (LoopPad repeats it)
+  long long video_windows(long long F) const {
+    const long long span = (long long)fpc * frame_step;
+    return 1 + (F > span ? (F - span + clip_stride - 1) / clip_stride : 0);
+  }
+  // windows of a buffer that holds whole windows only: F = (n - 1) * clip_stride + (fpc - 1) * frame_step + 1 for n >= 1
+  // (frame_step = 1, clip_stride = fpc: whole back-to-back clips); any other F is refused
+  int buffer_windows(const char* who, long long F, long long* n) const {
+    const long long reach = (long long)(fpc - 1) * frame_step + 1;  // frames from a window's first sampled frame to its last
+    const bool whole = F >= reach && (F - reach) % clip_stride == 0;
+    ADVHIP_REQUIRE(frame_step > 1 || whole, "%s: %lld frames are not whole clips of %d at stride %d", who, F, fpc, clip_stride);
+    ADVHIP_REQUIRE(whole, "%s: %lld frames are not whole clips of %d, one frame in %d, at stride %d", who, F, fpc, frame_step, clip_stride);
+    *n = (F - reach) / clip_stride + 1;
+    return ADVHIP_OK;
+  }
+};
+
+// torchvision center_crop's offset: int(round(d / 2.0)) with Python's round-half-to-even
+inline int half_even(int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); }
+
+}  // namespace advhip

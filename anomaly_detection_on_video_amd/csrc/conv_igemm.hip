@@ -3524,6 +3524,38 @@ extern "C" int64_t advhip_conv3d_relu_maxpool233_workspace_bytes(const advhip_co
   return bricks * d->Cout * POOL_SLOTS * (int64_t)sizeof(float);
 }
 
+// What the four ...maxpool233 launchers share: the pooled dims, the workspace and y checks, then `fill` (the form's own operand
+// set-up and checks), the brick plan, `launch` (the form's conv kernel, which leaves per-brick partial maxima in the workspace)
+// and the merge.  Every check before the first launch: a rejected call must not leave half an op enqueued.
+template <class Fill, class Launch>
+static int conv_pool233(const char* who, const advhip_conv3d_desc* d, const Geometry& g, float* y, int64_t y_batch_stride, void* workspace,
+                        int64_t workspace_bytes, void* stream, Fill fill, Launch launch) {
+  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
+  ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "%s: conv output (%d,%d,%d) smaller than the (2,3,3) window", who, g.To, g.Ho, g.Wo);
+  const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
+  ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= need && need < 0xF0000000ll, "%s: needs a %lld-byte workspace (got %lld)", who,
+                 (long long)need, (long long)workspace_bytes);
+  const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
+  const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
+  ADVHIP_REQUIRE(ybs >= y_dense, "%s: y batch stride %lld smaller than one pooled sample (%lld)", who, ybs, y_dense);
+  ConvArgs a;
+  if (int rc = fill(a)) return rc;
+  a.y = reinterpret_cast<float*>(workspace);
+  a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
+  const int nbh = (2 * Hp + 1 + 3) / 4, nbw = (2 * Wp + 1 + 15) / 16;
+  set_bricks(a, Tp, nbh, nbw);
+  ADVHIP_REQUIRE(nbw <= MERGE_MAX_NBW, "%s: pooled width %d above %d", who, Wp, MERGE_MAX_NBW * 8 - 1);
+  const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
+  ADVHIP_REQUIRE(rows < (1ll << 31), "%s: too many output rows", who);
+  hipStream_t st = (hipStream_t)stream;
+  launch(a, st);
+  if (int rc = check_launch(who)) return rc;
+  const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
+  hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
+                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
+  return check_launch("stem_pool_merge");
+}
+
 extern "C" int advhip_conv3d_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const float* x, int64_t x_batch_stride,
                                                     const float* w_packed, const int32_t* ktab, const float* scale,
                                                     const float* shift, float* y, int64_t y_batch_stride, void* workspace,
@@ -3531,34 +3563,15 @@ extern "C" int advhip_conv3d_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d,
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(x && w_packed && ktab && scale && shift && y, "conv3d+pool233: null pointer");
   const Geometry g = geometry(d);
-  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
-  ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
-  const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
-  ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= need && need < 0xF0000000ll,
-                 "conv3d+pool233: needs a %lld-byte workspace (got %lld)", (long long)need, (long long)workspace_bytes);
-  const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
-  const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
-  ADVHIP_REQUIRE(ybs >= y_dense, "conv3d+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
-  ConvArgs a;
-  if (int rc = fill_pool_args(a, d, g, x, x_batch_stride, w_packed, ktab, scale, shift, false)) return rc;
-  a.y = reinterpret_cast<float*>(workspace);  // per-brick partial maxima
-  a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
-  const int nbh = (2 * Hp + 1 + 3) / 4, nbw = (2 * Wp + 1 + 15) / 16;
-  set_bricks(a, Tp, nbh, nbw);
-  // (every check before the first launch: a rejected call must not leave half an op enqueued)
-  ADVHIP_REQUIRE(nbw <= MERGE_MAX_NBW, "conv3d+pool233: pooled width %d above %d", Wp, MERGE_MAX_NBW * 8 - 1);
-  const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
-  ADVHIP_REQUIRE(rows < (1ll << 31), "conv3d+pool233: too many output rows");
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
-  const bool nocheck = d->kt == 1 && d->kh == 1 && d->kw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 && g.K == g.Kpad;
-  if (nocheck) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_POOL233>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233>), grid, dim3(256), 0, st, a);
-  if (int rc = check_launch("conv3d+pool233")) return rc;
-  const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
-  hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
-                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
-  return check_launch("stem_pool_merge");
+  return conv_pool233(
+      "conv3d+pool233", d, g, y, y_batch_stride, workspace, workspace_bytes, stream,
+      [&](ConvArgs& a) { return fill_pool_args(a, d, g, x, x_batch_stride, w_packed, ktab, scale, shift, false); },
+      [&](const ConvArgs& a, hipStream_t st) {
+        const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
+        const bool nocheck = d->kt == 1 && d->kh == 1 && d->kw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 && g.K == g.Kpad;
+        if (nocheck) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_POOL233>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233>), grid, dim3(256), 0, st, a);
+      });
 }
 
 // ---- the same stem on column-parity planes of its input (16-byte A pieces for the stride-2 gather) --------------------------
@@ -3602,59 +3615,38 @@ extern "C" int advhip_conv3d_s2w_bn_relu_maxpool233_f32(const advhip_conv3d_desc
   ADVHIP_REQUIRE(xs && w_packed && ktab_s2w && scale && shift && y, "conv3d s2w+pool233: null pointer");
   const Geometry g = geometry(d);
   if (int rc = s2w_check(d, g)) return rc;
-  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
-  ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d s2w+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
-  const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
-  ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= need && need < 0xF0000000ll,
-                 "conv3d s2w+pool233: needs a %lld-byte workspace (got %lld)", (long long)need, (long long)workspace_bytes);
-  const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
-  const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
-  ADVHIP_REQUIRE(ybs >= y_dense, "conv3d s2w+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
-  const int WP = d->W / 2 + S2W_PAD, rowp = 2 * WP;
-  const long long xs_dense = (long long)d->Cin * d->T * d->H * rowp;
-  const long long xbs = xs_batch_stride > 0 ? xs_batch_stride : xs_dense;
-  ADVHIP_REQUIRE(xbs >= xs_dense && ((uintptr_t)xs & 15) == 0, "conv3d s2w+pool233: xs batch stride %lld smaller than one sample (%lld) or xs not 16-byte aligned", xbs, xs_dense);
-  ConvArgs a;
-  if (int rc = fill_pool_args(a, d, g, xs, 0, w_packed, ktab_s2w, scale, shift, false)) return rc;
-  // the gather's view of the input: rows of 2 * WP floats
-  const long long in_elems = (long long)(d->B - 1) * xbs + xs_dense;
-  ADVHIP_REQUIRE(in_elems < (1ll << 30), "conv3d s2w+pool233: input above 4 GiB");
-  a.x_bstride = (int)xbs;
-  a.s2w_rowp = rowp;
-  a.ktab_s2w = reinterpret_cast<const int2*>(ktab_s2w);
-  a.pad_off = (d->pt * d->H + d->ph) * rowp;
-  a.x_bytes = (unsigned)((in_elems + a.pad_off) * 4);
-  a.y = reinterpret_cast<float*>(workspace);  // per-brick partial maxima
-  a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
-  const int nbh = (2 * Hp + 1 + 3) / 4, nbw = (2 * Wp + 1 + 15) / 16;
-  set_bricks(a, Tp, nbh, nbw);
-  ADVHIP_REQUIRE(nbw <= MERGE_MAX_NBW, "conv3d s2w+pool233: pooled width %d above %d", Wp, MERGE_MAX_NBW * 8 - 1);
-  const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
-  ADVHIP_REQUIRE(rows < (1ll << 31), "conv3d s2w+pool233: too many output rows");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233, false, 1>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
-  if (int rc = check_launch("conv3d s2w+pool233")) return rc;
-  const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
-  hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
-                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
-  return check_launch("stem_pool_merge");
+  return conv_pool233(
+      "conv3d s2w+pool233", d, g, y, y_batch_stride, workspace, workspace_bytes, stream,
+      [&](ConvArgs& a) -> int {
+        const int WP = d->W / 2 + S2W_PAD, rowp = 2 * WP;
+        const long long xs_dense = (long long)d->Cin * d->T * d->H * rowp;
+        const long long xbs = xs_batch_stride > 0 ? xs_batch_stride : xs_dense;
+        ADVHIP_REQUIRE(xbs >= xs_dense && ((uintptr_t)xs & 15) == 0, "conv3d s2w+pool233: xs batch stride %lld smaller than one sample (%lld) or xs not 16-byte aligned", xbs, xs_dense);
+        if (int rc = fill_pool_args(a, d, g, xs, 0, w_packed, ktab_s2w, scale, shift, false)) return rc;
+        // the gather's view of the input: rows of 2 * WP floats
+        const long long in_elems = (long long)(d->B - 1) * xbs + xs_dense;
+        ADVHIP_REQUIRE(in_elems < (1ll << 30), "conv3d s2w+pool233: input above 4 GiB");
+        a.x_bstride = (int)xbs;
+        a.s2w_rowp = rowp;
+        a.ktab_s2w = reinterpret_cast<const int2*>(ktab_s2w);
+        a.pad_off = (d->pt * d->H + d->ph) * rowp;
+        a.x_bytes = (unsigned)((in_elems + a.pad_off) * 4);
+        return ADVHIP_OK;
+      },
+      [&](const ConvArgs& a, hipStream_t st) {
+        hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233, false, 1>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
+      });
 }
 
 // ---- stem + maxpool1 straight from resized uint8 frames (TenCrop, float conversion and normalisation in the load stage) ----
 namespace advhip {
-// the frames buffer of the fused stems holds whole windows: window w samples frames w * clip_stride + t * frame_step, t in [0, T),
-// so F = (n - 1) * clip_stride + (T - 1) * frame_step + 1 for n >= 1 windows (frame_step = 1, clip_stride = T: whole back-to-back
-// clips).  *n_clips receives n.
-static int u8_check_frames(const advhip_conv3d_desc* d, int64_t F, int FH, int FW, int clip_stride, int frame_step = 1, int64_t* n_clips = nullptr) {
-  ADVHIP_REQUIRE(frame_step >= 1 && (long long)d->T * frame_step < (1ll << 24), "conv3d u8: frame step %d", frame_step);
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= d->T * frame_step, "conv3d u8: clip stride %d outside [1, %d]", clip_stride,
-                 d->T * frame_step);
-  const int64_t reach = (int64_t)(d->T - 1) * frame_step + 1;  // frames from a window's first sampled frame to its last
-  ADVHIP_REQUIRE(frame_step > 1 || (F >= reach && (F - reach) % clip_stride == 0), "conv3d u8: %lld frames are not whole clips of %d at stride %d",
-                 (long long)F, d->T, clip_stride);
-  ADVHIP_REQUIRE(F >= reach && (F - reach) % clip_stride == 0, "conv3d u8: %lld frames are not whole clips of %d, one frame in %d, at stride %d",
-                 (long long)F, d->T, frame_step, clip_stride);
-  if (n_clips) *n_clips = (F - reach) / clip_stride + 1;
+// the stems' own limits on a frames buffer of whole windows (ClipSampling::buffer_windows); *n_clips receives their count
+static int u8_check_frames(const advhip_conv3d_desc* d, const ClipSampling& s, int64_t F, int FH, int FW, int64_t* n_clips = nullptr) {
+  const int frame_step = s.frame_step;
+  if (int rc = s.check_windows("conv3d u8", 1ll << 24)) return rc;
+  long long n = 0;
+  if (int rc = s.buffer_windows("conv3d u8", F, &n)) return rc;
+  if (n_clips) *n_clips = n;
   ADVHIP_REQUIRE(FH >= d->H && FW >= d->W, "conv3d u8: frames (%d x %d) smaller than the %d x %d crop", FH, FW, d->H, d->W);
   ADVHIP_REQUIRE(d->kt <= 10 && d->kh <= 10 && d->kw <= 10, "conv3d u8: kernel extents above 10");
   ADVHIP_REQUIRE(F * FH * FW * d->Cin < (1ll << 31) - (1 << 24), "conv3d u8: frames tensor above 2 GiB");
@@ -3676,17 +3668,17 @@ extern "C" int advhip_conv3d_u8_table_sizes(const advhip_conv3d_desc* d, int64_t
   return ADVHIP_OK;
 }
 
-extern "C" int advhip_conv3d_u8_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
-                                             int32_t* ktab_u8, float* corr, void* stream) {
-  return advhip_conv3d_u8_build_tables_sampled(d, FH, FW, 1, w_packed, mean, ktab_u8, corr, stream);
+// a one-window buffer: what a table build checks of the frame geometry and the step
+static int u8_check_one_window(const advhip_conv3d_desc* d, int FH, int FW, int frame_step) {
+  return u8_check_frames(d, {d->T, d->T * frame_step, frame_step, 10, TENCROP_ALL}, (int64_t)(d->T - 1) * frame_step + 1, FH, FW);
 }
 
-extern "C" int advhip_conv3d_u8_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
-                                                     const float* w_packed, float mean, int32_t* ktab_u8, float* corr, void* stream) {
+static int u8_build_tables(const advhip_conv3d_desc* d, int FH, int FW, int frame_step, const float* w_packed, float mean, int32_t* ktab_u8,
+                           float* corr, void* stream) {
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_u8 && corr, "conv3d u8 tables: null pointer");
   ADVHIP_REQUIRE(frame_step >= 1, "conv3d u8 tables: frame step %d", frame_step);
-  if (int rc = u8_check_frames(d, (int64_t)(d->T - 1) * frame_step + 1, FH, FW, d->T * frame_step, frame_step)) return rc;
+  if (int rc = u8_check_one_window(d, FH, FW, frame_step)) return rc;
   const Geometry g = geometry(d);
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
@@ -3699,95 +3691,17 @@ extern "C" int advhip_conv3d_u8_build_tables_sampled(const advhip_conv3d_desc* d
   return check_launch("conv3d_u8_build_tables");
 }
 
-extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
-                                                               int32_t FW, int64_t first_crop_clip, const float* w_packed,
-                                                               const int32_t* ktab_u8, const float* corr,
-                                                               const float* scale, const float* shift, float stdv, float* y,
-                                                               int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
-                                                               void* stream) {
-  if (int rc = validate(d)) return rc;
-  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(d, frames, F, FH, FW, d->T, first_crop_clip, w_packed, ktab_u8, corr, scale, shift,
-                                                                 stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
+extern "C" int advhip_conv3d_u8_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
+                                             int32_t* ktab_u8, float* corr, void* stream) {
+  return u8_build_tables(d, FH, FW, 1, w_packed, mean, ktab_u8, corr, stream);
 }
 
-extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
-                                                                       int32_t FW, int32_t clip_stride, int64_t first_crop_clip,
-                                                                       const float* w_packed, const int32_t* ktab_u8, const float* corr,
-                                                                       const float* scale, const float* shift, float stdv, float* y,
-                                                                       int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
-                                                                       void* stream) {
-  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(d, frames, F, FH, FW, clip_stride, 10, TENCROP_ALL, first_crop_clip, w_packed,
-                                                               ktab_u8, corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes,
-                                                               stream);
+extern "C" int advhip_conv3d_u8_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
+                                                     const float* w_packed, float mean, int32_t* ktab_u8, float* corr, void* stream) {
+  return u8_build_tables(d, FH, FW, frame_step, w_packed, mean, ktab_u8, corr, stream);
 }
 
-extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
-                                                                     int32_t FW, int32_t clip_stride, int32_t ncrops, uint64_t crops_packed,
-                                                                     int64_t first_crop_clip, const float* w_packed, const int32_t* ktab_u8,
-                                                                     const float* corr, const float* scale, const float* shift, float stdv,
-                                                                     float* y, int64_t y_batch_stride, void* workspace,
-                                                                     int64_t workspace_bytes, void* stream) {
-  return advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, first_crop_clip,
-                                                                 w_packed, ktab_u8, corr, scale, shift, stdv, y, y_batch_stride, workspace,
-                                                                 workspace_bytes, stream);
-}
-
-extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
-                                                                       int32_t FW, int32_t clip_stride, int32_t frame_step, int32_t ncrops,
-                                                                       uint64_t crops_packed, int64_t first_crop_clip, const float* w_packed,
-                                                                       const int32_t* ktab_u8, const float* corr, const float* scale,
-                                                                       const float* shift, float stdv, float* y, int64_t y_batch_stride,
-                                                                       void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  if (const char* why = crops_packed_error(ncrops, crops_packed))
-    ADVHIP_REQUIRE(false, "conv3d u8+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
-  ADVHIP_REQUIRE(frames && w_packed && ktab_u8 && corr && scale && shift && y, "conv3d u8+pool233: null pointer");
-  ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8+pool233: padding not smaller than the kernel");
-  ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8+pool233: std must be non-zero");
-  int64_t n_clips = 0;
-  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, frame_step, &n_clips)) return rc;
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
-                 "conv3d u8+pool233: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
-  const Geometry g = geometry(d);
-  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
-  ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
-  const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
-  ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= need && need < 0xF0000000ll,
-                 "conv3d u8+pool233: needs a %lld-byte workspace (got %lld)", (long long)need, (long long)workspace_bytes);
-  const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
-  const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
-  ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
-  ConvArgs a;
-  if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_packed, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride; a.u8_fstep = frame_step;
-  a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
-  // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
-  auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
-  a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
-  a.in_std = stdv;  // (the mean went into `corr` when the tables were built)
-  a.ktab_u8 = reinterpret_cast<const int2*>(ktab_u8); a.pad_corr = corr;
-  // byte offsets: the window origin of a border output lies up to (pt sampled frames, ph, pw + kw - 1) before the crop's corner
-  a.pad_off = (d->pt * frame_step * FH * FW + d->ph * FW + d->pw + d->kw) * d->Cin;
-  a.x_bytes = (unsigned)(F * FH * FW * d->Cin + a.pad_off);
-  a.y = reinterpret_cast<float*>(workspace);
-  a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
-  const int nbh = (2 * Hp + 1 + 3) / 4, nbw = (2 * Wp + 1 + 15) / 16;
-  set_bricks(a, Tp, nbh, nbw);
-  // (every check before the first launch: a rejected call must not leave half an op enqueued)
-  ADVHIP_REQUIRE(nbw <= MERGE_MAX_NBW, "conv3d u8+pool233: pooled width %d above %d", Wp, MERGE_MAX_NBW * 8 - 1);
-  const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
-  ADVHIP_REQUIRE(rows < (1ll << 31), "conv3d u8+pool233: too many output rows");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233, true>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
-  if (int rc = check_launch("conv3d u8+pool233")) return rc;
-  const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
-  hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
-                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
-  return check_launch("stem_pool_merge");
-}
-
-// ---- the same from whole pixels (stem_u8_tap_kernel): tables and launch ----------------------------------------------------
+// ---- the same from whole pixels (stem_u8_tap_kernel): tables ----------------------------------------------------
 namespace advhip {
 constexpr int U8_TAPS_PER_TILE = 8;  // (16: 2.62 ms against 2.50 at B = 32 -- 3 % more padded K and 4 instead of 6 workgroups per CU)
 static int u8_taps_pad(const advhip_conv3d_desc* d) {
@@ -3805,19 +3719,13 @@ extern "C" int advhip_conv3d_u8_taps_table_sizes(const advhip_conv3d_desc* d, in
   return ADVHIP_OK;
 }
 
-extern "C" int advhip_conv3d_u8_taps_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
-                                                  int32_t* ktab_taps, float* corr, float* w_taps, void* stream) {
-  return advhip_conv3d_u8_taps_build_tables_sampled(d, FH, FW, 1, w_packed, mean, ktab_taps, corr, w_taps, stream);
-}
-
-extern "C" int advhip_conv3d_u8_taps_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
-                                                          const float* w_packed, float mean, int32_t* ktab_taps, float* corr, float* w_taps,
-                                                          void* stream) {
+static int u8_taps_build_tables(const advhip_conv3d_desc* d, int FH, int FW, int frame_step, const float* w_packed, float mean, int32_t* ktab_taps,
+                                float* corr, float* w_taps, void* stream) {
   if (int rc = validate(d)) return rc;
   ADVHIP_REQUIRE(w_packed && ktab_taps && corr && w_taps, "conv3d u8 taps tables: null pointer");
   ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
   ADVHIP_REQUIRE(frame_step >= 1, "conv3d u8 taps tables: frame step %d", frame_step);
-  if (int rc = u8_check_frames(d, (int64_t)(d->T - 1) * frame_step + 1, FH, FW, d->T * frame_step, frame_step)) return rc;
+  if (int rc = u8_check_one_window(d, FH, FW, frame_step)) return rc;
   int64_t total = 0;
   advhip_conv3d_u8_table_sizes(d, nullptr, &total);
   ADVHIP_REQUIRE(total < (1ll << 28), "conv3d u8 taps tables: padding (%d,%d,%d) too large", d->pt, d->ph, d->pw);
@@ -3832,6 +3740,106 @@ extern "C" int advhip_conv3d_u8_taps_build_tables_sampled(const advhip_conv3d_de
   return check_launch("conv3d_u8_taps_build_tables");
 }
 
+extern "C" int advhip_conv3d_u8_taps_build_tables(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, const float* w_packed, float mean,
+                                                  int32_t* ktab_taps, float* corr, float* w_taps, void* stream) {
+  return u8_taps_build_tables(d, FH, FW, 1, w_packed, mean, ktab_taps, corr, w_taps, stream);
+}
+
+extern "C" int advhip_conv3d_u8_taps_build_tables_sampled(const advhip_conv3d_desc* d, int32_t FH, int32_t FW, int32_t frame_step,
+                                                          const float* w_packed, float mean, int32_t* ktab_taps, float* corr, float* w_taps,
+                                                          void* stream) {
+  return u8_taps_build_tables(d, FH, FW, frame_step, w_packed, mean, ktab_taps, corr, w_taps, stream);
+}
+
+// ---- the two fused stems: one launcher.  `taps` = whole pixels (stem_u8_tap_kernel on w_taps / ktab_taps, pixels fetched as 4-byte
+// pieces, hence `readable_bytes`); otherwise bytes (the LDS-DMA kernel on w_packed / ktab_u8; `readable_bytes` unused) ----
+static int u8_stem_pool233(bool taps, const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int FH, int FW, int clip_stride,
+                           int frame_step, int ncrops, uint64_t crops_packed, int64_t readable_bytes, int64_t first_crop_clip, const float* w,
+                           const int32_t* ktab, const float* corr, const float* scale, const float* shift, float stdv, float* y,
+                           int64_t y_batch_stride, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = taps ? "conv3d u8 taps+pool233" : "conv3d u8+pool233";
+  if (int rc = validate(d)) return rc;
+  const ClipSampling s{d->T, clip_stride, frame_step, ncrops, crops_packed};
+  if (int rc = s.check_crops(who)) return rc;
+  ADVHIP_REQUIRE(frames && w && ktab && corr && scale && shift && y, "%s: null pointer", who);
+  ADVHIP_REQUIRE(!taps || (d->Cin == 3 && d->Cout == 64), "%s: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", who, d->Cin, d->Cout);
+  ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "%s: padding not smaller than the kernel", who);
+  ADVHIP_REQUIRE(stdv != 0.f, "%s: std must be non-zero", who);
+  int64_t n_clips = 0;
+  if (int rc = u8_check_frames(d, s, F, FH, FW, &n_clips)) return rc;
+  const int64_t fbytes = F * FH * FW * d->Cin;
+  ADVHIP_REQUIRE(!taps || readable_bytes >= fbytes + 1, "%s: the frames allocation must extend one byte past the last pixel "
+                 "(pixels are fetched as 4-byte pieces): %lld readable, %lld needed", who, (long long)readable_bytes, (long long)fbytes + 1);
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
+                 "%s: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", who, (long long)first_crop_clip,
+                 (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
+  const Geometry g = geometry(d);
+  return conv_pool233(
+      who, d, g, y, y_batch_stride, workspace, workspace_bytes, stream,
+      [&](ConvArgs& a) -> int {
+        if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w, nullptr, scale, shift, false)) return rc;
+        a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride; a.u8_fstep = frame_step;
+        a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
+        a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
+        a.in_std = stdv;  // (the mean went into `corr` when the tables were built)
+        a.ktab_u8 = reinterpret_cast<const int2*>(ktab); a.pad_corr = corr;
+        // byte offsets: the window origin of a border output lies up to (pt sampled frames, ph, pw + kw - 1) before the crop's corner
+        a.pad_off = (d->pt * frame_step * FH * FW + d->ph * FW + d->pw + d->kw) * d->Cin;
+        a.x_bytes = (unsigned)((taps ? std::min<int64_t>(readable_bytes, fbytes + 4) : fbytes) + a.pad_off);
+        if (taps) {
+          a.Kpad = 3 * u8_taps_pad(d);
+          a.w_bytes = (unsigned)((long long)a.Kpad * d->Cout * 4);
+        }
+        return ADVHIP_OK;
+      },
+      [&](const ConvArgs& a, hipStream_t st) {
+        if (!taps) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233, true>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((stem_u8_tap_kernel<U8_TAPS_PER_TILE>), dim3((unsigned)a.tiles_m), dim3(256), 0, st, a);
+      });
+}
+
+// (the plain / _strided / _crops names fill in the sampling arguments they lack: back-to-back clips, all ten crops, every frame)
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                               int32_t FW, int64_t first_crop_clip, const float* w_packed,
+                                                               const int32_t* ktab_u8, const float* corr,
+                                                               const float* scale, const float* shift, float stdv, float* y,
+                                                               int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                               void* stream) {
+  if (int rc = validate(d)) return rc;
+  return u8_stem_pool233(false, d, frames, F, FH, FW, d->T, 1, 10, TENCROP_ALL, 0, first_crop_clip, w_packed, ktab_u8, corr, scale, shift, stdv, y,
+                         y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                       int32_t FW, int32_t clip_stride, int64_t first_crop_clip,
+                                                                       const float* w_packed, const int32_t* ktab_u8, const float* corr,
+                                                                       const float* scale, const float* shift, float stdv, float* y,
+                                                                       int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
+                                                                       void* stream) {
+  return u8_stem_pool233(false, d, frames, F, FH, FW, clip_stride, 1, 10, TENCROP_ALL, 0, first_crop_clip, w_packed, ktab_u8, corr, scale, shift,
+                         stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                     int32_t FW, int32_t clip_stride, int32_t ncrops, uint64_t crops_packed,
+                                                                     int64_t first_crop_clip, const float* w_packed, const int32_t* ktab_u8,
+                                                                     const float* corr, const float* scale, const float* shift, float stdv,
+                                                                     float* y, int64_t y_batch_stride, void* workspace,
+                                                                     int64_t workspace_bytes, void* stream) {
+  return u8_stem_pool233(false, d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, 0, first_crop_clip, w_packed, ktab_u8, corr, scale,
+                         shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
+                                                                       int32_t FW, int32_t clip_stride, int32_t frame_step, int32_t ncrops,
+                                                                       uint64_t crops_packed, int64_t first_crop_clip, const float* w_packed,
+                                                                       const int32_t* ktab_u8, const float* corr, const float* scale,
+                                                                       const float* shift, float stdv, float* y, int64_t y_batch_stride,
+                                                                       void* workspace, int64_t workspace_bytes, void* stream) {
+  return u8_stem_pool233(false, d, frames, F, FH, FW, clip_stride, frame_step, ncrops, crops_packed, 0, first_crop_clip, w_packed, ktab_u8, corr,
+                         scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
+}
+
 extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
                                                                     int32_t FW, int64_t readable_bytes, int64_t first_crop_clip,
                                                                     const float* w_taps, const int32_t* ktab_taps, const float* corr,
@@ -3839,9 +3847,8 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_f32(const advhip
                                                                     int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                     void* stream) {
   if (int rc = validate(d)) return rc;
-  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(d, frames, F, FH, FW, d->T, readable_bytes, first_crop_clip, w_taps, ktab_taps,
-                                                                      corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes,
-                                                                      stream);
+  return u8_stem_pool233(true, d, frames, F, FH, FW, d->T, 1, 10, TENCROP_ALL, readable_bytes, first_crop_clip, w_taps, ktab_taps, corr, scale,
+                         shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
 }
 
 extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F,
@@ -3850,9 +3857,8 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_strided_f32(cons
                                                                             const int32_t* ktab_taps, const float* corr, const float* scale,
                                                                             const float* shift, float stdv, float* y, int64_t y_batch_stride,
                                                                             void* workspace, int64_t workspace_bytes, void* stream) {
-  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(d, frames, F, FH, FW, clip_stride, 10, TENCROP_ALL, readable_bytes,
-                                                                    first_crop_clip, w_taps, ktab_taps, corr, scale, shift, stdv, y,
-                                                                    y_batch_stride, workspace, workspace_bytes, stream);
+  return u8_stem_pool233(true, d, frames, F, FH, FW, clip_stride, 1, 10, TENCROP_ALL, readable_bytes, first_crop_clip, w_taps, ktab_taps, corr,
+                         scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
 }
 
 extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F, int32_t FH,
@@ -3862,9 +3868,8 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(const 
                                                                           const float* scale, const float* shift, float stdv, float* y,
                                                                           int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
                                                                           void* stream) {
-  return advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, readable_bytes,
-                                                                      first_crop_clip, w_taps, ktab_taps, corr, scale, shift, stdv, y,
-                                                                      y_batch_stride, workspace, workspace_bytes, stream);
+  return u8_stem_pool233(true, d, frames, F, FH, FW, clip_stride, 1, ncrops, crops_packed, readable_bytes, first_crop_clip, w_taps, ktab_taps,
+                         corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
 }
 
 extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(const advhip_conv3d_desc* d, const uint8_t* frames, int64_t F,
@@ -3874,58 +3879,8 @@ extern "C" int advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(cons
                                                                             const int32_t* ktab_taps, const float* corr, const float* scale,
                                                                             const float* shift, float stdv, float* y, int64_t y_batch_stride,
                                                                             void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = validate(d)) return rc;
-  if (const char* why = crops_packed_error(ncrops, crops_packed))
-    ADVHIP_REQUIRE(false, "conv3d u8 taps+pool233: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
-  ADVHIP_REQUIRE(frames && w_taps && ktab_taps && corr && scale && shift && y, "conv3d u8 taps+pool233: null pointer");
-  ADVHIP_REQUIRE(d->Cin == 3 && d->Cout == 64, "conv3d u8 taps+pool233: 3-channel pixels and 64 output channels (Cin=%d, Cout=%d)", d->Cin, d->Cout);
-  ADVHIP_REQUIRE(d->pt < d->kt && d->ph < d->kh && d->pw < d->kw, "conv3d u8 taps+pool233: padding not smaller than the kernel");
-  ADVHIP_REQUIRE(stdv != 0.f, "conv3d u8 taps+pool233: std must be non-zero");
-  int64_t n_clips = 0;
-  if (int rc = u8_check_frames(d, F, FH, FW, clip_stride, frame_step, &n_clips)) return rc;
-  const int64_t fbytes = F * FH * FW * 3;
-  ADVHIP_REQUIRE(readable_bytes >= fbytes + 1, "conv3d u8 taps+pool233: the frames allocation must extend one byte past the last pixel "
-                 "(pixels are fetched as 4-byte pieces): %lld readable, %lld needed", (long long)readable_bytes, (long long)fbytes + 1);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && first_crop_clip + d->B <= n_clips * ncrops,
-                 "conv3d u8 taps+pool233: crop-clips [%lld, %lld) outside the %lld clips x %d crops of the frames", (long long)first_crop_clip,
-                 (long long)first_crop_clip + d->B, (long long)n_clips, ncrops);
-  const Geometry g = geometry(d);
-  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
-  ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "conv3d u8 taps+pool233: conv output (%d,%d,%d) smaller than the (2,3,3) window", g.To, g.Ho, g.Wo);
-  const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
-  ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= need && need < 0xF0000000ll,
-                 "conv3d u8 taps+pool233: needs a %lld-byte workspace (got %lld)", (long long)need, (long long)workspace_bytes);
-  const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
-  const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
-  ADVHIP_REQUIRE(ybs >= y_dense, "conv3d u8 taps+pool233: y batch stride %lld smaller than one pooled sample (%lld)", ybs, y_dense);
-  ConvArgs a;
-  if (int rc = fill_pool_args(a, d, g, reinterpret_cast<const float*>(frames), 0, w_taps, nullptr, scale, shift, false)) return rc;
-  a.u8_first = (int)first_crop_clip; a.u8_FH = FH; a.u8_FW = FW; a.u8_cstride = clip_stride; a.u8_fstep = frame_step;
-  a.u8_nc = ncrops; a.u8_dnc = FastDiv::make((unsigned)ncrops); a.u8_crops = crops_packed;
-  auto half_even = [](int v) { return (v % 2 == 0) ? v / 2 : ((v / 2) % 2 == 0 ? v / 2 : v / 2 + 1); };
-  a.u8_ctop = half_even(FH - d->H); a.u8_cleft = half_even(FW - d->W);
-  a.in_std = stdv;
-  a.ktab_u8 = reinterpret_cast<const int2*>(ktab_taps); a.pad_corr = corr;
-  const int tp = u8_taps_pad(d);
-  a.Kpad = 3 * tp;
-  a.w_bytes = (unsigned)((long long)a.Kpad * d->Cout * 4);
-  a.pad_off = (d->pt * frame_step * FH * FW + d->ph * FW + d->pw + d->kw) * 3;
-  a.x_bytes = (unsigned)(std::min<int64_t>(readable_bytes, fbytes + 4) + a.pad_off);
-  a.y = reinterpret_cast<float*>(workspace);
-  a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
-  const int nbh = (2 * Hp + 1 + 3) / 4, nbw = (2 * Wp + 1 + 15) / 16;
-  set_bricks(a, Tp, nbh, nbw);
-  // (every check before the first launch: a rejected call must not leave half an op enqueued)
-  ADVHIP_REQUIRE(nbw <= MERGE_MAX_NBW, "conv3d u8 taps+pool233: pooled width %d above %d", Wp, MERGE_MAX_NBW * 8 - 1);
-  const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
-  ADVHIP_REQUIRE(rows < (1ll << 31), "conv3d u8 taps+pool233: too many output rows");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((stem_u8_tap_kernel<U8_TAPS_PER_TILE>), dim3((unsigned)a.tiles_m), dim3(256), 0, st, a);
-  if (int rc = check_launch("conv3d u8 taps+pool233")) return rc;
-  const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
-  hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
-                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
-  return check_launch("stem_pool_merge");
+  return u8_stem_pool233(true, d, frames, F, FH, FW, clip_stride, frame_step, ncrops, crops_packed, readable_bytes, first_crop_clip, w_taps,
+                         ktab_taps, corr, scale, shift, stdv, y, y_batch_stride, workspace, workspace_bytes, stream);
 }
 
 extern "C" int advhip_conv3d_bn_act_maxpool211_f32(const advhip_conv3d_desc* d, const float* x, int64_t x_batch_stride,

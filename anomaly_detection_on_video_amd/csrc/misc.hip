@@ -182,102 +182,98 @@ __global__ __launch_bounds__(256) void frame_scores_kernel(const float* __restri
 
 using namespace advhip;
 
-// windows of a video of F frames: window w starts at frame w * clip_stride and spans fpc * frame_step frames (one sampled every
-// frame_step), the last one may be short (LoopPad)
-static long long window_count(long long F, int fpc, int clip_stride, int frame_step = 1) {
-  const long long span = (long long)fpc * frame_step;
-  return 1 + (F > span ? (F - span + clip_stride - 1) / clip_stride : 0);
+// ---- TenCrop + normalise from uint8 frames: one body per op; the plain / _strided / _crops names fill in the sampling arguments
+// they lack (back-to-back clips, all ten crops, every frame) ----
+static int tencrop_planes_u8(const uint8_t* frames, float* xs, int F, int H, int W, int C, const ClipSampling& s, int crop,
+                             int64_t first_crop_clip, int64_t count, float mean, float stdv, void* stream) {
+  const char* who = "tencrop_normalize_planes_u8";
+  if (int rc = s.check_crops(who)) return rc;
+  ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && s.fpc > 0 && crop > 0 && crop % 2 == 0, "%s: bad arguments", who);
+  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
+  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
+  ADVHIP_REQUIRE(stdv != 0.f, "%s: std must be non-zero", who);
+  const long long n_clips = s.video_windows(F);
+  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * s.ncrops,
+                 "%s: crop-clips [%lld, %lld) outside the video's %lld", who, (long long)first_crop_clip,
+                 (long long)(first_crop_clip + count), n_clips * s.ncrops);
+  const long long rows = (long long)count * C * s.fpc * crop;
+  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
+  hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, s.fpc,
+                     s.clip_stride, crop, half_even(H - crop), half_even(W - crop), mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4,
+                     s.ncrops, s.crops, s.frame_step);
+  return check_launch(who);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8_sampled(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                                           int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
                                                           int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
                                                           float mean, float stdv, void* stream) {
-  if (const char* why = crops_packed_error(ncrops, crops_packed))
-    ADVHIP_REQUIRE(false, "tencrop_normalize_planes_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
-  ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0 && crop % 2 == 0, "tencrop_normalize_planes_u8: bad arguments");
-  ADVHIP_REQUIRE(frame_step >= 1 && (long long)frames_per_clip * frame_step < (1ll << 31), "tencrop_normalize_planes_u8: frame step %d", frame_step);
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip * frame_step, "tencrop_normalize_planes_u8: clip stride %d outside [1, %d]",
-                 clip_stride, frames_per_clip * frame_step);
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_planes_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
-  ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_planes_u8: std must be non-zero");
-  const long long n_clips = window_count(F, frames_per_clip, clip_stride, frame_step);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * ncrops,
-                 "tencrop_normalize_planes_u8: crop-clips [%lld, %lld) outside the video's %lld", (long long)first_crop_clip,
-                 (long long)(first_crop_clip + count), n_clips * ncrops);
-  auto half_even = [](int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); };
-  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const long long rows = (long long)count * C * frames_per_clip * crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-  hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, frames_per_clip,
-                     clip_stride, crop, ctop, cleft, mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4, ncrops,
-                     (unsigned long long)crops_packed, frame_step);
-  return check_launch("tencrop_normalize_planes_u8");
+  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, first_crop_clip,
+                           count, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                                         int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
                                                         uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
                                                         float stdv, void* stream) {
-  return advhip_tencrop_normalize_planes_u8_sampled(frames, xs, F, H, W, C, frames_per_clip, clip_stride, 1, crop, ncrops, crops_packed,
-                                                    first_crop_clip, count, mean, stdv, stream);
+  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, first_crop_clip, count, mean,
+                           stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                                           int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
                                                           int64_t count, float mean, float stdv, void* stream) {
-  return advhip_tencrop_normalize_planes_u8_crops(frames, xs, F, H, W, C, frames_per_clip, clip_stride, crop, 10, TENCROP_ALL, first_crop_clip,
-                                                  count, mean, stdv, stream);
+  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, first_crop_clip, count, mean, stdv,
+                           stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
                                                   int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
                                                   float stdv, void* stream) {
-  return advhip_tencrop_normalize_planes_u8_strided(frames, xs, F, H, W, C, frames_per_clip, frames_per_clip, crop, first_crop_clip, count, mean,
-                                                    stdv, stream);
+  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, first_crop_clip, count, mean,
+                           stdv, stream);
+}
+
+static int tencrop_u8(const uint8_t* frames, float* y, int F, int H, int W, int C, const ClipSampling& s, int crop, float mean, float stdv,
+                      void* stream) {
+  const char* who = "tencrop_normalize_u8";
+  if (int rc = s.check_crops(who)) return rc;
+  ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && s.fpc > 0 && crop > 0, "%s: bad arguments", who);
+  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
+  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
+  ADVHIP_REQUIRE(stdv != 0.f, "%s: std must be non-zero", who);
+  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
+  const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
+  const long long rows = s.video_windows(F) * s.ncrops * C * s.fpc * (long long)crop;
+  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
+  if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C, s.fpc,
+                              s.clip_stride, crop, ctop, cleft, mean, stdv, rows, s.ncrops, s.crops, s.frame_step);
+  else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C, s.fpc,
+                          s.clip_stride, crop, ctop, cleft, mean, stdv, rows, s.ncrops, s.crops, s.frame_step);
+  return check_launch(who);
 }
 
 extern "C" int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                                    int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
                                                    int32_t ncrops, uint64_t crops_packed, float mean, float stdv, void* stream) {
-  if (const char* why = crops_packed_error(ncrops, crops_packed))
-    ADVHIP_REQUIRE(false, "tencrop_normalize_u8: crop set (%d, 0x%llx): %s", ncrops, (unsigned long long)crops_packed, why);
-  ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && frames_per_clip > 0 && crop > 0, "tencrop_normalize_u8: bad arguments");
-  ADVHIP_REQUIRE(frame_step >= 1 && (long long)frames_per_clip * frame_step < (1ll << 31), "tencrop_normalize_u8: frame step %d", frame_step);
-  ADVHIP_REQUIRE(clip_stride >= 1 && clip_stride <= frames_per_clip * frame_step, "tencrop_normalize_u8: clip stride %d outside [1, %d]", clip_stride,
-                 frames_per_clip * frame_step);
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "tencrop_normalize_u8: frames (%d x %d) smaller than the %d crop", H, W, crop);
-  ADVHIP_REQUIRE(stdv != 0.f, "tencrop_normalize_u8: std must be non-zero");
-  // torchvision center_crop: int(round((H - crop) / 2.0)) with Python's round-half-to-even
-  auto half_even = [](int d) { return (d % 2 == 0) ? d / 2 : ((d / 2) % 2 == 0 ? d / 2 : d / 2 + 1); };
-  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const long long n_clips = window_count(F, frames_per_clip, clip_stride, frame_step);
-  const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
-  const long long rows = n_clips * ncrops * C * frames_per_clip * (long long)crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-  if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                              frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed, frame_step);
-  else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C,
-                          frames_per_clip, clip_stride, crop, ctop, cleft, mean, stdv, rows, ncrops, (unsigned long long)crops_packed, frame_step);
-  return check_launch("tencrop_normalize_u8");
+  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                                  int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
                                                  uint64_t crops_packed, float mean, float stdv, void* stream) {
-  return advhip_tencrop_normalize_u8_sampled(frames, y, F, H, W, C, frames_per_clip, clip_stride, 1, crop, ncrops, crops_packed, mean, stdv,
-                                             stream);
+  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                                    int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
                                                    void* stream) {
-  return advhip_tencrop_normalize_u8_crops(frames, y, F, H, W, C, frames_per_clip, clip_stride, crop, 10, TENCROP_ALL, mean, stdv, stream);
+  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, mean, stdv, stream);
 }
 
 extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                            int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream) {
-  return advhip_tencrop_normalize_u8_strided(frames, y, F, H, W, C, frames_per_clip, frames_per_clip, crop, mean, stdv, stream);
+  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, mean, stdv, stream);
 }
 
 extern "C" int advhip_frame_scores_f32(const float* scores, float* out, int64_t n_windows, int32_t frames_per_clip, int32_t clip_stride,

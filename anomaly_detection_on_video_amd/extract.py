@@ -21,7 +21,7 @@ from . import dist as adist
 from . import mil_ops
 from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
-from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_crops, resolve_frame_step  # noqa: F401  (n_windows is part of this module's interface)
+from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_frame_step, resolve_sampling  # noqa: F401  (n_windows is part of this module's interface)
 
 FRAMES_PER_CLIP = 16
 NCROPS = 10
@@ -172,15 +172,13 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     (resize_u8(frame_step=d)), and the step then runs at (clip_stride // d, 1) -- the result is extract_video_frames(frames[::d],
     clip_stride=clip_stride // d) bit for bit.  Resized frames already on the device, and any stride d does not divide, are
     addressed in place by the kernels with d as a launch argument."""
-    fstep = resolve_frame_step(frame_step)
-    crops = resolve_crops(crops)
+    s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc = len(crops)
     subset = nc != 10  # ("ten" and (0, ..., 9) are None in every respect, the squeeze included)
     if clips_per_step is None:
         clips_per_step = max(1, 30 // nc) if subset else 3
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
-    s = resolve_clip_stride(frames_per_clip, clip_stride, fstep)
     dev = next(model.parameters()).device
     rows = []
     n_total = n_windows(frames.shape[0], frames_per_clip, s, fstep)
@@ -217,27 +215,24 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         else:
             fr = fr.to(dev, non_blocking=True)
         if not direct:
-            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=None if dd == 1 else dd)
+            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd)
             rows.append(run_chunks_on_lanes(model, [x[i : i + max_cc] for i in range(0, x.shape[0], max_cc)]))
             continue
         # the stem kernel reads the uint8 pixels itself (TenCrop + float + normalise in its load stage): only LoopPad is left,
         # and only for a last window shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
-        if dd == 1:
-            fr = pad_windows_u8(fr, frames_per_clip, ss).contiguous()
-        elif not hasattr(model, "frames_need_whole_windows") or model.frames_need_whole_windows(crop):
-            fr = pad_windows_u8(fr, frames_per_clip, ss, dd).contiguous()  # (else: a TenCrop pass runs first and LoopPads itself)
+        # (a sampled step whose model runs a TenCrop pass first is left as it is: that pass LoopPads itself)
+        if dd == 1 or not hasattr(model, "frames_need_whole_windows") or model.frames_need_whole_windows(crop):
+            fr = pad_windows_u8(fr, frames_per_clip, ss, dd).contiguous()
         n = (w1 - w0) * nc
         ranges = [(i, min(max_cc, n - i)) for i in range(0, n, max_cc)]
 
         def run_range(r, fr=fr, ss=ss, dd=dd):
             fr.record_stream(torch.cuda.current_stream(dev))  # (read on a lane stream, allocated on the caller's)
-            if dd == 1:
-                return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops)
             return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd)
 
         rows.append(run_chunks_on_lanes(
             model, ranges, fn=run_range,
-            prepare=lambda fr=fr, dd=dd: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b, **({} if dd == 1 else {"frame_step": dd}))
+            prepare=lambda fr=fr, dd=dd: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b, frame_step=dd)
                                           for b in sorted({r[1] for r in ranges})]))
     out = torch.cat(rows, dim=0).reshape(-1, nc, 2048).cpu().numpy()
     return out if subset else np.squeeze(out)  # (the reference's np.squeeze quirk belongs to its own ten-crop call only)
@@ -290,10 +285,9 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     With `crops` in `kw` the features are (n_clips, len(crops), 2048) and the files carry the set too, behind the stride:
     `<name>_s8_c4_<seg>.npy`.  With `frame_step` in `kw` the step comes first: `<name>_d2_<seg>.npy`, `<name>_d2_s8_c4_<seg>.npy`."""
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
-    d = resolve_frame_step(kw.get("frame_step"))
-    s = resolve_clip_stride(fpc, kw.get("clip_stride"), d)
-    nc = len(resolve_crops(kw.get("crops")))
-    tag = feature_tag(fpc, s, kw.get("crops"), d)
+    s, crops, d = resolve_sampling(fpc, kw.get("clip_stride"), kw.get("crops"), kw.get("frame_step"))
+    nc = len(crops)
+    tag = feature_tag(fpc, s, crops, d)
     seg_folder = os.path.join(outpath, name)
     plan = segment_windows(n_frames, seg_len, fpc, s, d)  # (refuses a seg_len the stride does not divide before anything is written)
     os.makedirs(seg_folder, exist_ok=True)

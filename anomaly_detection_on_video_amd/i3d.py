@@ -365,9 +365,7 @@ class I3Res50(nn.Module):
         `frame_step` d (default 1): clip w = frames w * clip_stride + t * d, t in [0, frames_per_clip) -- every d-th frame of a span
         of frames_per_clip * d, addressed in place; clip_stride defaults to the span and F is whole windows in that sense
         (ops.pad_windows_u8 with the same arguments)."""
-        fstep = ops.resolve_frame_step(frame_step)
-        s = ops.resolve_clip_stride(frames_per_clip, clip_stride, fstep)
-        crops = ops.resolve_crops(crops)
+        s, crops, fstep = ops.resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
         if self.training:
             raise _lib.HipExtensionError("I3Res50 HIP path implements eval-mode BatchNorm only; call .eval()")
         if self.in_channels != 3:
@@ -376,7 +374,7 @@ class I3Res50(nn.Module):
             raise _lib.HipExtensionError(f"forward_frames wants uint8 (F,H,W,3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
         if fstep != 1 and self.frames_need_whole_windows(crop):
             # (a whole-window buffer ends with the last window's last SAMPLED frame, short of its span: counted as the stem counts)
-            n = max(0, (frames.shape[0] - (frames_per_clip - 1) * fstep - 1) // s + 1) * len(crops)
+            n = ops.buffer_windows(frames.shape[0], frames_per_clip, s, fstep) * len(crops)
         else:
             n = ops.n_windows(frames.shape[0], frames_per_clip, s, fstep) * len(crops)
         if count <= 0 or first < 0 or first + count > n:

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
-from .ops import n_windows, pack_crops, resolve_clip_stride, resolve_frame_step
+from .ops import n_windows, pack_crops, resolve_clip_stride, resolve_frame_step, resolve_sampling
 
 
 class _MilMagnitude(torch.autograd.Function):
@@ -261,8 +261,7 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
     frames, clip_stride defaults to that span (1 <= clip_stride <= span), and a short last clip of L = ceil((F - w * s) / d)
     sampled frames repeats them (LoopPad): frame t >= L is frames[w * s + (t % L) * d].  Row w is the row of the call without
     `frame_step` on those frames as a one-clip video, bit for bit; nothing is gathered."""
-    d = resolve_frame_step(frame_step)
-    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    s, crops, d = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
@@ -273,12 +272,8 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
         raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
     n_clips = n_windows(f, frames_per_clip, s, d)
     out = torch.empty((n_clips * nc, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
-    if d == 1:
-        check(_lib.load().advhip_tencrop_normalize_u8_crops(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, crop, nc, packed, C_float(mean),
-                                                            C_float(std), stream()), "tencrop_normalize_u8")
-    else:
-        check(_lib.load().advhip_tencrop_normalize_u8_sampled(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
-                                                              C_float(mean), C_float(std), stream()), "tencrop_normalize_u8")
+    check(_lib.load().advhip_tencrop_normalize_u8_sampled(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
+                                                          C_float(mean), C_float(std), stream()), "tencrop_normalize_u8")
     return out
 
 

@@ -406,6 +406,21 @@ def n_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[in
     return 1 + max(0, -(-(n_frames - frames_per_clip * d) // s))
 
 
+def buffer_frames(n: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None, frame_step: Optional[int] = None) -> int:
+    """Frames of a buffer that holds `n` WHOLE windows, as the fused stems read it: it ends with the last window's last sampled
+    frame, (n - 1) * clip_stride + (frames_per_clip - 1) * frame_step + 1 (frame_step 1, back-to-back clips: n * frames_per_clip)."""
+    d = resolve_frame_step(frame_step)
+    return (n - 1) * resolve_clip_stride(frames_per_clip, clip_stride, d) + (frames_per_clip - 1) * d + 1
+
+
+def buffer_windows(n_frames: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None, frame_step: Optional[int] = None) -> int:
+    """Whole windows at the head of a buffer of `n_frames` (0: not even one); the buffer is whole where buffer_frames of that
+    count gives `n_frames` back."""
+    d = resolve_frame_step(frame_step)
+    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    return max(0, (n_frames - buffer_frames(1, frames_per_clip, s, d)) // s + 1)
+
+
 def window_frame_indices(n_frames: int, w: int, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
                          frame_step: Optional[int] = None) -> Tuple[int, ...]:
     """The frames_per_clip source frames window `w` of a video of `n_frames` is made of, LoopPad included: w * s + (t % L) * d with
@@ -447,6 +462,14 @@ def resolve_crops(crops) -> Tuple[int, ...]:
     return idx
 
 
+def resolve_sampling(frames_per_clip: int, clip_stride: Optional[int] = None, crops=None,
+                     frame_step: Optional[int] = None) -> Tuple[int, Tuple[int, ...], int]:
+    """The three clip-sampling arguments resolved once: (clip_stride, crops, frame_step) as resolve_clip_stride, resolve_crops and
+    resolve_frame_step give them."""
+    d = resolve_frame_step(frame_step)
+    return resolve_clip_stride(frames_per_clip, clip_stride, d), resolve_crops(crops), d
+
+
 def pack_crops(crops) -> Tuple[int, int]:
     """(ncrops, packed) as the kernels take a crop set: index j in bits [4 j, 4 j + 4) of one 64-bit launch argument."""
     idx = resolve_crops(crops)
@@ -472,8 +495,7 @@ def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_c
     frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride.  `crops`
     (resolve_crops): row = clip * len(crops) + j holds crop crops[j].  `frame_step` (default 1): clip w = frames w * clip_stride +
     t * frame_step, t in [0, frames_per_clip); clip_stride then defaults to frames_per_clip * frame_step."""
-    d = resolve_frame_step(frame_step)
-    s = resolve_clip_stride(frames_per_clip, clip_stride, d)
+    s, crops, d = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc, packed = pack_crops(crops)
     frames = frames.contiguous()
     require_gpu(frames)
@@ -484,13 +506,9 @@ def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_c
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
-    lib = _lib.load()
-    if d == 1:
-        check(lib.advhip_tencrop_normalize_planes_u8_crops(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, crop, nc, packed, first, count,
-                                                           C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
-    else:
-        check(lib.advhip_tencrop_normalize_planes_u8_sampled(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, first, count,
-                                                             C.c_float(mean), C.c_float(std), stream(frames)), "tencrop_normalize_planes_u8")
+    check(_lib.load().advhip_tencrop_normalize_planes_u8_sampled(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, first,
+                                                                 count, C.c_float(mean), C.c_float(std), stream(frames)),
+          "tencrop_normalize_planes_u8")
     return xs
 
 
@@ -565,14 +583,8 @@ def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride:
     d = resolve_frame_step(frame_step)
     s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     F = frames.shape[0]
-    start = (n_windows(F, frames_per_clip, s, d) - 1) * s
-    if d == 1:
-        length = F - start
-        if length == frames_per_clip:
-            return frames
-        idx = torch.arange(length, frames_per_clip, device=frames.device) % length + start
-        return torch.cat([frames, frames[idx]], dim=0)
-    whole = start + (frames_per_clip - 1) * d + 1
+    n = n_windows(F, frames_per_clip, s, d)
+    start, whole = (n - 1) * s, buffer_frames(n, frames_per_clip, s, d)
     length = min(frames_per_clip, -(-(F - start) // d))
     if length == frames_per_clip:
         return frames[:whole]
@@ -586,7 +598,7 @@ def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride:
 def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
                           frame_step: int = 1):
     """(`frame_step`: the temporal term of the gather table is frame_step frames per tap -- part of the cache key.)"""
-    key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean)) + ((int(frame_step),) if frame_step != 1 else ())
+    key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean), int(frame_step))
     cache = pc.__dict__.setdefault("_u8_tables", {})
     tabs = cache.get(key)
     if tabs is None:
@@ -598,13 +610,9 @@ def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw:
         ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
         corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
         wt = torch.empty((nw.value,), device=dev, dtype=torch.float32)
-        if frame_step == 1:
-            check(lib.advhip_conv3d_u8_taps_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
-                                                         ptr(corr), ptr(wt), stream(dev)), f"conv3d_u8_taps_build_tables[{pc.name}]")
-        else:
-            check(lib.advhip_conv3d_u8_taps_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
-                                                                 C.c_float(mean), ptr(ktab), ptr(corr), ptr(wt), stream(dev)),
-                  f"conv3d_u8_taps_build_tables[{pc.name}]")
+        check(lib.advhip_conv3d_u8_taps_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
+                                                             C.c_float(mean), ptr(ktab), ptr(corr), ptr(wt), stream(dev)),
+              f"conv3d_u8_taps_build_tables[{pc.name}]")
         tabs = cache[key] = (ktab, corr, wt)
     return tabs
 
@@ -614,7 +622,7 @@ def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tupl
     """Gather / border tables of the uint8-frame stem for frames of (FH, FW) and clips of (T, crop, crop); cached on the conv
     (built on the current stream: callers that fork streams build them first, like the other lazily built tables).  `frame_step`:
     the temporal term of the gather table is frame_step frames per tap -- part of the cache key."""
-    key = (tuple(frame_hw), tuple(clip_thw), float(mean)) + ((int(frame_step),) if frame_step != 1 else ())
+    key = (tuple(frame_hw), tuple(clip_thw), float(mean), int(frame_step))
     cache = pc.__dict__.setdefault("_u8_tables", {})
     tabs = cache.get(key)
     if tabs is None:
@@ -625,13 +633,9 @@ def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tupl
         dev = pc.w_packed.device
         ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
         corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
-        if frame_step == 1:
-            check(lib.advhip_conv3d_u8_build_tables(C.byref(d), frame_hw[0], frame_hw[1], ptr(pc.w_packed), C.c_float(mean), ptr(ktab),
-                                                    ptr(corr), stream(dev)), f"conv3d_u8_build_tables[{pc.name}]")
-        else:
-            check(lib.advhip_conv3d_u8_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
-                                                            C.c_float(mean), ptr(ktab), ptr(corr), stream(dev)),
-                  f"conv3d_u8_build_tables[{pc.name}]")
+        check(lib.advhip_conv3d_u8_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
+                                                        C.c_float(mean), ptr(ktab), ptr(corr), stream(dev)),
+              f"conv3d_u8_build_tables[{pc.name}]")
         tabs = cache[key] = (ktab, corr)
     return tabs
 
@@ -652,17 +656,16 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     (pad_windows_u8 with the same arguments).  Scalar set-up of the same kernel plus gather tables built for d."""
     require_gpu(frames)
     require_gpu(out, contiguous=False)
-    fstep = resolve_frame_step(frame_step)
-    s = resolve_clip_stride(frames_per_clip, clip_stride, fstep)
-    reach = (frames_per_clip - 1) * fstep + 1
+    s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc, packed = pack_crops(crops)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != pc.cin:
         raise ValueError(f"{pc.name}: expected uint8 (F,H,W,{pc.cin}) frames, got {frames.dtype} {tuple(frames.shape)}")
     F, FH, FW, _ = frames.shape
-    if F < reach or (F - reach) % s or FH < crop or FW < crop:
+    n = buffer_windows(F, frames_per_clip, s, fstep)
+    if n == 0 or buffer_frames(n, frames_per_clip, s, fstep) != F or FH < crop or FW < crop:
         raise ValueError(f"{pc.name}: {F} frames of {FH}x{FW} are not whole {frames_per_clip}-frame clips (stride {s}"
                          + (f", frame step {fstep}" if fstep != 1 else "") + f") of at least {crop}x{crop}")
-    n = ((F - reach) // s + 1) * nc
+    n *= nc
     if count <= 0 or first < 0 or first + count > n:
         raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {n}")
     d = pc.desc(count, frames_per_clip, crop, crop, True, 0, 1)
@@ -682,29 +685,16 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     if U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64:
         frames = with_slack(frames)
         ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean, fstep)
-        if fstep != 1:
-            check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed,
-                                                                                   readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
-                                                                                   ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
-                                                                                   batch_stride(y), ptr(ws), need, stream()),
-                  f"conv3d_u8_taps+pool233[{pc.name}]")
-            return y
-        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed,
-                                                                             readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
-                                                                             ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
-                                                                             batch_stride(y), ptr(ws), need, stream()),
+        check(lib.advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed,
+                                                                               readable_bytes(frames), first, ptr(wt), ptr(ktab), ptr(corr),
+                                                                               ptr(pc.scale), ptr(pc.shift), C.c_float(std), ptr(y),
+                                                                               batch_stride(y), ptr(ws), need, stream()),
               f"conv3d_u8_taps+pool233[{pc.name}]")
         return y
     ktab, corr = ensure_u8_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean, fstep)
-    if fstep != 1:
-        check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed, first,
-                                                                          ptr(pc.w_packed), ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
-                                                                          C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
-              f"conv3d_u8+pool233[{pc.name}]")
-        return y
-    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_crops_f32(C.byref(d), ptr(frames), F, FH, FW, s, nc, packed, first, ptr(pc.w_packed),
-                                                                    ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
-                                                                    C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
+    check(lib.advhip_conv3d_u8_tencrop_bn_relu_maxpool233_sampled_f32(C.byref(d), ptr(frames), F, FH, FW, s, fstep, nc, packed, first,
+                                                                      ptr(pc.w_packed), ptr(ktab), ptr(corr), ptr(pc.scale), ptr(pc.shift),
+                                                                      C.c_float(std), ptr(y), batch_stride(y), ptr(ws), need, stream()),
           f"conv3d_u8+pool233[{pc.name}]")
     return y
 

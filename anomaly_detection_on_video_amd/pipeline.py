@@ -162,8 +162,7 @@ class ExtractScoreStream:
                 if isinstance(local_clips, FrameCrops):
                     fc = local_clips
                     feats = self.backbone.forward_frames(fc.frames, fc.first, fc.count, fc.frames_per_clip, fc.crop,
-                                                         clip_stride=fc.clip_stride, crops=fc.crops,
-                                                         frame_step=None if fc.frame_step == 1 else fc.frame_step).reshape(fc.count, -1)
+                                                         clip_stride=fc.clip_stride, crops=fc.crops, frame_step=fc.frame_step).reshape(fc.count, -1)
                 else:
                     feats = self.backbone(local_clips).reshape(local_clips.shape[0], -1)
             finally:

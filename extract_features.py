@@ -92,7 +92,7 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
         extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops,
-                       **({} if frame_step is None else {"frame_step": frame_step}))
+                       frame_step=frame_step)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 

@@ -265,3 +265,72 @@ def test_tencrop_planes_pass_equals_the_two_pass_form(case):
     assert torch.equal(got, want)
     with pytest.raises(ValueError):
         ops.tencrop_planes_u8(fd, first, 10 * (-(-F // fpc)) - first + 1, fpc, crop)
+
+
+ALL_TEN = (10, 0x9876543210)
+
+
+def _names_for(fpc, stride, crop_set):
+    """(suffix, sampling arguments) of every C name of a uint8 op that can express windows at `stride` with `crop_set` (ncrops,
+    packed) at frame_step 1: the plain name has neither argument, _strided no crop set, _crops no frame step."""
+    names = [("_crops", (stride,), (), crop_set), ("_sampled", (stride,), (1,), crop_set)]
+    if crop_set == ALL_TEN:
+        names.insert(0, ("_strided", (stride,), (), ()))
+        if stride == fpc:
+            names.insert(0, ("", (), (), ()))
+    return names
+
+
+@pytest.mark.parametrize("op", ["pixels", "planes", "stem_bytes", "stem_taps"])
+def test_every_c_name_of_a_u8_op_runs_the_same_code(op):
+    """The plain, _strided, _crops and _sampled names of the four uint8-frame ops, called through ctypes with equivalent arguments
+    (the wrappers in ops / mil_ops call _sampled only): equal outputs bit for bit -- all four names for back-to-back clips of all
+    ten crops, the three that take a stride at stride 8, the two that take a crop set at crops (4, 9) from an odd first row."""
+    import ctypes as C
+
+    from anomaly_detection_on_video_amd import _lib, ops
+    from anomaly_detection_on_video_amd._lib import check, ptr, stream
+
+    lib, dev = _lib.load(), _dev()
+    fpc, crop, count = 16, 32, 6
+    fd = ops.with_slack(torch.from_numpy(_frames(9, (48, 40, 52, 3))).to(dev))  # whole at stride 16 (3 windows) and 8 (5 windows)
+    F, FH, FW, ch = fd.shape
+    mean, std = C.c_float(ops.PIXEL_MEAN), C.c_float(ops.PIXEL_STD)
+    pc, _ = _stem("u8names")
+    d = pc.desc(count, fpc, crop, crop, True, 0, 1)
+    tp, hp, wp = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wp)), "conv3d_pool_out_dims")
+    need = lib.advhip_conv3d_relu_maxpool233_workspace_bytes(C.byref(d))
+    ws = ops.workspace(dev, need)
+
+    def run(suffix, s_args, d_args, c_args, first, n_rows):
+        if op == "pixels":
+            y = torch.empty((n_rows, ch, fpc, crop, crop), device=dev)
+            rc = getattr(lib, "advhip_tencrop_normalize_u8" + suffix)(ptr(fd), ptr(y), F, FH, FW, ch, fpc, *s_args, *d_args, crop, *c_args, mean, std,
+                                                                      stream())
+        elif op == "planes":
+            y = torch.empty((count, ch, fpc, crop, 2, crop // 2 + 4), device=dev)
+            rc = getattr(lib, "advhip_tencrop_normalize_planes_u8" + suffix)(ptr(fd), ptr(y), F, FH, FW, ch, fpc, *s_args, *d_args, crop, *c_args,
+                                                                             first, count, mean, std, stream())
+        else:
+            y = torch.empty((count, 64, tp.value, hp.value, wp.value), device=dev)
+            tail = (ptr(pc.scale), ptr(pc.shift), std, ptr(y), 0, ptr(ws), need, stream())
+            if op == "stem_bytes":
+                ktab, corr = ops.ensure_u8_tables(pc, (FH, FW), (fpc, crop, crop))
+                rc = getattr(lib, f"advhip_conv3d_u8_tencrop_bn_relu_maxpool233{suffix}_f32")(
+                    C.byref(d), ptr(fd), F, FH, FW, *s_args, *d_args, *c_args, first, ptr(pc.w_packed), ptr(ktab), ptr(corr), *tail)
+            else:
+                ktab, corr, wt = ops.ensure_u8_taps_tables(pc, (FH, FW), (fpc, crop, crop))
+                rc = getattr(lib, f"advhip_conv3d_u8_taps_tencrop_bn_relu_maxpool233{suffix}_f32")(
+                    C.byref(d), ptr(fd), F, FH, FW, *s_args, *d_args, *c_args, ops.readable_bytes(fd), first, ptr(wt), ptr(ktab), ptr(corr), *tail)
+        check(rc, op + suffix)
+        return y
+
+    for stride, crop_set, first, n_names in [(fpc, ALL_TEN, 3, 4), (8, ALL_TEN, 3, 3), (8, (2, 0x94), 1, 2)]:
+        names = _names_for(fpc, stride, crop_set)
+        assert len(names) == n_names
+        n_rows = ops.n_windows(F, fpc, stride) * crop_set[0]
+        outs = [run(*name, first, n_rows) for name in names]
+        assert float(outs[-1].abs().max()) > 0
+        for name, y in zip(names[:-1], outs[:-1]):
+            assert torch.equal(y, outs[-1]), (op, name[0], stride, crop_set)
