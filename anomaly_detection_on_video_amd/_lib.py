@@ -45,6 +45,9 @@ ALGO_PERSIST_BASE = 224  # + tile id (2: 128x64, 3: 64x64) + 8 * (workgroups per
 PERSIST_ALGOS = tuple(ALGO_PERSIST_BASE + t + 8 * (w - 1) for w in (1, 2, 3) for t in (2, 3))
 
 
+NORM_STANDARDIZE, NORM_PIXEL_MINMAX, NORM_CHANNEL_MINMAX = 0, 1, 2  # ADVHIP_NORM_*: the modes of the `_modes` TenCrop passes
+
+
 def is_tfold(algo: int) -> bool:
     return ALGO_TFOLD_BASE <= algo < ALGO_TFOLD_BASE + 16
 
@@ -222,6 +225,11 @@ SIGNATURES = {
     "advhip_tencrop_normalize_u8_crops": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_planes_u8_sampled": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _L, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_u8_sampled": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, C.c_float, C.c_float, _P]),
+    "advhip_crop_minmax_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "advhip_tencrop_normalize_u8_modes": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, _I, C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_double), _P, _I, _P]),
+    "advhip_tencrop_normalize_planes_u8_modes": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.c_uint64, _L, _L, _I,
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _I, _P]),
     "advhip_frame_scores_f32": (C.c_int, [_P, _P, _L, _I, _I, _L, _P]),
     "advhip_normalize_permute_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_resize_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),

@@ -21,7 +21,7 @@ from . import dist as adist
 from . import mil_ops
 from . import resize as resize_mod
 from .i3d import build_i3d_feature_extractor
-from .ops import crops_tag, n_windows, pad_windows_u8, resolve_clip_stride, resolve_frame_step, resolve_sampling  # noqa: F401  (n_windows is part of this module's interface)
+from .ops import crop_minmax_u8, crop_stats_pitch, crops_tag, n_windows, normalize_is_default, normalize_tag, resolve_normalize, pad_windows_u8, resolve_clip_stride, resolve_frame_step, resolve_sampling  # noqa: F401  (n_windows is part of this module's interface)
 
 FRAMES_PER_CLIP = 16
 NCROPS = 10
@@ -141,7 +141,7 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
                          clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
-                         crops=None, frame_step: Optional[int] = None, **kw) -> np.ndarray:
+                         crops=None, frame_step: Optional[int] = None, normalize=None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -171,8 +171,17 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     that lattice is copied (and resized); decoded frames already on the device are resized straight from the lattice
     (resize_u8(frame_step=d)), and the step then runs at (clip_stride // d, 1) -- the result is extract_video_frames(frames[::d],
     clip_stride=clip_stride // d) bit for bit.  Resized frames already on the device, and any stride d does not divide, are
-    addressed in place by the kernels with d as a launch argument."""
+    addressed in place by the kernels with d as a launch argument.
+
+    `normalize` (ops.resolve_normalize; default None = the reference's (x - 114.75) / 57.375): ("standardize", mean, std) with
+    per-channel lists, "pixel_minmax" / ("pixel_minmax", lo, hi) or "channel_minmax" / ("channel_minmax", lo, hi) -- the reference's
+    GroupStandardizationTenCrop, GroupPixelMinmaxTenCrop and GroupRGBChannelMinmaxTenCrop (src/gtransforms.py:57-112), bit for
+    bit on the normalised pixels, NaN for a constant crop / channel included.  The min-max kinds take each (frame, crop)'s minimum
+    and maximum first: one statistics launch per step on the caller's stream (ops.crop_minmax_u8), shared by the step's ranges.  A
+    frame's statistics are its own: the normalised pixels do not depend on how the video is cut into steps."""
     s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
+    norm = resolve_normalize(normalize)
+    plain = normalize_is_default(norm)
     nc = len(crops)
     subset = nc != 10  # ("ten" and (0, ..., 9) are None in every respect, the squeeze included)
     if clips_per_step is None:
@@ -215,25 +224,36 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         else:
             fr = fr.to(dev, non_blocking=True)
         if not direct:
-            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd)
+            x = mil_ops.tencrop_normalize_u8(fr, frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd, normalize=norm)
             rows.append(run_chunks_on_lanes(model, [x[i : i + max_cc] for i in range(0, x.shape[0], max_cc)]))
             continue
         # the stem kernel reads the uint8 pixels itself (TenCrop + float + normalise in its load stage): only LoopPad is left,
         # and only for a last window shorter than frames_per_clip (src/gtransforms.py:119-132) -- a uint8 gather of <= 15 frames
         # (a sampled step whose model runs a TenCrop pass first is left as it is: that pass LoopPads itself)
-        if dd == 1 or not hasattr(model, "frames_need_whole_windows") or model.frames_need_whole_windows(crop):
+        # (nor is a step with another normalisation: it always runs a TenCrop pass)
+        if plain and (dd == 1 or not hasattr(model, "frames_need_whole_windows") or model.frames_need_whole_windows(crop)):
             fr = pad_windows_u8(fr, frames_per_clip, ss, dd).contiguous()
         n = (w1 - w0) * nc
         ranges = [(i, min(max_cc, n - i)) for i in range(0, n, max_cc)]
+        if plain:
+            more = {}
+        else:  # the step's statistics once, here on the caller's stream, before the lanes fork: every range reads the same table
+            fr = fr.contiguous()
+            stats = None if norm.kind == "standardize" else crop_minmax_u8(fr, crop, crop_stats_pitch(frames_per_clip, ss, dd))
+            more = dict(normalize=norm, crop_stats=stats)
 
-        def run_range(r, fr=fr, ss=ss, dd=dd):
-            fr.record_stream(torch.cuda.current_stream(dev))  # (read on a lane stream, allocated on the caller's)
-            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd)
+        def run_range(r, fr=fr, ss=ss, dd=dd, more=more):
+            for t in (fr, more.get("crop_stats")):  # (read on a lane stream, allocated on the caller's)
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+            return model.forward_frames(fr, r[0], r[1], frames_per_clip, crop, clip_stride=ss, crops=crops, frame_step=dd, **more)
 
-        rows.append(run_chunks_on_lanes(
-            model, ranges, fn=run_range,
-            prepare=lambda fr=fr, dd=dd: [model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b, frame_step=dd)
-                                          for b in sorted({r[1] for r in ranges})]))
+        def build_tables(fr=fr, dd=dd):
+            norm_kw = {} if plain else dict(normalize=norm)
+            for b in sorted({r[1] for r in ranges}):
+                model.ensure_frame_tables(tuple(fr.shape[1:3]), frames_per_clip, crop, b, frame_step=dd, **norm_kw)
+
+        rows.append(run_chunks_on_lanes(model, ranges, fn=run_range, prepare=build_tables))
     out = torch.cat(rows, dim=0).reshape(-1, nc, 2048).cpu().numpy()
     return out if subset else np.squeeze(out)  # (the reference's np.squeeze quirk belongs to its own ten-crop call only)
 
@@ -265,13 +285,14 @@ def segment_windows(n_frames: int, seg_len: int = SEGMENT_FRAMES, frames_per_cli
 
 
 def feature_tag(frames_per_clip: int = FRAMES_PER_CLIP, clip_stride: Optional[int] = None, crops=None,
-                frame_step: Optional[int] = None) -> str:
+                frame_step: Optional[int] = None, normalize=None) -> str:
     """What a feature file's name says about how it was extracted: "" for the reference's own (back-to-back clips, ten crops),
     "_d<step>" for temporal sampling, "_s<stride>" for a stride other than the window span (frames_per_clip * frame_step), then
-    "_c<digits>" for a crop subset ("_s8_c4", "_c01234", "_d2", "_d2_s8_c4").  Files made one way are never read another way."""
+    "_c<digits>" for a crop subset ("_s8_c4", "_c01234", "_d2", "_d2_s8_c4"), then the normalisation's tag (ops.normalize_tag: "_npix",
+    "_nch-1f3a...", "_d2_s8_c4_nstd-...").  Files made one way are never read another way."""
     d = resolve_frame_step(frame_step)
     s = resolve_clip_stride(frames_per_clip, clip_stride, d)
-    return ("" if d == 1 else f"_d{d}") + ("" if s == frames_per_clip * d else f"_s{s}") + crops_tag(crops)
+    return ("" if d == 1 else f"_d{d}") + ("" if s == frames_per_clip * d else f"_s{s}") + crops_tag(crops) + normalize_tag(normalize)
 
 
 def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Callable[[int, int], torch.Tensor], outpath: str,
@@ -283,11 +304,12 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     ones with `resize=...` in `kw`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
     in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another.
     With `crops` in `kw` the features are (n_clips, len(crops), 2048) and the files carry the set too, behind the stride:
-    `<name>_s8_c4_<seg>.npy`.  With `frame_step` in `kw` the step comes first: `<name>_d2_<seg>.npy`, `<name>_d2_s8_c4_<seg>.npy`."""
+    `<name>_s8_c4_<seg>.npy`.  With `frame_step` in `kw` the step comes first: `<name>_d2_<seg>.npy`, `<name>_d2_s8_c4_<seg>.npy`.
+    With `normalize` in `kw` its tag comes last: `<name>_npix_<seg>.npy`, `<name>_d2_s8_c4_nch-1f3a..._<seg>.npy`."""
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
     s, crops, d = resolve_sampling(fpc, kw.get("clip_stride"), kw.get("crops"), kw.get("frame_step"))
     nc = len(crops)
-    tag = feature_tag(fpc, s, crops, d)
+    tag = feature_tag(fpc, s, crops, d, kw.get("normalize"))
     seg_folder = os.path.join(outpath, name)
     plan = segment_windows(n_frames, seg_len, fpc, s, d)  # (refuses a seg_len the stride does not divide before anything is written)
     os.makedirs(seg_folder, exist_ok=True)
@@ -308,12 +330,13 @@ def extract_frames(sources: Iterable[Tuple[str, int, Callable[[int, int], torch.
     """Per-video driver for frame sources (name, n_frames, read_frames): `<name>_i3d.npy` per video with the reference's
     skip-if-exists rule (:106-110); videos longer than `long_video_frames` go through the per-segment cache.  With
     `clip_stride` (below frames_per_clip) the files are `<name>_i3d_s<stride>.npy`, with a crop subset
-    `<name>_i3d[_s<stride>]_c<digits>.npy`, with `frame_step` `<name>_i3d_d<step>[_s<stride>][_c<digits>].npy` (feature_tag)."""
+    `<name>_i3d[_s<stride>]_c<digits>.npy`, with `frame_step` `<name>_i3d_d<step>[_s<stride>][_c<digits>].npy`, with `normalize`
+    `<name>_i3d[_d<step>][_s<stride>][_c<digits>]_n<kind>[-<hash>].npy` (feature_tag)."""
     os.makedirs(outpath, exist_ok=True)
     fpc = kw.get("frames_per_clip", FRAMES_PER_CLIP)
     d = resolve_frame_step(kw.get("frame_step"))
     s = resolve_clip_stride(fpc, kw.get("clip_stride"), d)
-    suffix = "_i3d" + feature_tag(fpc, s, kw.get("crops"), d) + ".npy"
+    suffix = "_i3d" + feature_tag(fpc, s, kw.get("crops"), d, kw.get("normalize")) + ".npy"
     written = {}
     for name, n_frames, read_frames in sources:
         savepath = os.path.join(outpath, name + suffix)

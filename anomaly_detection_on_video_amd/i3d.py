@@ -330,30 +330,34 @@ class I3Res50(nn.Module):
                     and tuple(u.pool_unit.stride) == (2, 2, 2))
 
     def ensure_frame_tables(self, frame_hw: Tuple[int, int], frames_per_clip: int = 16, crop: int = 224, batch: Optional[int] = None,
-                            frame_step: Optional[int] = None) -> None:
+                            frame_step: Optional[int] = None, normalize=None) -> None:
         """ensure_tables for forward_frames: every lazily built table, on the current stream, before streams fork.  (The uint8
-        stems' gather tables are per frame_step.)"""
+        stems' gather tables are per frame_step; a non-default `normalize` never runs those stems.)"""
         self.ensure_tables((frames_per_clip, crop, crop), batch)
         if self.frames_fused():
             pc = self._plan[0].convs[0]
             if self._frames_planes(crop):
                 ops.ensure_ktab_s2w(pc, (frames_per_clip, crop, crop))
                 return
+            if not ops.normalize_is_default(normalize):
+                return
             build = ops.ensure_u8_taps_tables if ops.U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64 else ops.ensure_u8_tables
             build(pc, tuple(frame_hw), (frames_per_clip, crop, crop), frame_step=ops.resolve_frame_step(frame_step))
 
-    def frames_need_whole_windows(self, crop: int = 224) -> bool:
+    def frames_need_whole_windows(self, crop: int = 224, normalize=None) -> bool:
         """forward_frames reads `frames` from the stem kernel itself, which has no LoopPad: the caller hands over whole windows
         (ops.pad_windows_u8).  False: a TenCrop pass runs first (column-parity planes, or the separate-pass fallback) and
-        repeats a short last window's frames itself; whole windows are accepted there too (frame_step 1) but not needed."""
-        return self.frames_fused() and not self._frames_planes(crop)
+        repeats a short last window's frames itself; whole windows are accepted there too (frame_step 1) but not needed.
+        A non-default `normalize` always runs a TenCrop pass: the stems' tables fold one scalar mean."""
+        return self.frames_fused() and not self._frames_planes(crop) and ops.normalize_is_default(normalize)
 
     def _frames_planes(self, crop: int) -> bool:
         """forward_frames goes through column-parity planes (TenCrop pass writing them + the 16-byte-gather stem)."""
         return ops.U8_STEM_FORM == "planes" and ops.s2w_ok(self._plan[0].convs[0], crop)
 
     def forward_frames(self, frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224,
-                       clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None) -> torch.Tensor:
+                       clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None, normalize=None,
+                       crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Features (count, 2048, 1, 1, 1) of crop-clips [first, first + count) of a video given as resized uint8 frames
         (F, FH, FW, 3), F whole clips; row = clip * 10 + crop in TenCrop order.  What the reference does on the host per clip
         -- GroupTenCrop, ToTensor, GroupNormalize, the (T,C)->(C,T) permute (src/dataset.py:175-195, src/gtransforms.py:29-38,
@@ -364,15 +368,23 @@ class I3Res50(nn.Module):
         clip * len(crops) + j holds crop crops[j] -- the ten-crop row of that (clip, crop) bit for bit, at 1 / 10 .. 1 of the work.
         `frame_step` d (default 1): clip w = frames w * clip_stride + t * d, t in [0, frames_per_clip) -- every d-th frame of a span
         of frames_per_clip * d, addressed in place; clip_stride defaults to the span and F is whole windows in that sense
-        (ops.pad_windows_u8 with the same arguments)."""
+        (ops.pad_windows_u8 with the same arguments).
+        `normalize` (ops.resolve_normalize; default the reference's (x - 114.75) / 57.375): per-channel standardisation,
+        "pixel_minmax" or "channel_minmax".  Anything but the default runs a TenCrop pass with that normalisation in front of
+        the stem -- the planes pass where the column-parity stem applies, else mil_ops.tencrop_normalize_u8 and forward_single
+        -- never the whole-pixel / byte stems, whose tables fold one scalar mean; a short last window needs no padding then.
+        `crop_stats`: the min-max kinds' statistics of `frames` (ops.crop_minmax_u8 at ops.crop_stats_pitch(...)), computed here
+        when not given."""
         s, crops, fstep = ops.resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
+        norm = ops.resolve_normalize(normalize)
+        plain = ops.normalize_is_default(norm)
         if self.training:
             raise _lib.HipExtensionError("I3Res50 HIP path implements eval-mode BatchNorm only; call .eval()")
         if self.in_channels != 3:
             raise _lib.HipExtensionError("forward_frames takes RGB frames: the backbone was built with in_channels != 3")
         if frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_cuda:
             raise _lib.HipExtensionError(f"forward_frames wants uint8 (F,H,W,3) frames on the GPU, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
-        if fstep != 1 and self.frames_need_whole_windows(crop):
+        if fstep != 1 and self.frames_need_whole_windows(crop, norm):
             # (a whole-window buffer ends with the last window's last SAMPLED frame, short of its span: counted as the stem counts)
             n = ops.buffer_windows(frames.shape[0], frames_per_clip, s, fstep) * len(crops)
         else:
@@ -381,15 +393,18 @@ class I3Res50(nn.Module):
             raise ValueError(f"forward_frames: crop-clips [{first}, {first + count}) outside the video's {n}")
         self.prepare()
         with torch.no_grad():
-            if not self.frames_fused():  # other stems / ADV_I3D_FUSE_POOL=0: TenCrop + normalise as its own HIP pass
+            if not self.frames_fused() or not (plain or self._frames_planes(crop)):
+                # other stems / ADV_I3D_FUSE_POOL=0, or a normalisation the uint8 stems cannot fold: TenCrop + normalise as its own HIP pass
                 from . import mil_ops
 
-                return self.forward_single(mil_ops.tencrop_normalize_u8(frames, frames_per_clip, crop, clip_stride=s, crops=crops, frame_step=frame_step)[first : first + count])
+                return self.forward_single(mil_ops.tencrop_normalize_u8(frames, frames_per_clip, crop, clip_stride=s, crops=crops, frame_step=frame_step,
+                                                                        normalize=norm, crop_stats=crop_stats)[first : first + count])
             stem, pu = self._plan[0], self._plan[0].pool_unit
             if self._frames_planes(crop):
                 # one pass: TenCrop + float + normalise + permutes, written as column-parity planes; then the stem with 16-byte
                 # gather pieces.  Same arithmetic per pixel as the fp32 pipeline: the features equal model(tencrop_normalize_u8(..)).
-                xs = ops.tencrop_planes_u8(frames, first, count, frames_per_clip, crop, clip_stride=s, crops=crops, frame_step=frame_step)
+                xs = ops.tencrop_planes_u8(frames, first, count, frames_per_clip, crop, clip_stride=s, crops=crops, frame_step=frame_step,
+                                           normalize=norm, crop_stats=crop_stats)
                 stem_fn = lambda out=None: ops.conv3d_s2w_bn_relu_maxpool233(xs, stem.convs[0], out=out)
             else:
                 stem_fn = lambda out=None: ops.conv3d_u8_tencrop_bn_relu_maxpool233(frames, stem.convs[0], first, count, frames_per_clip, crop, out=out,

@@ -8,9 +8,12 @@ from __future__ import annotations
 import os
 
 import ctypes as C
+import hashlib
+import math
 import numbers
+import struct
 from dataclasses import dataclass, field
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -486,17 +489,167 @@ def crops_tag(crops) -> str:
     return "" if len(idx) == 10 else "_c" + "".join(str(c) for c in idx)
 
 
+class Normalize(NamedTuple):
+    """A normalisation of the uint8-frame path in canonical form (resolve_normalize): `kind` and two per-channel triples of
+    Python floats -- (mean, std) for "standardize", (lo, hi) for the two min-max kinds."""
+
+    kind: str
+    a: Tuple[float, float, float]
+    b: Tuple[float, float, float]
+
+
+# kind -> (its default parameters, its file-name tag, its ADVHIP_NORM_* mode)
+NORMALIZE_KINDS = {"standardize": ((114.75, 57.375), "_nstd", _lib.NORM_STANDARDIZE),
+                   "pixel_minmax": ((0.0, 1.0), "_npix", _lib.NORM_PIXEL_MINMAX),
+                   "channel_minmax": ((0.0, 1.0), "_nch", _lib.NORM_CHANNEL_MINMAX)}
+
+
+def _f32(v: float) -> float:
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+def _norm_triple(spec, v, scalar_only: bool) -> Tuple[float, float, float]:
+    def num(x):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(float(x)) or abs(float(x)) > 3.0e38:
+            raise ValueError(f"normalize {spec!r}: parameters are finite numbers (fp32 range)")
+        return float(x)
+
+    if isinstance(v, numbers.Real) and not isinstance(v, bool):
+        return (num(v),) * 3
+    try:
+        t = tuple(v)
+    except TypeError:
+        raise ValueError(f"normalize {spec!r}: a parameter is a number or three numbers, one per channel") from None
+    if len(t) != 3:
+        raise ValueError(f"normalize {spec!r}: a per-channel parameter has three entries")
+    t = tuple(num(x) for x in t)
+    if scalar_only and not t[0] == t[1] == t[2]:
+        raise ValueError(f"normalize {spec!r}: pixel_minmax takes one range for all channels")
+    return t
+
+
+def resolve_normalize(spec) -> Normalize:
+    """The normalisation of a uint8-frame call in canonical form, the reference's three normalisers (src/gtransforms.py:57-112):
+      None, "standardize", ("standardize", mean, std): (x - mean[c]) / std[c]; default (114.75, 57.375), the reference's own, and
+          in that form "none" in every respect: the existing kernels, no file-name tag;
+      "pixel_minmax", ("pixel_minmax", lo, hi): (x - mn) / (mx - mn) * (hi - lo) + lo with mn, mx over all channels of each
+          (frame, crop); scalars, lo < hi, default (0, 1);
+      "channel_minmax", ("channel_minmax", lo, hi): the same with mn, mx, lo, hi per channel; at least one channel has lo < hi
+          (the reference's condition), default (0, 1).
+    A parameter is a number (broadcast to the three channels) or three numbers; ints are numbers (the reference's
+    isinstance(x, float) quirk, where an int builds an empty tensor, is not reproduced).  Anything else raises ValueError."""
+    if isinstance(spec, Normalize):
+        kind, params = spec.kind, (spec.a, spec.b)
+    elif spec is None:
+        kind, params = "standardize", None
+    elif isinstance(spec, str):
+        kind, params = spec, None
+    else:
+        try:
+            t = tuple(spec)
+        except TypeError:
+            raise ValueError(f"normalize {spec!r}: a kind, or (kind, a, b)") from None
+        if len(t) != 3 or not isinstance(t[0], str):
+            raise ValueError(f"normalize {spec!r}: a kind, or (kind, a, b)")
+        kind, params = t[0], t[1:]
+    if kind not in NORMALIZE_KINDS:
+        raise ValueError(f"normalize {spec!r}: kind is one of {sorted(NORMALIZE_KINDS)}")
+    if params is None:
+        params = NORMALIZE_KINDS[kind][0]
+    a, b = (_norm_triple(spec, v, kind == "pixel_minmax") for v in params)
+    if kind == "standardize":
+        if any(_f32(s) == 0.0 for s in b):
+            raise ValueError(f"normalize {spec!r}: std must be non-zero")
+    elif kind == "pixel_minmax":
+        if not a[0] < b[0]:
+            raise ValueError(f"normalize {spec!r}: lo must be below hi")
+    elif not any(lo < hi for lo, hi in zip(a, b)):
+        raise ValueError(f"normalize {spec!r}: lo must be below hi in at least one channel")
+    return Normalize(kind, a, b)
+
+
+def normalize_is_default(spec) -> bool:
+    """The reference's own (x - 114.75) / 57.375 under any of its spellings (compared as the fp32 values the kernels take)."""
+    n = resolve_normalize(spec)
+    return n.kind == "standardize" and all(_f32(m) == PIXEL_MEAN for m in n.a) and all(_f32(s) == PIXEL_STD for s in n.b)
+
+
+def normalize_tag(spec) -> str:
+    """The file-name tag of a normalisation: "" for the default; else "_nstd", "_npix" or "_nch", and where the parameters are not
+    that kind's defaults "-" plus the first 8 hex digits of the SHA-1 of the six parameters as little-endian fp32 (mean or lo of
+    the three channels, then std or hi): "_npix", "_npix-5a2b...", "_nstd-...".  (Ranges that differ only below fp32 precision
+    share a tag.)"""
+    n = resolve_normalize(spec)
+    if normalize_is_default(n):
+        return ""
+    (da, db), tag, _ = NORMALIZE_KINDS[n.kind]
+    if all(_f32(v) == _f32(da) for v in n.a) and all(_f32(v) == _f32(db) for v in n.b):
+        return tag
+    return tag + "-" + hashlib.sha1(struct.pack("<6f", *n.a, *n.b)).hexdigest()[:8]
+
+
+def crop_stats_pitch(frames_per_clip: int, clip_stride: Optional[int] = None, frame_step: Optional[int] = None) -> int:
+    """The frame pitch of a call's statistics table: gcd(clip_stride, frame_step) -- every frame any window samples, w * clip_stride
+    + t * frame_step, is a multiple of it (frame_step 1: every frame)."""
+    d = resolve_frame_step(frame_step)
+    return math.gcd(resolve_clip_stride(frames_per_clip, clip_stride, d), d)
+
+
+def crop_minmax_u8(frames: torch.Tensor, crop: int = 224, frame_pitch: int = 1) -> torch.Tensor:
+    """Resized uint8 frames (F, H, W, C) -> uint8 (ceil(F / frame_pitch), 6, C, 2): (min, max) per channel of the six windows
+    that hold the pixels of TenCrop's ten crops -- the four corners, the centre, and the centre of the mirrored frame (the
+    centre's own window only where W - crop is even) -- of frames 0, frame_pitch, 2 * frame_pitch, ...: crop j < 5 has window j's
+    pixels, a mirrored corner 5..8 those of the opposite corner (j - 5) ^ 1, crop 9 those of window 5.  The statistics of the
+    min-max normalisations, one HIP launch, exact."""
+    frames = frames.contiguous()
+    require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
+    f, h, w, c = frames.shape
+    if isinstance(frame_pitch, bool) or not isinstance(frame_pitch, numbers.Integral) or frame_pitch < 1:
+        raise ValueError(f"crop_minmax_u8: frame_pitch {frame_pitch!r}: an integer >= 1")
+    if f < 1 or h < crop or w < crop or crop < 1:
+        raise ValueError(f"crop_minmax_u8: {f} frames of {h}x{w}, crop {crop}")
+    stats = torch.empty((-(-f // int(frame_pitch)), 6, c, 2), device=frames.device, dtype=torch.uint8)
+    check(_lib.load().advhip_crop_minmax_u8(ptr(frames), ptr(stats), f, h, w, c, crop, int(frame_pitch), stream(frames)), "crop_minmax_u8")
+    return stats
+
+
+def normalize_launch_args(norm: Normalize, frames: torch.Tensor, crop: int, frames_per_clip: int, clip_stride: int, frame_step: int,
+                          crop_stats: Optional[torch.Tensor]):
+    """(mode, a, b, stats, stats_pitch) as the `_modes` entry points take them for `frames` (F, H, W, C) on the device: the
+    min-max kinds' table is `crop_stats` (checked against the call's pitch and frames) or computed here on the current stream."""
+    mode = NORMALIZE_KINDS[norm.kind][2]
+    a, b = (C.c_double * 3)(*norm.a), (C.c_double * 3)(*norm.b)
+    pitch = crop_stats_pitch(frames_per_clip, clip_stride, frame_step)
+    if mode == _lib.NORM_STANDARDIZE:
+        return mode, a, b, None, pitch
+    if crop_stats is None:
+        crop_stats = crop_minmax_u8(frames, crop, pitch)
+    else:
+        require_gpu(crop_stats)
+        want = (-(-frames.shape[0] // pitch), 6, frames.shape[3], 2)
+        if crop_stats.dtype != torch.uint8 or tuple(crop_stats.shape) != want or crop_stats.device != frames.device:
+            raise ValueError(f"crop_stats {crop_stats.dtype} {tuple(crop_stats.shape)} on {crop_stats.device}: expected uint8 {want} on "
+                             f"{frames.device} (ops.crop_minmax_u8 at frame pitch {pitch})")
+    return mode, a, b, crop_stats, pitch
+
+
 def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = 114.75,
-                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None) -> torch.Tensor:
+                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None,
+                      normalize=None, crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Resized uint8 frames (F, H, W, C) -> column-parity planes (count, C, frames_per_clip, crop, 2, crop/2 + 4) of crop-clips
     [first, first + count) (row = clip * 10 + crop): TenCrop, float, normalise, LoopPad and the layout permutes of
     TenCropVideoFrameDataset / _extract (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass,
     written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's.  `clip_stride` (default
     frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride.  `crops`
     (resolve_crops): row = clip * len(crops) + j holds crop crops[j].  `frame_step` (default 1): clip w = frames w * clip_stride +
-    t * frame_step, t in [0, frames_per_clip); clip_stride then defaults to frames_per_clip * frame_step."""
+    t * frame_step, t in [0, frames_per_clip); clip_stride then defaults to frames_per_clip * frame_step.  `normalize`
+    (resolve_normalize; default: (x - mean) / std with the two scalars): per-channel standardisation or a min-max mode, whose
+    statistics are `crop_stats` (crop_minmax_u8 at frame pitch crop_stats_pitch(...)) or computed here."""
     s, crops, d = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc, packed = pack_crops(crops)
+    norm = resolve_normalize(normalize)
     frames = frames.contiguous()
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
@@ -506,6 +659,14 @@ def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_c
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
+    if not normalize_is_default(norm):
+        if (mean, std) != (PIXEL_MEAN, PIXEL_STD):
+            raise ValueError("tencrop_planes_u8: give the constants in `normalize`, not in `mean` / `std` as well")
+        mode, a, b, stats, pitch = normalize_launch_args(norm, frames, crop, frames_per_clip, s, d, crop_stats)
+        check(_lib.load().advhip_tencrop_normalize_planes_u8_modes(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
+                                                                   first, count, mode, a, b, ptr(stats), pitch, stream(frames)),
+              "tencrop_normalize_planes_u8_modes")
+        return xs
     check(_lib.load().advhip_tencrop_normalize_planes_u8_sampled(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, first,
                                                                  count, C.c_float(mean), C.c_float(std), stream(frames)),
           "tencrop_normalize_planes_u8")

@@ -26,20 +26,24 @@ class FrameCrops:
     itself (I3Res50.forward_frames); a `prepare` callable of step_async may return one of these.  `clip_stride` (default
     frames_per_clip): clip w = frames [w * clip_stride, w * clip_stride + frames_per_clip).  `crops` (ops.resolve_crops;
     default all ten): row = clip * len(crops) + j holds crop crops[j] -- feed a stream built with ncrops = len(crops).
-    `frame_step` d (default 1): clip w = frames w * clip_stride + t * d; clip_stride then defaults to frames_per_clip * d."""
+    `frame_step` d (default 1): clip w = frames w * clip_stride + t * d; clip_stride then defaults to frames_per_clip * d.
+    `normalize` (ops.resolve_normalize; default the reference's (x - 114.75) / 57.375): the normalisation forward_frames applies."""
 
     def __init__(self, frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224,
-                 clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None):
+                 clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None, normalize=None):
         self.frames, self.first, self.count, self.frames_per_clip, self.crop = frames, first, count, frames_per_clip, crop
         self.frame_step = ops.resolve_frame_step(frame_step)
         self.clip_stride = ops.resolve_clip_stride(frames_per_clip, clip_stride, self.frame_step)
         self.crops = None if crops is None else ops.resolve_crops(crops)
+        self.normalize = None if ops.normalize_is_default(normalize) else ops.resolve_normalize(normalize)
 
     def key(self):
         base = ("u8", self.count, tuple(self.frames.shape[1:3]), self.frames_per_clip, self.crop, self.clip_stride)
         if self.frame_step != 1:  # (its own launch arguments and gather tables)
             base += (("frame_step", self.frame_step),)
-        return base if self.crops is None else base + (self.crops,)
+        if self.crops is not None:
+            base += (self.crops,)
+        return base if self.normalize is None else base + (("normalize",) + tuple(self.normalize),)
 
 
 class ExtractScoreStream:
@@ -162,7 +166,8 @@ class ExtractScoreStream:
                 if isinstance(local_clips, FrameCrops):
                     fc = local_clips
                     feats = self.backbone.forward_frames(fc.frames, fc.first, fc.count, fc.frames_per_clip, fc.crop,
-                                                         clip_stride=fc.clip_stride, crops=fc.crops, frame_step=fc.frame_step).reshape(fc.count, -1)
+                                                         clip_stride=fc.clip_stride, crops=fc.crops, frame_step=fc.frame_step,
+                                                         normalize=fc.normalize).reshape(fc.count, -1)
                 else:
                     feats = self.backbone(local_clips).reshape(local_clips.shape[0], -1)
             finally:

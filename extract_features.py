@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET]]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET] [--normalize SPEC]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
@@ -14,6 +14,10 @@ the entry point for a real decoder's (name, n_frames, read_frames) triples.  `--
 (`<name>_i3d[_s<N>]_c<digits>.npy`, features (n_clips, len(SET), 2048)): a tenth to all of the backbone work per clip.
 `--frame-step N` (with `--frame-size`) samples every N-th frame: a window is 16 frames out of a span of 16 x N, windows start
 every `--clip-stride` frames (1 .. 16 x N, default the span), files are `<name>_i3d_d<N>[_s<stride>][_c<digits>].npy`.
+`--normalize SPEC` (with `--frame-size`) replaces the reference's (x - 114.75) / 57.375 by another of its normalisers, on the device:
+`standardize:MEAN:STD` (each one number or three, e.g. `standardize:123.675,116.28,103.53:58.395,57.12,57.375`), `pixel_minmax` or
+`pixel_minmax:LO,HI` (e.g. `pixel_minmax:-1,1`), `channel_minmax`, `channel_minmax:LO,HI` or `channel_minmax:LO,LO,LO:HI,HI,HI`; the
+files carry the normalisation last in their name (`<name>_i3d..._npix-<hash>.npy`).
 """
 import argparse
 import os
@@ -69,8 +73,33 @@ def parse_crops(text: str):
         raise argparse.ArgumentTypeError(f"--crops {text!r}: {e}")
 
 
+def parse_normalize(text: str):
+    """--normalize: KIND, KIND:A,B (two scalars) or KIND:A:B (each one number or three, comma-separated) -> ops.Normalize."""
+    from anomaly_detection_on_video_amd.ops import resolve_normalize
+
+    def numbers(part):
+        v = tuple(float(x) for x in part.split(","))
+        return v[0] if len(v) == 1 else v
+
+    try:
+        kind, *parts = text.split(":")
+        if not parts:
+            return resolve_normalize(kind)
+        if len(parts) == 1:
+            pair = numbers(parts[0])
+            if not isinstance(pair, tuple) or len(pair) != 2:
+                raise ValueError("KIND:A,B takes two numbers; per-channel values go in KIND:A,A,A:B,B,B")
+            return resolve_normalize((kind, pair[0], pair[1]))
+        if len(parts) == 2:
+            return resolve_normalize((kind, numbers(parts[0]), numbers(parts[1])))
+        raise ValueError("KIND, KIND:A,B or KIND:A:B")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--normalize {text!r}: {e}")
+
+
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
-         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None, frame_step: int = None):
+         model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None, frame_step: int = None,
+         normalize=None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if clip_stride is not None and frame_size is None:
@@ -84,6 +113,8 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
         raise ValueError(f"--clip-stride {clip_stride} outside [1, {span}]")
     if crops is not None and frame_size is None:
         raise ValueError("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
+    if normalize is not None and frame_size is None:
+        raise ValueError("--normalize needs --frame-size: the clip-tensor source is normalised already")
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
@@ -92,7 +123,7 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
         extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops,
-                       frame_step=frame_step)
+                       frame_step=frame_step, normalize=normalize)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -113,6 +144,9 @@ if __name__ == "__main__":
                     help="with --frame-size: temporal sampling, a window is every N-th frame of a span of 16 x N frames (default 1)")
     ap.add_argument("--crops", type=parse_crops, default=None, metavar="SET",
                     help="with --frame-size: ten (default), five, center, center_flip, or ascending TenCrop indices such as 0,4,9")
+    ap.add_argument("--normalize", type=parse_normalize, default=None, metavar="SPEC",
+                    help="with --frame-size: standardize:MEAN:STD, pixel_minmax[:LO,HI] or channel_minmax[:LO,HI | :LO,LO,LO:HI,HI,HI] "
+                         "(default: the reference's (x - 114.75) / 57.375)")
     a = ap.parse_args()
     if a.clip_stride is not None and a.frame_size is None:
         ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
@@ -124,4 +158,6 @@ if __name__ == "__main__":
         ap.error(f"--clip-stride {a.clip_stride} outside [1, {16 * (a.frame_step or 1)}]")
     if a.crops is not None and a.frame_size is None:
         ap.error("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step)
+    if a.normalize is not None and a.frame_size is None:
+        ap.error("--normalize needs --frame-size: the clip-tensor source is normalised already")
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step, a.normalize)

@@ -743,6 +743,46 @@ int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t
                                         int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop, int32_t ncrops,
                                         uint64_t crops_packed, float mean, float stdv, void* stream);
 
+/* --- normalisation modes of the two TenCrop passes (src/gtransforms.py:57-112) ---
+ * ADVHIP_NORM_STANDARDIZE:    y = (x - mean[c]) / std[c]                 (GroupStandardizationTenCrop with per-channel lists)
+ * ADVHIP_NORM_PIXEL_MINMAX:   y = (x - mn) / (mx - mn) * r + lo           (GroupPixelMinmaxTenCrop: mn, mx over all C * crop * crop
+ *                                                                          values of the (frame, crop); r = float(hi - lo), the
+ *                                                                          subtraction in double)
+ * ADVHIP_NORM_CHANNEL_MINMAX: the same with mn, mx, lo, r per channel     (GroupRGBChannelMinmaxTenCrop: r[c] = float(hi[c]) -
+ *                                                                          float(lo[c]))
+ * Every operation is one separately rounded fp32 operation (no FMA, a true division).  A constant crop / channel gives 0 / 0 = NaN,
+ * as the reference does; nothing is guarded. */
+#define ADVHIP_NORM_STANDARDIZE 0
+#define ADVHIP_NORM_PIXEL_MINMAX 1
+#define ADVHIP_NORM_CHANNEL_MINMAX 2
+
+/* The statistics of the min-max modes.  frames: resized uint8 (F, H, W, C).  stats: uint8 (ceil(F / frame_pitch), 6, C, 2) =
+ * (min, max) per channel of the six windows that hold the pixels of TenCrop's ten crops -- top-left, top-right, bottom-left,
+ * bottom-right, centre (the Python-rounded half offsets of the passes) and the centre of the mirrored frame, whose left edge is
+ * W - crop - (the centre's): the centre's own only where W - crop is even -- of frames 0, frame_pitch, 2 frame_pitch, ...
+ * Crop j < 5 reads window j, a mirrored corner 5..8 the opposite corner's window (j - 5) ^ 1, crop 9 window 5.
+ * Integer min / max on the bytes: exact, no atomics, the same bits on every run.  The pixel mode reduces the C pairs at look-up. */
+int advhip_crop_minmax_u8(const uint8_t* frames, uint8_t* stats, int32_t F, int32_t H, int32_t W, int32_t C, int32_t crop,
+                          int32_t frame_pitch, void* stream);
+
+/* advhip_tencrop_normalize_u8_sampled / advhip_tencrop_normalize_planes_u8_sampled with a mode: the same rows, layouts, LoopPad
+ * rule, crop sets and frame addressing.  a, b: HOST triples of doubles, (mean, std) or (lo, hi) per channel as the caller states
+ * them (C <= 3; channel c reads entry c).  stats / stats_pitch: the table above for the min-max modes (ignored by
+ * ADVHIP_NORM_STANDARDIZE); stats_pitch must divide clip_stride and frame_step, so that every sampled frame is one the table
+ * holds -- frame f reads entry f / stats_pitch, and a LoopPad copy of a frame its statistics.
+ * ADVHIP_EINVAL before anything launches: a null pointer, an unknown mode, a zero std, lo >= hi (pixel mode: in any channel;
+ * channel mode: in every channel -- the reference's own condition), stats_pitch < 1 or not a divisor, and everything the
+ * `_sampled` calls refuse. */
+int advhip_tencrop_normalize_u8_modes(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                      int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop, int32_t ncrops,
+                                      uint64_t crops_packed, int32_t mode, const double* a, const double* b, const uint8_t* stats,
+                                      int32_t stats_pitch, void* stream);
+int advhip_tencrop_normalize_planes_u8_modes(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                             int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                             int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
+                                             int32_t mode, const double* a, const double* b, const uint8_t* stats,
+                                             int32_t stats_pitch, void* stream);
+
 /* Per-window scores (n_windows,) -> per-frame scores (n_frames,): window w covers frames [w * clip_stride, w * clip_stride +
  * frames_per_clip); the score of a frame is the mean of the scores of the windows covering it (fp32, added in ascending window
  * order, one division by their count).  0 < n_frames <= (n_windows - 1) * clip_stride + frames_per_clip.  clip_stride =
