@@ -42,6 +42,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+// The backbone's ReLU and window maxima: NaN in, NaN out, as torch.relu / clamp_min / max_pool3d (fmaxf returns the operand that
+// is NOT a NaN, which would turn a NaN clip into finite features).  IEEE 754-2019 maximum = one v_maximum3_f32 on gfx950, the
+// instruction count of fmaxf; without a NaN operand the result is fmaxf's bit for bit (max(-0, +0) = +0 in both).
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return max_nan(v, 0.f); }
+
 // A crop subset of TenCrop as the kernels take it: `ncrops` 4-bit indices, entry j in bits [4 j, 4 j + 4) (row clip * ncrops + j
 // holds crop entry j).  All ten in order = the identity set.
 constexpr unsigned long long TENCROP_ALL = 0x9876543210ull;

@@ -190,7 +190,7 @@ __device__ __forceinline__ float act_gelu_grad(float x) {
 // the pre-activation itself), 4 none + the result multiplied by the `dact` tensor AS IS (a GELU' saved by a code-3 forward: the fused GELU
 // backward without an erf / exp in the backward epilogue)
 constexpr int ACT_GELU_D = 3, ACT_MUL = 4;
-__device__ __forceinline__ float act_apply(int code, float v) { return code == 1 ? fmaxf(v, 0.f) : ((code == 2 || code == ACT_GELU_D) ? act_gelu(v) : v); }
+__device__ __forceinline__ float act_apply(int code, float v) { return code == 1 ? relu_nan(v) : ((code == 2 || code == ACT_GELU_D) ? act_gelu(v) : v); }
 // what the second output holds for pre-activation value v
 __device__ __forceinline__ float act_second(int code, float v) { return code == ACT_GELU_D ? act_gelu_grad(v) : v; }
 // the `dact` factor for a stored operand value
@@ -261,7 +261,7 @@ __device__ __forceinline__ void igemm_epilogue_plain(const ConvArgs& a, f32x4 (&
       pre = cdf + v * expf(-0.5f * v * v) * 0.39894228040143267794f;
       v = v * cdf;
     } else if constexpr (MODE != EM_MUL) {
-      v = relu ? fmaxf(v, 0.f) : v;
+      v = relu ? relu_nan(v) : v;
     }
     if constexpr (MODE == EM_DACT) v *= act_gelu_grad(op);
     if constexpr (MODE == EM_MUL) v *= op;
@@ -932,8 +932,8 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
           const int c = c0 + 4 * i;
           const int n = n0 + 2 * c + jn;
           float v0 = smem[c * RS + pw] + r0[i], v1 = smem[c * RS + 64 + pw] + r1[i];
-          if (a.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-          a.y[(size_t)bk_b * a.y_bstride + ((size_t)n * a.Tp + bk_t) * a.HWo + ow] = fmaxf(v0, v1);
+          if (a.relu) { v0 = relu_nan(v0); v1 = relu_nan(v1); }
+          a.y[(size_t)bk_b * a.y_bstride + ((size_t)n * a.Tp + bk_t) * a.HWo + ow] = max_nan(v0, v1);
         }
       }
       __syncthreads();
@@ -972,21 +972,21 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
 #pragma unroll
           for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[4 * r + i] = fmaxf((acc[i][jn][r] + c0) * sc + sf, 0.f);
+            for (int i = 0; i < 4; ++i) v[4 * r + i] = relu_nan((acc[i][jn][r] + c0) * sc + sf);
         } else {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int wc = u8_border_class((ow0 + 4 * r + i) * a.sw - a.pw, a.kw_, a.W, a.pw);  // (outputs past Wo: any class, zeroed below)
-              v[4 * r + i] = fmaxf((acc[i][jn][r] + cr[(size_t)wc * a.Cout]) * sc + sf, 0.f);
+              v[4 * r + i] = relu_nan((acc[i][jn][r] + cr[(size_t)wc * a.Cout]) * sc + sf);
             }
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[4 * r + i] = fmaxf(acc[i][jn][r] * sc + sf, 0.f);
+          for (int i = 0; i < 4; ++i) v[4 * r + i] = relu_nan(acc[i][jn][r] * sc + sf);
       }
       if (!inside) {  // positions outside the tensor count as 0: neutral for maxima of post-ReLU values
 #pragma unroll
@@ -994,10 +994,10 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
       }
       float pr[8], cs[9];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) pr[j] = fmaxf(v[2 * j], v[2 * j + 1]);
+      for (int j = 0; j < 8; ++j) pr[j] = max_nan(v[2 * j], v[2 * j + 1]);
       cs[0] = v[0];
 #pragma unroll
-      for (int k = 1; k < 8; ++k) cs[k] = fmaxf(pr[k - 1], v[2 * k]);
+      for (int k = 1; k < 8; ++k) cs[k] = max_nan(pr[k - 1], v[2 * k]);
       cs[8] = pr[7];
       float* lrow = smem + c_w * LC + (wm * BH + lg) * LR;
       *reinterpret_cast<float4*>(lrow) = make_float4(cs[0], cs[1], cs[2], cs[3]);
@@ -1013,10 +1013,10 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
           const float* l0 = smem + c * LC + k;
           float h[4];
 #pragma unroll
-          for (int hh = 0; hh < 4; ++hh) h[hh] = fmaxf(l0[hh * LR], l0[(BH + hh) * LR]);  // max over the two t planes
+          for (int hh = 0; hh < 4; ++hh) h[hh] = max_nan(l0[hh * LR], l0[(BH + hh) * LR]);  // max over the two t planes
           P[q] = h[0];
-          P[CH * 9 + q] = fmaxf(fmaxf(h[0], h[1]), h[2]);
-          P[2 * CH * 9 + q] = fmaxf(h[2], h[3]);
+          P[CH * 9 + q] = max_nan(max_nan(h[0], h[1]), h[2]);
+          P[2 * CH * 9 + q] = max_nan(h[2], h[3]);
         }
       }
       __syncthreads();
@@ -1063,10 +1063,10 @@ __global__ __launch_bounds__(256) void stem_pool_merge_kernel(const float* __res
     const int ws = w2 ? 8 : 1 + (wp & 7);
     const float* l = L + wb * 288 + c * 9;
     float m = l[ws];
-    if (w2) m = fmaxf(m, l[288]);
+    if (w2) m = max_nan(m, l[288]);
     if (h2) {
-      m = fmaxf(m, l[nbw * 288 + ws]);
-      if (w2) m = fmaxf(m, l[nbw * 288 + 288]);
+      m = max_nan(m, l[nbw * 288 + ws]);
+      if (w2) m = max_nan(m, l[nbw * 288 + 288]);
     }
     const int n = tile_n * 64 + 2 * c + jn;
     y[(long long)b * ybs + (((long long)n * Tp + tp) * Hp + hp) * Wp + wp] = m;
@@ -1214,7 +1214,7 @@ __device__ __forceinline__ void avg_epilogue_body(const ConvArgs& a, f32x4 (&acc
         v += rv[k % W];
         if (k + W < NP) issue(k + W);
       }
-      v = relu ? fmaxf(v, 0.f) : v;
+      v = relu ? relu_nan(v) : v;
       v = wave_sum64(mok ? v : 0.f);
       if (lane == 0) part[wm * 64 + c] = v;
     }
@@ -2482,6 +2482,13 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& hi, uns
   hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
   const f32x2v r = {x0 - __builtin_bit_cast(float, hi << 16), x1 - __builtin_bit_cast(float, hi & 0xFFFF0000u)};
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+  // A non-finite x goes into the lo image alone (x - hi would be inf - inf).  There the only product it enters is x * w_hi: an
+  // infinity of the weight's own sign, as in fp32.  In the hi image it would meet w_lo as well, whose sign is the residue's:
+  // +inf - inf, a NaN where the fp32 kernels and torch give an infinity.  Finite operands: the same bits as before.
+  const unsigned nf = ((__float_as_uint(x0) & 0x7F800000u) == 0x7F800000u ? 0x0000FFFFu : 0u) |
+                      ((__float_as_uint(x1) & 0x7F800000u) == 0x7F800000u ? 0xFFFF0000u : 0u);
+  lo = (lo & ~nf) | (hi & nf);
+  hi &= ~nf;
 }
 
 template <int BN, bool CHECK>

@@ -751,7 +751,8 @@ int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t
  * ADVHIP_NORM_CHANNEL_MINMAX: the same with mn, mx, lo, r per channel     (GroupRGBChannelMinmaxTenCrop: r[c] = float(hi[c]) -
  *                                                                          float(lo[c]))
  * Every operation is one separately rounded fp32 operation (no FMA, a true division).  A constant crop / channel gives 0 / 0 = NaN,
- * as the reference does; nothing is guarded. */
+ * as the reference does; nothing is guarded.  The backbone hands it on as torch does -- NaN in, NaN out, confined to its crop-clip: the
+ * ReLU (activation code 1) and the window maxima / mean of every conv epilogue propagate NaN, and no other sample of a launch changes. */
 #define ADVHIP_NORM_STANDARDIZE 0
 #define ADVHIP_NORM_PIXEL_MINMAX 1
 #define ADVHIP_NORM_CHANNEL_MINMAX 2
