@@ -234,6 +234,8 @@ SIGNATURES = {
     "advhip_normalize_permute_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_resize_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "advhip_resize_u8_sampled": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "advhip_yuv420_to_rgb_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I] + [_I] * 6 + [_P]),
+    "advhip_resize_yuv420_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I] + [_I] * 6 + [_P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -141,7 +141,7 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
                          clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
-                         crops=None, frame_step: Optional[int] = None, normalize=None, **kw) -> np.ndarray:
+                         crops=None, frame_step: Optional[int] = None, normalize=None, pixel_format=None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -178,7 +178,15 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     GroupStandardizationTenCrop, GroupPixelMinmaxTenCrop and GroupRGBChannelMinmaxTenCrop (src/gtransforms.py:57-112), bit for
     bit on the normalised pixels, NaN for a constant crop / channel included.  The min-max kinds take each (frame, crop)'s minimum
     and maximum first: one statistics launch per step on the caller's stream (ops.crop_minmax_u8), shared by the step's ranges.  A
-    frame's statistics are its own: the normalised pixels do not depend on how the video is cut into steps."""
+    frame's statistics are its own: the normalised pixels do not depend on how the video is cut into steps.
+
+    `pixel_format` (resize.resolve_pixel_format; default None = packed RGB): "nv12", "i420" / "yuv420p", (layout, "bt709"),
+    (layout, matrix, "full") -- `frames` are the decoder's own 8-bit 4:2:0 frames, uint8 (F, 3H/2, W), on the host or the device.
+    Host frames cross PCIe as they are (1.5 bytes per pixel), the colour conversion runs on the device: inside the resize's
+    horizontal pass with `resize` (the full-size RGB frames never exist), as one launch of its own without (a decoder that scaled
+    already).  The features are those of the converted frames, extract_video_frames(yuv420_to_rgb_u8(frames), ...), bit for bit.
+    The conversion is resize.yuv_coefficients' integer formula with nearest chroma, not swscale's bytes: packed RGB frames
+    remain the reference-parity input.  Like `resize` it describes the source, so file names carry no tag for it."""
     s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     norm = resolve_normalize(normalize)
     plain = normalize_is_default(norm)
@@ -186,8 +194,14 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     subset = nc != 10  # ("ten" and (0, ..., 9) are None in every respect, the squeeze included)
     if clips_per_step is None:
         clips_per_step = max(1, 30 // nc) if subset else 3
-    if frames.dtype != torch.uint8 or frames.dim() != 4:
+    pf = resize_mod.resolve_pixel_format(pixel_format)
+    if pf is not None:
+        if frames.dtype != torch.uint8 or frames.dim() != 3:
+            raise ValueError(f"expected uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
+        resize_mod.frame_hw(frames.shape)  # (refuses an impossible geometry before anything is copied)
+    elif frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C) frames, got {frames.dtype} {tuple(frames.shape)}")
+    convert = resize is not None or pf is not None  # a device pass writes the RGB frames the step reads
     dev = next(model.parameters()).device
     rows = []
     n_total = n_windows(frames.shape[0], frames_per_clip, s, fstep)
@@ -199,7 +213,7 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
         fr = frames[w0 * s : (w1 - 1) * s + frames_per_clip * fstep]  # (the slice ends with the video: a short last window)
         ss, dd, rstep = s, fstep, None  # how the kernels address `fr`; the step of the resize
         if lattice:
-            if fr.is_cuda and resize is None:
+            if fr.is_cuda and not convert:
                 pass  # resized frames on the device: read in place, every fstep-th frame
             else:
                 ss, dd = s // fstep, 1  # downstream sees the lattice as a video of its own
@@ -207,13 +221,20 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
                     rstep = fstep  # decoded frames on the device: the resize reads the lattice in place
                 else:
                     fr = fr[::fstep]  # host frames: only the lattice crosses PCIe
-        if resize is not None:  # decoded frames -> GroupResize on the device, into a buffer with the stem's spare bytes
+        if convert:  # decoded frames -> (colour conversion +) GroupResize on the device, into a buffer with the stem's spare bytes
             fr = fr.to(dev, non_blocking=True).contiguous()
-            oh, ow = resize_mod.output_size(fr.shape[1], fr.shape[2], resize)
+            (h, w), c = ((fr.shape[1], fr.shape[2]), fr.shape[3]) if pf is None else (resize_mod.frame_hw(fr.shape), 3)
+            oh, ow = (h, w) if resize is None else resize_mod.output_size(h, w, resize)
             nf = fr.shape[0] if rstep is None else -(-fr.shape[0] // rstep)
-            n = nf * oh * ow * fr.shape[3]
+            n = nf * oh * ow * c
             buf = torch.empty((n + 16,), device=dev, dtype=torch.uint8)
-            fr = resize_mod.resize_u8(fr, resize, resample, out=buf[:n].view(nf, oh, ow, fr.shape[3]), frame_step=rstep)
+            out = buf[:n].view(nf, oh, ow, c)
+            if resize is None:  # 4:2:0 frames a decoder scaled already: the conversion launch alone
+                fr = resize_mod.yuv420_to_rgb_u8(fr, pf, out=out, frame_step=rstep)
+            elif pf is None:
+                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep)
+            else:
+                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, pixel_format=pf)
         elif direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
             buf = torch.empty((fr.numel() + 16,), device=dev, dtype=torch.uint8)
             if fr.is_contiguous():
@@ -301,7 +322,7 @@ def extract_long_video_frames(model, name: str, n_frames: int, read_frames: Call
     segments of `seg_len` frames (a multiple of 16, so only the last clip of the video is LoopPad-ed), each segment's
     (n_clips, 10, 2048) features are cached as `<outpath>/<name>/<name>_<seg>.npy` and re-used on a later run, and the
     segments are stacked.  `read_frames(start, stop)` returns the resized uint8 frames [start, stop) as (F, H, W, 3) (the decoded
-    ones with `resize=...` in `kw`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
+    ones with `resize=...` in `kw`, 4:2:0 frames (F, 3H/2, W) with `pixel_format=...`, see extract_video_frames).  With `clip_stride` in `kw` a segment owns the windows that start
     in it (segment_windows) and its files are `<name>_s<stride>_<seg>.npy`: a cache made at one stride is never read at another.
     With `crops` in `kw` the features are (n_clips, len(crops), 2048) and the files carry the set too, behind the stride:
     `<name>_s8_c4_<seg>.npy`.  With `frame_step` in `kw` the step comes first: `<name>_d2_<seg>.npy`, `<name>_d2_s8_c4_<seg>.npy`.

@@ -5,6 +5,11 @@ Host side (this module): torchvision's `Resize(int)` output-size rule and Pillow
 (Resample.c: `precompute_coeffs` + `normalize_coeffs_8bpc`), restated in double precision with Pillow's order of operations.
 Device side (csrc/resize.hip, `advhip_resize_u8`): Pillow's two passes, horizontal into a uint8 workspace then vertical,
 each `clamp((2**21 + sum(pixel * coef)) >> 22, 0, 255)` in int32.  NEAREST and HAMMING are not supported.
+
+Decoded frames as a decoder has them, 8-bit Y'CbCr 4:2:0 (NV12 / I420), go in through `pixel_format` (resolve_pixel_format):
+the colour conversion is the integer formula of `yuv_coefficients`, on the device, inside the horizontal pass.  That formula is
+this package's own definition, not ffmpeg swscale's bytes (the reference's RGB comes out of decord, i.e. swscale, which is not
+available to pin against): packed RGB frames remain the reference-parity path.
 """
 from __future__ import annotations
 
@@ -18,6 +23,73 @@ from . import _lib
 from ._lib import HipExtensionError, check, ptr, require_gpu, stream
 
 PRECISION_BITS = 22  # Pillow: 32 - 8 - 2
+
+LAYOUTS = {"nv12": 0, "i420": 1}  # ADVHIP_YUV420_*
+_LAYOUT_ALIASES = {"yuv420p": "i420"}
+LUMA_WEIGHTS = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}  # matrix -> (Kr, Kb)
+YUV_BITS = 16
+
+
+class PixelFormat(NamedTuple):
+    """How decoded 4:2:0 frames are laid out and which Y'CbCr they hold."""
+    layout: str  # "nv12" | "i420"
+    matrix: str  # "bt601" | "bt709"
+    full_range: bool
+
+
+_PF_ACCEPTED = ('None (packed RGB), "nv12", "i420" (or "yuv420p"), (layout, "bt601" | "bt709"), (layout, matrix, "limited" | "full") '
+                "or a PixelFormat")
+
+
+def resolve_pixel_format(spec) -> Optional[PixelFormat]:
+    """`pixel_format` of the frame entry points -> PixelFormat, or None for packed RGB (F, H, W, 3).  Accepted: None, "nv12",
+    "i420" (also spelt "yuv420p"; defaults bt601, limited range), (layout, matrix), (layout, matrix, "limited" | "full") and a
+    PixelFormat.  Anything else raises ValueError."""
+    if spec is None:
+        return None
+    parts = (spec,) if isinstance(spec, str) else spec
+    bad = ValueError(f"pixel_format {spec!r} is not supported: accepted are {_PF_ACCEPTED}")
+    if not isinstance(parts, (tuple, list)) or not 1 <= len(parts) <= 3:
+        raise bad
+    layout, matrix, rng = (list(parts) + ["bt601", "limited"][len(parts) - 1:])[:3]
+    if isinstance(rng, bool):  # (a PixelFormat's own field)
+        rng = "full" if rng else "limited"
+    if not all(isinstance(v, str) for v in (layout, matrix, rng)):
+        raise bad
+    layout = _LAYOUT_ALIASES.get(layout, layout)
+    if layout not in LAYOUTS or matrix not in LUMA_WEIGHTS or rng not in ("limited", "full"):
+        raise bad
+    return PixelFormat(layout, matrix, rng == "full")
+
+
+def frame_hw(shape) -> Tuple[int, int]:
+    """(H, W) of 4:2:0 frames shaped (..., 3H/2, W): both layouts store a frame as 3H/2 rows of W bytes (Y, then chroma)."""
+    if len(shape) < 2:
+        raise ValueError(f"4:2:0 frames are (F, 3H/2, W), got shape {tuple(shape)}")
+    rows, w = int(shape[-2]), int(shape[-1])
+    if rows < 3 or rows % 3:
+        raise ValueError(f"4:2:0 frames have 3H/2 rows: {rows} is not a positive multiple of 3")
+    if w < 2 or w % 2:
+        raise ValueError(f"4:2:0 frames need an even W, got W={w}")
+    return rows // 3 * 2, w  # (an odd H has no whole chroma rows: its 3H/2 is not a multiple of 3)
+
+
+def yuv_coefficients(pixel_format) -> Tuple[int, int, int, int, int, int]:
+    """(yoff, cy, crv, cgu, cgv, cbu) of a pixel format: round(real * 2**16) of the Y'CbCr -> RGB matrix that the luma weights
+    (Kr, Kb) and the range give.  The conversion, on the device and in any restatement, is
+        yi = cy * (Y - yoff) + 2**15
+        R = clip8((yi + crv * (Cr - 128)) >> 16)
+        G = clip8((yi - cgu * (Cb - 128) - cgv * (Cr - 128)) >> 16)        (arithmetic shifts)
+        B = clip8((yi + cbu * (Cb - 128)) >> 16)
+    which is within 1 of the rounded real formula for every (Y, Cb, Cr) and differs from it on fewer than 0.03 % of the values."""
+    pf = resolve_pixel_format(pixel_format)
+    if pf is None:
+        raise ValueError("yuv_coefficients: packed RGB has no conversion")
+    kr, kb = LUMA_WEIGHTS[pf.matrix]
+    kg = 1.0 - kr - kb
+    ys, cs, yoff = (1.0, 1.0, 0) if pf.full_range else (255.0 / 219.0, 255.0 / 224.0, 16)
+    real = (ys, 2.0 * (1.0 - kr) * cs, 2.0 * (1.0 - kb) * kb / kg * cs, 2.0 * (1.0 - kr) * kr / kg * cs, 2.0 * (1.0 - kb) * cs)
+    return (yoff,) + tuple(int(round(v * (1 << YUV_BITS))) for v in real)
 
 
 def _box(x: float) -> float:
@@ -165,18 +237,68 @@ def tables(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, st
     return t
 
 
+def _yuv_frames(who: str, frames: torch.Tensor, pf: PixelFormat) -> Tuple[int, int, int]:
+    """(F, H, W) of uint8 (F, 3H/2, W) 4:2:0 frames on the GPU."""
+    require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 3:
+        raise HipExtensionError(f"{who} wants uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
+    h, w = frame_hw(frames.shape)
+    return frames.shape[0], h, w
+
+
+def _check_out(who: str, frames: torch.Tensor, out: torch.Tensor, shape: tuple) -> None:
+    require_gpu(frames, out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape:
+        raise HipExtensionError(f"{who}: out must be uint8 {shape}, got {out.dtype} {tuple(out.shape)}")
+    a0, a1 = frames.data_ptr(), frames.data_ptr() + frames.numel()
+    if out.data_ptr() < a1 and a0 < out.data_ptr() + out.numel():
+        raise HipExtensionError(f"{who}: out overlaps the input frames")
+
+
+def _frame_step(who: str, frame_step) -> int:
+    d = 1 if frame_step is None else int(frame_step)
+    if d < 1:
+        raise ValueError(f"{who}: frame_step {frame_step!r} must be an integer >= 1")
+    return d
+
+
+def yuv420_to_rgb_u8(frames: torch.Tensor, pixel_format, out: Optional[torch.Tensor] = None,
+                     frame_step: Optional[int] = None) -> torch.Tensor:
+    """uint8 (F, 3H/2, W) 4:2:0 frames on the GPU (NV12 or I420, see resolve_pixel_format) -> packed RGB (F', H, W, 3), one
+    launch on the current stream: the integer conversion of `yuv_coefficients` with nearest chroma (pixel (y, x) uses chroma
+    sample (y >> 1, x >> 1)).  `frame_step` d: source frames 0, d, 2 d, ... only, F' = ceil(F / d).  `out` as in resize_u8.
+    Not ffmpeg swscale's bytes (the module docstring): the contract is the formula."""
+    pf = resolve_pixel_format(pixel_format)
+    if pf is None:
+        raise ValueError("yuv420_to_rgb_u8: pixel_format None is packed RGB, there is nothing to convert")
+    d = _frame_step("yuv420_to_rgb_u8", frame_step)
+    F_src, H, W = _yuv_frames("yuv420_to_rgb_u8", frames, pf)
+    F = -(-F_src // d)
+    if out is None:
+        out = torch.empty((F, H, W, 3), device=frames.device, dtype=torch.uint8)
+    else:
+        _check_out("yuv420_to_rgb_u8", frames, out, (F, H, W, 3))
+    check(_lib.load().advhip_yuv420_to_rgb_u8(ptr(frames), ptr(out), F_src, d, H, W, LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
+          "yuv420_to_rgb_u8")
+    return out
+
+
 def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, resample: Union[int, str] = "bilinear",
-              out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None, pixel_format=None) -> torch.Tensor:
     """uint8 (F, H, W, 3) frames on the GPU -> (F, OH, OW, 3), what `GroupResize(size, resample)` gives frame by frame (PIL
     `Image.resize`, bit for bit), on the current stream with no host synchronisation.  `out` places the result in a
     caller-owned contiguous (F, OH, OW, 3) uint8 tensor (e.g. a view of a larger buffer).  Without `out`, frames already at
     the output size are returned as they are (torchvision returns the image itself).
     `frame_step` d (default 1): only source frames 0, d, 2 d, ... are resized, into a compact (ceil(F / d), OH, OW, 3) result --
     resize_u8(frames[::d].contiguous()) byte for byte, read in place (a source frame pitch in the kernels; the workspace holds
-    the sampled frames only).  Frames already at the output size come back as the view frames[::d] (without `out`)."""
-    d = 1 if frame_step is None else int(frame_step)
-    if d < 1:
-        raise ValueError(f"resize_u8: frame_step {frame_step!r} must be an integer >= 1")
+    the sampled frames only).  Frames already at the output size come back as the view frames[::d] (without `out`).
+    `pixel_format` (resolve_pixel_format; default None = packed RGB): `frames` are 4:2:0 frames (F, 3H/2, W) and the result is
+    resize_u8(yuv420_to_rgb_u8(frames, pixel_format), ...) byte for byte without the full-size RGB frames: the horizontal pass
+    converts each tap's pixel as it reads it.  Frames already at the output size come back converted."""
+    d = _frame_step("resize_u8", frame_step)
+    pf = resolve_pixel_format(pixel_format)
+    if pf is not None:
+        return _resize_yuv420_u8(frames, size, resample, out, d, pf)
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise HipExtensionError(f"resize_u8 wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
@@ -189,12 +311,7 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
             return frames if d == 1 else frames[::d]
         out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
     else:
-        require_gpu(frames, out)
-        if out.dtype != torch.uint8 or tuple(out.shape) != (F, oh, ow, 3):
-            raise HipExtensionError(f"resize_u8: out must be uint8 {(F, oh, ow, 3)}, got {out.dtype} {tuple(out.shape)}")
-        a0, a1 = frames.data_ptr(), frames.data_ptr() + frames.numel()
-        if out.data_ptr() < a1 and a0 < out.data_ptr() + out.numel():
-            raise HipExtensionError("resize_u8: out overlaps the input frames")
+        _check_out("resize_u8", frames, out, (F, oh, ow, 3))
     t = tables(H, W, oh, ow, name, frames.device)
     p, b, (o_xb, o_xk, o_yb, o_yk) = t.plan, t.buf, t.offsets
     ws = None
@@ -210,4 +327,27 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
                                                    ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
                                                    ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
               "resize_u8")
+    return out
+
+
+def _resize_yuv420_u8(frames: torch.Tensor, size, resample, out: Optional[torch.Tensor], d: int, pf: PixelFormat) -> torch.Tensor:
+    """resize_u8 of 4:2:0 frames (advhip_resize_yuv420_u8)."""
+    F_src, H, W = _yuv_frames("resize_u8", frames, pf)
+    F = -(-F_src // d)
+    name = filter_name(resample)
+    oh, ow = output_size(H, W, size)
+    if out is None:
+        out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
+    else:
+        _check_out("resize_u8", frames, out, (F, oh, ow, 3))
+    t = tables(H, W, oh, ow, name, frames.device)
+    p, b, (o_xb, o_xk, o_yb, o_yk) = t.plan, t.buf, t.offsets
+    ws = None
+    if p.vertical:  # the horizontal pass's rows, or (a vertical-only resize) the converted frames
+        ws = torch.empty((F * p.rows * ow * 3 if p.horizontal else F * H * W * 3,), device=frames.device, dtype=torch.uint8)
+    check(_lib.load().advhip_resize_yuv420_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, 3, oh, ow,
+                                              ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
+                                              ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows,
+                                              LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
+          "resize_u8")
     return out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET] [--normalize SPEC]]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET] [--normalize SPEC] [--pixel-format FMT]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
@@ -18,6 +18,8 @@ every `--clip-stride` frames (1 .. 16 x N, default the span), files are `<name>_
 `standardize:MEAN:STD` (each one number or three, e.g. `standardize:123.675,116.28,103.53:58.395,57.12,57.375`), `pixel_minmax` or
 `pixel_minmax:LO,HI` (e.g. `pixel_minmax:-1,1`), `channel_minmax`, `channel_minmax:LO,HI` or `channel_minmax:LO,LO,LO:HI,HI,HI`; the
 files carry the normalisation last in their name (`<name>_i3d..._npix-<hash>.npy`).
+`--pixel-format nv12|i420[:bt601|bt709][:limited|full]` (with `--frame-size`, both sizes even) makes the source the decoder's own
+8-bit 4:2:0 frames, uint8 (F, 3H/2, W): the colour conversion runs on the device inside the resize (file names do not change).
 """
 import argparse
 import os
@@ -39,16 +41,18 @@ def synthetic_sources(n_videos: int, seed: int = 0):
         yield name, (lambda n=n_clips, s=seed + i: torch.randn((n, 10, 16, 3, 224, 224), generator=torch.Generator().manual_seed(s)))
 
 
-def synthetic_frame_sources(n_videos: int, frame_size, seed: int = 0):
-    """(name, n_frames, read_frames) of synthetic decoded uint8 (F, H, W, 3) videos of 2-5 clips plus a few frames."""
+def synthetic_frame_sources(n_videos: int, frame_size, seed: int = 0, pixel_format=None):
+    """(name, n_frames, read_frames) of synthetic decoded uint8 (F, H, W, 3) videos of 2-5 clips plus a few frames; with a
+    `pixel_format` the frames are seeded random 4:2:0 ones, (F, 3H/2, W)."""
     g = torch.Generator().manual_seed(seed)
     h, w = frame_size
+    shape = (h, w, 3) if pixel_format is None else (h // 2 * 3, w)
     for i in range(n_videos):
         n_frames = int(torch.randint(2 * 16, 6 * 16, (1,), generator=g))
         name = ("Normal_Videos_%03d_x264" if i % 2 == 0 else "Abuse%03d_x264") % i
 
         def read_frames(lo, hi, n=n_frames, s=seed + i):  # the same video on every call (a decoder reads a range of it)
-            return torch.randint(0, 256, (n, h, w, 3), generator=torch.Generator().manual_seed(s), dtype=torch.uint8)[lo:hi]
+            return torch.randint(0, 256, (n, *shape), generator=torch.Generator().manual_seed(s), dtype=torch.uint8)[lo:hi]
 
         yield name, n_frames, read_frames
 
@@ -97,9 +101,19 @@ def parse_normalize(text: str):
         raise argparse.ArgumentTypeError(f"--normalize {text!r}: {e}")
 
 
+def parse_pixel_format(text: str):
+    """--pixel-format: LAYOUT[:MATRIX][:RANGE], e.g. nv12, i420:bt709, nv12:bt601:full -> resize.PixelFormat."""
+    from anomaly_detection_on_video_amd.resize import resolve_pixel_format
+
+    try:
+        return resolve_pixel_format(tuple(text.split(":")))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--pixel-format {text!r}: {e}")
+
+
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
          model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None, frame_step: int = None,
-         normalize=None):
+         normalize=None, pixel_format=None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if clip_stride is not None and frame_size is None:
@@ -115,6 +129,10 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
         raise ValueError("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
     if normalize is not None and frame_size is None:
         raise ValueError("--normalize needs --frame-size: the clip-tensor source is normalised already")
+    if pixel_format is not None and frame_size is None:
+        raise ValueError("--pixel-format needs --frame-size: the clip-tensor source holds no decoded frames")
+    if pixel_format is not None and (frame_size[0] % 2 or frame_size[1] % 2):
+        raise ValueError(f"--pixel-format needs an even frame size (4:2:0 chroma), got {frame_size[0]}x{frame_size[1]}")
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
@@ -122,8 +140,8 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
     if frame_size is None:
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
-        extract_frames(synthetic_frame_sources(videos, frame_size), model, outpath, resize=256, clip_stride=clip_stride, crops=crops,
-                       frame_step=frame_step, normalize=normalize)
+        extract_frames(synthetic_frame_sources(videos, frame_size, pixel_format=pixel_format), model, outpath, resize=256, clip_stride=clip_stride,
+                       crops=crops, frame_step=frame_step, normalize=normalize, pixel_format=pixel_format)
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -147,6 +165,9 @@ if __name__ == "__main__":
     ap.add_argument("--normalize", type=parse_normalize, default=None, metavar="SPEC",
                     help="with --frame-size: standardize:MEAN:STD, pixel_minmax[:LO,HI] or channel_minmax[:LO,HI | :LO,LO,LO:HI,HI,HI] "
                          "(default: the reference's (x - 114.75) / 57.375)")
+    ap.add_argument("--pixel-format", type=parse_pixel_format, default=None, metavar="FMT",
+                    help="with --frame-size: the frames are 8-bit 4:2:0, nv12 or i420 (yuv420p), optionally :bt601 (default) or :bt709 and "
+                         ":limited (default) or :full; converted on the device (default: packed RGB)")
     a = ap.parse_args()
     if a.clip_stride is not None and a.frame_size is None:
         ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
@@ -160,4 +181,9 @@ if __name__ == "__main__":
         ap.error("--crops needs --frame-size: the clip-tensor source is already ten-cropped")
     if a.normalize is not None and a.frame_size is None:
         ap.error("--normalize needs --frame-size: the clip-tensor source is normalised already")
-    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step, a.normalize)
+    if a.pixel_format is not None and a.frame_size is None:
+        ap.error("--pixel-format needs --frame-size: the clip-tensor source holds no decoded frames")
+    if a.pixel_format is not None and (a.frame_size[0] % 2 or a.frame_size[1] % 2):
+        ap.error(f"--pixel-format needs an even frame size (4:2:0 chroma), got {a.frame_size[0]}x{a.frame_size[1]}")
+    main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step, a.normalize,
+         a.pixel_format)

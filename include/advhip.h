@@ -811,6 +811,35 @@ int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_t* ws, int6
                              int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                              const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream);
 
+/* --- decoded frames as the decoder has them: Y'CbCr 4:2:0, 8 bit -----------------------------------------------------------
+ * A frame is uint8 (3H/2, W), H and W even, row pitch == W: rows [0, H) are Y; NV12 then holds H/2 rows of interleaved (Cb, Cr)
+ * pairs, I420 (yuv420p) the (H/2, W/2) Cb plane followed by the (H/2, W/2) Cr plane.  Chroma is nearest: pixel (y, x) uses sample
+ * (y >> 1, x >> 1).  The conversion is integer, in int32, with 2^16 fixed-point coefficients passed by value (the library holds
+ * no table; resize.py derives them from the luma weights and the range):
+ *   yi = cy (Y - yoff) + 2^15
+ *   R = clip8((yi + crv (Cr - 128)) >> 16)
+ *   G = clip8((yi - cgu (Cb - 128) - cgv (Cr - 128)) >> 16)          (arithmetic shifts)
+ *   B = clip8((yi + cbu (Cb - 128)) >> 16)
+ * yoff is 16 (limited range) or 0 (full range), 0 < cy < 2^18 and 0 <= every other coefficient < 2^18 (every sum is exact in int32).
+ * This is a definition of its own, not swscale's bytes: the RGB entry points above remain the reference-parity path. */
+#define ADVHIP_YUV420_NV12 0
+#define ADVHIP_YUV420_I420 1
+
+/* The conversion alone: source frames 0, frame_step, 2 frame_step, ... of src (F_src, 3H/2, W) -> packed RGB dst
+ * (ceil(F_src / frame_step), H, W, 3).  One launch; a lane converts the two (or four) adjacent pixels that share a chroma
+ * sample.  Every argument is checked before the launch. */
+int advhip_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t layout,
+                            int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
+/* advhip_resize_u8_sampled on 4:2:0 source frames (F_src, 3H/2, W): dst is byte for byte what that call makes of the frames the
+ * call above converts, and the full-size RGB frames never exist -- the horizontal pass converts each tap's pixel as it reads it
+ * (Y row row0 + y, chroma row (row0 + y) >> 1), the vertical pass is the RGB resize's own.  C is the output's channel count (3).
+ * ws as there: uint8 (F, rows, OW, 3) when both passes run.  Where no horizontal pass runs (OW == W) the conversion launch runs
+ * first: into ws, uint8 (F, H, W, 3), when OH != H, else straight into dst.  Two launches at most, every argument checked first. */
+int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
+                            int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                            const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, int32_t layout,
+                            int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
