@@ -43,6 +43,7 @@ ALGO_TFOLD_BASE = 208  # + tile id of the 2-deep LDS-DMA family: (kt,1,1) convs 
 TFOLD_ALGOS = tuple(ALGO_TFOLD_BASE + a for a in (1, 2, 3, 4, 6, 7, 8, 9))
 ALGO_PERSIST_BASE = 224  # + tile id (2: 128x64, 3: 64x64) + 8 * (workgroups per CU - 1), 1..3: persistent wave-specialised kernel (opt-in), unsplit 1x1x1 stride-1 convs, K >= 64
 PERSIST_ALGOS = tuple(ALGO_PERSIST_BASE + t + 8 * (w - 1) for w in (1, 2, 3) for t in (2, 3))
+ALGO_STEM_BORDER = 256  # the planes-form stem + maxpool1 only: launch split by pool window in t, border windows on frame-uniform tiles that skip all-padding k-tiles
 
 
 NORM_STANDARDIZE, NORM_PIXEL_MINMAX, NORM_CHANNEL_MINMAX = 0, 1, 2  # ADVHIP_NORM_*: the modes of the `_modes` TenCrop passes
@@ -134,6 +135,7 @@ SIGNATURES = {
     "advhip_conv3d_bn_act_strided_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P]),
     "advhip_conv3d_pool_out_dims": (C.c_int, [C.POINTER(ConvDesc)] + [_I] * 6 + [C.POINTER(_I)] * 3),
     "advhip_conv3d_relu_maxpool233_workspace_bytes": (_L, [C.POINTER(ConvDesc)]),
+    "advhip_conv3d_active_ktiles": (C.c_int, [C.POINTER(ConvDesc), _I, _I, _P, _P]),
     "advhip_conv3d_bn_relu_maxpool233_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P]),
     "advhip_split_w_plane_floats": (_I, [_I]),
     "advhip_split_w_f32": (C.c_int, [_P, _P, _L, _I, _P]),

@@ -138,6 +138,16 @@ struct ConvArgs {
   const int2* ktab_u8;      // [2][Kpad] {byte offset, tap bits}: as stored, and mirrored along w
   const float* pad_corr;    // [(pt+1)^2][(ph+1)^2][(pw+1)^2][Cout]: -mean * (sum of the weights of the taps inside the clip), indexed per
                             //   dimension by border class = (taps before the clip) * (p + 1) + (taps past its end), see u8_border_class
+  // the stem + maxpool1 launch split by pool window in t (conv_pool233, StemSplit): the interior windows run the 2-frame brick
+  // kernel on a sub-range of brick rows in t, the border windows the frame-uniform tiles (EPI_POOL233F).  Both address the
+  // partial-maxima workspace by the brick's own coordinates, not by the launch's tile index
+  int bt_off;               // EPI_POOL233: first pool window of this launch (brick t = launch-local brick t + bt_off)
+  int ws_nbh;               // 4-row bricks per sample along h in the workspace (EPI_POOL233F decodes 8-row tiles: nbh = ws_nbh / 2)
+  int fr_n0, fr_skip;       // EPI_POOL233F: tile row f in t is output frame f (f < fr_n0) or f + fr_skip; pool window f >> 1 of the
+                            //   border windows, frame f & 1 of it
+  long long ws_frame1;      // brick index at which the border windows' second-frame slabs start: [sample][border window][ws_nbh][nbw]
+  int ws_nbwin;             // border windows per sample
+  unsigned long long fr_ktiles[4];  // EPI_POOL233F, per tile row f: bit kt set = k-tile kt holds a row whose temporal tap lies inside the clip
 };
 
 template <int VW>
@@ -842,9 +852,14 @@ enum : int {
                     //   three m-tiles that run ~47 tiles apart; 4(t) x BM/4 for T = 4
   EPI_AVG = 6,      // + AdaptiveAvgPool3d((1,1,1)) (src/i3d.py:314): a 1x1x1 conv on <= 128 positions per sample, every sample's rows
                     //   padded to ONE 128-row m-tile in the m index space (ConvArgs::MP = 128): the tile's column means are the result
+  EPI_POOL233F = 7, // EPI_POOL233 on FRAME-UNIFORM tiles, 1(t) x 8(h) x BM/8(w): the two wave rows are the 4 x 16 planes of two
+                    //   h-adjacent bricks of ONE output frame, so a k-tile whose rows all carry a temporal tap outside the clip is
+                    //   padding for the whole workgroup and is skipped -- fill, barrier, fragment reads and MFMAs (ConvArgs::fr_ktiles).
+                    //   Each plane writes its own 27 maxima; the max over the window's two frames moves to stem_pool_merge_kernel
 };
 constexpr bool epi_rows(int epi) { return epi == EPI_STD || epi == EPI_AVG; }  // m runs (sample, position) row-major (no bricks)
-constexpr int brick_t(int epi) { return epi == EPI_TSPAN4 ? 4 : 2; }
+constexpr int brick_t(int epi) { return epi == EPI_TSPAN4 ? 4 : (epi == EPI_POOL233F ? 1 : 2); }
+constexpr int brick_h(int epi) { return epi == EPI_POOL233 ? 4 : (epi == EPI_POOL233F ? 8 : 1); }
 
 // ---- pooling epilogues on brick-ordered tiles (128 x 64 tile, 2 x 2 waves) ----------------------------------------------
 // Wave (wm, wn) holds t plane wm of the brick (64 positions: BH rows of BW outputs) for 32 channels; accumulator element
@@ -868,7 +883,8 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
                                                int tid, const U8Corr& u8c = U8Corr{}) {
   constexpr int FM = BM / 32, FN = BN / 32, RS = BM + 4, CH = BN / FN;  // CH channels per pass
   static_assert(FM == 4 && FN == 2, "128 x 64 tile");
-  constexpr int BT = brick_t(EPI), BH = EPI == EPI_POOL233 ? 4 : 1, BW = BM / (BT * BH);
+  constexpr bool FU = EPI == EPI_POOL233F;  // frame-uniform tile: wave row wm = the 4 x 16 plane of brick 2 bk_h + wm of frame bk_t
+  constexpr int BT = brick_t(EPI), BH = (EPI == EPI_POOL233 || FU) ? 4 : 1, BW = BM / (BT * brick_h(EPI));
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 15, lg = lane >> 4;
   const int c_w = wn * 16 + li;  // this lane's channel row of the pass
@@ -950,9 +966,9 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
     //      row-slot values; the partial tensor is [brick][n-tile][jn][row slot][channel][column slot]: 288 consecutive
     //      floats per row slot and pass, i.e. coalesced stores.
     constexpr int LR = 12, LC = 100;
-    const int ot = bk_t * 2 + wm, oh = bk_h * BH + lg;
+    const int ot = FU ? bk_t : bk_t * 2 + wm, oh = FU ? (bk_h * 2 + wm) * BH + lg : bk_h * BH + lg;
     // bricks entirely inside the tensor (all of them at 16 x 224 x 224) skip the per-element range checks
-    const bool inside = bk_t * 2 + 1 < a.To && bk_h * BH + BH - 1 < a.Ho && bk_w * BW + BW - 1 < a.Wo;
+    const bool inside = (FU ? bk_t < a.To && bk_h * 2 * BH + 2 * BH - 1 < a.Ho : bk_t * 2 + 1 < a.To && bk_h * BH + BH - 1 < a.Ho) && bk_w * BW + BW - 1 < a.Wo;
     const int wlim = a.Wo - bk_w * BW;  // columns of the brick inside the tensor
     const bool row_ok = ot < a.To && oh < a.Ho;
 #pragma unroll
@@ -1004,19 +1020,40 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
       *reinterpret_cast<float4*>(lrow + 4) = make_float4(cs[4], cs[5], cs[6], cs[7]);
       lrow[8] = cs[8];
       __syncthreads();
+      // (tile_m: the brick's index in the workspace -- of wave row 0's brick on frame-uniform tiles, wave row 1's is nbw further)
       float* __restrict__ P = a.y + ((size_t)(tile_m * a.tiles_n + tile_n) * FN + jn) * (CH * POOL_SLOTS);
+      if constexpr (FU) {
+        // the same three row-slot values per plane, without the max over t: thread (plane, channel, column slot)
 #pragma unroll
-      for (int q0 = 0; q0 < CH * 9; q0 += 256) {
-        const int q = q0 + tid;
-        if (q < CH * 9) {
-          const int c = q / 9, k = q - c * 9;
-          const float* l0 = smem + c * LC + k;
-          float h[4];
+        for (int q0 = 0; q0 < 2 * CH * 9; q0 += 256) {
+          const int q = q0 + tid;
+          if (q < 2 * CH * 9) {
+            const int pl = q >= CH * 9 ? 1 : 0, qq = q - pl * (CH * 9);
+            const int c = qq / 9, k = qq - c * 9;
+            const float* l0 = smem + c * LC + pl * BH * LR + k;
+            float h[4];
 #pragma unroll
-          for (int hh = 0; hh < 4; ++hh) h[hh] = max_nan(l0[hh * LR], l0[(BH + hh) * LR]);  // max over the two t planes
-          P[q] = h[0];
-          P[CH * 9 + q] = max_nan(max_nan(h[0], h[1]), h[2]);
-          P[2 * CH * 9 + q] = max_nan(h[2], h[3]);
+            for (int hh = 0; hh < 4; ++hh) h[hh] = l0[hh * LR];
+            float* __restrict__ Pp = P + (size_t)pl * a.nbw * a.tiles_n * (FN * CH * POOL_SLOTS);
+            Pp[qq] = h[0];
+            Pp[CH * 9 + qq] = max_nan(max_nan(h[0], h[1]), h[2]);
+            Pp[2 * CH * 9 + qq] = max_nan(h[2], h[3]);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int q0 = 0; q0 < CH * 9; q0 += 256) {
+          const int q = q0 + tid;
+          if (q < CH * 9) {
+            const int c = q / 9, k = q - c * 9;
+            const float* l0 = smem + c * LC + k;
+            float h[4];
+#pragma unroll
+            for (int hh = 0; hh < 4; ++hh) h[hh] = max_nan(l0[hh * LR], l0[(BH + hh) * LR]);  // max over the two t planes
+            P[q] = h[0];
+            P[CH * 9 + q] = max_nan(max_nan(h[0], h[1]), h[2]);
+            P[2 * CH * 9 + q] = max_nan(h[2], h[3]);
+          }
         }
       }
       __syncthreads();
@@ -1031,7 +1068,8 @@ __device__ __forceinline__ void brick_epilogue(const ConvArgs& a, f32x4 (&acc)[B
 constexpr int MERGE_MAX_NBW = 16;
 __global__ __launch_bounds__(256) void stem_pool_merge_kernel(const float* __restrict__ P, float* __restrict__ y, int Cout, int Tp,
                                                               int Hp, int Wp, int nbh, int nbw, int tiles_n, FastDiv dWp,
-                                                              long long rows, long long ybs) {
+                                                              long long rows, long long ybs, int tp_lo, int tp_hi, int nbwin,
+                                                              long long frame1) {
   extern __shared__ __attribute__((aligned(16))) float L[];  // [2][nbw][288]
   const long long row = (long long)blockIdx.y * gridDim.x + blockIdx.x;  // ((((b * tiles_n + tile_n) * 2 + jn) * Tp + tp) * Hp + hp
   if (row >= rows) return;
@@ -1046,14 +1084,24 @@ __global__ __launch_bounds__(256) void stem_pool_merge_kernel(const float* __res
   const bool h2 = hp & 1;
   const int nu = h2 ? 2 : 1;
   const long long brick_row0 = (((long long)b * Tp + tp) * nbh + (hp >> 1)) * nbw;
+  // a border window of the split launch (windows outside [tp_lo, tp_hi); none: tp_lo = 0, tp_hi = Tp) holds the maxima of its
+  // first frame in its own bricks and those of its second frame in the slab at brick `frame1`: [sample][border window][nbh][nbw];
+  // max is exact and order-free, so the value is the one the 2-frame brick would have written
+  const bool two = tp < tp_lo || tp >= tp_hi;
+  const long long frame1_row0 = frame1 + (((long long)b * nbwin + (tp < tp_lo ? tp : tp - tp_hi + tp_lo)) * nbh + (hp >> 1)) * nbw;
   // 72 float4 per (row-slot, brick) block of 288 contiguous floats
   for (int e = tid; e < nu * nbw * 72; e += 256) {
     const int g = e / 72, j = e - g * 72;
     const int u = g >= nbw ? 1 : 0, wb = g - u * nbw;
     const int rs = h2 ? (u == 0 ? 2 : 0) : 1;
     const long long brick = brick_row0 + (long long)u * nbw + wb;
-    *reinterpret_cast<float4*>(L + g * 288 + j * 4) =
-        *reinterpret_cast<const float4*>(P + ((brick * tiles_n + tile_n) * 2 + jn) * (32 * POOL_SLOTS) + rs * 288 + j * 4);
+    float4 v = *reinterpret_cast<const float4*>(P + ((brick * tiles_n + tile_n) * 2 + jn) * (32 * POOL_SLOTS) + rs * 288 + j * 4);
+    if (two) {
+      const long long brick1 = frame1_row0 + (long long)u * nbw + wb;
+      const float4 w = *reinterpret_cast<const float4*>(P + ((brick1 * tiles_n + tile_n) * 2 + jn) * (32 * POOL_SLOTS) + rs * 288 + j * 4);
+      v = make_float4(max_nan(v.x, w.x), max_nan(v.y, w.y), max_nan(v.z, w.z), max_nan(v.w, w.w));
+    }
+    *reinterpret_cast<float4*>(L + g * 288 + j * 4) = v;
   }
   __syncthreads();
   for (int o = tid; o < 32 * Wp; o += 256) {
@@ -1260,7 +1308,8 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
   // beside the older workgroups' MFMA streams (profiles/r01_pmc_notes.md: 4-6 us of a short-K tile's life)
   constexpr bool A16ONLY = AMODE == 2;
   static_assert(!A16ONLY || (!CHECK && NS == 2 && !U8 && epi_rows(EPI)), "compile-time a16: unchecked 1x1x1 convs on the 2-deep ring");
-  constexpr int BRICK_T = brick_t(EPI), BRICK_H = EPI == EPI_POOL233 ? 4 : 1, BRICK_W = BM / (BRICK_T * BRICK_H);
+  constexpr int BRICK_T = brick_t(EPI), BRICK_H = brick_h(EPI), BRICK_W = BM / (BRICK_T * BRICK_H);
+  static_assert(EPI != EPI_POOL233F || (AMODE == 1 && NS == 2 && CHECK && !U8), "frame-uniform stem tiles: the planes form on the 2-deep ring");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1289,6 +1338,8 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
   int pb = 0, pot = 0, poh = 0, pow_ = 0;
   bool pvalid;
   int bk_b = 0, bk_t = 0, bk_h = 0, bk_w = 0;  // brick forms: sample and brick coordinates of this m-tile
+  int ws_brick = tile_m;                       // stem + pool: the brick's index in the partial-maxima workspace
+  unsigned long long ktiles = 0;               // EPI_POOL233F: the k-tiles this tile's frame needs (scalar)
   if constexpr (A16ONLY) {
     pvalid = false;  // (nothing below needs this thread's own position)
   } else if constexpr (epi_rows(EPI)) {
@@ -1311,6 +1362,21 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     const int r2 = r1 - bk_t * (int)a.dNbhw.d;
     bk_h = (int)a.dNbw.div((unsigned)r2);
     bk_w = r2 - bk_h * a.nbw;
+    if constexpr (EPI == EPI_POOL233 && !U8) {
+      // (a launch may cover a sub-range of the pool windows: the workspace is addressed by the brick's own coordinates)
+      bk_t += a.bt_off;
+      ws_brick = ((bk_b * a.Tp + bk_t) * a.nbh + bk_h) * a.nbw + bk_w;
+    }
+    if constexpr (EPI == EPI_POOL233F) {
+      // tile row f in t -> output frame bk_t; the frame's first-frame maxima live in the window's own bricks, its second-frame
+      // maxima in the slab behind them (the brick of wave row 0; wave row 1's is the next one along h)
+      const int f = bk_t;
+      bk_t = f + (f >= a.fr_n0 ? a.fr_skip : 0);
+      ws_brick = (f & 1) ? (int)a.ws_frame1 + ((bk_b * a.ws_nbwin + (f >> 1)) * a.ws_nbh + 2 * bk_h) * a.nbw + bk_w
+                         : ((bk_b * a.Tp + (bk_t >> 1)) * a.ws_nbh + 2 * bk_h) * a.nbw + bk_w;
+      const unsigned long long km = a.fr_ktiles[f & 3];
+      ktiles = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(km >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)km);
+    }
     pb = bk_b;
     pot = bk_t * BRICK_T + ml / (BRICK_H * BRICK_W);
     poh = bk_h * BRICK_H + (ml / BRICK_W) % BRICK_H;
@@ -1363,7 +1429,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
   const int rm[4] = {rsel == 0 ? -1 : 0, rsel == 1 ? -1 : 0, rsel == 2 ? -1 : 0, rsel == 3 ? -1 : 0};
   if constexpr (AMODE == 1) {
     static_assert(AMODE == 0 || (BK == 16 && NS == 2 && CHECK && !U8 && (BM == 256 || BM == 128 || BM == 64) &&
-                                 (EPI == EPI_STD || ((EPI == EPI_POOL233 || EPI == EPI_TSPAN2 || EPI == EPI_TSPAN4) && BM == 128))),
+                                 (EPI == EPI_STD || ((EPI == EPI_POOL233 || EPI == EPI_POOL233F || EPI == EPI_TSPAN2 || EPI == EPI_TSPAN4) && BM == 128))),
                   "16-byte gather pieces: the fused stem (column-parity planes), the T-spanning tiles and plain tiles of (kt,1,1) convs");
     const int ml4 = (lane % (BM / 4)) * 4;
     if constexpr (EPI == EPI_STD) {
@@ -1602,6 +1668,32 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     [&]<int... I>(std::integer_sequence<int, I...>) { (body(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, KS>{});
   };
 
+  if constexpr (EPI == EPI_POOL233F) {
+    // the K loop over the frame's active k-tiles only, in ascending order (the list is a bit set in two scalar registers: next
+    // tile = its lowest set bit).  The 2-deep ring, its waits and its one barrier per k-tile are those of the loop below, counted
+    // in active tiles; the skipped tiles' rows read zeros for every position of this tile, so every accumulator sees the same
+    // non-zero terms in the same order as on the whole K
+    int kcur = __builtin_ctzll(ktiles);
+    ktiles &= ktiles - 1;
+    issue_tile(kcur * BK, 0);
+    int stage = 0;
+    for (;;) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_barrier" ::: "memory");
+      const bool pre = ktiles != 0;
+      if (pre) {
+        kcur = __builtin_ctzll(ktiles);
+        ktiles &= ktiles - 1;
+        load_entries(kcur * BK);
+      }
+      compute(pre, stage, kcur * BK, stage ^ 1);
+      stage ^= 1;
+      if (!pre) break;
+    }
+    __syncthreads();
+    brick_epilogue<BM, BN, BK, EPI, U8>(a, acc, smem, ws_brick, tile_n, n0, bk_b, bk_t, bk_h, bk_w, wave, lane, tid, u8c);
+    return;
+  }
   const int nk_all = a.Kpad / BK;
   const int kt0 = (nk_all * split) / a.splits;
   const int kt1 = (nk_all * (split + 1)) / a.splits;
@@ -1678,7 +1770,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     avg_epilogue<BM, BN, BK>(a, acc, smem, tile_m, n0, wave, lane, tid);
     return;
   } else if constexpr (EPI != EPI_STD) {
-    brick_epilogue<BM, BN, BK, EPI, U8>(a, acc, smem, tile_m, tile_n, n0, bk_b, bk_t, bk_h, bk_w, wave, lane, tid, u8c);
+    brick_epilogue<BM, BN, BK, EPI, U8>(a, acc, smem, ws_brick, tile_n, n0, bk_b, bk_t, bk_h, bk_w, wave, lane, tid, u8c);
     return;
   }
   // (one epilogue call site: a second inlined copy costs ~25 VGPRs and with them a resident workgroup per CU)
@@ -3499,7 +3591,70 @@ static int fill_pool_args(ConvArgs& a, const advhip_conv3d_desc* d, const Geomet
   a.tiles_n = d->Cout / 64;
   a.dTilesN = FastDiv::make((unsigned)a.tiles_n);
   a.dSplits = FastDiv::make(1u);
+  a.bt_off = 0; a.ws_nbh = 0; a.fr_n0 = 0; a.fr_skip = 0; a.ws_frame1 = 0; a.ws_nbwin = 0;
+  for (unsigned long long& m : a.fr_ktiles) m = 0;
   return ADVHIP_OK;
+}
+
+// ---- the stem + maxpool1 launch split by pool window in t (ADVHIP_ALGO_STEM_BORDER) ------------------------------------------
+// taps [lo, hi) of output frame ot of conv d lie inside the clip
+static void frame_taps(const advhip_conv3d_desc* d, int ot, int* lo, int* hi) {
+  const int it0 = ot * d->st - d->pt;
+  *lo = it0 < 0 ? std::min(-it0, d->kt) : 0;
+  *hi = std::max(*lo, std::min(d->kt, d->T - it0));
+}
+// The k-tiles of `bk` rows that hold at least one row k < K whose temporal tap (k = ((ci * kt + dt) * kh + dh) * kw + dw) lies inside
+// the clip for output frame ot, ascending; the others multiply the zero padding of every position of that frame.  Returns the count.
+static int active_ktiles(const advhip_conv3d_desc* d, int ot, int bk, int32_t* tiles) {
+  int lo, hi;
+  frame_taps(d, ot, &lo, &hi);
+  const int K = d->Cin * d->kt * d->kh * d->kw, hw = d->kh * d->kw;
+  int n = 0;
+  for (int t0 = 0; t0 * bk < K; ++t0) {
+    bool any = false;
+    for (int k = t0 * bk; k < std::min(K, (t0 + 1) * bk) && !any; ++k) {
+      const int dt = (k / hw) % d->kt;
+      any = dt >= lo && dt < hi;
+    }
+    if (any) {
+      if (tiles) tiles[n] = t0;
+      ++n;
+    }
+  }
+  return n;
+}
+
+// How conv_pool233 splits the launch: pool windows [tp_lo, tp_hi) have no padded temporal tap and run the 2-frame bricks; the
+// nbwin = tp_lo + Tp - tp_hi <= 2 windows around them run frame by frame on frame-uniform tiles with the k-tile sets `ktiles`
+struct StemSplit {
+  bool on = false;
+  int tp_lo = 0, tp_hi = 0, nbwin = 0;
+  unsigned long long ktiles[4] = {0, 0, 0, 0};
+};
+static StemSplit stem_split(const advhip_conv3d_desc* d, const Geometry& g) {
+  StemSplit s;
+  const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2);
+  const int nbh = (2 * Hp + 1 + 3) / 4, nk = g.Kpad / 16;
+  // the stem's temporal window (one padded frame at either end of an even To), 8-row tiles that are whole pairs of bricks,
+  // a k-tile set that fits two scalar registers
+  if (d->algo != ADVHIP_ALGO_STEM_BORDER || d->kt != 5 || d->pt != 2 || d->st != 2 || g.To % 2 != 0 || Tp < 1 || nbh % 2 != 0 || nk > 64) return s;
+  s.tp_lo = 1;
+  s.tp_hi = std::max(1, Tp - 1);
+  s.nbwin = s.tp_lo + Tp - s.tp_hi;
+  for (int ot = 2 * s.tp_lo; ot < 2 * s.tp_hi; ++ot) {  // (holds by construction; the split is wrong without it)
+    int lo, hi;
+    frame_taps(d, ot, &lo, &hi);
+    if (lo != 0 || hi != d->kt) return StemSplit{};
+  }
+  int32_t tiles[64];
+  for (int f = 0; f < 2 * s.nbwin; ++f) {
+    const int ot = f < 2 * s.tp_lo ? f : f + 2 * (s.tp_hi - s.tp_lo);
+    const int n = active_ktiles(d, ot, 16, tiles);
+    if (n == 0) return StemSplit{};
+    for (int j = 0; j < n; ++j) s.ktiles[f] |= 1ull << tiles[j];
+  }
+  s.on = true;
+  return s;
 }
 
 static void set_bricks(ConvArgs& a, int nbt, int nbh, int nbw) {
@@ -3527,16 +3682,28 @@ extern "C" int64_t advhip_conv3d_relu_maxpool233_workspace_bytes(const advhip_co
   const Geometry g = geometry(d);
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   if (Tp <= 0 || Hp <= 0 || Wp <= 0) return 0;
-  const int64_t bricks = (int64_t)d->B * Tp * ((2 * Hp + 1 + 3) / 4) * ((2 * Wp + 1 + 15) / 16);
+  // (the split launch keeps the second frame of its border windows in slabs of their own behind the bricks)
+  const int64_t bricks = (int64_t)d->B * (Tp + stem_split(d, g).nbwin) * ((2 * Hp + 1 + 3) / 4) * ((2 * Wp + 1 + 15) / 16);
   return bricks * d->Cout * POOL_SLOTS * (int64_t)sizeof(float);
+}
+
+extern "C" int advhip_conv3d_active_ktiles(const advhip_conv3d_desc* d, int32_t ot, int32_t bk, int32_t* tiles, int32_t* n_tiles) {
+  if (int rc = validate(d)) return rc;
+  const Geometry g = geometry(d);
+  ADVHIP_REQUIRE(n_tiles && ot >= 0 && ot < g.To && bk > 0, "conv3d active k-tiles: frame %d of %d, %d rows per k-tile", ot, g.To, bk);
+  *n_tiles = active_ktiles(d, ot, bk, tiles);
+  return ADVHIP_OK;
 }
 
 // What the four ...maxpool233 launchers share: the pooled dims, the workspace and y checks, then `fill` (the form's own operand
 // set-up and checks), the brick plan, `launch` (the form's conv kernel, which leaves per-brick partial maxima in the workspace)
 // and the merge.  Every check before the first launch: a rejected call must not leave half an op enqueued.
-template <class Fill, class Launch>
+struct NoBorderLaunch {
+  void operator()(const ConvArgs&, hipStream_t) const {}
+};
+template <class Fill, class Launch, class LaunchBorder = NoBorderLaunch>
 static int conv_pool233(const char* who, const advhip_conv3d_desc* d, const Geometry& g, float* y, int64_t y_batch_stride, void* workspace,
-                        int64_t workspace_bytes, void* stream, Fill fill, Launch launch) {
+                        int64_t workspace_bytes, void* stream, Fill fill, Launch launch, LaunchBorder launch_border = LaunchBorder{}) {
   const int Tp = pool_out(g.To, 2, 2), Hp = pool_out(g.Ho, 3, 2), Wp = pool_out(g.Wo, 3, 2);
   ADVHIP_REQUIRE(Tp > 0 && Hp > 0 && Wp > 0, "%s: conv output (%d,%d,%d) smaller than the (2,3,3) window", who, g.To, g.Ho, g.Wo);
   const int64_t need = advhip_conv3d_relu_maxpool233_workspace_bytes(d);
@@ -3555,11 +3722,29 @@ static int conv_pool233(const char* who, const advhip_conv3d_desc* d, const Geom
   const long long rows = (long long)d->B * a.tiles_n * 2 * Tp * Hp;
   ADVHIP_REQUIRE(rows < (1ll << 31), "%s: too many output rows", who);
   hipStream_t st = (hipStream_t)stream;
-  launch(a, st);
+  // (only the form with a border kernel asks for the split; for every other form d->algo stays ignored)
+  const StemSplit sp = std::is_same_v<LaunchBorder, NoBorderLaunch> ? StemSplit{} : stem_split(d, g);
+  const long long frame1 = (long long)d->B * Tp * nbh * nbw;
+  if (sp.on) {
+    a.ws_nbh = nbh; a.ws_nbwin = sp.nbwin; a.ws_frame1 = frame1;
+    if (sp.tp_hi > sp.tp_lo) {  // the interior windows: the 2-frame bricks, on brick rows [tp_lo, tp_hi) in t
+      set_bricks(a, sp.tp_hi - sp.tp_lo, nbh, nbw);
+      a.bt_off = sp.tp_lo;
+      launch(a, st);
+      if (int rc = check_launch(who)) return rc;
+    }
+    // the border windows, frame by frame: 2 * nbwin tile rows in t of nbh / 2 8-row tiles each
+    set_bricks(a, 2 * sp.nbwin, nbh / 2, nbw);
+    a.bt_off = 0; a.fr_n0 = 2 * sp.tp_lo; a.fr_skip = 2 * (sp.tp_hi - sp.tp_lo);
+    for (int f = 0; f < 4; ++f) a.fr_ktiles[f] = sp.ktiles[f];
+    launch_border(a, st);
+  } else {
+    launch(a, st);
+  }
   if (int rc = check_launch(who)) return rc;
   const unsigned gx = (unsigned)std::min<long long>(rows, 1 << 20), gy = (unsigned)((rows + gx - 1) / gx);
   hipLaunchKernelGGL(stem_pool_merge_kernel, dim3(gx, gy), dim3(256), (size_t)2 * nbw * 288 * sizeof(float), st, reinterpret_cast<const float*>(workspace), y, d->Cout, Tp,
-                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs);
+                     Hp, Wp, nbh, nbw, a.tiles_n, FastDiv::make((unsigned)Wp), rows, ybs, sp.on ? sp.tp_lo : 0, sp.on ? sp.tp_hi : Tp, sp.nbwin, frame1);
   return check_launch("stem_pool_merge");
 }
 
@@ -3642,6 +3827,9 @@ extern "C" int advhip_conv3d_s2w_bn_relu_maxpool233_f32(const advhip_conv3d_desc
       },
       [&](const ConvArgs& a, hipStream_t st) {
         hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233, false, 1>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
+      },
+      [&](const ConvArgs& a, hipStream_t st) {
+        hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_POOL233F, false, 1>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), 0, st, a);
       });
 }
 

@@ -314,6 +314,11 @@ def conv_pool_out_dims(in_thw: Sequence[int], pc: "PackedConv", pool_kernel, poo
 # runs on one box: 3 796 -> 3 812 and 3 846 -> 3 872 clips/s; round 3 on its kernels: +0.3 %), bit-identical features: ON by
 # default since round 5 (ADV_STEM_S2W=0: the 4-byte gather straight from the NCDHW tensor).
 STEM_S2W = os.environ.get("ADV_STEM_S2W", "1") == "1"
+# The planes-form stem can split its launch by pool window in t (advhip.h: ADVHIP_ALGO_STEM_BORDER): the windows at either end of
+# the clip run frame by frame on 1(t) x 8(h) x 16(w) tiles that skip the k-tiles whose temporal taps all lie in the padding (23 of
+# 368 per sample column at T = 16, 6.25 % of the stem's MFMAs), the max over their two frames moves to the merge pass; bit-identical
+# features.  ADV_STEM_BORDER=0: the single launch on 2-frame bricks.
+STEM_BORDER = os.environ.get("ADV_STEM_BORDER", "1") == "1"
 
 
 def s2w_ok(pc: PackedConv, W: int) -> bool:
@@ -346,8 +351,21 @@ def ensure_ktab_s2w(pc: PackedConv, thw: Tuple[int, int, int]) -> torch.Tensor:
     return tab
 
 
-def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The fused stem on column-parity planes xs (B, Cin, T, H, 2, W/2 + 4) of its input (split_w / tencrop_planes_u8)."""
+def active_ktiles(pc: PackedConv, thw: Tuple[int, int, int], ot: int, bk: int = 16) -> list:
+    """The k-tiles of `bk` packed rows that hold a row whose temporal tap lies inside the clip for output frame `ot` of `pc` on
+    (T, H, W) inputs, ascending (host arithmetic: advhip_conv3d_active_ktiles) -- what a frame-uniform stem tile multiplies."""
+    d = pc.desc(1, *thw, relu=True, algo=0, splits=1)
+    k = pc.cin * pc.kernel[0] * pc.kernel[1] * pc.kernel[2]
+    tiles = (C.c_int32 * ((k + bk - 1) // bk))()
+    n = C.c_int32()
+    check(_lib.load().advhip_conv3d_active_ktiles(C.byref(d), ot, bk, tiles, C.byref(n)), f"conv3d_active_ktiles[{pc.name}]")
+    return list(tiles[: n.value])
+
+
+def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None, border: Optional[bool] = None) -> torch.Tensor:
+    """The fused stem on column-parity planes xs (B, Cin, T, H, 2, W/2 + 4) of its input (split_w / tencrop_planes_u8).
+    `border` (default STEM_BORDER): split the launch by pool window in t where the geometry allows (ADVHIP_ALGO_STEM_BORDER);
+    same results bit for bit."""
     require_gpu(xs)
     require_gpu(out, contiguous=False)
     if xs.dim() != 6 or xs.shape[1] != pc.cin or xs.shape[4] != 2:
@@ -356,7 +374,7 @@ def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optiona
     W = 2 * (wp - 4)
     if not s2w_ok(pc, W):
         raise ValueError(f"{pc.name}: the column-parity gather does not apply to W = {W} with k/s/p {pc.kernel[2]}/{pc.stride[2]}/{pc.padding[2]}")
-    d = pc.desc(B, T, H, W, True, 0, 1)
+    d = pc.desc(B, T, H, W, True, _lib.ALGO_STEM_BORDER if (STEM_BORDER if border is None else border) else 0, 1)
     lib = _lib.load()
     tp, hp, wpo = C.c_int32(), C.c_int32(), C.c_int32()
     check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wpo)), "conv3d_pool_out_dims")
@@ -673,11 +691,12 @@ def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_c
     return xs
 
 
-def conv3d_bn_relu_maxpool233(x: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None, s2w: Optional[bool] = None) -> torch.Tensor:
+def conv3d_bn_relu_maxpool233(x: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None, s2w: Optional[bool] = None,
+                              border: Optional[bool] = None) -> torch.Tensor:
     """maxpool3d(relu(conv3d(x) * scale + shift), (2,3,3), (2,2,2)) without the un-pooled activation ever reaching HBM
     (the stem of I3Res50, src/i3d.py:303-306).  Bit-identical to conv3d_bn_act(relu=True) + maxpool3d.  `s2w` (default: where
     the geometry allows): gather 16-byte pieces from column-parity planes of x (one extra pass over x, 4x fewer gather
-    instructions in the conv; same results bit for bit)."""
+    instructions in the conv; same results bit for bit).  `border`: see conv3d_s2w_bn_relu_maxpool233 (the planes form only)."""
     require_gpu(x, out, contiguous=False)
     if x.dim() != 5 or x.shape[1] != pc.cin:
         raise ValueError(f"{pc.name}: expected (B,{pc.cin},T,H,W), got {tuple(x.shape)}")
@@ -700,7 +719,7 @@ def conv3d_bn_relu_maxpool233(x: torch.Tensor, pc: PackedConv, out: Optional[tor
     if s2w is None:
         s2w = STEM_S2W
     if s2w and s2w_ok(pc, W) and x.is_contiguous():
-        return conv3d_s2w_bn_relu_maxpool233(split_w(x), pc, out=y)
+        return conv3d_s2w_bn_relu_maxpool233(split_w(x), pc, out=y, border=border)
     xbs, ybs = batch_stride(x), batch_stride(y)
     check(lib.advhip_conv3d_bn_relu_maxpool233_f32(C.byref(d), ptr(x), xbs, ptr(pc.w_packed), ptr(ktab), ptr(pc.scale), ptr(pc.shift),
                                                    ptr(y), ybs, ptr(ws), need, stream()), f"conv3d+pool233[{pc.name}]")

@@ -85,6 +85,15 @@ extern "C" {
  * other families: bit-identical results.  No LayerNorm fold / GELU-backward operand.  OPT-IN and never chosen by ADVHIP_ALGO_AUTO
  * or the tuned table: measured slower than the one-tile kernels on the B = 32 plan (profiles/r04_persist_kernel_study.md). */
 #define ADVHIP_ALGO_PERSIST_BASE 224
+/* advhip_conv3d_s2w_bn_relu_maxpool233_f32 (and its workspace size) only: the stem launch SPLIT BY POOL WINDOW IN T.  The pool
+ * windows whose two output frames have no temporal tap in the padding run the 2(t) x 4(h) x 16(w) bricks as before; the window at
+ * either end of the clip runs frame by frame on 1(t) x 8(h) x 16(w) tiles, where a k-tile whose rows all carry a padded temporal
+ * tap is padding for the whole workgroup and is skipped (fill, barrier, fragment reads, MFMAs): 23 of the 368 k-tiles of a sample
+ * column at T = 16.  The max over such a window's two frames moves to the merge launch.  Whole k-tiles are skipped and K keeps
+ * its order: every output sees the same non-zero terms in the same order, bit-identical results (for finite weights: a skipped
+ * product is 0 * w).  Applies to kt = 5, pt = 2, st = 2, an even output T and an even number of 4-row bricks along h; any other
+ * geometry runs the single launch.  Any other algo value on that entry point: the single launch. */
+#define ADVHIP_ALGO_STEM_BORDER 256
 
 typedef struct advhip_conv3d_desc {
   int32_t B, Cin, T, H, W;    /* input  (B, Cin, T, H, W) */
@@ -225,6 +234,11 @@ int advhip_conv3d_pool_out_dims(const advhip_conv3d_desc* d, int32_t pkt, int32_
  * (relu) + advhip_maxpool3d_f32.  x / y may be channel slices of wider tensors (batch strides in elements, 0 = dense).
  * d->relu and d->algo / d->splits are ignored (ReLU is part of the op; one tile configuration). */
 int64_t advhip_conv3d_relu_maxpool233_workspace_bytes(const advhip_conv3d_desc* d);
+/* Host arithmetic only: the k-tiles of `bk` packed rows (row k = ((ci*kt+dt)*kh+dh)*kw+dw) that hold at least one row k < K whose
+ * temporal tap lies inside the clip for output frame ot, ascending, into tiles[] (nullable; up to ceil(K / bk) entries) and their
+ * count into *n_tiles.  Every other k-tile multiplies zero padding at every position of that frame: what the frame-uniform tiles
+ * of ADVHIP_ALGO_STEM_BORDER skip (bk = 16).  A frame with no padded tap gets every k-tile. */
+int advhip_conv3d_active_ktiles(const advhip_conv3d_desc* d, int32_t ot, int32_t bk, int32_t* tiles, int32_t* n_tiles);
 int advhip_conv3d_bn_relu_maxpool233_f32(const advhip_conv3d_desc* d, const float* x, int64_t x_batch_stride,
                                          const float* w_packed, const int32_t* ktab, const float* scale, const float* shift,
                                          float* y, int64_t y_batch_stride, void* workspace, int64_t workspace_bytes,
