@@ -238,6 +238,10 @@ SIGNATURES = {
     "advhip_resize_u8_sampled": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "advhip_yuv420_to_rgb_u8": (C.c_int, [_P, _P, _L, _I, _I, _I, _I] + [_I] * 6 + [_P]),
     "advhip_resize_yuv420_u8": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I] + [_I] * 6 + [_P]),
+    # (..., frame_pitch, H, W, [resize arguments,] bits, shift, y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, coefficients)
+    "advhip_yuv420_surface_to_rgb_u8": (C.c_int, [_P, _P, _L, _I, _L, _I, _I] + [_I, _I, _L, _L, _L, _L, _L, _I] + [_I] * 6 + [_P]),
+    "advhip_resize_yuv420_surface_u8": (C.c_int, [_P, _P, _P, _L, _I, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I]
+                                        + [_I, _I, _L, _L, _L, _L, _L, _I] + [_I] * 6 + [_P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -86,30 +86,41 @@ struct YuvLayout {
       : cw(layout == 0 ? W : W / 2), cs(layout == 0 ? 2 : 1), cr_off(layout == 0 ? 1 : (long long)(H / 2) * (W / 2)) {}
 };
 
-// the three chroma terms of a sample, formed once for the pixels that share it
+// the three chroma terms of a sample, formed once for the pixels that share it (BITS: the sample depth, 8 or 10; the chroma
+// midpoint is 2^(BITS - 1) and the coefficients are 2^(8 + BITS) fixed point)
+template <int BITS>
 struct ChromaTerms {
   int rv, guv, bu;
   __device__ __forceinline__ ChromaTerms(int cb, int cr, const YuvCoef& k)
-      : rv(k.crv * (cr - 128)), guv(-k.cgu * (cb - 128) - k.cgv * (cr - 128)), bu(k.cbu * (cb - 128)) {}
+      : rv(k.crv * (cr - (1 << (BITS - 1)))),
+        guv(-k.cgu * (cb - (1 << (BITS - 1))) - k.cgv * (cr - (1 << (BITS - 1)))),
+        bu(k.cbu * (cb - (1 << (BITS - 1)))) {}
 };
 
-// clip8(v >> 16) with the arithmetic shift of the definition: below 0 -> 0, from 2^24 on -> 255.  The clamp comes BEFORE the shift
-// on purpose.  Written as clamp(v >> 16, 0, 255), two of these OR-ed into one word became gfx950's v_ashr_pk_u8_i32 with ROCm 7.2.0
-// (AMD clang 22.0.0git, roc-7.2.0), into a register that still held a 32-bit sum; on the MI355X the bytes OR-ed in above its 16-bit
-// result then came out as that sum's high half, so the instruction kept it where the compiler counted on zero.  Observed with that
-// compiler only, and another one may fuse this form as well: tests/test_hip_yuv420.py's
-// test_conversion_is_the_restatement_for_every_triple (every triple, clamped ones included, through the packing kernel) is the guard.
-__device__ __forceinline__ int sat8_shr16(int v) { return min(max(v, 0), 0xFFFFFF) >> 16; }
+// clip8(v >> S) with the arithmetic shift of the definition: below 0 -> 0, from 2^(8 + S) on -> 255 (S = 16 at 8 bits, 18 at 10
+// bits).  The clamp comes BEFORE the shift on purpose.  Written as clamp(v >> 16, 0, 255), two of these OR-ed into one word became
+// gfx950's v_ashr_pk_u8_i32 with ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0), into a register that still held a 32-bit sum; on the
+// MI355X the bytes OR-ed in above its 16-bit result then came out as that sum's high half, so the instruction kept it where the
+// compiler counted on zero.  Observed with that compiler only, and another one may fuse this form as well: tests/test_hip_yuv420.py's
+// test_conversion_is_the_restatement_for_every_triple (every triple, clamped ones included, through the packing kernel) is the guard,
+// and the every-value tests of tests/test_hip_surface.py are the guard of the surface kernels' instantiations.
+template <int S>
+__device__ __forceinline__ int sat8_shr(int v) {
+  return min(max(v, 0), (1 << (8 + S)) - 1) >> S;
+}
 
-__device__ __forceinline__ void yuv_rgb(int y, const ChromaTerms& c, const YuvCoef& k, int& r, int& g, int& b) {
-  const int yi = k.cy * (y - k.yoff) + (1 << 15);
-  r = sat8_shr16(yi + c.rv);
-  g = sat8_shr16(yi + c.guv);
-  b = sat8_shr16(yi + c.bu);
+template <int BITS>
+__device__ __forceinline__ void yuv_rgb(int y, const ChromaTerms<BITS>& c, const YuvCoef& k, int& r, int& g, int& b) {
+  constexpr int S = 8 + BITS;
+  const int yi = k.cy * (y - k.yoff) + (1 << (S - 1));
+  r = sat8_shr<S>(yi + c.rv);
+  g = sat8_shr<S>(yi + c.guv);
+  b = sat8_shr<S>(yi + c.bu);
 }
 
 // R | G << 8 | B << 16
-__device__ __forceinline__ uint32_t yuv_rgb_packed(int y, const ChromaTerms& c, const YuvCoef& k) {
+template <int BITS>
+__device__ __forceinline__ uint32_t yuv_rgb_packed(int y, const ChromaTerms<BITS>& c, const YuvCoef& k) {
   int r, g, b;
   yuv_rgb(y, c, k, r, g, b);
   return (uint32_t)(r | g << 8 | b << 16);
@@ -157,14 +168,14 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __
           const uint32_t u = load_as<uint16_t>(cb + 2 * q), v = load_as<uint16_t>(cr + 2 * q);
           cc = (u & 255) | (v & 255) << 8 | (u >> 8) << 16 | (v >> 8) << 24;
         }
-        const ChromaTerms c0(cc & 255, (cc >> 8) & 255, k), c1((cc >> 16) & 255, cc >> 24, k);
+        const ChromaTerms<8> c0(cc & 255, (cc >> 8) & 255, k), c1((cc >> 16) & 255, cc >> 24, k);
         const uint32_t p0 = yuv_rgb_packed(yy & 255, c0, k), p1 = yuv_rgb_packed((yy >> 8) & 255, c0, k);
         const uint32_t p2 = yuv_rgb_packed((yy >> 16) & 255, c1, k), p3 = yuv_rgb_packed(yy >> 24, c1, k);
         store_as(out + 12 * q, Rgb4{p0 | p1 << 24, p1 >> 8 | p2 << 16, p2 >> 16 | p3 << 8});
       }
     } else {
       for (int p = lane; p < W / 2; p += 64) {
-        const ChromaTerms c(cb[p * L.cs], cr[p * L.cs], k);
+        const ChromaTerms<8> c(cb[p * L.cs], cr[p * L.cs], k);
         const uint32_t p0 = yuv_rgb_packed(yrow[2 * p], c, k), p1 = yuv_rgb_packed(yrow[2 * p + 1], c, k);
         uint8_t* o = out + 6 * p;
         if (even) {
@@ -203,12 +214,152 @@ __global__ __launch_bounds__(256) void resize_h_yuv420_u8_kernel(const uint8_t* 
       const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
       int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
       for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
-        const ChromaTerms c(cb[xc * L.cs], cr[xc * L.cs], k);
+        const ChromaTerms<8> c(cb[xc * L.cs], cr[xc * L.cs], k);
 #pragma unroll
         for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
           if (xs >= x0 && xs < xe) {
             int pr, pg, pb;
             yuv_rgb(yrow[xs], c, k, pr, pg, pb);
+            const int wk = w[xs];
+            s0 += pr * wk;
+            s1 += pg * wk;
+            s2 += pb * wk;
+          }
+        }
+      }
+      out[3 * x] = clip8(s0);
+      out[3 * x + 1] = clip8(s1);
+      out[3 * x + 2] = clip8(s2);
+    }
+  }
+}
+
+// --- decoder surfaces (include/advhip.h): the same two kernels on frames described by byte geometry and sample depth.  A sample
+// is a byte (BITS 8) or a little-endian 16-bit word whose value is (word >> shift) & 1023 (BITS 10); every offset, pitch and
+// step is in bytes from the frame's first byte.  NV12 / NV21 / I420 / YV12 / P010 / yuv420p10le are nothing but these numbers.
+struct YuvSurface {
+  long long y_off, y_pitch, cb_off, cr_off, c_pitch;
+  int c_step, shift;
+};
+
+struct alignas(8) Word2 {
+  uint32_t lo, hi;
+};
+
+template <int BITS>
+__device__ __forceinline__ int yuv_sample(const uint8_t* p, int shift) {
+  if constexpr (BITS == 8) return *p;
+  else return (load_as<uint16_t>(p) >> shift) & 1023;
+}
+
+// two / four adjacent samples from one load of their bytes (p aligned to the load's size)
+template <int BITS>
+__device__ __forceinline__ void yuv_sample2(const uint8_t* p, int shift, int& a, int& b) {
+  if constexpr (BITS == 8) {
+    const uint32_t w = load_as<uint16_t>(p);
+    a = w & 255, b = w >> 8;
+  } else {
+    const uint32_t w = load_as<uint32_t>(p);
+    a = (w >> shift) & 1023, b = (w >> (16 + shift)) & 1023;
+  }
+}
+
+template <int BITS>
+__device__ __forceinline__ void yuv_sample4(const uint8_t* p, int shift, int (&v)[4]) {
+  if constexpr (BITS == 8) {
+    const uint32_t w = load_as<uint32_t>(p);
+    v[0] = w & 255, v[1] = (w >> 8) & 255, v[2] = (w >> 16) & 255, v[3] = w >> 24;
+  } else {
+    const Word2 w = load_as<Word2>(p);
+    v[0] = (w.lo >> shift) & 1023, v[1] = (w.lo >> (16 + shift)) & 1023;
+    v[2] = (w.hi >> shift) & 1023, v[3] = (w.hi >> (16 + shift)) & 1023;
+  }
+}
+
+// yuv420_to_rgb_u8_kernel on a surface.  QUAD is chosen on the host (launch_yuv420_to_rgb) from the alignment of everything that
+// enters an address: a lane converts four pixels from one load of four Y samples and one load of two (Cb, Cr) pairs (interleaved
+// chroma, in either order) or two loads of two samples (planar chroma).  Otherwise the pair path, as there.
+template <int BITS, bool QUAD>
+__global__ __launch_bounds__(256) void yuv420_surface_to_rgb_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
+                                                                      int H, int W, YuvSurface S, YuvCoef k, int even, long long nrows) {
+  constexpr int SB = BITS == 8 ? 1 : 2;  // bytes per sample
+  const int lane = threadIdx.x & 63;
+  for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
+    const long long f = r / H;
+    const int y = (int)(r - f * H);
+    const uint8_t* frame = src + f * fpitch;
+    const uint8_t* yrow = frame + S.y_off + y * S.y_pitch;
+    const uint8_t* cb = frame + S.cb_off + (y >> 1) * S.c_pitch;
+    const uint8_t* cr = frame + S.cr_off + (y >> 1) * S.c_pitch;
+    uint8_t* out = dst + r * W * 3;
+    if constexpr (QUAD) {
+      for (int q = lane; q < W / 4; q += 64) {
+        int yy[4], c[4];  // c: Cb0, Cr0, Cb1, Cr1
+        yuv_sample4<BITS>(yrow + 4 * SB * q, S.shift, yy);
+        if (S.c_step == 2 * SB) {  // interleaved pairs: the two offsets are one sample apart
+          yuv_sample4<BITS>((S.cb_off < S.cr_off ? cb : cr) + 4 * SB * q, S.shift, c);
+          if (S.cr_off < S.cb_off) {
+            const int c0 = c[0], c2 = c[2];
+            c[0] = c[1], c[1] = c0, c[2] = c[3], c[3] = c2;
+          }
+        } else {
+          yuv_sample2<BITS>(cb + 2 * SB * q, S.shift, c[0], c[2]);
+          yuv_sample2<BITS>(cr + 2 * SB * q, S.shift, c[1], c[3]);
+        }
+        const ChromaTerms<BITS> c0(c[0], c[1], k), c1(c[2], c[3], k);
+        const uint32_t p0 = yuv_rgb_packed(yy[0], c0, k), p1 = yuv_rgb_packed(yy[1], c0, k);
+        const uint32_t p2 = yuv_rgb_packed(yy[2], c1, k), p3 = yuv_rgb_packed(yy[3], c1, k);
+        store_as(out + 12 * q, Rgb4{p0 | p1 << 24, p1 >> 8 | p2 << 16, p2 >> 16 | p3 << 8});
+      }
+    } else {
+      for (int p = lane; p < W / 2; p += 64) {
+        const ChromaTerms<BITS> c(yuv_sample<BITS>(cb + (long long)p * S.c_step, S.shift), yuv_sample<BITS>(cr + (long long)p * S.c_step, S.shift), k);
+        const uint32_t p0 = yuv_rgb_packed(yuv_sample<BITS>(yrow + 2 * SB * p, S.shift), c, k);
+        const uint32_t p1 = yuv_rgb_packed(yuv_sample<BITS>(yrow + 2 * SB * p + SB, S.shift), c, k);
+        uint8_t* o = out + 6 * p;
+        if (even) {
+          store_as(o, (uint16_t)p0);
+          store_as(o + 2, (uint16_t)(p0 >> 16 | p1 << 8));
+          store_as(o + 4, (uint16_t)(p1 >> 8));
+        } else {
+          o[0] = (uint8_t)p0, o[1] = (uint8_t)(p0 >> 8), o[2] = (uint8_t)(p0 >> 16);
+          o[3] = (uint8_t)p1, o[4] = (uint8_t)(p1 >> 8), o[5] = (uint8_t)(p1 >> 16);
+        }
+      }
+    }
+  }
+}
+
+// resize_h_yuv420_u8_kernel on a surface: the same walk, chroma sample by chroma sample, and the same 2^21 rounding
+template <int BITS>
+__global__ __launch_bounds__(256) void resize_h_yuv420_surface_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
+                                                                        int W, int OW, int row0, int rows, const int* __restrict__ xb,
+                                                                        const int* __restrict__ xk, int ksize, YuvSurface S, YuvCoef k,
+                                                                        long long nrows) {
+  constexpr int SB = BITS == 8 ? 1 : 2;
+  const int lane = threadIdx.x & 63;
+  for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
+    const long long f = r / rows;
+    const int y = row0 + (int)(r - f * rows);
+    const uint8_t* frame = src + f * fpitch;
+    const uint8_t* yrow = frame + S.y_off + y * S.y_pitch;
+    const uint8_t* cb = frame + S.cb_off + (y >> 1) * S.c_pitch;
+    const uint8_t* cr = frame + S.cr_off + (y >> 1) * S.c_pitch;
+    uint8_t* out = dst + r * OW * 3;
+    for (int x = lane; x < OW; x += 64) {
+      int x0 = xb[2 * x];
+      int n = min(xb[2 * x + 1], ksize);
+      if (x0 < 0 || x0 + n > W) x0 = 0, n = 0;  // (never for tables from resize.py: a guard against a foreign table)
+      const int xe = x0 + n;
+      const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
+      int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
+      for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
+        const ChromaTerms<BITS> c(yuv_sample<BITS>(cb + (long long)xc * S.c_step, S.shift), yuv_sample<BITS>(cr + (long long)xc * S.c_step, S.shift), k);
+#pragma unroll
+        for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
+          if (xs >= x0 && xs < xe) {
+            int pr, pg, pb;
+            yuv_rgb(yuv_sample<BITS>(yrow + (long long)xs * SB, S.shift), c, k, pr, pg, pb);
             const int wk = w[xs];
             s0 += pr * wk;
             s1 += pg * wk;
@@ -297,16 +448,62 @@ extern "C" int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_
   return ADVHIP_OK;
 }
 
-// the checks both 4:2:0 entry points share: even geometry, a known layout, coefficients that keep every int32 sum exact
-static int check_yuv420(const char* who, int32_t H, int32_t W, int32_t layout, const YuvCoef& k) {
-  ADVHIP_REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: 4:2:0 frames need even H and W >= 2, got %d x %d", who, H, W);
-  ADVHIP_REQUIRE(layout == ADVHIP_YUV420_NV12 || layout == ADVHIP_YUV420_I420, "%s: layout %d is neither NV12 (0) nor I420 (1)", who, layout);
-  ADVHIP_REQUIRE(k.yoff == 0 || k.yoff == 16, "%s: luma offset %d is neither 0 (full range) nor 16 (limited range)", who, k.yoff);
+// where the 4:2:0 samples of a frame are: a surface by its numbers, with the frame pitch the caller gave
+struct Yuv420Source {
+  int bits;               // 8 | 10
+  long long frame_pitch;  // bytes from one source frame to the next
+  YuvSurface S;
+};
+
+// the compact 8-bit frame (3H/2, W) of the first two entry points as a surface (for the checks; its launches stay its own kernels)
+static Yuv420Source compact_source(int H, int W, int layout) {
+  const long long y = (long long)H * W, c = (long long)(H / 2) * (W / 2);
+  const bool nv12 = layout == ADVHIP_YUV420_NV12;
+  return {8, y + 2 * c, {0, W, y, nv12 ? y + 1 : y + c, nv12 ? W : W / 2, nv12 ? 2 : 1, 0}};
+}
+
+// coefficients that keep every int32 sum exact at that depth (Y < 2^bits, |chroma - mid| <= 2^(bits - 1), bits <= 10: below 2^30)
+static int check_yuv_coef(const char* who, const YuvCoef& k, int bits) {
+  ADVHIP_REQUIRE(k.yoff == 0 || k.yoff == 16 << (bits - 8), "%s: luma offset %d is neither 0 (full range) nor %d (limited range)", who, k.yoff,
+                 16 << (bits - 8));
   const int lim = 1 << 18;
   ADVHIP_REQUIRE(k.cy > 0 && k.cy < lim, "%s: luma coefficient %d outside (0, 2^18)", who, k.cy);
   ADVHIP_REQUIRE(k.crv >= 0 && k.crv < lim && k.cgu >= 0 && k.cgu < lim && k.cgv >= 0 && k.cgv < lim && k.cbu >= 0 && k.cbu < lim,
                  "%s: chroma coefficients (%d, %d, %d, %d) outside [0, 2^18)", who, k.crv, k.cgu, k.cgv, k.cbu);
   return ADVHIP_OK;
+}
+
+// the checks both compact 4:2:0 entry points share: even geometry, a known layout, the coefficients
+static int check_yuv420(const char* who, int32_t H, int32_t W, int32_t layout, const YuvCoef& k) {
+  ADVHIP_REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: 4:2:0 frames need even H and W >= 2, got %d x %d", who, H, W);
+  ADVHIP_REQUIRE(layout == ADVHIP_YUV420_NV12 || layout == ADVHIP_YUV420_I420, "%s: layout %d is neither NV12 (0) nor I420 (1)", who, layout);
+  return check_yuv_coef(who, k, 8);
+}
+
+// the checks both surface entry points share: the rules of include/advhip.h, every plane inside the frame, the coefficients
+static int check_surface(const char* who, const uint8_t* src, int32_t H, int32_t W, const Yuv420Source& Y, const YuvCoef& k) {
+  const YuvSurface& S = Y.S;
+  ADVHIP_REQUIRE(Y.bits == 8 || Y.bits == 10, "%s: %d-bit samples (8 or 10)", who, Y.bits);
+  const int sb = Y.bits == 8 ? 1 : 2;
+  ADVHIP_REQUIRE(S.shift >= 0 && S.shift <= 6 && (Y.bits == 10 || S.shift == 0), "%s: shift %d outside [0, 6], or not 0 at 8 bits", who, S.shift);
+  ADVHIP_REQUIRE(H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "%s: 4:2:0 frames need even H and W >= 2, got %d x %d", who, H, W);
+  ADVHIP_REQUIRE(Y.frame_pitch >= 1 && S.y_off >= 0 && S.cb_off >= 0 && S.cr_off >= 0, "%s: frame pitch %lld < 1 or a negative plane offset (%lld, %lld, %lld)",
+                 who, Y.frame_pitch, S.y_off, S.cb_off, S.cr_off);
+  ADVHIP_REQUIRE(S.c_step == sb || S.c_step == 2 * sb, "%s: chroma step %d is neither %d (planar) nor %d (interleaved)", who, S.c_step, sb, 2 * sb);
+  ADVHIP_REQUIRE(S.c_step == sb || S.cb_off - S.cr_off == sb || S.cr_off - S.cb_off == sb,
+                 "%s: interleaved chroma needs Cb and Cr one sample (%d bytes) apart, got offsets %lld and %lld", who, sb, S.cb_off, S.cr_off);
+  ADVHIP_REQUIRE(S.y_pitch >= (long long)W * sb, "%s: luma pitch %lld below a row of %d samples (%lld bytes)", who, S.y_pitch, W, (long long)W * sb);
+  ADVHIP_REQUIRE(S.c_pitch >= (long long)(W / 2) * S.c_step, "%s: chroma pitch %lld below a chroma row (%lld bytes)", who, S.c_pitch,
+                 (long long)(W / 2) * S.c_step);
+  if (Y.bits == 10)
+    ADVHIP_REQUIRE(((uintptr_t)src | Y.frame_pitch | S.y_off | S.y_pitch | S.cb_off | S.cr_off | S.c_pitch) % 2 == 0,
+                   "%s: 16-bit samples need an even address, frame pitch, offsets and pitches", who);
+  const __int128 y_end = (__int128)S.y_off + (__int128)(H - 1) * S.y_pitch + (long long)W * sb;
+  const __int128 c_last = (__int128)(H / 2 - 1) * S.c_pitch + (long long)(W / 2 - 1) * S.c_step + sb;
+  ADVHIP_REQUIRE(y_end <= Y.frame_pitch && S.cb_off + c_last <= Y.frame_pitch && S.cr_off + c_last <= Y.frame_pitch,
+                 "%s: a plane ends past the frame's %lld bytes (luma at %lld, Cb at %lld, Cr at %lld)", who, Y.frame_pitch, (long long)y_end,
+                 (long long)(S.cb_off + c_last), (long long)(S.cr_off + c_last));
+  return check_yuv_coef(who, k, Y.bits);
 }
 
 // (every argument checked by the caller) frames 0, frame_step, ... of src -> compact RGB frames in dst
@@ -322,64 +519,116 @@ static int launch_yuv420_to_rgb(const uint8_t* src, uint8_t* dst, long long F, l
   return check_launch("yuv420_to_rgb_u8");
 }
 
-extern "C" int advhip_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t layout,
-                                       int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
-  const YuvCoef k{yoff, cy, crv, cgu, cgv, cbu};
-  ADVHIP_REQUIRE(src && dst, "yuv420_to_rgb_u8: null frames or output");
-  ADVHIP_REQUIRE(frame_step >= 1, "yuv420_to_rgb_u8: frame step %d", frame_step);
-  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
-  ADVHIP_REQUIRE(F >= 1, "yuv420_to_rgb_u8: %lld frames", (long long)F_src);
-  if (const int rc = check_yuv420("yuv420_to_rgb_u8", H, W, layout, k); rc != ADVHIP_OK) return rc;
-  long long in_bytes, out_bytes, pitch;
-  ADVHIP_REQUIRE(mul_ok(F_src, H / 2, W, 3, &in_bytes) && mul_ok(F, H, W, 3, &out_bytes) && mul_ok(H / 2, W, 3, frame_step, &pitch),
-                 "yuv420_to_rgb_u8: frame sizes overflow int64");
-  ADVHIP_REQUIRE((long long)W * 3 <= INT32_MAX, "yuv420_to_rgb_u8: rows of %d pixels are too long", W);
-  return launch_yuv420_to_rgb(src, dst, F, F > 1 ? pitch : 0, H, W, layout, k, (hipStream_t)stream);
+template <int BITS>
+static void launch_surface_to_rgb_bits(bool quad, int grid, hipStream_t s, const uint8_t* src, uint8_t* dst, long long src_pitch, int H, int W,
+                                       const YuvSurface& S, const YuvCoef& k, long long nrows) {
+  if (quad) hipLaunchKernelGGL((yuv420_surface_to_rgb_u8_kernel<BITS, true>), dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, S, k, 1, nrows);
+  else
+    hipLaunchKernelGGL((yuv420_surface_to_rgb_u8_kernel<BITS, false>), dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, S, k,
+                       (int)((uintptr_t)dst % 2 == 0), nrows);
 }
 
-extern "C" int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
-                                       int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
-                                       const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, int32_t layout,
-                                       int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
-  const YuvCoef k{yoff, cy, crv, cgu, cgv, cbu};
-  ADVHIP_REQUIRE(src && dst, "resize_yuv420_u8: null frames or output");
-  ADVHIP_REQUIRE(frame_step >= 1, "resize_yuv420_u8: frame step %d", frame_step);
+// the same for a surface.  The four-pixel path needs every load and the 12-byte store aligned: Y and interleaved chroma are read
+// 4 sb bytes at a time, planar chroma 2 sb bytes, so everything that enters those addresses must be a multiple of that -- the
+// pointer, the frame pitch (where a second frame is read), the offsets and the pitches.
+static int launch_surface_to_rgb(const uint8_t* src, uint8_t* dst, long long F, long long src_pitch, int H, int W, const Yuv420Source& Y,
+                                 const YuvCoef& k, hipStream_t s) {
+  const YuvSurface& S = Y.S;
+  const long long nrows = F * H;
+  const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
+  const int sb = Y.bits == 8 ? 1 : 2;
+  const long long ya = 4 * sb, ca = S.c_step == 2 * sb ? 4 * sb : 2 * sb;
+  const bool quad = W % 4 == 0 && (uintptr_t)dst % 4 == 0 && ((uintptr_t)src | src_pitch | S.y_off | S.y_pitch) % ya == 0 &&
+                    ((uintptr_t)src | src_pitch | std::min(S.cb_off, S.cr_off) | S.c_pitch) % ca == 0 &&
+                    (S.c_step == 2 * sb || (S.cb_off | S.cr_off) % ca == 0);
+  if (Y.bits == 8) launch_surface_to_rgb_bits<8>(quad, grid, s, src, dst, src_pitch, H, W, S, k, nrows);
+  else launch_surface_to_rgb_bits<10>(quad, grid, s, src, dst, src_pitch, H, W, S, k, nrows);
+  return check_launch("yuv420_surface_to_rgb_u8");
+}
+
+// both conversion entry points: `compact` frames run their own kernels, a surface the surface kernels
+static int yuv420_to_rgb(const char* who, bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, int64_t F_src,
+                         int32_t frame_step, int32_t H, int32_t W, const YuvCoef& k, void* stream) {
+  ADVHIP_REQUIRE(src && dst, "%s: null frames or output", who);
+  ADVHIP_REQUIRE(frame_step >= 1, "%s: frame step %d", who, frame_step);
   const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
-  ADVHIP_REQUIRE(F >= 1 && OH >= 1 && OW >= 1, "resize_yuv420_u8: sizes must be >= 1 (F=%lld, -> %d x %d)", (long long)F, OH, OW);
-  ADVHIP_REQUIRE(C == 3, "resize_yuv420_u8: the output has 3 channels (RGB), got C=%d", C);
-  if (const int rc = check_yuv420("resize_yuv420_u8", H, W, layout, k); rc != ADVHIP_OK) return rc;
+  ADVHIP_REQUIRE(F >= 1, "%s: %lld frames", who, (long long)F_src);
+  if (const int rc = compact ? check_yuv420(who, H, W, layout, k) : check_surface(who, src, H, W, Y, k); rc != ADVHIP_OK) return rc;
+  long long in_bytes, out_bytes, pitch;
+  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, H, W, 3, &out_bytes) && mul_ok(Y.frame_pitch, frame_step, 1, 1, &pitch),
+                 "%s: frame sizes overflow int64", who);
+  ADVHIP_REQUIRE((long long)W * 3 <= INT32_MAX, "%s: rows of %d pixels are too long", who, W);
+  if (F == 1) pitch = 0;  // (F > 1: inside in_bytes)
+  if (compact) return launch_yuv420_to_rgb(src, dst, F, pitch, H, W, layout, k, (hipStream_t)stream);
+  return launch_surface_to_rgb(src, dst, F, pitch, H, W, Y, k, (hipStream_t)stream);
+}
+
+extern "C" int advhip_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t layout,
+                                       int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
+  return yuv420_to_rgb("yuv420_to_rgb_u8", true, layout, compact_source(H, W, layout), src, dst, F_src, frame_step, H, W,
+                       YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+}
+
+extern "C" int advhip_yuv420_surface_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int64_t frame_pitch, int32_t H,
+                                               int32_t W, int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset,
+                                               int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
+                                               int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
+  const Yuv420Source Y{bits, frame_pitch, {y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, shift}};
+  return yuv420_to_rgb("yuv420_surface_to_rgb_u8", false, -1, Y, src, dst, F_src, frame_step, H, W, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+}
+
+// both fused-resize entry points, as above
+static int resize_yuv420(const char* who, bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, uint8_t* ws,
+                         int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds,
+                         const int32_t* xcoef, int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0,
+                         int32_t rows, const YuvCoef& k, void* stream) {
+  ADVHIP_REQUIRE(src && dst, "%s: null frames or output", who);
+  ADVHIP_REQUIRE(frame_step >= 1, "%s: frame step %d", who, frame_step);
+  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
+  ADVHIP_REQUIRE(F >= 1 && OH >= 1 && OW >= 1, "%s: sizes must be >= 1 (F=%lld, -> %d x %d)", who, (long long)F, OH, OW);
+  ADVHIP_REQUIRE(C == 3, "%s: the output has 3 channels (RGB), got C=%d", who, C);
+  if (const int rc = compact ? check_yuv420(who, H, W, layout, k) : check_surface(who, src, H, W, Y, k); rc != ADVHIP_OK) return rc;
   const bool horiz = OW != W, vert = OH != H;
   long long in_bytes, out_bytes, rgb_bytes, src_pitch, ws_bytes = 0;
-  ADVHIP_REQUIRE(mul_ok(F_src, H / 2, W, 3, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes) && mul_ok(F, H, W, C, &rgb_bytes) &&
-                     mul_ok(H / 2, W, 3, frame_step, &src_pitch),
-                 "resize_yuv420_u8: frame sizes overflow int64");
+  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes) && mul_ok(F, H, W, C, &rgb_bytes) &&
+                     mul_ok(Y.frame_pitch, frame_step, 1, 1, &src_pitch),
+                 "%s: frame sizes overflow int64", who);
   if (F == 1) src_pitch = 0;  // (F > 1: inside in_bytes)
-  ADVHIP_REQUIRE((long long)W * C <= INT32_MAX && (long long)OW * C <= INT32_MAX, "resize_yuv420_u8: rows of %d / %d pixels are too long", W, OW);
+  ADVHIP_REQUIRE((long long)W * C <= INT32_MAX && (long long)OW * C <= INT32_MAX, "%s: rows of %d / %d pixels are too long", who, W, OW);
   if (horiz) {
-    ADVHIP_REQUIRE(xbounds && xcoef, "resize_yuv420_u8: null horizontal tables");
-    ADVHIP_REQUIRE(xksize >= 1, "resize_yuv420_u8: horizontal ksize %d < 1", xksize);
-    ADVHIP_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= H,
-                   "resize_yuv420_u8: rows [%d, %lld) of the horizontal pass outside the %d-row frames", row0, (long long)row0 + rows, H);
-    ADVHIP_REQUIRE(vert || (row0 == 0 && rows == H), "resize_yuv420_u8: without a vertical pass the horizontal pass must compute all %d rows", H);
-    ADVHIP_REQUIRE(mul_ok(F, rows, OW, C, &ws_bytes), "resize_yuv420_u8: workspace size overflows int64");
-    ADVHIP_REQUIRE(ws || !vert, "resize_yuv420_u8: null workspace for the horizontal pass (%lld bytes)", ws_bytes);
+    ADVHIP_REQUIRE(xbounds && xcoef, "%s: null horizontal tables", who);
+    ADVHIP_REQUIRE(xksize >= 1, "%s: horizontal ksize %d < 1", who, xksize);
+    ADVHIP_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= H, "%s: rows [%d, %lld) of the horizontal pass outside the %d-row frames", who,
+                   row0, (long long)row0 + rows, H);
+    ADVHIP_REQUIRE(vert || (row0 == 0 && rows == H), "%s: without a vertical pass the horizontal pass must compute all %d rows", who, H);
+    ADVHIP_REQUIRE(mul_ok(F, rows, OW, C, &ws_bytes), "%s: workspace size overflows int64", who);
+    ADVHIP_REQUIRE(ws || !vert, "%s: null workspace for the horizontal pass (%lld bytes)", who, ws_bytes);
   } else if (vert) {
-    ADVHIP_REQUIRE(ws, "resize_yuv420_u8: null workspace for the converted frames of a vertical-only resize (%lld bytes)", rgb_bytes);
+    ADVHIP_REQUIRE(ws, "%s: null workspace for the converted frames of a vertical-only resize (%lld bytes)", who, rgb_bytes);
   }
   if (vert) {
-    ADVHIP_REQUIRE(ybounds && ycoef, "resize_yuv420_u8: null vertical tables");
-    ADVHIP_REQUIRE(yksize >= 1, "resize_yuv420_u8: vertical ksize %d < 1", yksize);
+    ADVHIP_REQUIRE(ybounds && ycoef, "%s: null vertical tables", who);
+    ADVHIP_REQUIRE(yksize >= 1, "%s: vertical ksize %d < 1", who, yksize);
   }
   hipStream_t s = (hipStream_t)stream;
   if (horiz) {
     const long long nrows = F * rows;
     const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_h_yuv420_u8_kernel, dim3(grid), dim3(256), 0, s, src, vert ? ws : dst, src_pitch, H, W, OW, row0, rows, xbounds, xcoef,
-                       xksize, layout, k, nrows);
+    uint8_t* to = vert ? ws : dst;
+    if (compact)
+      hipLaunchKernelGGL(resize_h_yuv420_u8_kernel, dim3(grid), dim3(256), 0, s, src, to, src_pitch, H, W, OW, row0, rows, xbounds, xcoef, xksize, layout,
+                         k, nrows);
+    else if (Y.bits == 8)
+      hipLaunchKernelGGL(resize_h_yuv420_surface_u8_kernel<8>, dim3(grid), dim3(256), 0, s, src, to, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
+                         Y.S, k, nrows);
+    else
+      hipLaunchKernelGGL(resize_h_yuv420_surface_u8_kernel<10>, dim3(grid), dim3(256), 0, s, src, to, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
+                         Y.S, k, nrows);
     const int rc = check_launch("resize_yuv420_u8 horizontal pass");
     if (rc != ADVHIP_OK) return rc;
   } else {  // rare: the conversion launch, into dst (the identity) or into the workspace the vertical pass then reads
-    const int rc = launch_yuv420_to_rgb(src, vert ? ws : dst, F, src_pitch, H, W, layout, k, s);
+    const int rc = compact ? launch_yuv420_to_rgb(src, vert ? ws : dst, F, src_pitch, H, W, layout, k, s)
+                           : launch_surface_to_rgb(src, vert ? ws : dst, F, src_pitch, H, W, Y, k, s);
     if (rc != ADVHIP_OK) return rc;
   }
   if (vert) {  // the RGB resize's own vertical pass
@@ -390,4 +639,23 @@ extern "C" int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t
     return check_launch("resize_yuv420_u8 vertical pass");
   }
   return ADVHIP_OK;
+}
+
+extern "C" int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
+                                       int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                                       const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, int32_t layout,
+                                       int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
+  return resize_yuv420("resize_yuv420_u8", true, layout, compact_source(H, W, layout), src, dst, ws, F_src, frame_step, H, W, C, OH, OW, xbounds, xcoef,
+                       xksize, ybounds, ycoef, yksize, row0, rows, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+}
+
+extern "C" int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int64_t frame_pitch,
+                                               int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef,
+                                               int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0,
+                                               int32_t rows, int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset,
+                                               int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
+                                               int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
+  const Yuv420Source Y{bits, frame_pitch, {y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, shift}};
+  return resize_yuv420("resize_yuv420_surface_u8", false, -1, Y, src, dst, ws, F_src, frame_step, H, W, C, OH, OW, xbounds, xcoef, xksize, ybounds,
+                       ycoef, yksize, row0, rows, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
 }

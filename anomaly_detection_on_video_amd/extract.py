@@ -141,7 +141,8 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 @torch.no_grad()
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
                          clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
-                         crops=None, frame_step: Optional[int] = None, normalize=None, pixel_format=None, **kw) -> np.ndarray:
+                         crops=None, frame_step: Optional[int] = None, normalize=None, pixel_format=None, surface=None,
+                         **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -186,7 +187,12 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     horizontal pass with `resize` (the full-size RGB frames never exist), as one launch of its own without (a decoder that scaled
     already).  The features are those of the converted frames, extract_video_frames(yuv420_to_rgb_u8(frames), ...), bit for bit.
     The conversion is resize.yuv_coefficients' integer formula with nearest chroma, not swscale's bytes: packed RGB frames
-    remain the reference-parity input.  Like `resize` it describes the source, so file names carry no tag for it."""
+    remain the reference-parity input.  Like `resize` it describes the source, so file names carry no tag for it.
+
+    `surface` (a resize.Surface, e.g. from resize.surface; with `pixel_format`; default None = the compact frames above): `frames`
+    are the decoder's surfaces as they are, uint8 (F, frame_bytes) -- a row pitch above W, aligned rows, plane offsets, NV21 / YV12
+    order, 10-bit P010 / yuv420p10le -- and the conversion or the fused resize reads them in place by that geometry.  Host frames
+    cross PCIe as they are, padding included.  The features are again those of the converted frames, bit for bit; no file-name tag."""
     s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     norm = resolve_normalize(normalize)
     plain = normalize_is_default(norm)
@@ -195,7 +201,11 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     if clips_per_step is None:
         clips_per_step = max(1, 30 // nc) if subset else 3
     pf = resize_mod.resolve_pixel_format(pixel_format)
-    if pf is not None:
+    if surface is not None:  # (refuses a missing pixel format and an impossible geometry before anything is copied)
+        if frames.dtype != torch.uint8 or frames.dim() != 2:
+            raise ValueError(f"expected uint8 (F, frame_bytes) surfaces, got {frames.dtype} {tuple(frames.shape)}")
+        surface = resize_mod.resolve_surface(surface, pf, frames.shape[1])
+    elif pf is not None:
         if frames.dtype != torch.uint8 or frames.dim() != 3:
             raise ValueError(f"expected uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
         resize_mod.frame_hw(frames.shape)  # (refuses an impossible geometry before anything is copied)
@@ -223,18 +233,21 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
                     fr = fr[::fstep]  # host frames: only the lattice crosses PCIe
         if convert:  # decoded frames -> (colour conversion +) GroupResize on the device, into a buffer with the stem's spare bytes
             fr = fr.to(dev, non_blocking=True).contiguous()
-            (h, w), c = ((fr.shape[1], fr.shape[2]), fr.shape[3]) if pf is None else (resize_mod.frame_hw(fr.shape), 3)
+            if surface is not None:
+                (h, w), c = (surface.height, surface.width), 3
+            else:
+                (h, w), c = ((fr.shape[1], fr.shape[2]), fr.shape[3]) if pf is None else (resize_mod.frame_hw(fr.shape), 3)
             oh, ow = (h, w) if resize is None else resize_mod.output_size(h, w, resize)
             nf = fr.shape[0] if rstep is None else -(-fr.shape[0] // rstep)
             n = nf * oh * ow * c
             buf = torch.empty((n + 16,), device=dev, dtype=torch.uint8)
             out = buf[:n].view(nf, oh, ow, c)
             if resize is None:  # 4:2:0 frames a decoder scaled already: the conversion launch alone
-                fr = resize_mod.yuv420_to_rgb_u8(fr, pf, out=out, frame_step=rstep)
+                fr = resize_mod.yuv420_to_rgb_u8(fr, pf, out=out, frame_step=rstep, surface=surface)
             elif pf is None:
                 fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep)
             else:
-                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, pixel_format=pf)
+                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, pixel_format=pf, surface=surface)
         elif direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
             buf = torch.empty((fr.numel() + 16,), device=dev, dtype=torch.uint8)
             if fr.is_contiguous():

@@ -10,6 +10,10 @@ Decoded frames as a decoder has them, 8-bit Y'CbCr 4:2:0 (NV12 / I420), go in th
 the colour conversion is the integer formula of `yuv_coefficients`, on the device, inside the horizontal pass.  That formula is
 this package's own definition, not ffmpeg swscale's bytes (the reference's RGB comes out of decord, i.e. swscale, which is not
 available to pin against): packed RGB frames remain the reference-parity path.
+
+A decoder's surface as it is -- a row pitch above W, aligned rows, plane offsets, NV21 / YV12 chroma order, 10-bit samples (P010,
+yuv420p10le) -- goes in through `surface=` (Surface, surface, resolve_surface) next to `pixel_format`: the frames are then uint8
+(F, frame_bytes) and the same kernels read them in place by byte geometry.
 """
 from __future__ import annotations
 
@@ -74,22 +78,131 @@ def frame_hw(shape) -> Tuple[int, int]:
     return rows // 3 * 2, w  # (an odd H has no whole chroma rows: its 3H/2 is not a multiple of 3)
 
 
-def yuv_coefficients(pixel_format) -> Tuple[int, int, int, int, int, int]:
-    """(yoff, cy, crv, cgu, cgv, cbu) of a pixel format: round(real * 2**16) of the Y'CbCr -> RGB matrix that the luma weights
-    (Kr, Kb) and the range give.  The conversion, on the device and in any restatement, is
-        yi = cy * (Y - yoff) + 2**15
-        R = clip8((yi + crv * (Cr - 128)) >> 16)
-        G = clip8((yi - cgu * (Cb - 128) - cgv * (Cr - 128)) >> 16)        (arithmetic shifts)
-        B = clip8((yi + cbu * (Cb - 128)) >> 16)
-    which is within 1 of the rounded real formula for every (Y, Cb, Cr) and differs from it on fewer than 0.03 % of the values."""
+def yuv_coefficients(pixel_format, bits: int = 8) -> Tuple[int, int, int, int, int, int]:
+    """(yoff, cy, crv, cgu, cgv, cbu) of a pixel format at a sample depth of `bits` (8 or 10): round(real * 2**S), S = 8 + bits,
+    of the Y'CbCr -> RGB matrix that the luma weights (Kr, Kb), the range and the depth give (limited range: yoff = 16 * 2**(bits -
+    8), luma scale 255 / (219 * 2**(bits - 8)), chroma scale 255 / (224 * 2**(bits - 8)); full range: yoff = 0, both scales 255 /
+    (2**bits - 1)).  The conversion, on the device and in any restatement, is with mid = 2**(bits - 1)
+        yi = cy * (Y - yoff) + 2**(S - 1)
+        R = clip8((yi + crv * (Cr - mid)) >> S)
+        G = clip8((yi - cgu * (Cb - mid) - cgv * (Cr - mid)) >> S)        (arithmetic shifts)
+        B = clip8((yi + cbu * (Cb - mid)) >> S)
+    At 8 bits this is within 1 of the rounded real formula for every (Y, Cb, Cr) and differs from it on fewer than 0.03 % of the
+    values; at 10 bits within 1 and on at most 0.110 % of the lattice of tests/test_surface_host.py."""
     pf = resolve_pixel_format(pixel_format)
     if pf is None:
         raise ValueError("yuv_coefficients: packed RGB has no conversion")
+    if bits not in (8, 10):
+        raise ValueError(f"yuv_coefficients: bits {bits!r} is neither 8 nor 10")
     kr, kb = LUMA_WEIGHTS[pf.matrix]
     kg = 1.0 - kr - kb
-    ys, cs, yoff = (1.0, 1.0, 0) if pf.full_range else (255.0 / 219.0, 255.0 / 224.0, 16)
+    up = 1 << (bits - 8)
+    ys, cs, yoff = (255.0 / ((1 << bits) - 1),) * 2 + (0,) if pf.full_range else (255.0 / (219.0 * up), 255.0 / (224.0 * up), 16 * up)
     real = (ys, 2.0 * (1.0 - kr) * cs, 2.0 * (1.0 - kb) * kb / kg * cs, 2.0 * (1.0 - kr) * kr / kg * cs, 2.0 * (1.0 - kb) * cs)
-    return (yoff,) + tuple(int(round(v * (1 << YUV_BITS))) for v in real)
+    return (yoff,) + tuple(int(round(v * (1 << (8 + bits)))) for v in real)
+
+
+class Surface(NamedTuple):
+    """Where the samples of one 4:2:0 frame are inside its `frame_bytes` bytes: every offset, pitch and step in bytes from the
+    frame's first byte (what VAImage.offsets / pitches or an AVFrame's planes and linesizes give).  A sample is a byte at `bits`
+    8, a little-endian 16-bit word with the value (word >> shift) & 1023 at `bits` 10 (shift 6: P010, 0: yuv420p10le).  Luma (y, x)
+    is at y_offset + y * y_pitch + x * sb; chroma sample (r, c) of Cb at cb_offset + r * chroma_pitch + c * chroma_step, of Cr the
+    same from cr_offset.  `surface` builds the common cases; resolve_surface states the rules."""
+    height: int
+    width: int
+    bits: int
+    shift: int
+    y_offset: int
+    y_pitch: int
+    cb_offset: int
+    cr_offset: int
+    chroma_pitch: int
+    chroma_step: int
+
+    @property
+    def sample_bytes(self) -> int:
+        return 2 if self.bits == 10 else 1
+
+    @property
+    def frame_bytes_min(self) -> int:
+        """The end of the last plane: the fewest bytes a frame of this surface can have."""
+        sb = self.sample_bytes
+        c_last = (self.height // 2 - 1) * self.chroma_pitch + (self.width // 2 - 1) * self.chroma_step + sb
+        return max(self.y_offset + (self.height - 1) * self.y_pitch + self.width * sb, self.cb_offset + c_last, self.cr_offset + c_last)
+
+
+def surface(pixel_format, height: int, width: int, *, pitch: Optional[int] = None, rows: Optional[int] = None,
+            chroma_pitch: Optional[int] = None, bits: int = 8, shift: Optional[int] = None, chroma_order: str = "uv",
+            y_offset: int = 0) -> Surface:
+    """The Surface of the usual allocations of `pixel_format`'s layout ("nv12" or "i420"): luma rows of `pitch` bytes (default
+    W * sb), `rows` allocated luma rows (default H; a hardware decoder aligns them), chroma directly behind them at y_offset +
+    pitch * rows.  "nv12": interleaved pairs, rows of `chroma_pitch` bytes (default `pitch`); "i420": two planes of (rows + 1) // 2
+    rows of `chroma_pitch` bytes (default half the luma pitch, in whole samples).  `chroma_order` "vu" puts Cr first (NV21, YV12).
+    `shift` defaults to 6 for "nv12" at 10 bits (P010) and to 0 otherwise (yuv420p10le).  The defaults are the compact frame."""
+    layout = resolve_pixel_format(pixel_format).layout if pixel_format is not None else None
+    if layout is None:
+        raise ValueError("surface: packed RGB has no surface; the layout is \"nv12\" or \"i420\"")
+    if chroma_order not in ("uv", "vu"):
+        raise ValueError(f"surface: chroma_order {chroma_order!r} is neither \"uv\" nor \"vu\"")
+    if bits not in (8, 10):
+        raise ValueError(f"surface: bits {bits!r} is neither 8 nor 10")
+    h, w, sb = int(height), int(width), 2 if bits == 10 else 1
+    pitch = w * sb if pitch is None else int(pitch)
+    rows = h if rows is None else int(rows)
+    if rows < h:
+        raise ValueError(f"surface: {rows} allocated rows are fewer than the frame's {h}")
+    if shift is None:
+        shift = 6 if bits == 10 and layout == "nv12" else 0
+    c0 = int(y_offset) + pitch * rows
+    if layout == "nv12":
+        cp = pitch if chroma_pitch is None else int(chroma_pitch)
+        first, second, step = c0, c0 + sb, 2 * sb
+    else:
+        cp = pitch // (2 * sb) * sb if chroma_pitch is None else int(chroma_pitch)
+        first, second, step = c0, c0 + cp * ((rows + 1) // 2), sb
+    cb, cr = (first, second) if chroma_order == "uv" else (second, first)
+    return Surface(h, w, int(bits), int(shift), int(y_offset), pitch, cb, cr, cp, step)
+
+
+def resolve_surface(surface: Surface, pixel_format, frame_bytes: int) -> Surface:
+    """A Surface checked against `pixel_format`'s layout and frames of `frame_bytes` bytes, as plain ints; ValueError names the
+    rule it breaks."""
+    pf = resolve_pixel_format(pixel_format)
+    if pf is None:
+        raise ValueError("surface= describes 4:2:0 frames: it needs a pixel_format (for the layout, the matrix and the range)")
+    if not isinstance(surface, Surface):
+        if not isinstance(surface, (tuple, list)) or len(surface) != len(Surface._fields):
+            raise ValueError(f"surface {surface!r} is not a resize.Surface {Surface._fields}")
+        surface = Surface(*surface)
+    try:
+        sf = Surface(*(int(v) for v in surface))
+    except (TypeError, ValueError):
+        raise ValueError(f"surface {surface!r}: every field is an integer")
+    bad = lambda rule: ValueError(f"surface {tuple(sf)}: {rule}")  # noqa: E731
+    if sf.height < 2 or sf.width < 2 or sf.height % 2 or sf.width % 2:
+        raise bad(f"4:2:0 frames need even H and W >= 2, got {sf.height} x {sf.width}")
+    if sf.bits not in (8, 10):
+        raise bad(f"bits {sf.bits} is neither 8 nor 10")
+    sb = sf.sample_bytes
+    if not 0 <= sf.shift <= 6 or (sf.bits == 8 and sf.shift):
+        raise bad(f"shift {sf.shift} outside [0, 6], or not 0 at 8 bits")
+    if min(sf.y_offset, sf.cb_offset, sf.cr_offset) < 0:
+        raise bad("negative offset")
+    if sf.bits == 10 and any(v % 2 for v in sf[4:] + (int(frame_bytes),)):
+        raise bad(f"at 10 bits every offset, pitch and step and the frame's {frame_bytes} bytes must be even (16-bit samples)")
+    if sf.y_pitch < sf.width * sb:
+        raise bad(f"y_pitch {sf.y_pitch} below a row of {sf.width} samples ({sf.width * sb} bytes)")
+    if sf.chroma_step not in (sb, 2 * sb):
+        raise bad(f"chroma_step {sf.chroma_step} is neither {sb} (planar) nor {2 * sb} (interleaved)")
+    if sf.chroma_pitch < sf.width // 2 * sf.chroma_step:
+        raise bad(f"chroma_pitch {sf.chroma_pitch} shorter than a chroma row ({sf.width // 2 * sf.chroma_step} bytes)")
+    if pf.layout == "nv12" and (sf.chroma_step != 2 * sb or abs(sf.cb_offset - sf.cr_offset) != sb):
+        raise bad(f"contradicts pixel_format \"nv12\": interleaved chroma has chroma_step {2 * sb} and Cb, Cr offsets {sb} apart")
+    if pf.layout == "i420" and sf.chroma_step != sb:
+        raise bad(f"contradicts pixel_format \"i420\": planar chroma has chroma_step {sb}")
+    if sf.frame_bytes_min > int(frame_bytes):
+        raise bad(f"a plane ends at byte {sf.frame_bytes_min}, beyond the frame's {frame_bytes} bytes")
+    return sf
 
 
 def _box(x: float) -> float:
@@ -262,29 +375,53 @@ def _frame_step(who: str, frame_step) -> int:
     return d
 
 
+def _surface_frames(who: str, frames: torch.Tensor, pf: PixelFormat, surface) -> Tuple[int, Surface]:
+    """(F, the resolved Surface) of uint8 (F, frame_bytes) frames on the GPU."""
+    require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 2:
+        raise HipExtensionError(f"{who} with surface= wants uint8 (F, frame_bytes) frames, got {frames.dtype} {tuple(frames.shape)}")
+    return frames.shape[0], resolve_surface(surface, pf, frames.shape[1])
+
+
+def _surface_args(sf: Surface, pf: PixelFormat) -> tuple:
+    """The tail of both surface entry points: bits, shift, the geometry, the coefficients."""
+    return (sf.bits, sf.shift, sf.y_offset, sf.y_pitch, sf.cb_offset, sf.cr_offset, sf.chroma_pitch, sf.chroma_step) + yuv_coefficients(pf, sf.bits)
+
+
 def yuv420_to_rgb_u8(frames: torch.Tensor, pixel_format, out: Optional[torch.Tensor] = None,
-                     frame_step: Optional[int] = None) -> torch.Tensor:
+                     frame_step: Optional[int] = None, surface: Optional[Surface] = None) -> torch.Tensor:
     """uint8 (F, 3H/2, W) 4:2:0 frames on the GPU (NV12 or I420, see resolve_pixel_format) -> packed RGB (F', H, W, 3), one
     launch on the current stream: the integer conversion of `yuv_coefficients` with nearest chroma (pixel (y, x) uses chroma
     sample (y >> 1, x >> 1)).  `frame_step` d: source frames 0, d, 2 d, ... only, F' = ceil(F / d).  `out` as in resize_u8.
-    Not ffmpeg swscale's bytes (the module docstring): the contract is the formula."""
+    Not ffmpeg swscale's bytes (the module docstring): the contract is the formula.
+    `surface` (a Surface; default None = the compact frames above): `frames` are uint8 (F, frame_bytes), each frame laid out as
+    the surface says and read in place -- pitch, offsets, chroma order and 10-bit samples included (advhip_yuv420_surface_to_rgb_u8)."""
     pf = resolve_pixel_format(pixel_format)
     if pf is None:
         raise ValueError("yuv420_to_rgb_u8: pixel_format None is packed RGB, there is nothing to convert")
     d = _frame_step("yuv420_to_rgb_u8", frame_step)
-    F_src, H, W = _yuv_frames("yuv420_to_rgb_u8", frames, pf)
+    if surface is None:
+        F_src, H, W = _yuv_frames("yuv420_to_rgb_u8", frames, pf)
+    else:
+        F_src, sf = _surface_frames("yuv420_to_rgb_u8", frames, pf, surface)
+        H, W = sf.height, sf.width
     F = -(-F_src // d)
     if out is None:
         out = torch.empty((F, H, W, 3), device=frames.device, dtype=torch.uint8)
     else:
         _check_out("yuv420_to_rgb_u8", frames, out, (F, H, W, 3))
-    check(_lib.load().advhip_yuv420_to_rgb_u8(ptr(frames), ptr(out), F_src, d, H, W, LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
-          "yuv420_to_rgb_u8")
+    if surface is None:
+        check(_lib.load().advhip_yuv420_to_rgb_u8(ptr(frames), ptr(out), F_src, d, H, W, LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
+              "yuv420_to_rgb_u8")
+    else:
+        check(_lib.load().advhip_yuv420_surface_to_rgb_u8(ptr(frames), ptr(out), F_src, d, frames.shape[1], H, W, *_surface_args(sf, pf),
+                                                          stream(frames)), "yuv420_to_rgb_u8")
     return out
 
 
 def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, resample: Union[int, str] = "bilinear",
-              out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None, pixel_format=None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None, pixel_format=None,
+              surface: Optional[Surface] = None) -> torch.Tensor:
     """uint8 (F, H, W, 3) frames on the GPU -> (F, OH, OW, 3), what `GroupResize(size, resample)` gives frame by frame (PIL
     `Image.resize`, bit for bit), on the current stream with no host synchronisation.  `out` places the result in a
     caller-owned contiguous (F, OH, OW, 3) uint8 tensor (e.g. a view of a larger buffer).  Without `out`, frames already at
@@ -294,11 +431,15 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     the sampled frames only).  Frames already at the output size come back as the view frames[::d] (without `out`).
     `pixel_format` (resolve_pixel_format; default None = packed RGB): `frames` are 4:2:0 frames (F, 3H/2, W) and the result is
     resize_u8(yuv420_to_rgb_u8(frames, pixel_format), ...) byte for byte without the full-size RGB frames: the horizontal pass
-    converts each tap's pixel as it reads it.  Frames already at the output size come back converted."""
+    converts each tap's pixel as it reads it.  Frames already at the output size come back converted.
+    `surface` (with `pixel_format`; default None = the compact frames): `frames` are uint8 (F, frame_bytes) decoder surfaces, as
+    in yuv420_to_rgb_u8, and the result is again resize_u8(yuv420_to_rgb_u8(frames, pixel_format, surface=surface), ...)."""
     d = _frame_step("resize_u8", frame_step)
     pf = resolve_pixel_format(pixel_format)
     if pf is not None:
-        return _resize_yuv420_u8(frames, size, resample, out, d, pf)
+        return _resize_yuv420_u8(frames, size, resample, out, d, pf, surface)
+    if surface is not None:
+        raise ValueError("resize_u8: surface= describes 4:2:0 frames and needs a pixel_format")
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise HipExtensionError(f"resize_u8 wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
@@ -330,9 +471,14 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     return out
 
 
-def _resize_yuv420_u8(frames: torch.Tensor, size, resample, out: Optional[torch.Tensor], d: int, pf: PixelFormat) -> torch.Tensor:
-    """resize_u8 of 4:2:0 frames (advhip_resize_yuv420_u8)."""
-    F_src, H, W = _yuv_frames("resize_u8", frames, pf)
+def _resize_yuv420_u8(frames: torch.Tensor, size, resample, out: Optional[torch.Tensor], d: int, pf: PixelFormat,
+                      surface: Optional[Surface] = None) -> torch.Tensor:
+    """resize_u8 of 4:2:0 frames (advhip_resize_yuv420_u8; of surfaces, advhip_resize_yuv420_surface_u8)."""
+    if surface is None:
+        F_src, H, W = _yuv_frames("resize_u8", frames, pf)
+    else:
+        F_src, sf = _surface_frames("resize_u8", frames, pf, surface)
+        H, W = sf.height, sf.width
     F = -(-F_src // d)
     name = filter_name(resample)
     oh, ow = output_size(H, W, size)
@@ -345,9 +491,13 @@ def _resize_yuv420_u8(frames: torch.Tensor, size, resample, out: Optional[torch.
     ws = None
     if p.vertical:  # the horizontal pass's rows, or (a vertical-only resize) the converted frames
         ws = torch.empty((F * p.rows * ow * 3 if p.horizontal else F * H * W * 3,), device=frames.device, dtype=torch.uint8)
-    check(_lib.load().advhip_resize_yuv420_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, 3, oh, ow,
-                                              ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
-                                              ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows,
-                                              LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
-          "resize_u8")
+    resize_args = (3, oh, ow, ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1], ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows)
+    if surface is None:
+        check(_lib.load().advhip_resize_yuv420_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, *resize_args,
+                                                  LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
+              "resize_u8")
+    else:
+        check(_lib.load().advhip_resize_yuv420_surface_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, frames.shape[1], H, W, *resize_args,
+                                                          *_surface_args(sf, pf), stream(frames)),
+              "resize_u8")
     return out

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """I3D feature extraction entry point (the reference's extract_features.py surface).
 
-    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET] [--normalize SPEC] [--pixel-format FMT]]
+    python extract_features.py --outdir OUT [--videos N] [--weights path.pt | --synthetic-weights] [--frame-size HxW [--clip-stride N] [--frame-step N] [--crops SET] [--normalize SPEC] [--pixel-format FMT [--surface GEOMETRY]]]
 
 The reference decodes the UCF-Crime videos with decord + torchvision TenCrop (not available in
 the MI355X image, and outside the hot path).  Here the video source is synthetic TenCrop'd clip
@@ -20,6 +20,9 @@ every `--clip-stride` frames (1 .. 16 x N, default the span), files are `<name>_
 files carry the normalisation last in their name (`<name>_i3d..._npix-<hash>.npy`).
 `--pixel-format nv12|i420[:bt601|bt709][:limited|full]` (with `--frame-size`, both sizes even) makes the source the decoder's own
 8-bit 4:2:0 frames, uint8 (F, 3H/2, W): the colour conversion runs on the device inside the resize (file names do not change).
+`--surface pitch=2048,rows=1088,bits=10,shift=6,order=vu` (with `--pixel-format`; any subset of the keys, also `chroma_pitch=` and
+`y_offset=`) makes the source a decoder's surfaces, uint8 (F, frame_bytes) with that row pitch, allocated rows, sample depth and
+chroma order (`resize.surface`), read in place on the device.
 """
 import argparse
 import os
@@ -41,12 +44,15 @@ def synthetic_sources(n_videos: int, seed: int = 0):
         yield name, (lambda n=n_clips, s=seed + i: torch.randn((n, 10, 16, 3, 224, 224), generator=torch.Generator().manual_seed(s)))
 
 
-def synthetic_frame_sources(n_videos: int, frame_size, seed: int = 0, pixel_format=None):
+def synthetic_frame_sources(n_videos: int, frame_size, seed: int = 0, pixel_format=None, surface=None):
     """(name, n_frames, read_frames) of synthetic decoded uint8 (F, H, W, 3) videos of 2-5 clips plus a few frames; with a
-    `pixel_format` the frames are seeded random 4:2:0 ones, (F, 3H/2, W)."""
+    `pixel_format` the frames are seeded random 4:2:0 ones, (F, 3H/2, W); with a `surface` (a resize.Surface) seeded random
+    surfaces, (F, surface.frame_bytes_min), with noise in the padding and in the bits a 10-bit sample ignores."""
     g = torch.Generator().manual_seed(seed)
     h, w = frame_size
     shape = (h, w, 3) if pixel_format is None else (h // 2 * 3, w)
+    if surface is not None:
+        shape = (surface.frame_bytes_min,)
     for i in range(n_videos):
         n_frames = int(torch.randint(2 * 16, 6 * 16, (1,), generator=g))
         name = ("Normal_Videos_%03d_x264" if i % 2 == 0 else "Abuse%03d_x264") % i
@@ -111,9 +117,34 @@ def parse_pixel_format(text: str):
         raise argparse.ArgumentTypeError(f"--pixel-format {text!r}: {e}")
 
 
+_SURFACE_KEYS = ("pitch", "rows", "chroma_pitch", "bits", "shift", "y_offset")
+
+
+def parse_surface(text: str):
+    """--surface: comma-separated KEY=VALUE with the keys pitch, rows, chroma_pitch, bits, shift, y_offset (integers) and order
+    (uv | vu) -> the keyword arguments of resize.surface."""
+    kw = {}
+    try:
+        for item in text.split(","):
+            key, sep, value = item.partition("=")
+            if not sep or key in kw or (key == "order" and "chroma_order" in kw):
+                raise ValueError(f"{item!r} is not KEY=VALUE, or repeats a key")
+            if key == "order":
+                if value not in ("uv", "vu"):
+                    raise ValueError(f"order {value!r} is neither uv nor vu")
+                kw["chroma_order"] = value
+            elif key in _SURFACE_KEYS:
+                kw[key] = int(value)
+            else:
+                raise ValueError(f"unknown key {key!r} (pitch, rows, chroma_pitch, bits, shift, y_offset, order)")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(f"--surface {text!r}: {e}")
+    return kw
+
+
 def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthetic_weights: bool = False,
          model_name: str = "i3d_8x8_r50", frame_size=None, clip_stride: int = None, crops=None, frame_step: int = None,
-         normalize=None, pixel_format=None):
+         normalize=None, pixel_format=None, surface=None):
     """`model_name` defaults to the reference's (extract_features.py:34,46); that variant is parity-unpinned here (a warning
     says so) -- `--model-name tushar-n-baseline` is the I3Res50 pinned against the reference."""
     if clip_stride is not None and frame_size is None:
@@ -133,6 +164,13 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
         raise ValueError("--pixel-format needs --frame-size: the clip-tensor source holds no decoded frames")
     if pixel_format is not None and (frame_size[0] % 2 or frame_size[1] % 2):
         raise ValueError(f"--pixel-format needs an even frame size (4:2:0 chroma), got {frame_size[0]}x{frame_size[1]}")
+    if surface is not None:
+        if pixel_format is None:
+            raise ValueError("--surface needs --pixel-format: the geometry describes 4:2:0 frames")
+        from anomaly_detection_on_video_amd import resize as resize_mod
+
+        surface = resize_mod.surface(pixel_format, *frame_size, **surface)
+        surface = resize_mod.resolve_surface(surface, pixel_format, surface.frame_bytes_min)
     if synthetic_weights:
         os.environ["ADV_I3D_SYNTHETIC"] = "1"
     model, _device = load_feature_extraction_model(model_name, state_dict_path=weights, check_model_size=True)
@@ -140,8 +178,9 @@ def main(outdir: str = "ucf_crime", videos: int = 4, weights: str = None, synthe
     if frame_size is None:
         extract(synthetic_sources(videos), model, outpath)
     else:  # decoded frames: GroupResize(256) + TenCrop + normalise on the device
-        extract_frames(synthetic_frame_sources(videos, frame_size, pixel_format=pixel_format), model, outpath, resize=256, clip_stride=clip_stride,
-                       crops=crops, frame_step=frame_step, normalize=normalize, pixel_format=pixel_format)
+        extract_frames(synthetic_frame_sources(videos, frame_size, pixel_format=pixel_format, surface=surface), model, outpath, resize=256,
+                       clip_stride=clip_stride, crops=crops, frame_step=frame_step, normalize=normalize, pixel_format=pixel_format,
+                       **({} if surface is None else {"surface": surface}))
     seg_length = 32
     segment(outpath, os.path.join(outdir, f"segment_features_{seg_length}"), seg_length)
 
@@ -168,6 +207,9 @@ if __name__ == "__main__":
     ap.add_argument("--pixel-format", type=parse_pixel_format, default=None, metavar="FMT",
                     help="with --frame-size: the frames are 8-bit 4:2:0, nv12 or i420 (yuv420p), optionally :bt601 (default) or :bt709 and "
                          ":limited (default) or :full; converted on the device (default: packed RGB)")
+    ap.add_argument("--surface", type=parse_surface, default=None, metavar="GEOMETRY",
+                    help="with --pixel-format: the frames are decoder surfaces, KEY=VALUE pairs such as pitch=2048,rows=1088,bits=10,shift=6,order=vu "
+                         "(also chroma_pitch=, y_offset=); default: compact 8-bit frames")
     a = ap.parse_args()
     if a.clip_stride is not None and a.frame_size is None:
         ap.error("--clip-stride needs --frame-size: the clip-tensor source has no frames to stride over")
@@ -185,5 +227,7 @@ if __name__ == "__main__":
         ap.error("--pixel-format needs --frame-size: the clip-tensor source holds no decoded frames")
     if a.pixel_format is not None and (a.frame_size[0] % 2 or a.frame_size[1] % 2):
         ap.error(f"--pixel-format needs an even frame size (4:2:0 chroma), got {a.frame_size[0]}x{a.frame_size[1]}")
+    if a.surface is not None and a.pixel_format is None:
+        ap.error("--surface needs --pixel-format: the geometry describes 4:2:0 frames")
     main(a.outdir, a.videos, a.weights, a.synthetic_weights, a.model_name, a.frame_size, a.clip_stride, a.crops, a.frame_step, a.normalize,
-         a.pixel_format)
+         a.pixel_format, a.surface)

@@ -825,7 +825,8 @@ int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_t* ws, int6
                              int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                              const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream);
 
-/* --- decoded frames as the decoder has them: Y'CbCr 4:2:0, 8 bit -----------------------------------------------------------
+/* --- decoded frames as the decoder has them: Y'CbCr 4:2:0 --------------------------------------------------------------------
+ * Compact 8-bit frames first (surfaces with a row pitch, plane offsets, NV21 / YV12 and 10-bit samples follow below).
  * A frame is uint8 (3H/2, W), H and W even, row pitch == W: rows [0, H) are Y; NV12 then holds H/2 rows of interleaved (Cb, Cr)
  * pairs, I420 (yuv420p) the (H/2, W/2) Cb plane followed by the (H/2, W/2) Cr plane.  Chroma is nearest: pixel (y, x) uses sample
  * (y >> 1, x >> 1).  The conversion is integer, in int32, with 2^16 fixed-point coefficients passed by value (the library holds
@@ -853,6 +854,42 @@ int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64
                             int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                             const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, int32_t layout,
                             int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
+
+/* --- decoder surfaces: 4:2:0 frames described by byte geometry and sample depth ---------------------------------------------
+ * What a hardware decoder or an AVFrame hands over, read in place.  A source frame is a run of frame_pitch bytes (source frame f
+ * starts at byte f * frame_pitch of src); inside it, with every offset, pitch and step in bytes from the frame's first byte:
+ *   luma (y, x)            at y_offset + y * y_pitch + x * sb
+ *   Cb of chroma (r, c)    at cb_offset + r * chroma_pitch + c * chroma_step,   Cr the same from cr_offset
+ * where sb is the sample size: 1 at bits = 8; 2 at bits = 10, a little-endian 16-bit word whose value is (word >> shift) & 1023
+ * (shift 6: P010; shift 0: yuv420p10le; the other bits are ignored).  Pixel (y, x) uses chroma sample (y >> 1, x >> 1).
+ * The layouts are nothing but these numbers:  NV12 chroma_step = 2 sb, cr_offset = cb_offset + sb;  NV21 cb_offset = cr_offset +
+ * sb;  I420 / YV12 chroma_step = sb with the two planes in either order.
+ * Rules (each refused by name before any launch): H and W even and >= 2; bits 8 or 10; shift in [0, 6] and 0 at 8 bits;
+ * chroma_step sb or 2 sb, and with 2 sb the two chroma offsets exactly sb apart; y_pitch >= W sb; chroma_pitch >= (W / 2)
+ * chroma_step; no negative offset; every plane ends at or before frame_pitch; at 10 bits src, frame_pitch and every offset and
+ * pitch are even.
+ * The conversion at depth b = bits, with S = 8 + b and 2^S fixed-point coefficients passed by value:
+ *   yi = cy (Y - yoff) + 2^(S-1)
+ *   R = clip8((yi + crv (Cr - 2^(b-1))) >> S)
+ *   G = clip8((yi - cgu (Cb - 2^(b-1)) - cgv (Cr - 2^(b-1))) >> S)      (arithmetic shifts)
+ *   B = clip8((yi + cbu (Cb - 2^(b-1))) >> S)
+ * yoff is 16 * 2^(b-8) (limited range) or 0 (full range); the coefficient bounds are those above (every sum is below 2^30).  At
+ * b = 8 this is the formula above, and the compact frame as a surface gives the bytes of the calls above.
+ *
+ * The conversion alone, as advhip_yuv420_to_rgb_u8: one launch.  Where the alignment of src, frame_pitch, the offsets, the
+ * pitches and dst allows it, a lane converts four pixels from one load of four Y samples; otherwise two. */
+int advhip_yuv420_surface_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int64_t frame_pitch, int32_t H,
+                                    int32_t W, int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset,
+                                    int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
+                                    int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
+/* advhip_resize_yuv420_u8 on surfaces: dst is byte for byte advhip_resize_u8_sampled of what the call above converts.  ws, the
+ * tables and the launches are as there. */
+int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int64_t frame_pitch,
+                                    int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef,
+                                    int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0,
+                                    int32_t rows, int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset,
+                                    int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
+                                    int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
 
 #ifdef __cplusplus
 }
