@@ -219,6 +219,8 @@ SIGNATURES = {
     "advhip_mgfn_loss_bwd_f32": (C.c_int, [_P] * 14 + [_I] * 5 + [_P]),
     "advhip_segment_features_f32": (C.c_int, [_P, _P, _I, _I, _I, _I, _P]),
     "advhip_add_magnitude_f32": (C.c_int, [_P, _P, _L, _I, _P]),
+    "advhip_add_magnitude_np_f32": (C.c_int, [_P, _P, _L, _I, _I, _I, _P]),
+    "advhip_add_magnitude_np_leaves": (C.c_int, [_I, C.POINTER(_I), C.POINTER(_I)]),
     "advhip_tencrop_normalize_planes_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _L, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_u8": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "advhip_tencrop_normalize_planes_u8_strided": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, C.c_float, C.c_float, _P]),

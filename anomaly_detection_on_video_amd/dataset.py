@@ -84,10 +84,191 @@ def _build_feature_dataset(filepath: str, mode: str, dynamic_load: bool, ground_
     return out
 
 
+# ---------------------------------------------------------------------------------- device-resident datasets
+DEFAULT_RESIDENT_MAX_BYTES = 32 << 30  # a guard against a corpus that cannot fit, not a tuned value (UCF-Crime: about 10 GB)
+
+
+class ResidentFeatureDataset:
+    """A feature zip held in device memory, every item as `FeatureDataset.__getitem__` returns it (magnitude channel appended,
+    bit for bit: mil_ops.add_magnitude_np), so that a training step's input work is a device-to-device copy of a slice.
+
+    Train mode (one per class, `name` = "normal" / "abnormal"): `features` (N, ncrops, seg, C+1) and `anomaly` (N,) on the device;
+    item i = views of row i.  Test mode (`labels` given): `store` is one flat allocation, video i lives at floats
+    [offsets[i], offsets[i+1]) TRANSPOSED, `videos[i]` = (ncrops, T, C+1) -- the layout validation_step's
+    permute(0, 2, 1, 3).contiguous() asks for; item i's feature is the (T, ncrops, C+1) view of it, the label stays on the host."""
+
+    def __init__(self, filenames: List[str], name: str = "", features=None, anomaly=None, store=None, videos=None,
+                 offsets: Optional[List[int]] = None, labels: Optional[List[np.ndarray]] = None):
+        self.filenames, self.name = list(filenames), name
+        self.features, self.anomaly = features, anomaly
+        self.store, self.videos, self.offsets, self.labels = store, videos, offsets, labels
+
+    @property
+    def nbytes(self) -> int:
+        t = self.features if self.features is not None else self.store
+        return int(t.numel() * t.element_size()) + (0 if self.anomaly is None else int(self.anomaly.numel() * self.anomaly.element_size()))
+
+    def __len__(self) -> int:
+        return len(self.filenames)
+
+    def get_filename(self, idx: int) -> str:
+        return self.filenames[idx]
+
+    def __getitem__(self, idx: int):
+        if not -len(self) <= idx < len(self):
+            raise IndexError(idx)
+        if self.videos is None:
+            return {"feature": self.features[idx], "anomaly": self.anomaly[idx]}
+        return {"feature": self.videos[idx].permute(1, 0, 2),
+                "anomaly": np.array(0.0 if "Normal" in self.filenames[idx] else 1.0, dtype=np.float32), "label": self.labels[idx]}
+
+
+class ResidentBatches:
+    """DataLoader(ds, batch_size, shuffle=False, drop_last=True) over a resident train dataset: len = N // batch_size, batch i =
+    {"feature": ds.features[i*B:(i+1)*B], "anomaly": ds.anomaly[i*B:(i+1)*B]} as views (nothing is copied or launched)."""
+
+    def __init__(self, dataset, batch_size: int):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size {batch_size} must be at least 1")
+        if len(dataset) < self.batch_size:
+            raise ValueError(f"the {getattr(dataset, 'name', '') or 'train'} class has {len(dataset)} videos, fewer than batch_size "
+                             f"{self.batch_size}: drop_last would leave no batch")
+
+    def __len__(self) -> int:
+        return len(self.dataset) // self.batch_size
+
+    def __iter__(self):
+        b = self.batch_size
+        for i in range(len(self)):
+            yield {"feature": self.dataset.features[i * b:(i + 1) * b], "anomaly": self.dataset.anomaly[i * b:(i + 1) * b]}
+
+
+class ResidentItems:
+    """DataLoader(ds, batch_size=1, shuffle=False) over a resident test dataset: every item with a leading 1, the feature a view
+    of the store."""
+
+    def __init__(self, dataset):
+        self.dataset = dataset
+
+    def __len__(self) -> int:
+        return len(self.dataset)
+
+    def __iter__(self):
+        import torch
+
+        for i in range(len(self.dataset)):
+            item = self.dataset[i]
+            yield {"feature": item["feature"].unsqueeze(0), "anomaly": torch.from_numpy(item["anomaly"].reshape(1)),
+                   "label": torch.from_numpy(item["label"]).unsqueeze(0)}
+
+
+def _npy_header(fp):
+    """(shape, dtype) of an .npy stream, which is left at the first data byte."""
+    from numpy.lib import format as npf
+
+    version = npf.read_magic(fp)
+    read = {(1, 0): npf.read_array_header_1_0, (2, 0): npf.read_array_header_2_0}.get(tuple(version))
+    if read is None:
+        raise ValueError(f"unsupported .npy version {version}")
+    shape, fortran, dtype = read(fp)
+    if fortran and len(shape) > 1:
+        raise ValueError("Fortran-ordered array")
+    return tuple(int(d) for d in shape), dtype
+
+
+def _build_resident_dataset(filepath: str, mode: str, ground_truth: Optional[Dict], device, max_bytes: int):
+    import torch
+
+    zipf = zipfile.ZipFile(filepath)
+    members = [m for m in zipf.infolist() if not m.is_dir()]
+    names = [m.filename.split("/")[-1] for m in members]
+    # pass 1, headers only: every shape is known, and the byte total checked, before anything is allocated
+    shapes = []
+    for m, name in zip(members, names):
+        with zipf.open(m) as fp:
+            try:
+                shape, dtype = _npy_header(fp)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e}") from e
+        if dtype != np.float32 or len(shape) != 3 or 0 in shape:
+            raise ValueError(f"{name}: a resident dataset holds non-empty float32 (a, b, C) features, got {dtype} {shape}")
+        shapes.append(shape)
+    if not members:
+        raise ValueError(f"{filepath}: no features")
+    if mode == "train":
+        for name, shape in zip(names, shapes):
+            if shape != shapes[0]:
+                raise ValueError(f"{name} has shape {shape}, {names[0]} has {shapes[0]}: a resident train store needs one shape")
+    elif len({s[1:] for s in shapes}) != 1:
+        bad = next(i for i, s in enumerate(shapes) if s[1:] != shapes[0][1:])
+        raise ValueError(f"{names[bad]} has shape {shapes[bad]}, {names[0]} has {shapes[0]}: crops and channels must agree")
+    out_floats = [s[0] * s[1] * (s[2] + 1) for s in shapes]
+    need = 4 * sum(out_floats) + (4 * len(members) if mode == "train" else 0)
+    if need > max_bytes:
+        raise ValueError(f"{filepath}: a resident {mode} dataset needs {need} bytes of device memory, above resident_max_bytes = {max_bytes}")
+    if mode == "test" and ground_truth is None:
+        from huggingface_hub import hf_hub_download
+
+        with open(hf_hub_download(repo_id=DEFAULT_FEATURE_HUB, filename="ground_truth.json", repo_type="dataset")) as f:
+            ground_truth = json.load(f)
+
+    from . import mil_ops
+
+    device = torch.device(device)
+    if device.type != "cuda":
+        from ._lib import HipExtensionError
+
+        raise HipExtensionError(f"a resident dataset lives in GPU memory; got device '{device}' (there is no CPU fallback)")
+    # pass 2: zip member -> pinned staging -> device staging (a, b, C) -> magnitude kernel -> its slot of the store, all on the
+    # current stream.  The device staging buffer is reused in stream order; the two pinned buffers alternate, each refilled only
+    # once the copy that last read it has completed (its event).  One synchronisation at the end.
+    in_floats = max(s[0] * s[1] * s[2] for s in shapes)
+    pinned = [torch.empty(in_floats, dtype=torch.float32).pin_memory() for _ in range(2)]
+    done = [None, None]
+    stage = torch.empty(in_floats, dtype=torch.float32, device=device)
+    if mode == "train":
+        a, b, c = shapes[0]
+        order = [i for i, n in enumerate(names) if "Normal" in n] + [i for i, n in enumerate(names) if "Normal" not in n]
+        n_normal = sum("Normal" in n for n in names)
+        store = torch.empty((len(members), a, b, c + 1), dtype=torch.float32, device=device)
+        slots = {i: store[k] for k, i in enumerate(order)}
+    else:
+        offsets = [0]
+        for n in out_floats:
+            offsets.append(offsets[-1] + n)
+        store = torch.empty(offsets[-1], dtype=torch.float32, device=device)
+        slots = {i: store[offsets[i]:offsets[i + 1]].view(s[1], s[0], s[2] + 1) for i, s in enumerate(shapes)}
+    for i, (m, shape) in enumerate(zip(members, shapes)):
+        k, n = i % 2, shape[0] * shape[1] * shape[2]
+        if done[k] is not None:
+            done[k].synchronize()
+        with zipf.open(m) as fp:
+            pinned[k].numpy()[:n] = np.load(fp).reshape(-1)
+        stage[:n].copy_(pinned[k][:n], non_blocking=True)
+        done[k] = torch.cuda.Event()
+        done[k].record()
+        mil_ops.add_magnitude_np(stage[:n].view(shape), transpose=mode == "test", out=slots[i])
+    torch.cuda.current_stream(device).synchronize()
+    if mode == "test":
+        labels = []
+        for name in names:
+            key = name if name in ground_truth else name.replace("_i3d.npy", "")
+            labels.append(np.array(ground_truth[key], dtype=np.float32))
+        return ResidentFeatureDataset(names, "test", store=store, videos=[slots[i] for i in range(len(members))], offsets=offsets, labels=labels)
+    anomaly = torch.tensor([0.0] * n_normal + [1.0] * (len(members) - n_normal), dtype=torch.float32, device=device)
+    split = {"normal": slice(0, n_normal), "abnormal": slice(n_normal, len(members))}
+    return {cls: ResidentFeatureDataset([names[i] for i in order[sl]], cls, features=store[sl], anomaly=anomaly[sl]) for cls, sl in split.items()}
+
+
 def build_feature_dataset(mode: str = "train", local_path: Optional[str] = None, filename: Optional[str] = None,
-                          cache_dir: Optional[str] = None, revision: str = "main", dynamic_load: bool = True):
+                          cache_dir: Optional[str] = None, revision: str = "main", dynamic_load: bool = True,
+                          resident=None, resident_max_bytes: int = DEFAULT_RESIDENT_MAX_BYTES):
     """Reference signature (dataset.py:73-95).  With `local_path`+`filename` the zip (and, in test
-    mode, `<local_path>/ground_truth.json`) is read locally; otherwise it is fetched from the hub."""
+    mode, `<local_path>/ground_truth.json`) is read locally; otherwise it is fetched from the hub.
+    `resident` (a GPU device; default None = the host datasets above): the whole zip is loaded once into device memory, magnitude
+    channel included, and `ResidentFeatureDataset`s are returned (`dynamic_load` does not apply).  More than `resident_max_bytes`
+    of device memory is refused before anything is allocated."""
     assert mode in ("train", "test")
     assert sum([local_path is None, filename is None]) != 1
     gt = None
@@ -102,6 +283,8 @@ def build_feature_dataset(mode: str = "train", local_path: Optional[str] = None,
         if mode == "test" and os.path.exists(gt_path):
             with open(gt_path) as f:
                 gt = json.load(f)
+    if resident is not None:
+        return _build_resident_dataset(filepath, mode, gt, resident, int(resident_max_bytes))
     return _build_feature_dataset(filepath, mode, dynamic_load, gt)
 
 

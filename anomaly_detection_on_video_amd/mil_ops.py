@@ -234,6 +234,38 @@ def add_magnitude(feats: torch.Tensor) -> torch.Tensor:
     return out
 
 
+ADD_MAGNITUDE_NP_MAX_C = 8192  # numpy reduces in chunks of 8192 elements: the order of its sum changes above that
+
+
+def add_magnitude_np(feats: torch.Tensor, transpose: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(a, b, C) fp32 -> (a, b, C+1), or (b, a, C+1) with `transpose`: FeatureDataset.add_magnitude on the device with numpy's
+    bits -- out[..., C] equals np.linalg.norm(feats, axis=2) bit for bit (`add_magnitude` agrees with it to 1e-6), out[..., :C]
+    is the input.  `out`: a contiguous fp32 tensor of that shape on the same device to write into (a slot of a resident store).
+    C <= 8192."""
+    require_gpu(feats, out)
+    if feats.dtype != torch.float32 or feats.dim() != 3:
+        raise ValueError(f"add_magnitude_np: expected fp32 (a, b, C), got {feats.dtype} {tuple(feats.shape)}")
+    a, b, C = feats.shape
+    shape = (b, a, C + 1) if transpose else (a, b, C + 1)
+    if out is None:
+        out = torch.empty(shape, device=feats.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != feats.device:
+        raise ValueError(f"add_magnitude_np: out must be fp32 {shape} on {feats.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    check(_lib.load().advhip_add_magnitude_np_f32(ptr(feats), ptr(out), a, b, C, int(bool(transpose)), stream()), "add_magnitude_np")
+    return out
+
+
+def add_magnitude_np_leaves(C: int):
+    """[(start, len, adds)]: the blocks of at most 128 elements `add_magnitude_np` sums a row of C by, in order, and after how
+    many of them a pending partial sum is added (host arithmetic only; nothing is launched)."""
+    import ctypes
+
+    buf = (ctypes.c_int32 * (3 * 128))()
+    n = ctypes.c_int32()
+    check(_lib.load().advhip_add_magnitude_np_leaves(int(C), buf, ctypes.byref(n)), "add_magnitude_np_leaves")
+    return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n.value)]
+
+
 PIXEL_MEAN, PIXEL_STD = 114.75, 57.375  # GroupNormalize constants, src/dataset.py:180-181
 
 

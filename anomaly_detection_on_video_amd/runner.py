@@ -20,7 +20,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import metrics, mgfn_ops
-from .dataset import build_feature_dataset
+from .dataset import ResidentBatches, ResidentFeatureDataset, ResidentItems, build_feature_dataset
 
 
 class VideoAnomalyDetectionRunner:
@@ -94,16 +94,30 @@ class VideoAnomalyDetectionRunner:
         d = self.hparams.data
         kw = dict(revision=d.get("revision", "main"), cache_dir=d.get("cache_dir"), dynamic_load=bool(d.get("dynamic_load", False)))
         local = d.get("local_path")
+        if bool(d.get("resident", False)):
+            # both zips into device memory once, magnitude channel included (dataset.ResidentFeatureDataset): the loaders below
+            # then hand out views of it.  One budget for the two of them.
+            budget = int(float(d.get("resident_max_gib", 32)) * (1 << 30))
+            self.train_dataset = build_feature_dataset(mode="train", local_path=local, filename="train.zip" if local else None,
+                                                       resident=self.device, resident_max_bytes=budget, **kw)
+            budget -= sum(ds.nbytes for ds in self.train_dataset.values())
+            self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None,
+                                                       resident=self.device, resident_max_bytes=budget, **kw)
+            return
         self.train_dataset = build_feature_dataset(mode="train", local_path=local, filename="train.zip" if local else None, **kw)
         self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None, **kw)
 
     # runner.py:108-124 -- two loaders zipped, shuffle=False, drop_last=True
     def train_dataloader(self) -> Tuple[DataLoader, DataLoader]:
         d = self.hparams.data
+        if isinstance(self.train_dataset["normal"], ResidentFeatureDataset):
+            return tuple(ResidentBatches(self.train_dataset[cls], int(d["batch_size"])) for cls in ("normal", "abnormal"))
         mk = lambda ds: DataLoader(ds, batch_size=int(d["batch_size"]), shuffle=False, drop_last=True, num_workers=int(d.get("num_workers", 0)))
         return mk(self.train_dataset["normal"]), mk(self.train_dataset["abnormal"])
 
     def val_dataloader(self) -> DataLoader:
+        if isinstance(self.valid_dataset, ResidentFeatureDataset):
+            return ResidentItems(self.valid_dataset)
         return DataLoader(self.valid_dataset, batch_size=1, shuffle=False)
 
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:

@@ -718,6 +718,27 @@ int advhip_segment_features_f32(const float* feats, float* out, int32_t n_clips,
  * = L2 norm of the row. */
 int advhip_add_magnitude_f32(const float* feats, float* out, int64_t rows, int32_t C, void* stream);
 
+/* The same channel with numpy's bits: feats (a, b, C) contiguous -> out (a, b, C+1), or (b, a, C+1) when `transpose` is 1 (a
+ * test video (T, ncrops, C) stored the way the scorer reads it).  out[..., :C] is the input bit for bit; out[..., C] equals
+ * np.linalg.norm(feats, axis=2) of the float32 array BIT FOR BIT (advhip_add_magnitude_f32 sums in another order and agrees
+ * to 1e-6).  numpy's arithmetic, every operation rounded to fp32 on its own (no FMA):
+ *   s[i] = x[i] * x[i]
+ *   sum  = 0.0f + pw(s, C), where pw(a, n) is
+ *            n < 8         : 0.0f + a[0] + a[1] + ... in order
+ *            8 <= n <= 128 : r[j] = a[j] (j < 8); for i = 8, 16, ... < n - n % 8: r[j] += a[i + j];
+ *                            res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)); then res += a[i] for the last n % 8
+ *            n > 128       : n2 = n / 2; n2 -= n2 % 8; pw(a, n2) + pw(a + n2, n - n2)
+ *   out  = sqrt(sum), correctly rounded
+ * C <= 8192: numpy reduces in chunks of 8192 elements and the order changes above that; a larger C is refused
+ * (ADVHIP_EINVAL, advhip_last_error), as are null pointers, before anything is launched. */
+int advhip_add_magnitude_np_f32(const float* feats, float* out, int64_t a, int32_t b, int32_t C,
+                                int32_t transpose, void* stream);
+
+/* Host only: the blocks of at most 128 elements the recursion above ends in for a row of C (1 <= C <= 8192), in order, as
+ * (start, len, adds) int32 triples into `leaves` (room for 128 triples); `adds` = how many pending partial sums are added once
+ * that block's sum is known (the tree of `+` walked with a stack).  This is the table the kernel sums by. */
+int advhip_add_magnitude_np_leaves(int32_t C, int32_t* leaves, int32_t* n_leaves);
+
 /* Clip pre-processing on the device: uint8 frames (N, T, C, H, W) -> fp32 (N, C, T, H, W) with
  * y = (x - mean) / std.  Replaces PILToTensor().float() + GroupNormalize(114.75, 57.375)
  * (src/dataset.py:175-183) and the permute of extract_features.py:83, so that only uint8 pixels
