@@ -324,14 +324,14 @@ def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: 
 
 
 def frame_scores(scores: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
-                 n_frames: Optional[int] = None, frame_step: Optional[int] = None) -> torch.Tensor:
+                 n_frames: Optional[int] = None, frame_step: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Per-window scores (n,) -> per-frame scores (n_frames,) on the device.  Window w covers frames [w * clip_stride,
     w * clip_stride + frames_per_clip); a frame's score is the mean of the scores of the windows covering it (fp32, ascending
     window order, one division by the count).  n_frames defaults to (n - 1) * clip_stride + frames_per_clip; clip_stride =
     frames_per_clip gives np.repeat(scores, frames_per_clip) (src/runner.py:66-76) bit for bit.
     `frame_step` d: the windows are spans of frames_per_clip * d frames -- window w covers [w * clip_stride, w * clip_stride +
     frames_per_clip * d), clip_stride defaults to the span: the same kernel at that clip length; the default stride gives
-    np.repeat(scores, frames_per_clip * d)."""
+    np.repeat(scores, frames_per_clip * d).  `out`: a contiguous fp32 (n_frames,) tensor on the same device to write into."""
     d = resolve_frame_step(frame_step)
     s = resolve_clip_stride(frames_per_clip, clip_stride, d)
     frames_per_clip = frames_per_clip * d
@@ -344,6 +344,56 @@ def frame_scores(scores: torch.Tensor, frames_per_clip: int = 16, clip_stride: O
     nf = covered if n_frames is None else int(n_frames)
     if not 0 < nf <= covered:
         raise ValueError(f"frame_scores: {nf} frames, but {n} windows of {frames_per_clip} at stride {s} cover {covered}")
-    out = torch.empty((nf,), device=scores.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((nf,), device=scores.device, dtype=torch.float32)
+    else:
+        require_gpu(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != (nf,) or out.device != scores.device:
+            raise ValueError(f"frame_scores: out must be fp32 ({nf},) on {scores.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
     check(_lib.load().advhip_frame_scores_f32(ptr(scores), ptr(out), n, frames_per_clip, s, nf, stream()), "frame_scores")
     return out
+
+
+def roc_counts_workspace(m: int, device) -> torch.Tensor:
+    """The scratch buffer `roc_counts` needs for m items (uint8; reusable across calls of that size or smaller)."""
+    nbytes = _lib.load().advhip_roc_counts_ws_bytes(int(m))
+    if nbytes < 0:
+        check(int(nbytes), "roc_counts_ws_bytes")
+    return torch.empty((nbytes,), device=device, dtype=torch.uint8)
+
+
+def roc_counts(scores: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+               workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Items (score fp32, pos int32, neg int32), each standing for pos positive and neg negative frames of that score, ->
+    (thresholds fp32 (G,), tps int64 (G,), fps int64 (G,)) on the device: entry g is the g-th distinct score in descending order
+    with the numbers of positive / negative frames scored at or above it -- what metrics._ranked computes from the expanded
+    frames, integer for integer (metrics.roc_auc_from_counts / pr_auc_from_counts turn them into the two areas).  Equal floats
+    are one entry: -0.0 and +0.0 together (the threshold carries either sign), denormals on their own; an item with pos = neg = 0
+    still makes or joins the entry of its score.  One read-back of four
+    integers is the only synchronisation.  ValueError for NaN / inf scores (with their number), as sklearn refuses them.
+    `workspace`: a buffer from roc_counts_workspace(m >= len(scores), device) to reuse."""
+    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() == 0:
+        raise ValueError(f"roc_counts: scores must be a non-empty fp32 (M,) tensor, got {scores.dtype} {tuple(scores.shape)}")
+    m = scores.shape[0]
+    for name, t in (("pos", pos), ("neg", neg)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (m,):
+            raise ValueError(f"roc_counts: {name} must be int32 ({m},) like the scores, got {t.dtype} {tuple(t.shape)}")
+    if m >= 1 << 31:
+        raise ValueError(f"roc_counts: {m} items, the limit is 2^31 - 1")
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.dim() != 1):
+        raise ValueError(f"roc_counts: workspace must be a uint8 (bytes,) tensor, got {workspace.dtype} {tuple(workspace.shape)}")
+    require_gpu(scores, pos, neg, workspace)
+    lib = _lib.load()
+    if workspace is None:
+        workspace = roc_counts_workspace(m, scores.device)
+    dev = scores.device
+    thresholds = torch.empty((m,), device=dev, dtype=torch.float32)
+    tps = torch.empty((m,), device=dev, dtype=torch.int64)
+    fps = torch.empty((m,), device=dev, dtype=torch.int64)
+    meta = torch.empty((4,), device=dev, dtype=torch.int64)
+    check(lib.advhip_roc_counts(ptr(scores), ptr(pos), ptr(neg), m, ptr(thresholds), ptr(tps), ptr(fps), ptr(meta), ptr(workspace),
+                                workspace.numel(), stream()), "roc_counts")
+    g, bad, _, _ = meta.tolist()  # the one synchronisation
+    if bad:
+        raise ValueError(f"roc_counts: {bad} non-finite scores (NaN or inf) among {m}: the curve is undefined")
+    return thresholds[:g], tps[:g], fps[:g]

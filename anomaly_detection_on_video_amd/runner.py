@@ -28,6 +28,7 @@ class VideoAnomalyDetectionRunner:
         self.model = model
         self.hparams = type("HParams", (), {"optimizer": optimizer, "data": data})()
         self.validation_step_outputs: List[Dict[str, np.ndarray]] = []
+        self.auc_plan: Optional[metrics.FrameAucPlan] = None  # data.device_metrics: the validation metrics' device state (setup)
         self.logged: Dict[str, float] = {}
         self.device = torch.device("cpu")
 
@@ -57,6 +58,11 @@ class VideoAnomalyDetectionRunner:
     def validation_step(self, batch, batch_idx) -> None:
         features = batch["feature"].permute(0, 2, 1, 3).contiguous()
         outputs = self.model(video=features)
+        if self.auc_plan is not None:
+            # data.device_metrics: the scores stay on the device, in the video's slot of the plan (a device-to-device copy on the
+            # current stream; the host is not touched and nothing waits)
+            self.auc_plan.slot(batch_idx).copy_(outputs.scores.detach().reshape(-1), non_blocking=True)
+            return
         self.validation_step_outputs.append({
             "preds": outputs.scores.squeeze(0).squeeze(-1).detach().cpu().numpy(),
             "labels": batch["label"].squeeze(0).cpu().numpy(),
@@ -82,8 +88,11 @@ class VideoAnomalyDetectionRunner:
     # runner.py:62-90 (metrics; the matplotlib/wandb chart is out of scope)
     def on_validation_epoch_end(self) -> Dict[str, float]:
         outs = self.validation_step_outputs
-        rec_auc, pr_auc = metrics.frame_level_auc([o["preds"] for o in outs], [o["labels"] for o in outs],
-                                                  int(self.hparams.data["frames_per_clip"]))
+        if self.auc_plan is not None and not outs:
+            rec_auc, pr_auc = self.auc_plan.compute()  # sort and counts on the device: the pass's one synchronisation
+        else:
+            rec_auc, pr_auc = metrics.frame_level_auc([o["preds"] for o in outs], [o["labels"] for o in outs],
+                                                      int(self.hparams.data["frames_per_clip"]))
         self.log("valid/rec_auc", rec_auc)
         self.log("valid/pr_auc", pr_auc)
         self.validation_step_outputs = []
@@ -94,6 +103,11 @@ class VideoAnomalyDetectionRunner:
         d = self.hparams.data
         kw = dict(revision=d.get("revision", "main"), cache_dir=d.get("cache_dir"), dynamic_load=bool(d.get("dynamic_load", False)))
         local = d.get("local_path")
+        self.auc_plan = None
+        device_metrics = bool(d.get("device_metrics", False))
+        if device_metrics and not bool(d.get("resident", False)):
+            raise ValueError("data.device_metrics=true needs data.resident=true: the validation scores stay on the device only "
+                             "when the test set is served from it")
         if bool(d.get("resident", False)):
             # both zips into device memory once, magnitude channel included (dataset.ResidentFeatureDataset): the loaders below
             # then hand out views of it.  One budget for the two of them.
@@ -103,6 +117,11 @@ class VideoAnomalyDetectionRunner:
             budget -= sum(ds.nbytes for ds in self.train_dataset.values())
             self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None,
                                                        resident=self.device, resident_max_bytes=budget, **kw)
+            # (a subclass with its own validation_step keeps the host metrics, which its outputs feed)
+            if device_metrics and type(self).validation_step is VideoAnomalyDetectionRunner.validation_step:
+                valid = self.valid_dataset
+                self.auc_plan = metrics.FrameAucPlan(valid.labels, [int(v.shape[1]) for v in valid.videos],
+                                                     int(d["frames_per_clip"]), device=self.device)
             return
         self.train_dataset = build_feature_dataset(mode="train", local_path=local, filename="train.zip" if local else None, **kw)
         self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None, **kw)

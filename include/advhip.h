@@ -912,6 +912,25 @@ int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* w
                                     int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
                                     int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
 
+/* Weighted ROC counts: what the frame-level ROC / PR curves of src/runner.py:62-79 are made of, from one item per clip.
+ *   scores fp32 (M,), pos / neg int32 (M,) non-negative weights (the positive / negative frames an item stands for), 1 <= M < 2^31.
+ *   thresholds fp32 (M,), tps / fps int64 (M,), meta int64 (4,) = {G, non-finite scores, sum of pos, sum of neg}.
+ * Entry g < G is the g-th distinct score in descending order: thresholds[g] is that score (a copy of one of the inputs that carry
+ * it), tps[g] / fps[g] the sums of pos / neg over all items whose score is >= it; entries [G, M) are not written.  Two scores
+ * are one entry iff they are equal as floats (np.diff(float64(s)) != 0): -0.0 and +0.0 are one entry (either sign may come
+ * back), denormals are values of their own.  An item with pos = neg = 0 still makes, or joins, the entry of its score.
+ * NaN / +-inf scores are counted into meta[1]; when that is not zero the rest of the output is unspecified (every write stays
+ * inside the arrays).  All sums are int64; every result is an integer or a copied input, the same for every run.
+ * Method: uint32 keys whose ascending order is the floats' descending one, a stable LSD radix sort of (key, item) in four 8-bit
+ * passes (tile histograms, a scan of the (digit, tile) table, a stable scatter), then an int64 scan of (pos, neg, group end)
+ * over the sorted order that writes one entry per group end.  Multi-block scans are reduce / scan of the partials / apply as
+ * separate launches: no workgroup waits on another.  One 32-byte memset and 14 to 36 launches on `stream` (24 at M = 70 000);
+ * nothing synchronises.  workspace: advhip_roc_counts_ws_bytes(M) bytes (ADVHIP_EINVAL for an M outside the range), 8-byte aligned,
+ * scratch only.  Null pointers, M < 1 and a short workspace: ADVHIP_EINVAL before anything is launched. */
+int64_t advhip_roc_counts_ws_bytes(int64_t M);
+int advhip_roc_counts(const float* scores, const int32_t* pos, const int32_t* neg, int64_t M, float* thresholds, int64_t* tps,
+                      int64_t* fps, int64_t* meta, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
