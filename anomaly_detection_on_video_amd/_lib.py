@@ -247,6 +247,13 @@ SIGNATURES = {
     "advhip_roc_counts_ws_bytes": (_L, [_L]),
     # (scores, pos, neg, M, thresholds, tps, fps, meta, workspace, workspace_bytes, stream)
     "advhip_roc_counts": (C.c_int, [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P]),
+    # padded batches of sequences of unequal length (batched validation): row lengths are a device int32 array
+    "advhip_glance_attention_fwd_lens_f32": (C.c_int, [_P, _P, _P, _I, _L, _I, _I, C.c_float, _P]),
+    "advhip_dwconv_t_fwd_lens_f32": (C.c_int, [_P] * 4 + [_I, _I, _L, _I, _I, _P, _L, _P]),
+    "advhip_amp_combine_fwd_lens_f32": (C.c_int, [_P, _P, _P, _L, _P, _P, C.c_float, _P, _I, _L, _I, _P, _P]),
+    "advhip_mask_tail_f32": (C.c_int, [_P, _I, _L, _I, _P, _P]),
+    "advhip_pack_padded_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "advhip_crop_mean_scatter_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

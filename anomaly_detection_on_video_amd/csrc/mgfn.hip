@@ -382,18 +382,25 @@ static bool launch_ln_bwd_v4(const float* dy, const float* x, const float* g, co
 }
 
 // out[c, b, t] = bias[c % H] + sum_j w[c % H][j] * v[c, b, t + j - K/2]   (zero outside [0, T)); one thread per element
-template <int K>
+// LENS: row r of (C, rows, T) ends at row_lens[r] (clamped to T) -- the taps stop there (what lies behind is never read) and the
+// positions behind it are stored as 0.  Without LENS the length is T itself: the same code as before the flag existed.
+template <int K, bool LENS>
 __global__ __launch_bounds__(256) void dwconv_t_fwd_kernel(const float* __restrict__ v, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ out, int H, int T,
-                                                           long long rows_per_c, long long total) {
+                                                           long long rows_per_c, long long total, const int* __restrict__ row_lens) {
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int t = (int)(i % T);
     const int h = (int)((i / (rows_per_c * T)) % H);
+    const int L = LENS ? min(row_lens[(i / T) % rows_per_c], T) : T;
+    if (LENS && t >= L) {
+      out[i] = 0.f;
+      continue;
+    }
     float acc = bias[h];
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const int tt = t + j - K / 2;
-      if (tt >= 0 && tt < T) acc += w[h * K + j] * v[i + j - K / 2];
+      if (tt >= 0 && tt < L) acc += w[h * K + j] * v[i + j - K / 2];
     }
     out[i] = acc;
   }
@@ -1280,23 +1287,37 @@ __device__ __forceinline__ void ga_load_tile_p(float (*dst)[GA_P], const float* 
   }
 }
 
+// LENS (padded batches of sequences of unequal length, inference): sequence b still starts at column b * T but holds only
+// L = row_lens[b] (clamped to T) clips -- L takes T's place in the key loop and in every mask, so nothing behind L is read, a
+// sequence with L = T runs exactly the arithmetic below, and queries in [L, T) are stored as 0 (a workgroup whose tile starts
+// there stores its zeros and leaves).  Without LENS, L is T: the same code as before the flag existed.
+template <bool LENS>
 __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
-                                                                   int inner, int heads, int T, long long N, float scale, int bh0) {
+                                                                   int inner, int heads, int T, long long N, float scale, int bh0,
+                                                                   const int* __restrict__ row_lens) {
   __shared__ __attribute__((aligned(16))) float q[GA_D][GA_P], k[GA_D][GA_P], v[GA_D][GA_P], pT[GA_T][GA_P];  // pT[j][i] = p[i][j]
   __shared__ float alpha_s[GA_T], l_s[GA_T];
   const int bh = bh0 + blockIdx.y, b = bh / heads, h = bh % heads, tid = threadIdx.x;
   const int i_base = blockIdx.x * GA_T;
   const long long col0 = (long long)b * T, row0 = (long long)h * GA_D;
-  ga_load_tile_p(q, qkv, row0, N, col0, i_base, T, tid);
+  const int L = LENS ? min(row_lens[b], T) : T;
+  if (LENS && i_base >= L) {  // (the same for the whole workgroup: nobody waits at a barrier)
+    for (int e = tid; e < GA_D * GA_T; e += 256) {
+      const int d = e / GA_T, t = i_base + e % GA_T;
+      if (t < T) out[(row0 + d) * N + col0 + t] = 0.f;
+    }
+    return;
+  }
+  ga_load_tile_p(q, qkv, row0, N, col0, i_base, L, tid);
   const int i = tid >> 3, j0 = (tid & 7) * 4;   // sim: row i, columns j0 .. j0 + 3
   const int d2 = tid >> 2, i0 = (tid & 3) * 8;  // out: channel d2, queries i0 .. i0 + 7
   float m = GA_NEG, l = 0.f, o[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int jb = 0; jb < T; jb += GA_T) {
+  for (int jb = 0; jb < L; jb += GA_T) {
     __syncthreads();  // (the previous tile's readers of k, v, pT, alpha_s are done; first pass: q is complete)
-    ga_load_tile_p(k, qkv, inner + row0, N, col0, jb, T, tid);
-    ga_load_tile_p(v, qkv, 2ll * inner + row0, N, col0, jb, T, tid);
+    ga_load_tile_p(k, qkv, inner + row0, N, col0, jb, L, tid);
+    ga_load_tile_p(v, qkv, 2ll * inner + row0, N, col0, jb, L, tid);
     __syncthreads();
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     for (int d = 0; d < GA_D; ++d) {
@@ -1307,7 +1328,7 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
     float mx = GA_NEG;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      s[e] = (jb + j0 + e < T) ? s[e] * scale : GA_NEG;
+      s[e] = (jb + j0 + e < L) ? s[e] * scale : GA_NEG;
       mx = fmaxf(mx, s[e]);
     }
 #pragma unroll
@@ -1317,7 +1338,7 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
     float sum = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      s[e] = (jb + j0 + e < T) ? expf(s[e] - m_new) : 0.f;
+      s[e] = (jb + j0 + e < L) ? expf(s[e] - m_new) : 0.f;
       sum += s[e];
       pT[j0 + e][i] = s[e];
     }
@@ -1338,12 +1359,13 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
   }
   if ((tid & 7) == 0) {
     l_s[i] = l;
-    if (lse != nullptr && i_base + i < T) lse[(long long)bh * T + i_base + i] = m + logf(l);
+    if (lse != nullptr && i_base + i < L) lse[(long long)bh * T + i_base + i] = m + logf(l);
   }
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < 8; ++e)
-    if (i_base + i0 + e < T) out[(row0 + d2) * N + col0 + i_base + i0 + e] = o[e] / l_s[i0 + e];
+    if (i_base + i0 + e < L) out[(row0 + d2) * N + col0 + i_base + i0 + e] = o[e] / l_s[i0 + e];
+    else if (LENS && i_base + i0 + e < T) out[(row0 + d2) * N + col0 + i_base + i0 + e] = 0.f;
 }
 
 // ---- the same forward on the matrix pipe (v_mfma_f32_16x16x4_f32, exact fp32 products) for whole-video lengths -----------------
@@ -1361,8 +1383,11 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
 // The next tile's K / V rows are fetched into registers while the current tile is multiplied.  Same recurrence, masks and lse as
 // glance_attn_fwd_anyt_kernel; the summation order inside a dot product differs (MFMA chains of 4), so the two agree to rounding.
 constexpr int GM_Q = 64, GM_K = 64, GM_KP = GA_D + 4, GM_VP = GM_K + 4;  // LDS pitches: 272-byte rows -> conflict-free b128 fragment reads
+// (LENS: as in glance_attn_fwd_anyt_kernel -- L = row_lens[b] in T's place, zeros stored for the queries in [L, T))
+template <bool LENS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void glance_attn_fwd_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse,
-                                                                   int inner, int heads, int T, long long N, float scale, int bh0) {
+                                                                   int inner, int heads, int T, long long N, float scale, int bh0,
+                                                                   const int* __restrict__ row_lens) {
   __shared__ __attribute__((aligned(16))) float kt[GM_K][GM_KP];  // kt[key][d]
   __shared__ __attribute__((aligned(16))) float vs[GA_D][GM_VP];  // vs[d][key]
   const int bh = bh0 + blockIdx.y, b = bh / heads, h = bh % heads, tid = threadIdx.x;
@@ -1371,8 +1396,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   const float* __restrict__ qp = qkv + row0 * N + col0;
   const float* __restrict__ kp = qkv + ((long long)inner + row0) * N + col0;
   const float* __restrict__ vp = qkv + (2ll * inner + row0) * N + col0;
+  const int L = LENS ? min(row_lens[b], T) : T;
+  if (LENS && (int)(blockIdx.x * GM_Q) >= L) {  // (the same for the whole workgroup: nobody waits at a barrier)
+    for (int e = tid; e < GA_D * GM_Q; e += 256) {
+      const int d = e / GM_Q, t = blockIdx.x * GM_Q + e % GM_Q;
+      if (t < T) out[(row0 + d) * N + col0 + t] = 0.f;
+    }
+    return;
+  }
   const int qi = blockIdx.x * GM_Q + wave * 16 + li;  // this lane's query (a column of every fragment)
-  const bool q_ok = qi < T;
+  const bool q_ok = qi < L;
   // B operand of the first product: qreg[c][e] = Q[d = 16 c + 4 lg + e][qi]
   float qreg[4][4];
 #pragma unroll
@@ -1386,7 +1419,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   const float* __restrict__ kpl = kp + (long long)wrow * N + lane;  // this thread's column of the wave's first row; the rest is wave-uniform
   const float* __restrict__ vpl = vp + (long long)wrow * N + lane;
   auto fetch = [&](int jb) __attribute__((always_inline)) {
-    if (jb + lane < T) {
+    if (jb + lane < L) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1415,11 +1448,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   for (int jd = 0; jd < 4; ++jd) o[jd] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = GA_NEG, l = 0.f;
   fetch(0);
-  for (int jb = 0; jb < T; jb += GM_K) {
+  for (int jb = 0; jb < L; jb += GM_K) {
     __syncthreads();  // the previous tile's fragment reads are done
     stash();
     __syncthreads();
-    if (jb + GM_K < T) fetch(jb + GM_K);  // in flight under this tile's products
+    if (jb + GM_K < L) fetch(jb + GM_K);  // in flight under this tile's products
     f32x4 s[4];  // S^T fragment jk: rows key = jb + 16 jk + 4 lg + r, column qi
 #pragma unroll
     for (int jk = 0; jk < 4; ++jk) s[jk] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1439,7 +1472,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     for (int jk = 0; jk < 4; ++jk)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float v = (jb + 16 * jk + 4 * lg + r < T) ? s[jk][r] * scale : GA_NEG;
+        const float v = (jb + 16 * jk + 4 * lg + r < L) ? s[jk][r] * scale : GA_NEG;
         s[jk][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -1452,7 +1485,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
     for (int jk = 0; jk < 4; ++jk)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float pv = (jb + 16 * jk + 4 * lg + r < T) ? expf(s[jk][r] - m_new) : 0.f;
+        const float pv = (jb + 16 * jk + 4 * lg + r < L) ? expf(s[jk][r] - m_new) : 0.f;
         s[jk][r] = pv;
         sum += pv;
       }
@@ -1473,9 +1506,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
         for (int jd = 0; jd < 4; ++jd) o[jd] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jd][e], s[jk][e], o[jd], 0, 0, 0);
     }
   }
-  if (!q_ok) return;
-  const float inv = 1.f / l;
   float* __restrict__ op = out + row0 * N + col0 + qi;
+  if (!q_ok) {
+    if (LENS && qi < T) {
+#pragma unroll
+      for (int jd = 0; jd < 4; ++jd)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) op[(long long)(16 * jd + 4 * lg + r) * N] = 0.f;
+    }
+    return;
+  }
+  const float inv = 1.f / l;
 #pragma unroll
   for (int jd = 0; jd < 4; ++jd)
 #pragma unroll
@@ -1656,26 +1697,65 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const advhip_pack_item*
 // z[j] = W_j X (one GEMM on the input as stored); this launch finishes it -- the shifted add over the taps (zero outside [0, T)),
 // the bias -- and adds the whole 1 -> 64 magnitude conv, which is three multiply-adds per output.  torch: pad, slices, adds,
 // a second unfold + GEMM + bias for the magnitude, scale, add: ~20 launches forward, ~20 backward.
+// LENS: row r ends at row_lens[r] (clamped to T): z and mag behind it are never read (the tap GEMM ran over the padded rows too, so
+// they may hold anything), y behind it is 0.
+template <bool LENS>
 __global__ __launch_bounds__(256) void amp_combine_fwd_kernel(const float* __restrict__ z, const float* __restrict__ bias, const float* __restrict__ mag,
                                                               long long mag_stride, const float* __restrict__ wm, const float* __restrict__ bm,
-                                                              float ratio, float* __restrict__ y, int O, long long rows, int T) {
+                                                              float ratio, float* __restrict__ y, int O, long long rows, int T,
+                                                              const int* __restrict__ row_lens) {
   const long long n = rows * T, total = (long long)O * n;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int o = (int)(i / n);
     const long long p = i - (long long)o * n;
     const int t = (int)(p % T);
+    const int L = LENS ? min(row_lens[p / T], T) : T;
+    if (LENS && t >= L) {
+      y[i] = 0.f;
+      continue;
+    }
     float acc = bias[o] + z[((long long)O + o) * n + p];                  // tap 1: the position itself
     float m = wm[o * 3 + 1] * mag[p * mag_stride];
     if (t > 0) {
       acc += z[(long long)o * n + p - 1];                                  // tap 0 reads t - 1
       m += wm[o * 3] * mag[(p - 1) * mag_stride];
     }
-    if (t + 1 < T) {
+    if (t + 1 < L) {
       acc += z[((long long)2 * O + o) * n + p + 1];                        // tap 2 reads t + 1
       m += wm[o * 3 + 2] * mag[(p + 1) * mag_stride];
     }
     y[i] = acc + ratio * (m + bm[o]);
   }
+}
+
+// ---- padded batches of sequences of unequal length (inference) ------------------------------------------------------------------
+// x (C, rows, T) in place: x[c, r, t] = 0 for t >= row_lens[r].  One workgroup per (row, 16 channels), a wave per channel, lanes along
+// the tail: only tail elements are touched, a full-length row costs its workgroups one load of the length.
+constexpr int MT_CH = 16;
+__global__ __launch_bounds__(256) void mask_tail_kernel(float* __restrict__ x, int C, long long rows, int T, const int* __restrict__ row_lens) {
+  const long long r = blockIdx.x;
+  const int L = max(min(row_lens[r], T), 0);
+  if (L >= T) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = blockIdx.y * MT_CH + wave; c < min(C, (int)(blockIdx.y + 1) * MT_CH); c += 4) {
+    float* __restrict__ p = x + ((long long)c * rows + r) * T;
+    for (int t = L + lane; t < T; t += 64) p[t] = 0.f;
+  }
+}
+
+// dst (n_videos, ncrops, Tmax, width) <- video v stored (ncrops, lens[v], width) at element src_offsets[v] of `store`; rows
+// t >= lens[v] of dst are left as they are.  One workgroup per dst row.
+__global__ __launch_bounds__(256) void pack_padded_kernel(const float* __restrict__ store, const long long* __restrict__ src_offsets,
+                                                          const int* __restrict__ lens, float* __restrict__ dst, int ncrops, int Tmax, int width) {
+  const long long row = blockIdx.x;  // (v * ncrops + c) * Tmax + t
+  const int t = (int)(row % Tmax);
+  const long long vc = row / Tmax;
+  const int v = (int)(vc / ncrops), c = (int)(vc % ncrops);
+  const int L = min(lens[v], Tmax);
+  if (t >= L) return;
+  const float* __restrict__ s = store + src_offsets[v] + ((long long)c * L + t) * width;
+  float* __restrict__ d = dst + row * width;
+  for (int i = threadIdx.x; i < width; i += 256) d[i] = s[i];
 }
 
 // backward: dz[j][o][p] = dy[o][p - j + 1] inside the row, else 0; one block per output channel o also reduces, in a fixed order,
@@ -1818,9 +1898,21 @@ extern "C" int advhip_dwconv_t_fwd_f32(const float* v, const float* w, const flo
     else hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<3>, dim3(grid4), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total / 4);
     return check_launch("dwconv_t_fwd");
   }
-  if (K == 5) hipLaunchKernelGGL(dwconv_t_fwd_kernel<5>, dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total);
-  else hipLaunchKernelGGL(dwconv_t_fwd_kernel<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total);
+  if (K == 5) hipLaunchKernelGGL((dwconv_t_fwd_kernel<5, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)nullptr);
+  else hipLaunchKernelGGL((dwconv_t_fwd_kernel<3, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)nullptr);
   return check_launch("dwconv_t_fwd");
+}
+
+extern "C" int advhip_dwconv_t_fwd_lens_f32(const float* v, const float* w, const float* bias, float* out, int32_t C, int32_t H,
+                                            int64_t rows, int32_t T, int32_t K, const int32_t* row_lens_per_row, int64_t n_rows, void* stream) {
+  ADVHIP_REQUIRE(v && w && bias && out && row_lens_per_row && C > 0 && H > 0 && rows > 0 && T > 0 && C % H == 0, "dwconv_t_fwd_lens: bad arguments");
+  ADVHIP_REQUIRE(n_rows == rows, "dwconv_t_fwd_lens: %lld lengths for %lld rows", (long long)n_rows, (long long)rows);
+  ADVHIP_REQUIRE(K == 5 || K == 3, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
+  const long long total = (long long)C * rows * T;
+  const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
+  if (K == 5) hipLaunchKernelGGL((dwconv_t_fwd_kernel<5, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)row_lens_per_row);
+  else hipLaunchKernelGGL((dwconv_t_fwd_kernel<3, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)row_lens_per_row);
+  return check_launch("dwconv_t_fwd_lens");
 }
 
 extern "C" int32_t advhip_dwconv_t_bwd_chunks(int32_t C, int64_t rows) {
@@ -1881,13 +1973,32 @@ extern "C" int advhip_glance_attention_fwd_anyt_f32(const float* qkv, float* out
   for (long long bh0 = 0; bh0 < B * heads; bh0 += 32768) {  // (grid.y is 16 bits wide)
     const unsigned ny = (unsigned)std::min<long long>(32768, B * heads - bh0);
     if (mfma)
-      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
-                         (long long)B * T, scale, (int)bh0);
+      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel<false>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
+                         (long long)B * T, scale, (int)bh0, (const int*)nullptr);
     else
-      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
-                         (long long)B * T, scale, (int)bh0);
+      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel<false>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
+                         (long long)B * T, scale, (int)bh0, (const int*)nullptr);
   }
   return check_launch("glance_attention_fwd_anyt");
+}
+
+extern "C" int advhip_glance_attention_fwd_lens_f32(const float* qkv, float* out, const int32_t* row_lens, int32_t heads, int64_t B, int32_t T,
+                                                    int32_t dim_head, float scale, void* stream) {
+  ADVHIP_REQUIRE(qkv && out && row_lens && heads > 0 && B > 0 && T > 0, "glance_attention_fwd_lens: bad arguments");
+  ADVHIP_REQUIRE(dim_head == GA_D, "glance_attention_lens: dim_head = %d (the kernel is built for %d)", dim_head, GA_D);
+  ADVHIP_REQUIRE(B * heads < (1ll << 31), "glance_attention_lens: too many (sequence, head) pairs");
+  const bool mfma = T >= GLANCE_MFMA_MIN_T;  // (per launch, from the padded length: the rule of advhip_glance_attention_fwd_anyt_f32)
+  const unsigned tiles = mfma ? (unsigned)((T + GM_Q - 1) / GM_Q) : (unsigned)((T + GA_T - 1) / GA_T);
+  for (long long bh0 = 0; bh0 < B * heads; bh0 += 32768) {
+    const unsigned ny = (unsigned)std::min<long long>(32768, B * heads - bh0);
+    if (mfma)
+      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel<true>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, (float*)nullptr, heads * GA_D, heads,
+                         T, (long long)B * T, scale, (int)bh0, (const int*)row_lens);
+    else
+      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel<true>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, (float*)nullptr, heads * GA_D, heads,
+                         T, (long long)B * T, scale, (int)bh0, (const int*)row_lens);
+  }
+  return check_launch("glance_attention_fwd_lens");
 }
 
 extern "C" int advhip_glance_attention_bwd_anyt_f32(const float* dout, const float* qkv, const float* out, const float* lse, float* dqkv, int32_t heads,
@@ -2072,9 +2183,36 @@ extern "C" int advhip_amp_combine_fwd_f32(const float* z, const float* bias, con
                                           float ratio, float* y, int32_t O, int64_t rows, int32_t T, void* stream) {
   ADVHIP_REQUIRE(z && bias && mag && wm && bm && y && O > 0 && rows > 0 && T > 0 && mag_stride > 0, "amp_combine_fwd: bad arguments");
   const long long total = (long long)O * rows * T;
-  hipLaunchKernelGGL(amp_combine_fwd_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, z, bias, mag,
-                     (long long)mag_stride, wm, bm, ratio, y, O, (long long)rows, T);
+  hipLaunchKernelGGL(amp_combine_fwd_kernel<false>, dim3((unsigned)std::min<long long>((total + 255) / 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, z, bias, mag,
+                     (long long)mag_stride, wm, bm, ratio, y, O, (long long)rows, T, (const int*)nullptr);
   return check_launch("amp_combine_fwd");
+}
+
+extern "C" int advhip_amp_combine_fwd_lens_f32(const float* z, const float* bias, const float* mag, int64_t mag_stride, const float* wm, const float* bm,
+                                               float ratio, float* y, int32_t O, int64_t rows, int32_t T, const int32_t* row_lens, void* stream) {
+  ADVHIP_REQUIRE(z && bias && mag && wm && bm && y && row_lens && O > 0 && rows > 0 && T > 0 && mag_stride > 0, "amp_combine_fwd_lens: bad arguments");
+  const long long total = (long long)O * rows * T;
+  hipLaunchKernelGGL(amp_combine_fwd_kernel<true>, dim3((unsigned)std::min<long long>((total + 255) / 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, z, bias, mag,
+                     (long long)mag_stride, wm, bm, ratio, y, O, (long long)rows, T, (const int*)row_lens);
+  return check_launch("amp_combine_fwd_lens");
+}
+
+extern "C" int advhip_mask_tail_f32(float* x, int32_t C, int64_t rows, int32_t T, const int32_t* row_lens, void* stream) {
+  ADVHIP_REQUIRE(x && row_lens && C > 0 && rows > 0 && T > 0, "mask_tail: bad arguments");
+  ADVHIP_REQUIRE(rows < (1ll << 31) && (C + MT_CH - 1) / MT_CH <= 65535, "mask_tail: %lld rows x %d channels is outside the launch grid", (long long)rows, C);
+  hipLaunchKernelGGL(mask_tail_kernel, dim3((unsigned)rows, (unsigned)((C + MT_CH - 1) / MT_CH)), dim3(256), 0, (hipStream_t)stream, x, C, (long long)rows, T,
+                     (const int*)row_lens);
+  return check_launch("mask_tail");
+}
+
+extern "C" int advhip_pack_padded_f32(const float* store, const int64_t* src_offsets, const int32_t* lens, float* dst, int32_t n_videos, int32_t ncrops,
+                                      int32_t Tmax, int32_t width, void* stream) {
+  ADVHIP_REQUIRE(store && src_offsets && lens && dst && n_videos > 0 && ncrops > 0 && Tmax > 0 && width > 0, "pack_padded: bad arguments");
+  const long long rows = (long long)n_videos * ncrops * Tmax;
+  ADVHIP_REQUIRE(rows < (1ll << 31), "pack_padded: %lld rows is outside the launch grid", rows);
+  hipLaunchKernelGGL(pack_padded_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, store, (const long long*)src_offsets, (const int*)lens, dst, ncrops,
+                     Tmax, width);
+  return check_launch("pack_padded");
 }
 
 extern "C" int advhip_amp_combine_bwd_f32(const float* dy, const float* mag, int64_t mag_stride, float ratio, float* dz, float* d_bias, float* d_wm,

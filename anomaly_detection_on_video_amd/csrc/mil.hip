@@ -53,6 +53,20 @@ __global__ void mil_magnitude_kernel(const float* __restrict__ feat, const float
   }
 }
 
+// Validation over a padded batch of videos of unequal length: the crop mean of mil_magnitude_kernel's `sc` (summed in crop order from
+// 0.f, one division: the same bits) for the lens[v] real clips of video v, written at dst_offsets[v] of a flat per-clip score buffer.
+__global__ __launch_bounds__(256) void crop_mean_scatter_kernel(const float* __restrict__ scores, const int* __restrict__ lens,
+                                                                const long long* __restrict__ dst_offsets, float* __restrict__ dst,
+                                                                int n_videos, int ncrops, int Tmax) {
+  const long long w = blockIdx.x * 256ll + threadIdx.x;
+  if (w >= (long long)n_videos * Tmax) return;
+  const int v = (int)(w / Tmax), t = (int)(w % Tmax);
+  if (t >= min(lens[v], Tmax)) return;
+  float s = 0.f;
+  for (int c = 0; c < ncrops; ++c) s += scores[((size_t)v * ncrops + c) * Tmax + t];
+  dst[dst_offsets[v] + t] = s / (float)ncrops;
+}
+
 __global__ void mil_magnitude_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ d_mag,
                                          const float* __restrict__ d_sc, float* __restrict__ d_feat,
                                          float* __restrict__ d_scores, int bs, int ncrops, int T, int F) {
@@ -220,4 +234,14 @@ extern "C" int advhip_mil_topk_select_bwd_f32(const int64_t* idx, const float* d
   hipLaunchKernelGGL(mil_scatter_kernel, dim3(n * ncrops * k), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const long long*>(idx), d_sel, d_score, d_features, d_sc, n, ncrops, T, F, k);
   return check_launch("mil_scatter");
+}
+
+extern "C" int advhip_crop_mean_scatter_f32(const float* scores, const int32_t* lens, const int64_t* dst_offsets, float* dst, int32_t n_videos,
+                                            int32_t ncrops, int32_t Tmax, void* stream) {
+  ADVHIP_REQUIRE(scores && lens && dst_offsets && dst, "crop_mean_scatter: null pointer");
+  ADVHIP_REQUIRE(n_videos > 0 && ncrops > 0 && Tmax > 0, "crop_mean_scatter: bad shape");
+  const long long n = (long long)n_videos * Tmax;
+  hipLaunchKernelGGL(crop_mean_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, (const int*)lens,
+                     (const long long*)dst_offsets, dst, n_videos, ncrops, Tmax);
+  return check_launch("crop_mean_scatter");
 }

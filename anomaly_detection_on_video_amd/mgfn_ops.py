@@ -55,8 +55,26 @@ MIN_CHANNELS_TRAIN = int(os.environ.get("ADV_MGFN_HIP_MIN_CHANNELS_TRAIN", "64")
 STRICT = os.environ.get("ADV_MGFN_STRICT", "0") == "1"
 
 
+_PADDED = False  # inside MGFNForVideoAnomalyDetection.score_padded: a torch expression knows no row lengths, so that branch is closed
+
+
+class padded_pass:
+    """The scope of a padded-batch scoring pass: `torch_path` raises inside it (read only where a layer is about to leave the kernels)."""
+
+    def __enter__(self):
+        global _PADDED
+        self._was, _PADDED = _PADDED, True
+
+    def __exit__(self, *exc):
+        global _PADDED
+        _PADDED = self._was
+
+
 def torch_path(x: torch.Tensor, what: str) -> None:
     """Called where modeling_mgfn.py is about to run a layer on torch ops."""
+    if _PADDED:
+        raise _lib.HipExtensionError(f"score_padded: {what} on {tuple(x.shape)} would run on torch ops, which know no row lengths (outside the HIP "
+                                     "kernels' shape rules: mgfn_ops.eligible / fused_ok / glance_attention_ok)")
     if STRICT and x.is_cuda:
         raise _lib.HipExtensionError(f"ADV_MGFN_STRICT=1: {what} on {tuple(x.shape)} would run on torch ops (outside the HIP kernels' shape rules, see mgfn_ops.eligible)")
 
@@ -935,8 +953,65 @@ def glance_attention_ok(qkv: torch.Tensor, heads: int, dim_head: int) -> bool:
     return fused_ok(qkv) and qkv.is_contiguous() and qkv.shape[2] >= 1 and dim_head == 64 and qkv.shape[0] == 3 * heads * dim_head
 
 
-def glance_attention_core(qkv: torch.Tensor, heads: int, dim_head: int, scale: float) -> torch.Tensor:
-    return _GlanceAttnCore.apply(qkv, heads, dim_head, scale)
+def glance_attention_core(qkv: torch.Tensor, heads: int, dim_head: int, scale: float, lens=None) -> torch.Tensor:
+    """`lens`: one length per sequence of a padded batch (row_lens): keys and queries behind it do not exist, `out` is 0 there."""
+    if lens is None:
+        return _GlanceAttnCore.apply(qkv, heads, dim_head, scale)
+    _no_autograd("glance_attention_core")
+    _lib.require_gpu(qkv)
+    c3, b, t = qkv.shape
+    if dim_head != 64 or c3 != 3 * heads * dim_head:
+        raise _lib.HipExtensionError(f"glance_attention_core with lens: dim_head = {dim_head}, {c3} rows (the kernel is built for dim_head 64 and 3 * heads * 64 rows)")
+    rl = row_lens(lens, b, t, qkv.device)
+    out = torch.empty((c3 // 3, b, t), device=qkv.device, dtype=torch.float32)
+    check(_lib.load().advhip_glance_attention_fwd_lens_f32(ptr(qkv), ptr(out), ptr(rl), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
+          "glance_attention_fwd_lens")
+    return out
+
+
+# ---- padded batches of sequences of unequal length (inference): the row lengths of a (C, rows, T) activation -------------------
+def _no_autograd(what: str) -> None:
+    if torch.is_grad_enabled():
+        raise _lib.HipExtensionError(f"{what} with lens has no backward pass: call it under torch.no_grad()")
+
+
+def check_lens(lens, t: int, what: str = "lens"):
+    """Host lengths as a list of ints, each in 1 .. t."""
+    out = []
+    for v in lens:
+        if isinstance(v, bool) or int(v) != v:
+            raise _lib.HipExtensionError(f"{what}: {v!r} is not an integer")
+        if not 1 <= int(v) <= t:
+            raise _lib.HipExtensionError(f"{what}: length {int(v)} is outside 1 .. {t}")
+        out.append(int(v))
+    return out
+
+
+def row_lens(lens, rows: int, t: int, dev) -> torch.Tensor:
+    """The kernels' `row_lens`: a device int32 tensor with one length per row, taken as it is (its values were validated when it was
+    built: nothing is read back), or host ints, validated (1 .. t, one per row) and uploaded."""
+    if torch.is_tensor(lens):
+        if not (lens.is_cuda and lens.device == torch.device(dev) and lens.dtype == torch.int32 and lens.dim() == 1 and lens.is_contiguous()):
+            raise _lib.HipExtensionError(f"lens: expected a contiguous int32 vector on {dev}, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+        if lens.numel() != rows:
+            raise _lib.HipExtensionError(f"lens: {lens.numel()} lengths for {rows} rows")
+        return lens
+    host = check_lens(lens, t)
+    if len(host) != rows:
+        raise _lib.HipExtensionError(f"lens: {len(host)} lengths for {rows} rows")
+    return torch.tensor(host, dtype=torch.int32).to(dev)
+
+
+def mask_tail_(x: torch.Tensor, lens) -> torch.Tensor:
+    """x (C, rows, T) in place: zero at t >= lens[row] (only those elements are written).  The k = 3 convs are GEMMs of the conv
+    kernels, which know no lengths: this stands in front of them where a pointwise layer has left something in the tails."""
+    _no_autograd("mask_tail_")
+    _lib.require_gpu(x)
+    if x.dim() != 3:
+        raise _lib.HipExtensionError(f"mask_tail_: expected (C, rows, T), got {tuple(x.shape)}")
+    c, b, t = x.shape
+    check(_lib.load().advhip_mask_tail_f32(ptr(x), c, b, t, ptr(row_lens(lens, b, t, x.device)), stream(x)), "mask_tail")
+    return x
 
 
 class _HeadLnFc(torch.autograd.Function):
@@ -1226,8 +1301,19 @@ def amp_combine_ok(z: torch.Tensor, conv: torch.nn.Conv1d, to_mag: torch.nn.Conv
             and mag.stride(1) == mag.shape[2] * mag.stride(2) and not mag.requires_grad and mag.dtype == torch.float32 and _on_current_device(mag))
 
 
-def amp_combine(z, conv, to_mag, mag, ratio: float) -> torch.Tensor:
-    return _AmpCombine.apply(z, conv.bias, mag, to_mag.weight, to_mag.bias, float(ratio))
+def amp_combine(z, conv, to_mag, mag, ratio: float, lens=None) -> torch.Tensor:
+    """`lens`: one length per row of a padded batch: z and mag behind a row's end are not read, the tokens there are 0."""
+    if lens is None:
+        return _AmpCombine.apply(z, conv.bias, mag, to_mag.weight, to_mag.bias, float(ratio))
+    _no_autograd("amp_combine")
+    bias, wm, bm = conv.bias.detach(), to_mag.weight.detach(), to_mag.bias.detach()
+    _lib.require_gpu(z, bias, wm, bm)
+    _lib.require_gpu(mag, contiguous=False)
+    k, o, b, t = z.shape
+    y = torch.empty((o, b, t), device=z.device, dtype=torch.float32)
+    check(_lib.load().advhip_amp_combine_fwd_lens_f32(ptr(z), ptr(bias), ptr(mag), mag.stride(2), ptr(wm), ptr(bm), C.c_float(float(ratio)), ptr(y), o, b, t,
+                                                      ptr(row_lens(lens, b, t, z.device)), stream(z)), "amp_combine_fwd_lens")
+    return y
 
 
 def fused_ok(x: torch.Tensor) -> bool:
@@ -1238,8 +1324,20 @@ def chan_layernorm(x: torch.Tensor, g: torch.Tensor, b: torch.Tensor, eps: float
     return _ChanLayerNorm.apply(x.contiguous(), g, b, eps)
 
 
-def dwconv_t(v: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
-    return _DWConvT.apply(v.contiguous(), weight, bias)
+def dwconv_t(v: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, lens=None) -> torch.Tensor:
+    """`lens`: one length per row of a padded batch: the taps stop at a row's end, the output behind it is 0."""
+    if lens is None:
+        return _DWConvT.apply(v.contiguous(), weight, bias)
+    _no_autograd("dwconv_t")
+    v = v.contiguous()
+    _lib.require_gpu(v, weight, bias, contiguous=False)
+    c, b, t = v.shape
+    h, _, k = weight.shape
+    out = torch.empty_like(v)
+    rl = row_lens(lens, b, t, v.device)
+    check(_lib.load().advhip_dwconv_t_fwd_lens_f32(ptr(v), ptr(weight.detach().reshape(h, k).contiguous()), ptr(bias.detach().contiguous()), ptr(out), c, h, b, t, k,
+                                                   ptr(rl), rl.numel(), stream(v)), "dwconv_t_fwd_lens")
+    return out
 
 
 class _BNRowsTrain(torch.autograd.Function):

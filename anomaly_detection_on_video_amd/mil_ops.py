@@ -202,6 +202,40 @@ def mil_topk_select(mag, keep: Optional[torch.Tensor], sc, features, ncrops: int
     return _MilTopkSelect.apply(mag, keep, sc, features, ncrops, k)
 
 
+def _device_vec(t, dtype, n: int, what: str) -> torch.Tensor:
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.dim() == 1 and t.numel() == n and t.is_contiguous()):
+        raise _lib.HipExtensionError(f"{what}: expected a contiguous {dtype} device vector of {n}")
+    return t
+
+
+def crop_mean_scatter(scores: torch.Tensor, lens: torch.Tensor, dst_offsets: torch.Tensor, dst: torch.Tensor, n_videos: int, ncrops: int) -> torch.Tensor:
+    """The crop mean of a padded batch's per-crop scores (n_videos * ncrops, Tmax) -- mil_magnitude's `sc`, bit for bit -- for the
+    lens[v] real clips of every video, written at dst[dst_offsets[v] + t] of a flat fp32 buffer.  lens (int32) and dst_offsets
+    (int64) are device vectors whose values the caller has validated: nothing is read back.  No autograd."""
+    require_gpu(scores, dst)
+    if scores.dtype != torch.float32 or dst.dtype != torch.float32 or scores.numel() % (n_videos * ncrops) or scores.numel() == 0:
+        raise _lib.HipExtensionError(f"crop_mean_scatter: scores {scores.dtype} {tuple(scores.shape)} for {n_videos} videos x {ncrops} crops")
+    tmax = scores.numel() // (n_videos * ncrops)
+    check(_lib.load().advhip_crop_mean_scatter_f32(ptr(scores), ptr(_device_vec(lens, torch.int32, n_videos, "crop_mean_scatter lens")),
+                                                   ptr(_device_vec(dst_offsets, torch.int64, n_videos, "crop_mean_scatter dst_offsets")), ptr(dst),
+                                                   n_videos, ncrops, tmax, stream()), "crop_mean_scatter")
+    return dst
+
+
+def pack_padded(store: torch.Tensor, src_offsets: torch.Tensor, lens: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """One launch fills a padded batch dst (n_videos, ncrops, Tmax, width): video v, stored (ncrops, lens[v], width) at element
+    src_offsets[v] of the flat fp32 `store`, goes to dst[v, :, :lens[v]]; the rows behind stay as they are.  src_offsets (int64) and
+    lens (int32) are device vectors whose values the caller has validated against the store and Tmax."""
+    require_gpu(store, dst)
+    if store.dtype != torch.float32 or dst.dtype != torch.float32 or dst.dim() != 4:
+        raise _lib.HipExtensionError(f"pack_padded: fp32 store and (n_videos, ncrops, Tmax, width) fp32 dst, got {store.dtype} and {dst.dtype} {tuple(dst.shape)}")
+    n, ncrops, tmax, width = dst.shape
+    check(_lib.load().advhip_pack_padded_f32(ptr(store), ptr(_device_vec(src_offsets, torch.int64, n, "pack_padded src_offsets")),
+                                             ptr(_device_vec(lens, torch.int32, n, "pack_padded lens")), ptr(dst), n, ncrops, tmax, width, stream()),
+          "pack_padded")
+    return dst
+
+
 LOSS_TERMS = ("total", "bce", "con", "con_a", "con_n", "smooth", "sparse", "mgfn")
 
 

@@ -173,20 +173,22 @@ class MGFNFeatureAmplifier(nn.Module):
         self.to_tokens = nn.Conv1d(config.channels, config.dims[0], kernel_size=3, stride=1, padding=1)
         self.to_mag = nn.Conv1d(1, config.dims[0], kernel_size=3, stride=1, padding=1)
 
-    def forward(self, x):
+    def forward(self, x, lens=None):
+        """`lens` (a padded batch, MGFNForVideoAnomalyDetection.score_padded): one length per (video, crop) row; the tokens behind a
+        row's end are 0 and the input there is never read as a value."""
         bs, ncrops, t, c = x.shape
         rows = x.reshape(bs * ncrops * t, c)               # the input as stored: (positions, channels + magnitude)
         x = x.reshape(bs * ncrops, t, c).permute(2, 0, 1)  # (C+1, B, T) view
         if (torch.is_grad_enabled() and self.to_tokens.weight.requires_grad) or mgfn_ops.fused_ok(x):
             # (with autograd, and on the GPU without it too: no unfolded input, no torch GEMM -- eval's 1 -> 64 magnitude conv included)
-            tokens, whole = self._tokens_by_taps(x, bs * ncrops, t, rows)
+            tokens, whole = self._tokens_by_taps(x, bs * ncrops, t, rows, lens)
             if whole:  # (the magnitude conv, the scale and the sum went into the launch that finishes the token conv)
                 return tokens
         else:
             tokens = _conv_k(self.to_tokens, x[: self.channels])
         return tokens + self.mag_ratio * _conv_k(self.to_mag, x[self.channels :])
 
-    def _tokens_by_taps(self, x, b, t, rows=None):
+    def _tokens_by_taps(self, x, b, t, rows=None, lens=None):
         """The 2048 -> 64 token conv with autograd, without unfolding its input: a k-tap conv is linear in its taps,
         conv_k(x)[o, t] = sum_j (W_j x)[o, t + j - k/2], so ONE GEMM of the stacked tap matrices (k*64 x 2048) with the input AS
         STORED (positions x channels, read through its strides: no transposed / padded / tap-stacked copy, 84 + 252 MB at the
@@ -206,7 +208,7 @@ class MGFNFeatureAmplifier(nn.Module):
         mag = x[c:]
         if k == 3 and mgfn_ops.amp_combine_ok(z, conv, self.to_mag, mag):
             # the shifted add, the bias AND mag_ratio * to_mag(magnitude): one HIP launch forward, one backward -> (tokens, True)
-            return mgfn_ops.amp_combine(z, conv, self.to_mag, mag, self.mag_ratio), True
+            return mgfn_ops.amp_combine(z, conv, self.to_mag, mag, self.mag_ratio, lens), True
         mgfn_ops.torch_path(x, "token conv tap sum (k != 3, a conv without bias, or a magnitude channel that is not a view of the input rows)")
         zp = F.pad(z, (k // 2, k // 2))
         y = zp[0, :, :, 0:t]
@@ -226,7 +228,7 @@ class GlanceAttention(nn.Module):
         self.to_qkv = nn.Conv1d(dim, dim_head * heads * 3, 1, bias=False)
         self.to_out = nn.Conv1d(dim_head * heads, dim, 1)
 
-    def forward(self, x, residual: Optional[torch.Tensor] = None):  # (C, B, T)
+    def forward(self, x, residual: Optional[torch.Tensor] = None, lens=None):  # (C, B, T); lens: the rows' lengths in a padded batch
         _, b, n = x.shape
         if (mgfn_ops.GLANCE_BLOCK and residual is x and torch.is_grad_enabled() and mgfn_ops.fused_ok(x) and _hip(self.to_qkv, x) and _hip(self.to_out, x)
                 and self.to_qkv.bias is None and self.to_out.bias is not None and self.dim_head == 64
@@ -235,7 +237,7 @@ class GlanceAttention(nn.Module):
             return mgfn_ops.glance_attention_block_cn(x, self.norm, self.to_qkv, self.to_out, self.heads, self.dim_head, self.scale)
         qkv = _pointwise(self.to_qkv, self.norm(x))
         if mgfn_ops.glance_attention_ok(qkv, self.heads, self.dim_head):  # scale, sim, softmax, v attn^T, layout: one HIP launch
-            return _pointwise(self.to_out, mgfn_ops.glance_attention_core(qkv, self.heads, self.dim_head, self.scale), residual)
+            return _pointwise(self.to_out, mgfn_ops.glance_attention_core(qkv, self.heads, self.dim_head, self.scale, lens), residual)
         mgfn_ops.torch_path(x, "Glance attention core (dim_head != 64)")
         qkv = qkv.view(3, self.heads, self.dim_head, b, n)
         q, k, v = (t.permute(2, 0, 1, 3) for t in qkv.unbind(0))  # (b, h, d, n)
@@ -283,7 +285,7 @@ class FocusAttention(nn.Module):
         scale = bn.weight * torch.rsqrt(var + bn.eps)
         return x * scale[:, None, None] + (bn.bias - mean * scale)[:, None, None]
 
-    def forward(self, x, residual: Optional[torch.Tensor] = None):  # (C, B, T)
+    def forward(self, x, residual: Optional[torch.Tensor] = None, lens=None):  # (C, B, T); lens: the rows' lengths in a padded batch
         _, b, n = x.shape
         bn = self.norm
         if (residual is x and torch.is_grad_enabled() and bn.training and bn.momentum is not None and bn.affine
@@ -300,7 +302,7 @@ class FocusAttention(nn.Module):
         v = v.view(inner // h, h, b, n)  # channel = c_idx*heads + h_idx  ("b (c h) n -> (b c) h n")
         k = self.rel_pos.weight.shape[-1]
         if mgfn_ops.fused_ok(x) and k in (3, 5):  # the per-head depth-wise temporal conv as one HIP launch (fwd) / one (bwd)
-            out = mgfn_ops.dwconv_t(v.reshape(inner, b, n), self.rel_pos.weight, self.rel_pos.bias)
+            out = mgfn_ops.dwconv_t(v.reshape(inner, b, n), self.rel_pos.weight, self.rel_pos.bias, lens)
             return _pointwise(self.to_out, out, residual)
         mgfn_ops.torch_path(x, f"depth-wise temporal conv with k = {k} (the kernel is built for 3 and 5)")
         vp = F.pad(v, (k // 2, k // 2))
@@ -312,11 +314,15 @@ class FocusAttention(nn.Module):
 
 
 class _Block(nn.Module):
-    def forward(self, x):
+    def forward(self, x, lens=None, clean_tails: bool = False):
         # x = scc(x) + x;  x = attention(x) + x;  x = ffn(x) + x  (modeling_mgfn.py:143-147, 201-205): the residual adds ride
         # in the epilogue of the GEMM that ends each branch
+        if lens is not None and not clean_tails:
+            # a padded batch: scc reads t - 1 and t + 1, and the pointwise layers since the last temporal operator have written the
+            # tails -- zero them in place (x is the previous layer's own output).  The attention takes the lengths itself.
+            mgfn_ops.mask_tail_(x, lens)
         x = _conv_k(self.scc, x, residual=x)
-        x = self.attention(x, residual=x)
+        x = self.attention(x, residual=x, lens=lens)
         return self.ffn(x, residual=x)
 
 
@@ -401,6 +407,23 @@ class MGFNModel(MGFNPreTrainedModel):
             mgfn_ops.end_step_packs()
             mgfn_ops.flush_counters(discard=not ok)  # (the BatchNorm layers' num_batches_tracked += 1, all in one launch)
         return MGFNModelOutput(outputs=y.permute(1, 0, 2))
+
+    def forward_padded(self, x: torch.Tensor, row_lens: torch.Tensor) -> torch.Tensor:
+        """The body on a padded batch x (nb, ncrops, Tmax, C+1), `row_lens` = a device int32 length per (video, crop) row; inference
+        only (the caller holds no_grad, eval mode and mgfn_ops.padded_pass).  Returns the (C, nb*ncrops, Tmax) activation.  The four
+        operators that read a position's neighbours in time see zeros behind a row's end: the amplifier and the two attentions take
+        the lengths, every scc conv but the first (whose input the amplifier has just written) has mask_tail_ in front of it; every
+        other layer acts on one position at a time and may leave anything in the tails."""
+        y = self.amplifier(x, row_lens)
+        clean = True
+        for stage in self.layers:
+            for block in stage:
+                if isinstance(block, _Block):
+                    y = block(y, row_lens, clean_tails=clean)
+                    clean = False
+                else:
+                    y = block(y)
+        return y
 
     def _gemm_convs(self):
         """The Conv1d layers whose training forward runs on the HIP GEMMs (mgfn_ops.eligible's channel rules): their packed
@@ -496,6 +519,60 @@ class MGFNForVideoAnomalyDetection(MGFNPreTrainedModel):
             loss=loss, abnormal_scores=abn_s, normal_scores=nor_s,
             a_feat_magnitude=a_feat, n_feat_magnitude=n_feat, scores=sc,
         )
+
+    def _score_padded_rows(self, video: torch.Tensor, lens) -> Tuple[torch.Tensor, "PaddedLens"]:
+        """score_padded up to the per-crop scores: ((nb * ncrops, Tmax, 1) scores, the batch's PaddedLens).  Every refusal happens here,
+        before anything is launched."""
+        err = mgfn_ops._lib.HipExtensionError
+        if self.training:
+            raise err("score_padded runs in eval mode only: training-mode BatchNorm would take its batch statistics over the padding")
+        if not torch.is_tensor(video) or video.dim() != 4:
+            raise err("score_padded: video must be a (nb, ncrops, Tmax, C+1) tensor")
+        if not (video.is_cuda and video.device.index == torch.cuda.current_device() and video.dtype == torch.float32):
+            raise err(f"score_padded: video must be an fp32 tensor on the current GPU, got {video.dtype} on '{video.device}' (there is no CPU fallback)")
+        nb, ncrops, tmax, _ = video.shape
+        if isinstance(lens, PaddedLens):
+            pl = lens
+            if (len(pl.lens), pl.ncrops, pl.device) != (nb, ncrops, video.device) or pl.tmax != tmax:
+                raise err(f"score_padded: lengths built for {len(pl.lens)} videos x {pl.ncrops} crops x {pl.tmax} clips on {pl.device}, video is {tuple(video.shape)} on {video.device}")
+        else:
+            lens = list(lens)
+            if len(lens) != nb:
+                raise err(f"score_padded: {len(lens)} lengths for {nb} videos")
+            pl = PaddedLens(lens, ncrops, tmax, video.device)
+        with torch.no_grad(), mgfn_ops.padded_pass():
+            y = self.backbone.forward_padded(video.contiguous(), pl.row_lens)
+            if not mgfn_ops.head_ok(y, self.layer_norm, self.fc):
+                mgfn_ops.torch_path(y, "head (LayerNorm + Linear + sigmoid) off the fused kernel")
+            _, scores = mgfn_ops.head_ln_fc(y, self.layer_norm, self.fc)
+        return scores, pl
+
+    def score_padded(self, video: torch.Tensor, lens) -> torch.Tensor:
+        """Frame scores of nb videos of unequal length in ONE pass: `video` (nb, ncrops, Tmax, C+1) fp32 on the current GPU, video v's
+        lens[v] clips at the front of its rows (what stands behind them is ignored: it may be uninitialised memory); `lens`: nb host
+        ints in 1 .. Tmax, or a PaddedLens built from them.  Returns (nb, Tmax) fp32: [v, :lens[v]] = what
+        `self(video=video[v:v+1, :, :lens[v]]).scores` holds (the crop mean of the per-clip scores; equal bits when all lengths are
+        Tmax, equal within the GEMM kernels' shape-dependent tiling otherwise), 0 behind.  Eval mode, no autograd, no top-k selection,
+        no losses, and never a torch expression: an architecture outside the kernels' shape rules raises HipExtensionError."""
+        scores, pl = self._score_padded_rows(video, lens)
+        out = torch.zeros((len(pl.lens), pl.tmax), device=video.device, dtype=torch.float32)
+        return mil_ops.crop_mean_scatter(scores, pl.video_lens, pl.dense_offsets, out, len(pl.lens), pl.ncrops)
+
+
+class PaddedLens:
+    """The lengths of one padded batch on the device, built (validated, uploaded) once: `lens` nb host ints in 1 .. tmax,
+    `video_lens` int32 (nb,), `row_lens` int32 (nb * ncrops,) -- one per (video, crop) row -- and `dense_offsets` int64 (nb,) =
+    v * tmax, where video v's scores start in a (nb, tmax) result.  score_padded takes one in place of host lengths and then
+    uploads nothing."""
+
+    def __init__(self, lens, ncrops: int, tmax: int, device):
+        self.lens = mgfn_ops.check_lens(lens, int(tmax), "score_padded lens")
+        if not self.lens or int(ncrops) < 1:
+            raise mgfn_ops._lib.HipExtensionError(f"score_padded: {len(self.lens)} lengths, {ncrops} crops")
+        self.ncrops, self.tmax, self.device = int(ncrops), int(tmax), torch.device(device)
+        self.video_lens = torch.tensor(self.lens, dtype=torch.int32).to(self.device)
+        self.row_lens = torch.tensor([n for n in self.lens for _ in range(self.ncrops)], dtype=torch.int32).to(self.device)
+        self.dense_offsets = torch.tensor([v * self.tmax for v in range(len(self.lens))], dtype=torch.int64).to(self.device)
 
 
 def mgfn_param_shapes(config: Optional[MGFNConfig] = None) -> "OrderedDict[str, Tuple[int, ...]]":

@@ -29,6 +29,8 @@ class VideoAnomalyDetectionRunner:
         self.hparams = type("HParams", (), {"optimizer": optimizer, "data": data})()
         self.validation_step_outputs: List[Dict[str, np.ndarray]] = []
         self.auc_plan: Optional[metrics.FrameAucPlan] = None  # data.device_metrics: the validation metrics' device state (setup)
+        self.score_plan = None  # data.val_batch_videos > 1: val_batch.ScoreBatchPlan of the resident test set (setup)
+        self._val_scores = None  # ... and, without device_metrics, the flat device buffer its passes write
         self.logged: Dict[str, float] = {}
         self.device = torch.device("cpu")
 
@@ -68,6 +70,18 @@ class VideoAnomalyDetectionRunner:
             "labels": batch["label"].squeeze(0).cpu().numpy(),
         })
 
+    def validate_batched(self) -> None:
+        """data.val_batch_videos > 1: the whole test set in length-sorted padded buckets (val_batch.ScoreBatchPlan) instead of one
+        validation_step per video.  With data.device_metrics the scores go straight into the AUC plan's buffer; without it ONE
+        device-to-host copy of the flat score buffer feeds validation_step_outputs, split per video."""
+        plan = self.score_plan
+        if self.auc_plan is not None:
+            plan.run(self.model, self.auc_plan.scores)
+            return
+        flat = plan.run(self.model, self._val_scores).cpu().numpy()
+        for i, labels in enumerate(self.valid_dataset.labels):
+            self.validation_step_outputs.append({"preds": flat[plan.offsets[i]:plan.offsets[i + 1]], "labels": labels})
+
     # runner.py:53-59 -- Adam with L2-in-gradient weight decay, no scheduler
     def configure_optimizers(self) -> List[torch.optim.Optimizer]:
         opt = self.hparams.optimizer
@@ -103,11 +117,17 @@ class VideoAnomalyDetectionRunner:
         d = self.hparams.data
         kw = dict(revision=d.get("revision", "main"), cache_dir=d.get("cache_dir"), dynamic_load=bool(d.get("dynamic_load", False)))
         local = d.get("local_path")
-        self.auc_plan = None
+        self.auc_plan = self.score_plan = None
         device_metrics = bool(d.get("device_metrics", False))
         if device_metrics and not bool(d.get("resident", False)):
             raise ValueError("data.device_metrics=true needs data.resident=true: the validation scores stay on the device only "
                              "when the test set is served from it")
+        batch_videos = int(d.get("val_batch_videos", 1))
+        if batch_videos < 1:
+            raise ValueError(f"data.val_batch_videos={batch_videos} must be at least 1")
+        if batch_videos > 1 and not bool(d.get("resident", False)):
+            raise ValueError(f"data.val_batch_videos={batch_videos} needs data.resident=true: the buckets are packed on the device "
+                             "from the resident test set")
         if bool(d.get("resident", False)):
             # both zips into device memory once, magnitude channel included (dataset.ResidentFeatureDataset): the loaders below
             # then hand out views of it.  One budget for the two of them.
@@ -117,14 +137,28 @@ class VideoAnomalyDetectionRunner:
             budget -= sum(ds.nbytes for ds in self.train_dataset.values())
             self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None,
                                                        resident=self.device, resident_max_bytes=budget, **kw)
-            # (a subclass with its own validation_step keeps the host metrics, which its outputs feed)
-            if device_metrics and type(self).validation_step is VideoAnomalyDetectionRunner.validation_step:
-                valid = self.valid_dataset
-                self.auc_plan = metrics.FrameAucPlan(valid.labels, [int(v.shape[1]) for v in valid.videos],
-                                                     int(d["frames_per_clip"]), device=self.device)
+            self.build_validation_plans()
             return
         self.train_dataset = build_feature_dataset(mode="train", local_path=local, filename="train.zip" if local else None, **kw)
         self.valid_dataset = build_feature_dataset(mode="test", local_path=local, filename="test.zip" if local else None, **kw)
+
+    def build_validation_plans(self) -> None:
+        """The device state of validation over the resident test set (`self.valid_dataset`), from data.device_metrics and
+        data.val_batch_videos; the last step of `setup`."""
+        d = self.hparams.data
+        self.auc_plan = self.score_plan = None
+        # (a subclass with its own validation_step keeps the per-video loop and the host metrics, which its outputs feed)
+        if type(self).validation_step is not VideoAnomalyDetectionRunner.validation_step:
+            return
+        valid = self.valid_dataset
+        if bool(d.get("device_metrics", False)):
+            self.auc_plan = metrics.FrameAucPlan(valid.labels, [int(v.shape[1]) for v in valid.videos],
+                                                 int(d["frames_per_clip"]), device=self.device)
+        if int(d.get("val_batch_videos", 1)) > 1:
+            from .val_batch import ScoreBatchPlan
+
+            self.score_plan = ScoreBatchPlan(valid, int(d["val_batch_videos"]), device=self.device)
+            self._val_scores = None if self.auc_plan is not None else self.score_plan.new_scores()
 
     # runner.py:108-124 -- two loaders zipped, shuffle=False, drop_last=True
     def train_dataloader(self) -> Tuple[DataLoader, DataLoader]:
@@ -380,6 +414,9 @@ class Trainer:
     @torch.no_grad()
     def validate(self, runner: VideoAnomalyDetectionRunner) -> Dict[str, float]:
         runner.model.eval()
+        if getattr(runner, "score_plan", None) is not None:  # data.val_batch_videos > 1: padded buckets instead of one step per video
+            runner.validate_batched()
+            return runner.on_validation_epoch_end()
         for i, batch in enumerate(runner.val_dataloader()):
             runner.validation_step(_to_device(batch, self.device), i)
         return runner.on_validation_epoch_end()

@@ -568,6 +568,24 @@ int advhip_amp_combine_fwd_f32(const float* z, const float* bias, const float* m
 int advhip_amp_combine_bwd_f32(const float* dy, const float* mag, int64_t mag_stride, float ratio, float* dz, float* d_bias, float* d_wm,
                                float* d_bm, int32_t O, int64_t rows, int32_t T, void* stream);
 
+/* --- Padded batches of sequences of unequal length (inference: batched validation) ---------------------------------------------
+ * A batch of videos of unequal length is a (C, rows, T) activation with T = the longest and one length per row, row_lens (device
+ * int32[rows], 1 <= len <= T; validated by the caller, clamped to T here -- nothing is ever indexed past T).  The four operators that
+ * read a position's neighbours in time take the lengths; all of them STORE 0 at t >= len (they never multiply by a mask, so
+ * NaN / uninitialised values behind a row's end cannot reach a real position) and write every element of their output.  For a
+ * row with len = T each computes exactly what its entry point without lengths computes.  Forward only.
+ *
+ * advhip_amp_combine_fwd_lens_f32: advhip_amp_combine_fwd_f32 whose taps stop at the row's end; z and mag at t >= len are never read. */
+int advhip_amp_combine_fwd_lens_f32(const float* z, const float* bias, const float* mag, int64_t mag_stride, const float* wm, const float* bm,
+                                    float ratio, float* y, int32_t O, int64_t rows, int32_t T, const int32_t* row_lens, void* stream);
+/* x (C, rows, T) in place: x[c, r, t] = 0 for t >= row_lens[r]; only those elements are touched.  What stands in front of a k = 3
+ * conv (a GEMM of the conv kernels, which know no lengths) whose input's tails a pointwise layer has filled. */
+int advhip_mask_tail_f32(float* x, int32_t C, int64_t rows, int32_t T, const int32_t* row_lens, void* stream);
+/* One launch fills a padded batch: video v, stored (ncrops, lens[v], width) at element src_offsets[v] of `store`, goes to
+ * dst[v, c, t < lens[v], :] of dst (n_videos, ncrops, Tmax, width).  Rows t >= lens[v] of dst are left as they are. */
+int advhip_pack_padded_f32(const float* store, const int64_t* src_offsets, const int32_t* lens, float* dst, int32_t n_videos, int32_t ncrops,
+                           int32_t Tmax, int32_t width, void* stream);
+
 /* dst[c] = sum over r, in row order, of src[r][c]: the per-block partial sums the backward kernels above leave to the caller
  * (rows = a few hundred blocks). */
 int advhip_colsum_f32(const float* src, float* dst, int64_t rows, int32_t cols, void* stream);
@@ -615,6 +633,10 @@ int advhip_dwconv_t_fwd_f32(const float* v, const float* w, const float* bias, f
 /* Backward: dv, and partial[(C / H) * chunks][H][K + 1] = per-block sums of (dout * v shifted by tap j, j < K; dout) of channel
  * c = c_idx * H + h -- the caller adds the (C / H) * chunks rows (advhip_colsum_f32; chunks = advhip_dwconv_t_bwd_chunks(C, rows)). */
 int32_t advhip_dwconv_t_bwd_chunks(int32_t C, int64_t rows);
+/* advhip_dwconv_t_fwd_f32 on a padded batch ("Padded batches" below): row r of (C, rows, T) ends at row_lens_per_row[r]; the taps
+ * stop there, out is 0 behind it.  n_rows = the number of lengths, which must be `rows`. */
+int advhip_dwconv_t_fwd_lens_f32(const float* v, const float* w, const float* bias, float* out, int32_t C, int32_t H, int64_t rows,
+                                 int32_t T, int32_t K, const int32_t* row_lens_per_row, int64_t n_rows, void* stream);
 int advhip_dwconv_t_bwd_f32(const float* dout, const float* v, const float* w, float* dv, float* partial, int32_t C, int32_t H,
                             int64_t rows, int32_t T, int32_t K, void* stream);
 
@@ -637,6 +659,11 @@ int advhip_glance_attention_fwd_anyt_f32(const float* qkv, float* out, float* ls
                                          float scale, void* stream);
 int advhip_glance_attention_bwd_anyt_f32(const float* dout, const float* qkv, const float* out, const float* lse, float* dqkv, int32_t heads,
                                          int64_t B, int32_t T, int32_t dim_head, float scale, void* stream);
+/* The any-T forward on a padded batch ("Padded batches" above): sequence b still starts at column b * T but has row_lens[b] keys
+ * and queries; out is 0 for the queries behind them.  The same two kernels (chosen per launch from T, as above) with the length in
+ * T's place: a sequence with row_lens[b] = T gets the bits of advhip_glance_attention_fwd_anyt_f32.  No lse, no backward. */
+int advhip_glance_attention_fwd_lens_f32(const float* qkv, float* out, const int32_t* row_lens, int32_t heads, int64_t B, int32_t T,
+                                         int32_t dim_head, float scale, void* stream);
 
 /* A per-input-channel affine map x -> mul[c] x[c] + add[c] folded into the 1x1 layer W (O, C) (+ bias, nullable) that follows it:
  *   Wf[o][c] = W[o][c] mul[c];  bias_f[o] = bias[o] + sum_c W[o][c] add[c] (add nullable: 0);  rowsum[o] = sum_c Wf[o][c] (nullable).
@@ -664,6 +691,11 @@ int advhip_head_ln_fc_bwd_f32(const float* d_xn, const float* d_score, const flo
  * (bs*ncrops, T): mag[b,t] = mean_c ||features[b*ncrops+c, t, :]||_2, sc[b,t] = mean_c scores. */
 int advhip_mil_magnitude_f32(const float* features, const float* scores, float* mag, float* sc,
                              int32_t bs, int32_t ncrops, int32_t T, int32_t F, void* stream);
+/* The crop mean of a padded batch's per-crop scores (n_videos * ncrops, Tmax), scattered into a flat per-clip buffer:
+ * dst[dst_offsets[v] + t] = (sum_c scores[(v * ncrops + c) * Tmax + t]) / ncrops for t < lens[v] -- summed in crop order from 0.f,
+ * one division: the bits of advhip_mil_magnitude_f32's sc.  Nothing else of dst is written. */
+int advhip_crop_mean_scatter_f32(const float* scores, const int32_t* lens, const int64_t* dst_offsets, float* dst, int32_t n_videos,
+                                 int32_t ncrops, int32_t Tmax, void* stream);
 
 /* Top-k over T of mag*keep (ties -> lowest index first, as torch.topk on CPU/ROCm for distinct
  * values; modeling_mgfn.py:345-346), gather of the k selected feature rows for every crop in

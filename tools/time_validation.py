@@ -10,6 +10,12 @@ without it).  The two runners are validated alternately, `--rounds` rounds after
 Trainer.validate (its result is a pair of Python floats, so the pass has ended when it returns), medians and ranges; every
 round's two results must be equal.  The model is the configured MGFN at its initial weights (the time does not depend on them).
 
+Batched validation (data.val_batch_videos = 8, 16, 32 with device_metrics=true: length-sorted padded buckets, one scoring pass per
+bucket) runs as three more legs of the same alternation, on the same resident corpus (all legs read ONE resident copy).  Its
+baseline is the device_metrics=true leg of the same run.  Per leg also: buckets, padded / real positions, the plan's input buffer and
+the peak of device memory allocated during a pass above what was allocated before it, the two AUC floats and their difference
+from the per-video leg's, and the largest per-video relative error (max |a - b| / max |b|) of the scores against that leg's.
+
 Also mil_ops.roc_counts alone (its read-back included: wall time) against metrics._ranked on the expanded frames, on the two
 item shapes the plan makes of about 1.1 M frames: 70 000 items of 16 frames each (the default stride) and 1 100 000 items of one
 frame each (overlapping windows).
@@ -42,6 +48,9 @@ ap.add_argument("--label", default="")
 ap.add_argument("--step", choices=["corpus", "validate", "counts"], help="(internal) run one step in this process")
 ap.add_argument("--dir", help="(internal) the working directory of the steps")
 args = ap.parse_args()
+
+
+BATCH_LEGS = (8, 16, 32)
 
 
 def median_range(v):
@@ -89,35 +98,66 @@ def step_validate(workdir):
     if not torch.cuda.is_available():
         raise SystemExit("time_validation: no GPU visible")
 
-    def runner_for(flag):
+    loaded = []
+
+    def runner_for(flag, batch_videos=1):
         cfg = compose(os.path.join(ROOT, "configs"), "default", ["data=synthetic", f"data.local_path={workdir}", "data.batch_size=2",
-                                                                 "data.resident=true", f"data.device_metrics={flag}"])
+                                                                 "data.resident=true", f"data.device_metrics={flag}",
+                                                                 f"data.val_batch_videos={batch_videos}"])
         torch.manual_seed(0)
         model = _locate(cfg.runner.model_class)(instantiate(cfg.runner.model_config))
         runner = _locate(cfg.runner.cls)(model=model, optimizer=cfg.runner.optimizer, data=cfg.data)
         trainer = Trainer(max_epochs=1)
-        runner.to(trainer.device).setup("fit")
+        runner.to(trainer.device)
+        if not loaded:
+            runner.setup("fit")
+            loaded.append(runner)
+        else:  # the same resident corpus for every leg: what setup does after loading
+            runner.train_dataset, runner.valid_dataset = loaded[0].train_dataset, loaded[0].valid_dataset
+            runner.build_validation_plans()
         return trainer, runner
 
-    sides = {"host metrics (device_metrics=false)": runner_for("false"), "device metrics (device_metrics=true)": runner_for("true")}
+    HOST, DEVICE = "host metrics (device_metrics=false)", "device metrics (device_metrics=true)"
+    sides = {HOST: runner_for("false"), DEVICE: runner_for("true")}
+    batched = {f"batched, val_batch_videos={k} (device_metrics=true)": k for k in BATCH_LEGS}
+    sides.update({name: runner_for("true", k) for name, k in batched.items()})
     runs = {k: [] for k in sides}
-    results = []
+    peak = {k: 0 for k in sides}
+    results, got = [], {}
     for rnd in range(-1, args.rounds):  # round -1: the warm-up
         got = {}
         for name, (trainer, runner) in sides.items():
             torch.cuda.synchronize()
+            before = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
             t = time.perf_counter()
             got[name] = trainer.validate(runner)
             ms = (time.perf_counter() - t) * 1e3
+            peak[name] = max(peak[name], torch.cuda.max_memory_allocated() - before)
             if rnd >= 0:
                 runs[name].append(ms)
             print(rnd, name, f"{ms:.2f} ms", json.dumps(got[name]), flush=True)
-        a, b = got.values()
-        if a != b:
-            raise SystemExit(f"time_validation: the two paths disagree: {a} vs {b}")
-        results.append(a)
+        if got[HOST] != got[DEVICE]:
+            raise SystemExit(f"time_validation: the two per-video paths disagree: {got[HOST]} vs {got[DEVICE]}")
+        results.append(got[HOST])
+    # the batched legs against the per-video leg of the same process: scores video by video, the two AUCs
+    base_runner = sides[DEVICE][1]
+    base = base_runner.auc_plan.scores.double().cpu().numpy()
+    offs = base_runner.auc_plan.items.window_offsets
+    legs = {}
+    for name, k in batched.items():
+        runner = sides[name][1]
+        sc = runner.auc_plan.scores.double().cpu().numpy()
+        errs = [float(np.abs(sc[int(offs[i]):int(offs[i + 1])] - base[int(offs[i]):int(offs[i + 1])]).max() / np.abs(base[int(offs[i]):int(offs[i + 1])]).max())
+                for i in range(len(offs) - 1)]
+        plan = runner.score_plan
+        legs[name] = {"val_batch_videos": k, "buckets": len(plan.buckets), "padded_over_real_positions": round(plan.padding_ratio, 4),
+                      "plan_input_buffer_bytes": plan.buffer_bytes, "peak_bytes_allocated_during_a_pass": int(peak[name]),
+                      "metrics": got[name], "metrics_minus_per_video": {m: got[name][m] - got[DEVICE][m] for m in got[name]},
+                      "max_per_video_rel_err_vs_per_video": max(errs),
+                      "every_round_below_every_per_video_round": max(runs[name]) < min(runs[DEVICE])}
     return {"ms_per_validate": {k: median_range(v) for k, v in runs.items()}, "ms_per_validate_runs": runs, "metrics": results[-1],
-            "device": torch.cuda.get_device_name(0)}
+            "peak_bytes_allocated_during_a_pass": {k: int(v) for k, v in peak.items()}, "batched": legs, "device": torch.cuda.get_device_name(0)}
 
 
 def step_counts():
@@ -164,7 +204,7 @@ if args.step:
 
 rec = {"tool": "tools/time_validation.py", "label": args.label, "rounds": args.rounds}
 with tempfile.TemporaryDirectory() as tmp:
-    for step, limit in (("corpus", 600), ("validate", 480), ("counts", 180)):  # seconds; the first failure ends the run
+    for step, limit in (("corpus", 600), ("validate", 600), ("counts", 180)):  # seconds; the first failure ends the run
         t = time.perf_counter()
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--dir", tmp,
                "--rounds", str(args.rounds), "--videos", str(args.videos), "--channels", str(args.channels)]
@@ -175,10 +215,12 @@ with tempfile.TemporaryDirectory() as tmp:
         with open(os.path.join(tmp, step + ".json")) as f:
             rec[step] = json.load(f)
 v = rec["validate"]["ms_per_validate"]
-off, on = (v[k]["median"] for k in v)
+off, on = (v[k]["median"] for k in list(v)[:2])  # the two per-video legs: metrics on the host, on the device
 rec["device"] = rec["validate"].pop("device")
 rec["ratio_device_over_host_metrics"] = round(on / off, 4)
-print(json.dumps({"ms_per_validate": v, "ratio": rec["ratio_device_over_host_metrics"], "counts": rec["counts"]}), flush=True)
+rec["ratio_batched_over_per_video_device_metrics"] = {k: round(v[k]["median"] / on, 4) for k in list(v)[2:]}
+print(json.dumps({"ms_per_validate": v, "ratio": rec["ratio_device_over_host_metrics"], "batched_ratio": rec["ratio_batched_over_per_video_device_metrics"],
+                  "batched": rec["validate"]["batched"], "counts": rec["counts"]}), flush=True)
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "w") as f:
     json.dump(rec, f, indent=1)
