@@ -254,6 +254,8 @@ SIGNATURES = {
     "advhip_mask_tail_f32": (C.c_int, [_P, _I, _L, _I, _P, _P]),
     "advhip_pack_padded_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "advhip_crop_mean_scatter_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    # (src0, idx0, lab0, n0, b0, src1, idx1, lab1, n1, b1, dst, dst_lab0, dst_lab1, R, stream): rows of two stores by index, one launch
+    "advhip_gather_batch_f32": (C.c_int, [_P, _P, _P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _P, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -67,6 +67,56 @@ __global__ __launch_bounds__(256) void crop_mean_scatter_kernel(const float* __r
   dst[dst_offsets[v] + t] = s / (float)ncrops;
 }
 
+// A shuffled training step's input in one launch: rows idx0[0..b0) of store 0 and rows idx1[0..b1) of store 1 (fp32 rows of R floats)
+// into rows [0, b0) and [b0, b0 + b1) of dst, the rows' labels beside them.  A row (2.6 MB at the training shape) is cut into chunks
+// of 256 * GATHER_UNROLL elements of V: blockIdx.x = chunk, blockIdx.y = destination row, so 32 rows fill the chip.  V = u32x4 when
+// both stores, dst and R * 4 are multiples of 16 bytes (the host decides), else one dword: never an unaligned 16-byte access.  Every
+// lane issues its GATHER_UNROLL loads before its first store.  Bits are moved as integers.  An index outside [0, n) reads nothing:
+// its row and its label become NaN.  All element offsets are 64-bit (idx * R passes 2^31 in a store of 810 such rows).
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+constexpr int GATHER_UNROLL = 4;
+constexpr unsigned GATHER_NAN = 0x7fc00000u;
+
+template <typename V>
+__device__ __forceinline__ V gather_nan();
+template <>
+__device__ __forceinline__ unsigned gather_nan<unsigned>() { return GATHER_NAN; }
+template <>
+__device__ __forceinline__ u32x4 gather_nan<u32x4>() { return u32x4{GATHER_NAN, GATHER_NAN, GATHER_NAN, GATHER_NAN}; }
+
+template <typename V>
+__global__ __launch_bounds__(256) void gather_batch_kernel(const float* __restrict__ src0, const long long* __restrict__ idx0,
+                                                           const float* __restrict__ lab0, long long n0, int b0,
+                                                           const float* __restrict__ src1, const long long* __restrict__ idx1,
+                                                           const float* __restrict__ lab1, long long n1, float* __restrict__ dst,
+                                                           float* __restrict__ dst_lab0, float* __restrict__ dst_lab1, long long R) {
+  const int row = blockIdx.y;
+  const bool second = row >= b0;
+  const long long i = second ? idx1[row - b0] : idx0[row];
+  const bool valid = i >= 0 && i < (second ? n1 : n0);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const float* lab = second ? lab1 : lab0;
+    float* dl = second ? dst_lab1 : dst_lab0;
+    if (dl) reinterpret_cast<unsigned*>(dl)[second ? row - b0 : row] = valid ? reinterpret_cast<const unsigned*>(lab)[i] : GATHER_NAN;
+  }
+  const long long RV = R / (long long)(sizeof(V) / 4);  // a row in elements of V
+  const V* s = reinterpret_cast<const V*>((second ? src1 : src0) + (valid ? i : 0) * R);
+  V* d = reinterpret_cast<V*>(dst + (long long)row * R);
+  const long long e0 = (long long)blockIdx.x * (256 * GATHER_UNROLL) + threadIdx.x;
+  V v[GATHER_UNROLL];
+#pragma unroll
+  for (int u = 0; u < GATHER_UNROLL; ++u) {
+    const long long e = e0 + u * 256;
+    v[u] = gather_nan<V>();
+    if (valid && e < RV) v[u] = s[e];
+  }
+#pragma unroll
+  for (int u = 0; u < GATHER_UNROLL; ++u) {
+    const long long e = e0 + u * 256;
+    if (e < RV) d[e] = v[u];
+  }
+}
+
 __global__ void mil_magnitude_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ d_mag,
                                          const float* __restrict__ d_sc, float* __restrict__ d_feat,
                                          float* __restrict__ d_scores, int bs, int ncrops, int T, int F) {
@@ -244,4 +294,32 @@ extern "C" int advhip_crop_mean_scatter_f32(const float* scores, const int32_t* 
   hipLaunchKernelGGL(crop_mean_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, (const int*)lens,
                      (const long long*)dst_offsets, dst, n_videos, ncrops, Tmax);
   return check_launch("crop_mean_scatter");
+}
+
+extern "C" int advhip_gather_batch_f32(const float* src0, const int64_t* idx0, const float* lab0, int64_t n0, int32_t b0, const float* src1,
+                                       const int64_t* idx1, const float* lab1, int64_t n1, int32_t b1, float* dst, float* dst_lab0,
+                                       float* dst_lab1, int64_t R, void* stream) {
+  ADVHIP_REQUIRE(src0 && idx0 && dst, "gather_batch: null pointer");
+  ADVHIP_REQUIRE(n0 > 0 && b0 > 0 && R > 0 && b1 >= 0, "gather_batch: bad sizes (n0=%lld b0=%d b1=%d R=%lld)", (long long)n0, b0, b1, (long long)R);
+  ADVHIP_REQUIRE((lab0 == nullptr) == (dst_lab0 == nullptr), "gather_batch: labels of store 0 need both a source and a destination");
+  if (b1 > 0) {
+    ADVHIP_REQUIRE(src1 && idx1 && n1 > 0, "gather_batch: second store: null pointer or n1=%lld", (long long)n1);
+    ADVHIP_REQUIRE((lab1 == nullptr) == (dst_lab1 == nullptr), "gather_batch: labels of store 1 need both a source and a destination");
+  } else {
+    src1 = nullptr, idx1 = nullptr, lab1 = nullptr, dst_lab1 = nullptr;
+  }
+  const auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = (R & 3) == 0 && aligned(src0) && aligned(dst) && (b1 == 0 || aligned(src1));
+  const long long rows = (long long)b0 + b1, per_chunk = 256ll * GATHER_UNROLL * (vec ? 4 : 1);
+  const long long chunks = (R + per_chunk - 1) / per_chunk;
+  ADVHIP_REQUIRE(rows <= 65535 && chunks * rows * 256 < (1ll << 32), "gather_batch: %lld rows of %lld floats are outside the launch grid", rows,
+                 (long long)R);
+  const dim3 grid((unsigned)chunks, (unsigned)rows);
+  if (vec)
+    hipLaunchKernelGGL(gather_batch_kernel<u32x4>, grid, dim3(256), 0, (hipStream_t)stream, src0, (const long long*)idx0, lab0, (long long)n0, b0, src1,
+                       (const long long*)idx1, lab1, (long long)n1, dst, dst_lab0, dst_lab1, (long long)R);
+  else
+    hipLaunchKernelGGL(gather_batch_kernel<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, src0, (const long long*)idx0, lab0, (long long)n0, b0, src1,
+                       (const long long*)idx1, lab1, (long long)n1, dst, dst_lab0, dst_lab1, (long long)R);
+  return check_launch("gather_batch");
 }

@@ -17,7 +17,7 @@ import zipfile
 from typing import Callable, Dict, List, Optional, Union
 
 import numpy as np
-from torch.utils.data import Dataset
+from torch.utils.data import Dataset, Sampler
 
 DEFAULT_FEATURE_HUB = "jinmang2/ucf_crime_tencrop_i3d_seg32"
 DEFAULT_FILENAMES = {"train": "train.zip", "test": "test.zip"}
@@ -84,6 +84,39 @@ def _build_feature_dataset(filepath: str, mode: str, dynamic_load: bool, ground_
     return out
 
 
+# ---------------------------------------------------------------------------------- epoch shuffling (data.shuffle)
+def epoch_order(n: int, seed: int, stream: int, epoch: int, restart: int = 0) -> np.ndarray:
+    """The order (int64, a permutation of range(n)) in which a class's videos are visited: a stated function of four integers,
+    np.random.RandomState([seed, stream, epoch, restart]).permutation(n) -- NumPy's frozen generator, so it depends on no torch
+    version and no process state, and a resumed run reproduces it.  `stream`: 0 = the normal class, 1 = the abnormal one;
+    `restart`: how often that class's loader has been started again inside the epoch (Trainer._max_size_cycle restarts the shorter
+    class).  Each of the four lies in [0, 2**32)."""
+    for name, v in (("seed", seed), ("stream", stream), ("epoch", epoch), ("restart", restart)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 32:
+            raise ValueError(f"epoch_order: {name}={v!r} is outside [0, 2**32)")
+    if int(n) < 0:
+        raise ValueError(f"epoch_order: n={n!r} is negative")
+    return np.random.RandomState([int(seed), int(stream), int(epoch), int(restart)]).permutation(int(n)).astype(np.int64, copy=False)
+
+
+class ShuffledSampler(Sampler):
+    """The sampler of a host DataLoader under data.shuffle: every __iter__ yields the next restart's `epoch_order`, starting at
+    restart 0.  A DataLoader iterates its sampler in the main process, so the order is the same at any num_workers."""
+
+    def __init__(self, n: int, seed: int, stream: int, epoch: int):
+        epoch_order(0, seed, stream, epoch)  # (refuses bad values here, not at the first batch)
+        self.n, self.seed, self.stream, self.epoch = int(n), int(seed), int(stream), int(epoch)
+        self.restart = 0
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __iter__(self):
+        order = epoch_order(self.n, self.seed, self.stream, self.epoch, self.restart)
+        self.restart += 1
+        return iter(order.tolist())
+
+
 # ---------------------------------------------------------------------------------- device-resident datasets
 DEFAULT_RESIDENT_MAX_BYTES = 32 << 30  # a guard against a corpus that cannot fit, not a tuned value (UCF-Crime: about 10 GB)
 
@@ -142,6 +175,57 @@ class ResidentBatches:
         b = self.batch_size
         for i in range(len(self)):
             yield {"feature": self.dataset.features[i * b:(i + 1) * b], "anomaly": self.dataset.anomaly[i * b:(i + 1) * b]}
+
+
+class StoreRows:
+    """One class's half of a shuffled resident step: rows `rows` (a device int64 vector, a view of the loader's order table) of
+    `dataset`'s store.  Trainer._feed_graph_inputs gathers a pair of them straight into the captured step's buffers
+    (mil_ops.gather_batch: one launch); `materialize()` gives the ordinary batch dict, gathered with the same op into a buffer the
+    loader owns (overwritten by the loader's next materialised step)."""
+
+    def __init__(self, loader: "ShuffledResidentBatches", rows):
+        self.loader, self.dataset, self.rows = loader, loader.dataset, rows
+
+    def materialize(self) -> Dict:
+        from . import mil_ops
+
+        ds = self.dataset
+        feature, anomaly = self.loader.buffers()
+        mil_ops.gather_batch(ds.features, self.rows, None, None, feature, labels0=ds.anomaly, dst_labels0=anomaly)
+        return {"feature": feature, "anomaly": anomaly}
+
+
+class ShuffledResidentBatches(ResidentBatches):
+    """ResidentBatches under data.shuffle: every __iter__ takes the next restart's epoch_order(len(dataset), seed, stream, epoch,
+    restart), keeps its first len(self) * batch_size entries (what drop_last keeps) and puts them on the device once -- from pinned
+    memory, non-blocking, on the current stream; no per-step upload, no synchronisation.  Step i is a `StoreRows` over the view
+    [i*B, (i+1)*B) of that table (`self.table`: the last one uploaded)."""
+
+    def __init__(self, dataset, batch_size: int, seed: int, stream: int, epoch: int):
+        super().__init__(dataset, batch_size)
+        epoch_order(0, seed, stream, epoch)
+        self.seed, self.stream, self.epoch, self.restart = int(seed), int(stream), int(epoch), 0
+        self.table = None
+        self._buffers = None
+
+    def buffers(self):
+        if self._buffers is None:
+            import torch
+
+            f = self.dataset.features
+            self._buffers = (torch.empty((self.batch_size,) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device),
+                             torch.empty((self.batch_size,), dtype=self.dataset.anomaly.dtype, device=f.device))
+        return self._buffers
+
+    def __iter__(self):
+        import torch
+
+        b, steps = self.batch_size, len(self)
+        order = epoch_order(len(self.dataset), self.seed, self.stream, self.epoch, self.restart)[:steps * b]
+        self.restart += 1
+        # (a fresh pinned block per start: torch's host allocator hands it out again only after this copy has run)
+        table = self.table = torch.from_numpy(np.ascontiguousarray(order)).pin_memory().to(self.dataset.features.device, non_blocking=True)
+        return (StoreRows(self, table[i * b:(i + 1) * b]) for i in range(steps))
 
 
 class ResidentItems:

@@ -236,6 +236,62 @@ def pack_padded(store: torch.Tensor, src_offsets: torch.Tensor, lens: torch.Tens
     return dst
 
 
+def _gather_side(store, idx, labels, dst_labels, what: str):
+    """Checks of one store of `gather_batch` -> (n, R, b)."""
+    err = _lib.HipExtensionError
+    if not (torch.is_tensor(store) and store.dtype == torch.float32 and store.dim() >= 1 and store.numel() > 0 and store.is_contiguous()):
+        raise err(f"{what}: the store must be a non-empty contiguous fp32 tensor (n, ...), got "
+                  f"{getattr(store, 'dtype', type(store))} {tuple(getattr(store, 'shape', ()))}")
+    if not (torch.is_tensor(idx) and idx.dtype == torch.int64 and idx.dim() == 1 and idx.numel() > 0 and idx.is_contiguous()
+            and idx.device == store.device):
+        raise err(f"{what}: the index must be a non-empty contiguous int64 vector on {store.device}, got "
+                  f"{getattr(idx, 'dtype', type(idx))} {tuple(getattr(idx, 'shape', ()))} on {getattr(idx, 'device', None)}")
+    n, b = store.shape[0], idx.numel()
+    if (labels is None) != (dst_labels is None):
+        raise err(f"{what}: labels need both a source and a destination")
+    if labels is not None:
+        for t, k, name in ((labels, n, "labels"), (dst_labels, b, "label destination")):
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == (k,) and t.is_contiguous() and t.device == store.device):
+                raise err(f"{what}: the {name} must be a contiguous fp32 ({k},) vector on {store.device}")
+    return n, store.numel() // n, b
+
+
+def gather_batch(store0: torch.Tensor, idx0: torch.Tensor, store1: Optional[torch.Tensor], idx1: Optional[torch.Tensor], dst: torch.Tensor,
+                 labels0: Optional[torch.Tensor] = None, labels1: Optional[torch.Tensor] = None, dst_labels0: Optional[torch.Tensor] = None,
+                 dst_labels1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch fills dst (b0 + b1, *row) fp32: dst[i] = store0[idx0[i]] for i < b0, dst[b0 + i] = store1[idx1[i]], for contiguous
+    fp32 stores (n, *row) of one row shape and device int64 index vectors (nothing is read back); with labels, dst_labels0[i] =
+    labels0[idx0[i]] and dst_labels1[i] = labels1[idx1[i]].  `store1` / `idx1` None: one store.  A copy of bits.  An index outside
+    [0, n) gives a NaN row and a NaN label.  Stores and dst may be views at any 4-byte boundary.  No autograd."""
+    err = _lib.HipExtensionError
+    require_gpu(store0, idx0, store1, idx1, dst, labels0, labels1, dst_labels0, dst_labels1)
+    n0, R, b0 = _gather_side(store0, idx0, labels0, dst_labels0, "gather_batch")
+    n1 = b1 = 0
+    if store1 is not None or idx1 is not None:
+        n1, R1, b1 = _gather_side(store1, idx1, labels1, dst_labels1, "gather_batch (second store)")
+        if tuple(store1.shape[1:]) != tuple(store0.shape[1:]) or store1.device != store0.device:
+            raise err(f"gather_batch: the stores' rows differ: {tuple(store0.shape[1:])} on {store0.device} and {tuple(store1.shape[1:])} on {store1.device}")
+    elif labels1 is not None or dst_labels1 is not None:
+        raise err("gather_batch: labels of a second store that is not given")
+    want = (b0 + b1,) + tuple(store0.shape[1:])
+    if not (torch.is_tensor(dst) and dst.dtype == torch.float32 and tuple(dst.shape) == want and dst.device == store0.device):
+        raise err(f"gather_batch: dst must be fp32 {want} on {store0.device}, got {getattr(dst, 'dtype', type(dst))} "
+                  f"{tuple(getattr(dst, 'shape', ()))} on {getattr(dst, 'device', None)}")
+    check(_lib.load().advhip_gather_batch_f32(ptr(store0), ptr(idx0), ptr(labels0), n0, b0, ptr(store1), ptr(idx1), ptr(labels1), n1, b1, ptr(dst),
+                                              ptr(dst_labels0), ptr(dst_labels1), R, stream()), "gather_batch")
+    return dst
+
+
+def gather_rows(store: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """store[idx] for a contiguous fp32 store (n, *row) and a device int64 index vector, bit for bit, as one HIP launch (`gather_batch`
+    with one store).  `out`: a contiguous fp32 (len(idx), *row) tensor on the same device to write into.  An index outside [0, n)
+    gives a NaN row (torch indexing would wrap a negative one and fault on a large one)."""
+    require_gpu(store, idx, out)
+    if out is None and torch.is_tensor(store) and torch.is_tensor(idx) and idx.dim() == 1:
+        out = torch.empty((idx.numel(),) + tuple(store.shape[1:]), device=store.device, dtype=torch.float32)
+    return gather_batch(store, idx, None, None, out)
+
+
 LOSS_TERMS = ("total", "bce", "con", "con_a", "con_n", "smooth", "sparse", "mgfn")
 
 

@@ -20,7 +20,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from . import metrics, mgfn_ops
-from .dataset import ResidentBatches, ResidentFeatureDataset, ResidentItems, build_feature_dataset
+from .dataset import (ResidentBatches, ResidentFeatureDataset, ResidentItems, ShuffledResidentBatches, ShuffledSampler, StoreRows,
+                      build_feature_dataset)
 
 
 class VideoAnomalyDetectionRunner:
@@ -33,6 +34,7 @@ class VideoAnomalyDetectionRunner:
         self._val_scores = None  # ... and, without device_metrics, the flat device buffer its passes write
         self.logged: Dict[str, float] = {}
         self.device = torch.device("cpu")
+        self.current_epoch = 0  # set by Trainer.fit before every train_dataloader(): what data.shuffle's order is a function of
 
     # -- logging hook the Trainer reads back
     def log(self, name: str, value, **_kw) -> None:
@@ -118,6 +120,9 @@ class VideoAnomalyDetectionRunner:
         kw = dict(revision=d.get("revision", "main"), cache_dir=d.get("cache_dir"), dynamic_load=bool(d.get("dynamic_load", False)))
         local = d.get("local_path")
         self.auc_plan = self.score_plan = None
+        seed = d.get("seed", 0)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"data.seed={seed!r} is outside [0, 2**32): the shuffled order is NumPy's RandomState([seed, class, epoch, restart])")
         device_metrics = bool(d.get("device_metrics", False))
         if device_metrics and not bool(d.get("resident", False)):
             raise ValueError("data.device_metrics=true needs data.resident=true: the validation scores stay on the device only "
@@ -163,6 +168,14 @@ class VideoAnomalyDetectionRunner:
     # runner.py:108-124 -- two loaders zipped, shuffle=False, drop_last=True
     def train_dataloader(self) -> Tuple[DataLoader, DataLoader]:
         d = self.hparams.data
+        if bool(d.get("shuffle", False)):
+            # data.shuffle: both classes in dataset.epoch_order(n, seed, class, current_epoch, restart) -- the same rule in both paths
+            seed, epoch, bs = int(d.get("seed", 0)), int(self.current_epoch), int(d["batch_size"])
+            classes = tuple(enumerate(("normal", "abnormal")))
+            if isinstance(self.train_dataset["normal"], ResidentFeatureDataset):
+                return tuple(ShuffledResidentBatches(self.train_dataset[cls], bs, seed, stream, epoch) for stream, cls in classes)
+            return tuple(DataLoader(self.train_dataset[cls], batch_size=bs, sampler=ShuffledSampler(len(self.train_dataset[cls]), seed, stream, epoch),
+                                    drop_last=True, num_workers=int(d.get("num_workers", 0))) for stream, cls in classes)
         if isinstance(self.train_dataset["normal"], ResidentFeatureDataset):
             return tuple(ResidentBatches(self.train_dataset[cls], int(d["batch_size"])) for cls in ("normal", "abnormal"))
         mk = lambda ds: DataLoader(ds, batch_size=int(d["batch_size"]), shuffle=False, drop_last=True, num_workers=int(d.get("num_workers", 0)))
@@ -347,6 +360,7 @@ class Trainer:
         self.graphed_step = graphed
         for epoch in range(first_epoch, self.max_epochs):
             runner.model.train()
+            runner.current_epoch = epoch  # (Lightning's name for it: data.shuffle's order is a function of the epoch, hence resumable)
             nloader, aloader = runner.train_dataloader()
             for batch_idx, batch in enumerate(self._max_size_cycle(nloader, aloader)):
                 if 0 <= self.max_steps <= self.global_step:
@@ -355,9 +369,9 @@ class Trainer:
                     # (the host batch went straight into the captured step's input buffers: no torch.cat, no staging copy)
                     runner.log("train_loss", graphed(*graphed.inputs()))
                 elif graphed is not None:
-                    runner.log("train_loss", graphed(*runner.training_batch(_to_device(batch, self.device))))
+                    runner.log("train_loss", graphed(*runner.training_batch(_to_device(self._plain_batch(batch), self.device))))
                 else:
-                    batch = _to_device(batch, self.device)
+                    batch = _to_device(self._plain_batch(batch), self.device)
                     optimizer.zero_grad(set_to_none=True)
                     loss = runner.training_step(batch, batch_idx)
                     loss.backward()
@@ -383,6 +397,14 @@ class Trainer:
                 break
 
     @staticmethod
+    def _plain_batch(batch):
+        """data.shuffle on the resident path hands out `StoreRows`; outside a graph replay (eager steps, the capture, a subclass's
+        training_step) the step gets the ordinary batch dicts, gathered into the loaders' own buffers.  Other batches pass as given."""
+        if isinstance(batch, (tuple, list)) and any(isinstance(b, StoreRows) for b in batch):
+            return tuple(b.materialize() if isinstance(b, StoreRows) else b for b in batch)
+        return batch
+
+    @staticmethod
     def _feed_graph_inputs(graphed, batch) -> bool:
         """Copy a (normal, abnormal) loader batch into the captured step's input buffers: normal features into rows [0, B) of the
         video buffer, abnormal ones into [B, 2B) (src/runner.py:29-39's torch.cat order), the two label vectors into theirs.
@@ -390,6 +412,21 @@ class Trainer:
         static = graphed.inputs()
         if static is None:
             return False
+        if isinstance(batch, (tuple, list)) and len(batch) == 2 and isinstance(batch[0], StoreRows) and isinstance(batch[1], StoreRows):
+            # data.shuffle, resident: one gather launch writes both classes' rows and labels from the stores into the buffers -- on
+            # the current stream, like the copies below; no batch tensor in between
+            from . import mil_ops
+
+            (nds, nrows), (ads, arows) = ((b.dataset, b.rows) for b in batch)
+            video, s_al, s_nl = static
+            b = nrows.shape[0]
+            if (arows.shape[0] != b or (2 * b,) + tuple(nds.features.shape[1:]) != tuple(video.shape) or ads.features.shape[1:] != nds.features.shape[1:]
+                    or tuple(s_al.shape) != (b,) or tuple(s_nl.shape) != (b,)
+                    or any(t.dtype != video.dtype or t.device != video.device for t in (nds.features, ads.features, nds.anomaly, ads.anomaly, s_al, s_nl))):
+                return False
+            mil_ops.gather_batch(nds.features, nrows, ads.features, arows, video, labels0=nds.anomaly, labels1=ads.anomaly, dst_labels0=s_nl,
+                                 dst_labels1=s_al)
+            return True
         try:
             ninputs, ainputs = batch
             nf, af, al, nl = ninputs["feature"], ainputs["feature"], ainputs["anomaly"], ninputs["anomaly"]

@@ -585,6 +585,15 @@ int advhip_mask_tail_f32(float* x, int32_t C, int64_t rows, int32_t T, const int
  * dst[v, c, t < lens[v], :] of dst (n_videos, ncrops, Tmax, width).  Rows t >= lens[v] of dst are left as they are. */
 int advhip_pack_padded_f32(const float* store, const int64_t* src_offsets, const int32_t* lens, float* dst, int32_t n_videos, int32_t ncrops,
                            int32_t Tmax, int32_t width, void* stream);
+/* A shuffled training step's input in one launch: dst (b0 + b1, R) fp32 gets src0[idx0[i]] in row i < b0 and src1[idx1[i]] in row
+ * b0 + i, for stores src0 (n0, R) and src1 (n1, R) and device int64 index vectors; dst_lab0[i] = lab0[idx0[i]] and dst_lab1[i] =
+ * lab1[idx1[i]] beside them (lab / dst_lab of a store: both or neither).  b1 = 0: no second store (its arguments are not read).
+ * A copy of bits: NaN payloads, -0.0 and denormals arrive as they are.  An index outside [0, n) reads nothing; its row of dst and
+ * its label are NaN, and no other row changes.  16-byte accesses when the stores, dst and R * 4 are 16-byte multiples, 4-byte ones
+ * otherwise (any 4-byte-aligned view works); element offsets are 64-bit.  b0 + b1 <= 65535. */
+int advhip_gather_batch_f32(const float* src0, const int64_t* idx0, const float* lab0, int64_t n0, int32_t b0, const float* src1,
+                            const int64_t* idx1, const float* lab1, int64_t n1, int32_t b1, float* dst, float* dst_lab0,
+                            float* dst_lab1, int64_t R, void* stream);
 
 /* dst[c] = sum over r, in row order, of src[r][c]: the per-block partial sums the backward kernels above leave to the caller
  * (rows = a few hundred blocks). */

@@ -4,16 +4,20 @@ profiles/train_input_run.json).  bench.py's mgfn_train_step times the captured s
 buffers; this times the loop a user runs.
 
 Corpus: write_synthetic_feature_zips, 64 normal + 64 abnormal train videos at C = 2048 (336 MB of features), batch_size 16 (a step
-reads 2 x 16 videos: 83.9 MB with the magnitude channel), 4 steps per epoch.  Three configurations of the same fit:
+reads 2 x 16 videos: 83.9 MB with the magnitude channel), 4 steps per epoch.  Five configurations of the same fit:
   (a) the host loaders, num_workers=0     (b) the host loaders, num_workers=8     (c) data.resident=true
+  (d) (c) with data.shuffle=true: one advhip_gather_batch_f32 launch per step into the graph's buffers
+  (e) (d)'s order served by four torch.index_select(..., out=) launches per step instead (the formulation the kernel replaces)
 Each fit runs `--epochs` epochs without validation; a callback records a HIP event after every step.  Steps up to `--skip` (the
 eager steps, the capture, the first replays) are left out; over the rest (>= 20 steps):
   ms_per_step              median interval between two consecutive steps' events (the steady step; an epoch's first step, where
                            the loaders are started again, is an outlier the median leaves out)
   ms_per_step_with_starts  (last event - first event) / steps: the epoch starts included, at this corpus' 4 steps per epoch
-The three are alternated, `--rounds` rounds in one process; medians over rounds and every configuration's own spread are kept.
-Also: the one-time resident load (seconds, both zips, synchronised) and the replay alone (the captured step called back to back
-on the buffers as they are), for scale.
+The five are alternated, `--rounds` rounds in one process; medians over rounds and every configuration's own spread are kept.
+(d) and (e) are judged against (c) of the same run, give or take (c)'s own spread (max - min over the rounds): `shuffle` in the record.
+Also: the one-time resident load (seconds, both zips, synchronised), the replay alone (the captured step called back to back
+on the buffers as they are), for scale, and the gather alone (`gather_alone`: the launch called back to back at the step's shape on
+stores of this corpus' size, against the four index_select launches on the same rows).
 
     python tools/time_train_input.py [out.json] [--rounds 5] [--epochs 8] [--skip 8] [--label TEXT]
 """
@@ -30,7 +34,8 @@ import numpy as np
 import torch
 
 from anomaly_detection_on_video_amd.config import _locate, compose, instantiate
-from anomaly_detection_on_video_amd.dataset import write_synthetic_feature_zips
+from anomaly_detection_on_video_amd import mil_ops
+from anomaly_detection_on_video_amd.dataset import StoreRows, epoch_order, write_synthetic_feature_zips
 from anomaly_detection_on_video_amd.runner import Trainer
 
 ap = argparse.ArgumentParser()
@@ -62,7 +67,25 @@ class StepClock:
         return {}
 
 
-def fit(data_dir, overrides):
+REAL_FEED = Trainer._feed_graph_inputs
+
+
+def feed_index_select(graphed, batch):
+    """Trainer._feed_graph_inputs for leg (e): the StoreRows pair through torch.index_select into the graph's buffers."""
+    static = graphed.inputs()
+    if static is None or not all(isinstance(b, StoreRows) for b in batch):
+        return REAL_FEED(graphed, batch)
+    video, s_al, s_nl = static
+    n, a = batch
+    b = n.rows.shape[0]
+    torch.index_select(n.dataset.features, 0, n.rows, out=video[:b])
+    torch.index_select(a.dataset.features, 0, a.rows, out=video[b:])
+    torch.index_select(n.dataset.anomaly, 0, n.rows, out=s_nl)
+    torch.index_select(a.dataset.anomaly, 0, a.rows, out=s_al)
+    return True
+
+
+def fit(data_dir, overrides, feed=None):
     cfg = compose(os.path.join(ROOT, "configs"), "default", ["data=synthetic", f"data.local_path={data_dir}", f"data.batch_size={args.batch}"] + overrides)
     torch.manual_seed(0)
     model = _locate(cfg.runner.model_class)(instantiate(cfg.runner.model_config))
@@ -79,7 +102,11 @@ def fit(data_dir, overrides):
     runner.setup = timed_setup
     clock = StepClock()
     trainer = Trainer(max_epochs=args.epochs, check_val_every_n_epoch=10**9, log_every_n_steps=1, callbacks=[clock])
-    trainer.fit(model=runner)
+    Trainer._feed_graph_inputs = staticmethod(feed or REAL_FEED)
+    try:
+        trainer.fit(model=runner)
+    finally:
+        Trainer._feed_graph_inputs = staticmethod(REAL_FEED)
     torch.cuda.synchronize()
     ev = clock.events[args.skip:]
     gaps = [ev[i].elapsed_time(ev[i + 1]) for i in range(len(ev) - 1)]
@@ -99,7 +126,56 @@ def fit(data_dir, overrides):
     return out
 
 
-CONFIGS = {"loader, num_workers=0": ["data.num_workers=0"], "loader, num_workers=8": ["data.num_workers=8"], "resident": ["data.resident=true"]}
+def gather_alone(videos, batch, calls=40):
+    """The gather launch alone, back to back, at the step's shape: two (videos, 10, 32, 2049) stores, `batch` shuffled rows of each per
+    call (another window of the order every call), against the four index_select launches on the same rows.  The stores together
+    (336 MB at 64 videos) exceed the 256 MB Infinity Cache, but a back-to-back loop still finds part of them there: a lower bound of
+    what the launch costs between two training steps."""
+    shape = (videos, 10, 32, 2049)
+    stores = [torch.randn(shape, device="cuda") for _ in range(2)]
+    labels = [torch.zeros(videos, device="cuda"), torch.ones(videos, device="cuda")]
+    orders = [torch.from_numpy(epoch_order(videos, 0, s, 0)).cuda() for s in (0, 1)]
+    video = torch.empty((2 * batch,) + shape[1:], device="cuda")
+    dl = [torch.empty(batch, device="cuda") for _ in range(2)]
+    windows = videos // batch
+
+    def rows(i):
+        lo = (i % windows) * batch
+        return orders[0][lo:lo + batch], orders[1][lo:lo + batch]
+
+    def kernel(i):
+        r0, r1 = rows(i)
+        mil_ops.gather_batch(stores[0], r0, stores[1], r1, video, labels0=labels[0], labels1=labels[1], dst_labels0=dl[0], dst_labels1=dl[1])
+
+    def index_select(i):
+        r0, r1 = rows(i)
+        torch.index_select(stores[0], 0, r0, out=video[:batch])
+        torch.index_select(stores[1], 0, r1, out=video[batch:])
+        torch.index_select(labels[0], 0, r0, out=dl[0])
+        torch.index_select(labels[1], 0, r1, out=dl[1])
+
+    out = {"calls": calls, "bytes_read_plus_written": 2 * video.numel() * 4}
+    for name, fn in (("kernel", kernel), ("index_select_x4", index_select)):
+        for i in range(5):
+            fn(i)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(calls):
+            fn(i)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1e3 / calls
+        out[name] = {"us": round(us, 2), "TB_per_s": round(out["bytes_read_plus_written"] / (us * 1e-6) / 1e12, 3)}
+    r0, r1 = rows(1)
+    kernel(1)
+    out["kernel_equals_torch_indexing"] = bool(torch.equal(video.view(torch.int32), torch.cat((stores[0][r0], stores[1][r1])).view(torch.int32)))
+    return out
+
+
+SHUFFLED = ["data.resident=true", "data.shuffle=true", "data.seed=1"]
+CONFIGS = {"loader, num_workers=0": ["data.num_workers=0"], "loader, num_workers=8": ["data.num_workers=8"], "resident": ["data.resident=true"],
+           "resident, shuffled": SHUFFLED, "resident, shuffled, index_select": SHUFFLED}
+FEEDS = {"resident, shuffled, index_select": feed_index_select}
 rec = {"tool": "tools/time_train_input.py", "label": args.label, "device": torch.cuda.get_device_name(0), "rounds": args.rounds,
        "corpus": {"train_videos_per_class": args.videos, "channels": 2048, "batch_size": args.batch, "steps_per_epoch": steps_per_epoch,
                   "epochs": args.epochs, "skipped_steps": args.skip}, "runs": {k: [] for k in CONFIGS}}
@@ -109,7 +185,7 @@ with tempfile.TemporaryDirectory() as tmp:
     print(f"corpus written in {time.perf_counter() - t:.1f} s", flush=True)
     for rnd in range(args.rounds):
         for name, ov in CONFIGS.items():
-            r = fit(data_dir, ov)
+            r = fit(data_dir, ov, FEEDS.get(name))
             rec["runs"][name].append(r)
             print(rnd, name, json.dumps(r), flush=True)
 
@@ -122,6 +198,14 @@ for name, runs in rec["runs"].items():
 rec["summary"] = summary
 res = summary["resident"]["ms_per_step"]["median"]
 rec["ratios"] = {f"resident / {k}": round(res / summary[k]["ms_per_step"]["median"], 4) for k in CONFIGS if k != "resident"}
+spread = round(summary["resident"]["ms_per_step"]["max"] - summary["resident"]["ms_per_step"]["min"], 3)
+shuf, isel = (summary[k]["ms_per_step"]["median"] for k in ("resident, shuffled", "resident, shuffled, index_select"))
+rec["shuffle"] = {"resident_ms": res, "resident_spread_ms": spread, "shuffled_ms": shuf, "index_select_ms": isel,
+                  "shuffled_minus_resident_ms": round(shuf - res, 3), "shuffled_minus_index_select_ms": round(shuf - isel, 3),
+                  "shuffled_costs_no_more_than_resident": bool(shuf <= res + spread),
+                  "kernel_not_slower_than_index_select": bool(shuf <= isel + spread)}
+rec["gather_alone"] = gather_alone(args.videos, args.batch)
+print(json.dumps({"shuffle": rec["shuffle"], "gather_alone": rec["gather_alone"]}), flush=True)
 rec["ratios"]["resident / replay alone"] = round(res / summary["resident"]["replay_alone_ms"]["median"], 4)
 rec["resident_load_s"] = summary["resident"]["setup_s"]
 print(json.dumps({"summary": summary, "ratios": rec["ratios"]}), flush=True)
