@@ -105,6 +105,10 @@ class AdamItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq", "step")] + [("n", C.c_int64)]
 
 
+class NormItem(C.Structure):
+    _fields_ = [("grad", C.c_void_p), ("n", C.c_int64)]
+
+
 class NtItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("A", "B", "C", "rowsum")] + [("M", C.c_int32), ("N", C.c_int32), ("lda", C.c_int64), ("ldb", C.c_int64)]
 
@@ -193,6 +197,10 @@ SIGNATURES = {
     "advhip_colsum_f32": (C.c_int, [_P, _P, _L, _I, _P]),
     "advhip_colsum_group_f32": (C.c_int, [C.POINTER(ColsumItem), _I, _P]),
     "advhip_adam_multi_f32": (C.c_int, [C.POINTER(AdamItem), _I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    # (items, n_items, lr_dev (double*), grad_scale_dev (float*, may be null), beta1, beta2, eps, weight_decay, stream)
+    "advhip_adam_multi_dev_f32": (C.c_int, [C.POINTER(AdamItem), _I, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    # (items, n_items, max_norm, partials (double*), n_partials, norm_out, scale_out, stream)
+    "advhip_grad_norm_multi_f32": (C.c_int, [C.POINTER(NormItem), _I, C.c_double, _P, _L, _P, _P, _P]),
     "advhip_pack_item_tiles": (C.c_int64, [_I, _I, _I, _I]),
     "advhip_pack_weights_multi_f32": (C.c_int, [_P, _I, _I, _P]),
     "advhip_unfold3_f32": (C.c_int, [_P, _P, _I, _L, _I, _P]),

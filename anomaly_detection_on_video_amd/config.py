@@ -47,7 +47,9 @@ def _merge(dst: Dict, src: Dict) -> Dict:
 def _set_path(cfg: Dict, dotted: str, value) -> None:
     parts = dotted.split(".")
     for p in parts[:-1]:
-        cfg = cfg.setdefault(p, {})
+        if cfg.get(p) is None:  # (a key that is `null` in the YAML, e.g. runner.optimizer.schedule, opens as a mapping)
+            cfg[p] = {}
+        cfg = cfg[p]
     cfg[parts[-1]] = value
 
 

@@ -24,8 +24,25 @@ from .dataset import (ResidentBatches, ResidentFeatureDataset, ResidentItems, Sh
                       build_feature_dataset)
 
 
+def check_optimizer_options(optimizer, gradient_clip_val=None) -> None:
+    """The optional keys of `runner.optimizer` -- `schedule` (optim.lr_at's spec) and `max_grad_norm` (optim.HipAdam's fused clip) --
+    refused here, before anything is loaded, when they cannot be honoured; `gradient_clip_val`: trainer.cls.gradient_clip_val, torch's
+    clip_grad_norm_ path, which excludes the fused one."""
+    from .optim import check_max_grad_norm, check_schedule
+
+    check_schedule(optimizer.get("schedule"))
+    try:
+        fused = check_max_grad_norm(optimizer.get("max_grad_norm"))
+    except ValueError as e:
+        raise ValueError(f"runner.optimizer.{e}") from None
+    if fused is not None and gradient_clip_val:
+        raise ValueError(f"trainer.cls.gradient_clip_val={gradient_clip_val} and runner.optimizer.max_grad_norm={fused} are both set: they clip the same "
+                         "gradient norm (torch's clip_grad_norm_ launches / HipAdam's fused reduction); set one of them")
+
+
 class VideoAnomalyDetectionRunner:
     def __init__(self, model: torch.nn.Module, optimizer, data):
+        check_optimizer_options(optimizer)
         self.model = model
         self.hparams = type("HParams", (), {"optimizer": optimizer, "data": data})()
         self.validation_step_outputs: List[Dict[str, np.ndarray]] = []
@@ -84,9 +101,12 @@ class VideoAnomalyDetectionRunner:
         for i, labels in enumerate(self.valid_dataset.labels):
             self.validation_step_outputs.append({"preds": flat[plan.offsets[i]:plan.offsets[i + 1]], "labels": labels})
 
-    # runner.py:53-59 -- Adam with L2-in-gradient weight decay, no scheduler
+    # runner.py:53-59 -- Adam with L2-in-gradient weight decay; the reference has no scheduler, here `runner.optimizer.schedule` is one
+    # (Trainer.fit sets the lr from optim.lr_at before every step) and `runner.optimizer.max_grad_norm` a clip fused into HipAdam
     def configure_optimizers(self) -> List[torch.optim.Optimizer]:
         opt = self.hparams.optimizer
+        check_optimizer_options(opt)
+        clip, scheduled = opt.get("max_grad_norm"), opt.get("schedule") is not None
         params = list(self.model.parameters())
         # same update rule as the reference's torch.optim.Adam; on GPU parameters torch's fused implementation (a few launches
         # instead of ~25 multi-tensor ones: 0.73 -> 0.3 ms of the 19-ms step)
@@ -97,7 +117,12 @@ class VideoAnomalyDetectionRunner:
             # ... and here the whole update as one launch per 80 tensors (optim.HipAdam: torch.optim.Adam's rule and state layout)
             from .optim import HipAdam
 
-            return [HipAdam(params, lr=float(opt["learning_rate"]), weight_decay=float(opt["weight_decay"]))]
+            # (a schedule: the lr in device memory, so the captured step survives its per-step changes)
+            return [HipAdam(params, lr=float(opt["learning_rate"]), weight_decay=float(opt["weight_decay"]), device_lr=scheduled,
+                            max_grad_norm=None if clip is None else float(clip))]
+        if clip is not None:
+            raise ValueError(f"runner.optimizer.max_grad_norm={clip} is the clip fused into optim.HipAdam, which this run does not use (ADV_HIP_ADAM=0, or "
+                             "parameters that are not contiguous fp32 on the GPU); trainer.cls.gradient_clip_val clips with torch's launches")
         return [torch.optim.Adam(params, lr=float(opt["learning_rate"]), weight_decay=float(opt["weight_decay"]), fused=fused,
                                  capturable=fused)]
 
@@ -237,6 +262,8 @@ def checkpoint_state(runner: "VideoAnomalyDetectionRunner", optimizer, epoch: in
         "pytorch-lightning_version": LIGHTNING_LAYOUT_VERSION, "loops": {}, "callbacks": {},
         "epoch": epoch, "global_step": global_step,
         "state_dict": {"model." + k: v for k, v in runner.model.state_dict().items()},
+        # (a configured runner.optimizer.schedule is a function of global_step, optim.lr_at: the spec is in hyper_parameters.optimizer,
+        # and there is no scheduler state to save)
         "optimizer_states": [optimizer.state_dict()], "lr_schedulers": [],
         "hyper_parameters": {"optimizer": dict(runner.hparams.optimizer), "data": dict(runner.hparams.data)},
         "metrics": dict(metrics_),
@@ -338,6 +365,7 @@ class Trainer:
     def fit(self, model: VideoAnomalyDetectionRunner, ckpt_path: Optional[str] = None) -> None:
         """`ckpt_path`: resume from a checkpoint (this trainer's or the reference's Lightning layout): weights,
         optimizer state, epoch and global step."""
+        check_optimizer_options(model.hparams.optimizer, self.gradient_clip_val)
         runner = model.to(self.device)
         runner.setup("fit")
         (optimizer,) = runner.configure_optimizers()
@@ -358,10 +386,29 @@ class Trainer:
 
             graphed = GraphedTrainStep(runner.model, optimizer, eager_steps=3, clip_grad_norm=self.gradient_clip_val)
         self.graphed_step = graphed
+        # runner.optimizer.schedule: group["lr"] = optim.lr_at(spec, base, global_step) ahead of every step, eager and graphed alike (with
+        # HipAdam(device_lr) the captured step reads it from device memory; any other optimizer re-captures, then stays eager)
+        from .optim import check_schedule, lr_at
+
+        schedule = check_schedule(runner.hparams.optimizer.get("schedule"))
+        base_lr = float(runner.hparams.optimizer["learning_rate"])
+        self.schedule_total_steps = None if schedule is None else schedule["total_steps"] if schedule["total_steps"] is not None else \
+            self.max_steps if self.max_steps >= 0 else None
+
+        def set_lr():
+            if schedule is not None:
+                lr = lr_at(schedule, base_lr, self.global_step, self.schedule_total_steps)
+                for g in optimizer.param_groups:
+                    g["lr"] = lr
+
+        clipped = getattr(optimizer, "max_grad_norm", None) is not None
         for epoch in range(first_epoch, self.max_epochs):
             runner.model.train()
             runner.current_epoch = epoch  # (Lightning's name for it: data.shuffle's order is a function of the epoch, hence resumable)
             nloader, aloader = runner.train_dataloader()
+            if schedule is not None and self.schedule_total_steps is None:
+                self.schedule_total_steps = self.max_epochs * max(len(nloader), len(aloader))
+            set_lr()
             for batch_idx, batch in enumerate(self._max_size_cycle(nloader, aloader)):
                 if 0 <= self.max_steps <= self.global_step:
                     break
@@ -380,8 +427,11 @@ class Trainer:
                     optimizer.step()
                     mgfn_ops.invalidate_caches()  # (fused optimizers do not move version counters)
                 self.global_step += 1
+                set_lr()  # (the next step's: what LearningRateMonitor logs below is lr_at(global_step), as after a torch scheduler's step())
                 if self.global_step % self.log_every_n_steps == 0:
                     m = {"train_loss": runner.logged["train_loss"], "epoch": epoch}
+                    if clipped:
+                        m["grad_norm"] = float(optimizer.grad_norm)  # (the pre-clip norm of this step: the fused clip's one read-back)
                     for cb in self.callbacks:
                         if hasattr(cb, "on_step"):
                             m.update(cb.on_step(self, optimizer))

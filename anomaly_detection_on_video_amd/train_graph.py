@@ -71,26 +71,38 @@ class GraphedTrainStep:
         self.optimizer.step()
         return loss
 
-    MAX_CAPTURES = 4  # hyper-parameters that keep changing (a per-step LR schedule): after this many captures the step stays eager
+    # hyper-parameters the graph holds BY VALUE that keep changing (a per-step LR schedule on torch's Adam or a default HipAdam): after this
+    # many captures the step stays eager.  HipAdam(device_lr=True) keeps the lr in device memory instead: no re-capture, no limit.
+    MAX_CAPTURES = 4
 
     def _baked(self) -> Tuple:
         """Everything a captured graph holds by value or by address: the parameters' storage (a `.data =` / `.to()` moves it)
         and the optimizer's scalar hyper-parameters (the fused capturable Adam takes lr / betas / eps / weight_decay as kernel
         arguments) and the clip value.  A replay with a different stamp would train with stale numbers or touch freed memory:
-        __call__ compares and captures again."""
-        groups = tuple((float(g["lr"]) if not torch.is_tensor(g["lr"]) else ("t", g["lr"].data_ptr()), tuple(g.get("betas", ())), g.get("eps"),
-                        g.get("weight_decay"), g.get("amsgrad"), g.get("maximize"), tuple(p.data_ptr() for p in g["params"]))
+        __call__ compares and captures again.  An optimizer with `device_lr` (optim.HipAdam) reads its lr from device memory on every
+        replay: the lr is then no part of the stamp; its own clip value and device buffers (`graph_stamp()`) are."""
+        live_lr = bool(getattr(self.optimizer, "device_lr", False))
+        groups = tuple((None if live_lr else float(g["lr"]) if not torch.is_tensor(g["lr"]) else ("t", g["lr"].data_ptr()), tuple(g.get("betas", ())),
+                        g.get("eps"), g.get("weight_decay"), g.get("amsgrad"), g.get("maximize"), tuple(p.data_ptr() for p in g["params"]))
                        for g in self.optimizer.param_groups)
         state = self.optimizer.state  # (optimizer.load_state_dict() replaces these tensors: a replay would update orphaned moments)
         moments = tuple(tuple(state[p][k].data_ptr() if torch.is_tensor(state[p].get(k)) else None for k in ("exp_avg", "exp_avg_sq", "step"))
                         for g in self.optimizer.param_groups for p in g["params"] if p in state)
-        return (groups, self.clip, tuple(p.data_ptr() for p in self.model.parameters()), moments)
+        own = self.optimizer.graph_stamp() if hasattr(self.optimizer, "graph_stamp") else getattr(self.optimizer, "max_grad_norm", None)
+        return (groups, self.clip, tuple(p.data_ptr() for p in self.model.parameters()), moments, own)
 
     def inputs(self) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """The captured graph's own input buffers (video, abnormal_labels, normal_labels), or None while there is no graph.  A feeder
         that writes the next batch straight into them -- runner.Trainer copies the host batch there -- and then calls
         `step(*step.inputs())` saves the device-to-device staging copy of the batch (84 MB at the runner's batch shape)."""
         return self.static if self.graph is not None else None
+
+    def _sync_lr(self) -> None:
+        """A device-side lr is written OUTSIDE the graph (a captured write would replay the captured value): before a replay and before
+        a capture; an eager `optimizer.step()` does it itself."""
+        sync = getattr(self.optimizer, "sync_lr", None)
+        if sync is not None:
+            sync()
 
     def _finish(self) -> None:
         mgfn_ops.invalidate_caches()  # (fused / captured optimizers do not move version counters)
@@ -110,6 +122,7 @@ class GraphedTrainStep:
             for dst, src in zip(self.static, (video, abnormal_labels, normal_labels)):
                 if src.data_ptr() != dst.data_ptr():  # (a caller that filled `inputs()` in place has nothing to copy)
                     dst.copy_(src)
+            self._sync_lr()
             self.graph.replay()
             self.replays += 1
             self._finish()
@@ -130,6 +143,7 @@ class GraphedTrainStep:
         # capture (records, does not run), then replay on this batch
         self._key = key
         self.static = tuple(t.detach().clone() for t in (video, abnormal_labels, normal_labels))
+        self._sync_lr()
         torch.cuda.synchronize()
         self.optimizer.zero_grad(set_to_none=True)  # the captured backward allocates the gradients in the graph's pool
         graph = torch.cuda.CUDAGraph()

@@ -629,6 +629,30 @@ typedef struct advhip_adam_item {
 int advhip_adam_multi_f32(const advhip_adam_item* items, int32_t n_items, double lr, double beta1, double beta2, double eps,
                           double weight_decay, void* stream);
 
+/* The same update with its two per-step scalars in DEVICE memory, where a replay of a captured launch reads them live:
+ *   lr = *lr_dev (a double: lr / (1 - b1^t) is still formed in double and rounded once);
+ *   g  = grad * *grad_scale_dev first, as one separately rounded fp32 product (torch's in-place `g.mul_(coef)` of
+ *        clip_grad_norm_), unless grad_scale_dev is null.  `grad` itself is not written.
+ * Everything after the scaled gradient is the arithmetic of advhip_adam_multi_f32: with *lr_dev == lr and no scale (or 1.0) the
+ * results are bit for bit the same. */
+int advhip_adam_multi_dev_f32(const advhip_adam_item* items, int32_t n_items, const double* lr_dev, const float* grad_scale_dev, double beta1,
+                              double beta2, double eps, double weight_decay, void* stream);
+
+/* Global L2 norm of many fp32 tensors and clip_grad_norm_'s factor, on the device (`items`: a HOST array, carried in the kernel
+ * arguments, 240 tensors per launch):
+ *   *norm_out  = (float)sqrt(sum of squares), the squares formed and added in double (no overflow at |g| > 1.8e19);
+ *   *scale_out = min(1, max_norm / (*norm_out + 1e-6)) in torch's fp32 operations and order: (1 / (norm + 1e-6f)) * (float)max_norm,
+ *                clamped from above; a NaN stays a NaN, an infinite norm gives 0.
+ * Stage 1 writes one double per 4096 consecutive elements of a tensor to `partials` (room for n_partials of them; needed:
+ * the sum over the items of ceil(n / 4096)), stage 2 is one workgroup that adds them.  All orders are fixed and there are no
+ * atomics: the same inputs give the same bits.  max_norm: finite, > 0. */
+typedef struct advhip_norm_item {
+  const float* grad;
+  int64_t n;
+} advhip_norm_item;
+int advhip_grad_norm_multi_f32(const advhip_norm_item* items, int32_t n_items, double max_norm, double* partials, int64_t n_partials,
+                               float* norm_out, float* scale_out, void* stream);
+
 /* The operand of a k = 3, padding 1 Conv1d's weight gradient (autograd of nn.Conv1d, modeling_mgfn.py:101,155):
  * u[(c*3 + j), r, t] = x[c, r, t + j - 1] (zero outside [0, T)), x (C, rows, T) -> u (3C, rows, T); dW = dY . u^T by
  * advhip_gemm_nt_f32.  T a multiple of 4. */
