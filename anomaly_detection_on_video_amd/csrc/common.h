@@ -67,8 +67,9 @@ inline const char* crops_packed_error(int ncrops, unsigned long long packed) {
 }
 
 // The clip-sampling rule of the uint8-frame ops, host side.  Window w of a video samples frames w * clip_stride + t * frame_step,
-// t in [0, fpc); row w * ncrops + j of an op's output holds crop (crops >> 4 j) & 15 of window w.  The kernels restate the frame
-// index on the device; every count and every check of the five numbers is here.
+// t in [0, fpc); row w * ncrops + j of an op's output holds crop (crops >> 4 j) & 15 of window w.  The device restates the frame
+// index once for the TenCrop passes (normalize.hip: crop_row) and in the stems' gather tables; every count and every check of the
+// five numbers is here.
 struct ClipSampling {
   int fpc, clip_stride, frame_step, ncrops;
   unsigned long long crops;

@@ -1,6 +1,9 @@
 // On-device analogues of the numpy post-processing either side of the hot path.
-//   segment_features : /root/reference/extract_features.py:171-183
-//   add_magnitude    : /root/reference/src/dataset.py:121-124
+//   segment_features     : extract_features.py:171-183
+//   add_magnitude        : src/dataset.py:121-124
+//   normalize_permute_u8 : src/dataset.py:175-183 on already cropped uint8 clips
+//   frame_scores         : src/runner.py:66-76
+// (The TenCrop passes from uint8 frames are normalize.hip's.)
 #include <algorithm>
 
 #include "common.h"
@@ -56,7 +59,7 @@ __global__ void add_magnitude_kernel(const float* __restrict__ f, float* __restr
 
 // uint8 frames (N, T, C, H, W) -> fp32 (N, C, T, H, W), y = (x - mean) / std: the reference's
 // PILToTensor().float() + GroupNormalize + the (B,10,16,3,H,W)->(B,10,3,16,H,W) permute
-// (/root/reference/src/dataset.py:175-183, extract_features.py:83) in one pass, so only uint8 crosses
+// (src/dataset.py:175-183, extract_features.py:83) in one pass, so only uint8 crosses
 // PCIe.  Each thread converts 4 consecutive pixels of a row (one 32-bit load, one 16-byte store).
 __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int T, int C,
                                             long long HW, float mean, float stdv, long long total4) {
@@ -79,91 +82,6 @@ __global__ void normalize_permute_u8_kernel(const uint8_t* __restrict__ x, float
   }
 }
 
-// TenCrop + float + normalise + LoopPad + permute in one pass (src/gtransforms.py:20-73, 115-132; src/dataset.py:175-195;
-// extract_features.py:83): resized uint8 frames (F, H, W, C) -- the HWC bytes a decoder / PIL hands over -- to the backbone's
-// input (n_clips * 10, C, fpc, cs, cs) fp32.  Crop j < 5 of a frame = its (top_j, left_j) window: top-left, top-right,
-// bottom-left, bottom-right, centre (torchvision five_crop order; centre offsets are Python-rounded halves, computed by the
-// caller); crops 5..9 = the same five windows of the horizontally flipped frame: pixel (y, x) = frame[top + y][W - 1 - (left + x)].
-// Frame t of clip c = frames[c * cstride + (t % len_c) * fstep], len_c = min(fpc, ceil((F - c * cstride) / fstep)) (LoopPad: a short
-// last clip repeats itself); cstride = the distance between clip starts, fpc * fstep for back-to-back clips, less for overlapping
-// windows; fstep = the temporal sampling step (1: consecutive frames, the reference's clips; d: every d-th frame).
-// A crop SUBSET (nc of the ten, ascending, 4-bit indices packed into `crops`): output row clip * nc + j holds crop
-// (crops >> 4 j) & 15 of that clip -- the same arithmetic per pixel, so the row is the ten-crop pass's row clip * 10 + that crop.
-// One wave per output row (clip, crop, c, t, y): the row decode (five divisions) happens once per 224 outputs, the lanes run
-// along x with 16-byte stores (the first form decoded every float4 separately and indexed a by-value crop table: 165 us for
-// 40 crop-clips, VALU-bound at 2.3 TB/s).
-template <int VW>
-__global__ __launch_bounds__(256) void tencrop_normalize_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int F, int H, int W,
-                                                                   int C, int fpc, int cstride, int cs, int ctop, int cleft, float mean,
-                                                                   float stdv, long long rows, int nc, unsigned long long crops, int fstep) {
-  const int lane = threadIdx.x & 63;
-  const int csv = cs / VW;
-  for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
-    long long r = r0;  // output order: (clip, crop, c, t, y, x)
-    const int yo = (int)(r % cs);
-    r /= cs;
-    const int t = (int)(r % fpc);
-    r /= fpc;
-    const int c = (int)(r % C);
-    r /= C;
-    const int clip = (int)(r / nc);
-    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;  // (the subset's j-th crop: a nibble of the argument)
-    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
-    const int f = clip * cstride + (t % len) * fstep;
-    const int j = crop % 5;
-    const int top = j == 4 ? ctop : ((j >> 1) ? H - cs : 0), left = j == 4 ? cleft : ((j & 1) ? W - cs : 0);
-    const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
-    float* out = y + r0 * cs;
-    for (int q = lane; q < csv; q += 64) {
-      float v[VW];
-#pragma unroll
-      for (int e = 0; e < VW; ++e) {
-        const int xo = q * VW + e;
-        const int sx = crop < 5 ? left + xo : W - 1 - (left + xo);
-        v[e] = ((float)row[(long long)sx * C] - mean) / stdv;
-      }
-      if constexpr (VW == 4) reinterpret_cast<float4*>(out)[q] = make_float4(v[0], v[1], v[2], v[3]);
-      else out[q] = v[0];
-    }
-  }
-}
-
-// The same pass writing COLUMN-PARITY PLANES (the operand of the stem's 16-byte gather, advhip_conv3d_s2w_*): crop-clips
-// [first, first + count), xs[(clip-crop, c, t, y)][par][2 + j] = normalised pixel of crop column 2 j + par, zero in the
-// padding columns.  One wave per (row, both planes); the arithmetic per pixel is the pass above's, so the values are its values.
-__global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, int F, int H,
-                                                                          int W, int C, int fpc, int cstride, int cs, int ctop, int cleft,
-                                                                          float mean, float stdv, long long first, long long rows, int WP,
-                                                                          int nc, unsigned long long crops, int fstep) {
-  const int lane = threadIdx.x & 63;
-  for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
-    long long r = r0;  // (clip-crop - first, c, t, y)
-    const int yo = (int)(r % cs);
-    r /= cs;
-    const int t = (int)(r % fpc);
-    r /= fpc;
-    const int c = (int)(r % C);
-    r = r / C + first;
-    const int clip = (int)(r / nc);
-    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;
-    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
-    const int f = clip * cstride + (t % len) * fstep;
-    const int j5 = crop % 5;
-    const int top = j5 == 4 ? ctop : ((j5 >> 1) ? H - cs : 0), left = j5 == 4 ? cleft : ((j5 & 1) ? W - cs : 0);
-    const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
-    float* out = xs + r0 * 2 * WP;
-    for (int q = lane; q < 2 * WP; q += 64) {
-      const int par = q >= WP, idx = q - par * WP, xo = 2 * (idx - 2) + par;
-      float v = 0.f;
-      if (idx >= 2 && xo < cs) {
-        const int sx = crop < 5 ? left + xo : W - 1 - (left + xo);
-        v = ((float)row[(long long)sx * C] - mean) / stdv;
-      }
-      out[q] = v;
-    }
-  }
-}
-
 // Per-window scores (n,) -> per-frame scores: window w covers frames [w * cstride, w * cstride + fpc); the score of a frame is
 // the mean of the scores of the windows covering it, added in ascending window order, one division by their count (cstride =
 // fpc: one window per frame, np.repeat(scores, fpc) of runner.py:66-76).  One thread per frame, at most ceil(fpc / cstride) adds.
@@ -181,100 +99,6 @@ __global__ __launch_bounds__(256) void frame_scores_kernel(const float* __restri
 }  // namespace advhip
 
 using namespace advhip;
-
-// ---- TenCrop + normalise from uint8 frames: one body per op; the plain / _strided / _crops names fill in the sampling arguments
-// they lack (back-to-back clips, all ten crops, every frame) ----
-static int tencrop_planes_u8(const uint8_t* frames, float* xs, int F, int H, int W, int C, const ClipSampling& s, int crop,
-                             int64_t first_crop_clip, int64_t count, float mean, float stdv, void* stream) {
-  const char* who = "tencrop_normalize_planes_u8";
-  if (int rc = s.check_crops(who)) return rc;
-  ADVHIP_REQUIRE(frames && xs && F > 0 && C > 0 && s.fpc > 0 && crop > 0 && crop % 2 == 0, "%s: bad arguments", who);
-  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
-  ADVHIP_REQUIRE(stdv != 0.f, "%s: std must be non-zero", who);
-  const long long n_clips = s.video_windows(F);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * s.ncrops,
-                 "%s: crop-clips [%lld, %lld) outside the video's %lld", who, (long long)first_crop_clip,
-                 (long long)(first_crop_clip + count), n_clips * s.ncrops);
-  const long long rows = (long long)count * C * s.fpc * crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-  hipLaunchKernelGGL(tencrop_normalize_planes_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C, s.fpc,
-                     s.clip_stride, crop, half_even(H - crop), half_even(W - crop), mean, stdv, (long long)first_crop_clip, rows, crop / 2 + 4,
-                     s.ncrops, s.crops, s.frame_step);
-  return check_launch(who);
-}
-
-extern "C" int advhip_tencrop_normalize_planes_u8_sampled(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
-                                                          int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
-                                                          float mean, float stdv, void* stream) {
-  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, first_crop_clip,
-                           count, mean, stdv, stream);
-}
-
-extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
-                                                        uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
-                                                        float stdv, void* stream) {
-  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, first_crop_clip, count, mean,
-                           stdv, stream);
-}
-
-extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
-                                                          int64_t count, float mean, float stdv, void* stream) {
-  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, first_crop_clip, count, mean, stdv,
-                           stream);
-}
-
-extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                  int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
-                                                  float stdv, void* stream) {
-  return tencrop_planes_u8(frames, xs, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, first_crop_clip, count, mean,
-                           stdv, stream);
-}
-
-static int tencrop_u8(const uint8_t* frames, float* y, int F, int H, int W, int C, const ClipSampling& s, int crop, float mean, float stdv,
-                      void* stream) {
-  const char* who = "tencrop_normalize_u8";
-  if (int rc = s.check_crops(who)) return rc;
-  ADVHIP_REQUIRE(frames && y && F > 0 && C > 0 && s.fpc > 0 && crop > 0, "%s: bad arguments", who);
-  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
-  ADVHIP_REQUIRE(stdv != 0.f, "%s: std must be non-zero", who);
-  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0;
-  const long long rows = s.video_windows(F) * s.ncrops * C * s.fpc * (long long)crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-  if (vec) hipLaunchKernelGGL(tencrop_normalize_u8_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C, s.fpc,
-                              s.clip_stride, crop, ctop, cleft, mean, stdv, rows, s.ncrops, s.crops, s.frame_step);
-  else hipLaunchKernelGGL(tencrop_normalize_u8_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C, s.fpc,
-                          s.clip_stride, crop, ctop, cleft, mean, stdv, rows, s.ncrops, s.crops, s.frame_step);
-  return check_launch(who);
-}
-
-extern "C" int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
-                                                   int32_t ncrops, uint64_t crops_packed, float mean, float stdv, void* stream) {
-  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, mean, stdv, stream);
-}
-
-extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                 int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
-                                                 uint64_t crops_packed, float mean, float stdv, void* stream) {
-  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, mean, stdv, stream);
-}
-
-extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
-                                                   void* stream) {
-  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, mean, stdv, stream);
-}
-
-extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
-                                           int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream) {
-  return tencrop_u8(frames, y, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, mean, stdv, stream);
-}
 
 extern "C" int advhip_frame_scores_f32(const float* scores, float* out, int64_t n_windows, int32_t frames_per_clip, int32_t clip_stride,
                                        int64_t n_frames, void* stream) {

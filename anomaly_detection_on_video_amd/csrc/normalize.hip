@@ -1,8 +1,11 @@
-// The normalisation modes of the uint8-frame path (src/gtransforms.py:57-112): per-channel standardisation and the two min-max
-// normalisers, whose statistics are taken per (frame, crop[, channel]) over the crop's pixels before any pixel can be written.
-//   crop_minmax_u8                      : (min, max) per channel of the six TenCrop windows of every pitch-th frame
-//   tencrop_normalize[_planes]_u8_modes : the two TenCrop passes of misc.hip with a mode, per-channel constants and that table
-// The default normalisation ((x - 114.75) / 57.375, one scalar pair) stays on misc.hip's kernels and entry points.
+// The uint8-frame front end: TenCrop + float + normalise + LoopPad + permute from resized frames, in every sampling (clip_stride,
+// crops, frame_step) and with each of the reference's normalisers (src/gtransforms.py:57-112): the scalar pair (x - 114.75) / 57.375,
+// per-channel standardisation, and the two min-max normalisers, whose statistics are taken per (frame, crop[, channel]) over the
+// crop's pixels before any pixel can be written.
+//   crop_minmax_u8               : (min, max) per channel of the six TenCrop windows of every pitch-th frame
+//   tencrop_normalize[_planes]_u8: ONE row decode (crop_row), two writers (dense rows, column-parity planes), three normaliser
+//                                  policies, one host launcher behind the ten entry points (plain / _strided / _crops / _sampled /
+//                                  _modes of each writer)
 #include <algorithm>
 
 #include "common.h"
@@ -125,143 +128,172 @@ __global__ __launch_bounds__(256) void crop_minmax_u8_kernel(const uint8_t* __re
   }
 }
 
-// ---- the two TenCrop passes with a mode ---------------------------------------------------------------------------------------
+// ---- the TenCrop passes -------------------------------------------------------------------------------------------------------
 
-// Per-channel constants as the kernels take them (by value).  Standardisation: y = (x - sub) / div with (sub, div) = (mean[c],
-// std[c]).  Min-max: y = (x - mn) / (mx - mn) * r[c] + lo[c] with (mn, mx) from the statistics table, of channel c
-// (ADVHIP_NORM_CHANNEL_MINMAX) or over all channels (ADVHIP_NORM_PIXEL_MINMAX).
-struct NormConsts {
-  float a[3], b[3];  // (mean, std) or (lo, r)
+// TenCrop + float + normalise + LoopPad + permute in one pass (src/gtransforms.py:20-73, 115-132; src/dataset.py:175-195;
+// extract_features.py:83): resized uint8 frames (F, H, W, C) -- the HWC bytes a decoder / PIL hands over -- to the backbone's
+// input (n_clips * nc, C, fpc, cs, cs) fp32, or to column-parity planes of it.  One wave per output row (clip, crop, c, t, y): the
+// row decode (five divisions) and the normaliser's lookup happen once per row, the lanes run along x (the first form decoded
+// every float4 separately and indexed a by-value crop table: 165 us for 40 crop-clips, VALU-bound at 2.3 TB/s).
+
+// The launch scalars of a pass.  (ctop, cleft): the centre crop's offsets, Python-rounded halves (half_even).
+struct TenCrop {
+  int F, H, W, C, fpc, cstride, fstep, cs, ctop, cleft, nc;
+  unsigned long long crops;
 };
 
-// What one output row (one frame, one crop, one channel) needs: looked up once per wave-row.
+// One output row: channel c of crop `crop` of source frame f; pixel x of it is at(g, x).
+struct CropRow {
+  const uint8_t* src;  // channel c of the first pixel of the frame row the crop row lies in
+  int f, crop, c, left;
+
+  // crops 5..9 are the five windows of the horizontally flipped frame: pixel (y, x) = frame[top + y][W - 1 - (left + x)]
+  __device__ __forceinline__ uint8_t at(const TenCrop& g, int xo) const {
+    const int sx = crop < 5 ? left + xo : g.W - 1 - (left + xo);
+    return src[(long long)sx * g.C];
+  }
+};
+
+// THE row decode: output row r = (clip-crop - first, c, t, y) of a pass that starts at crop-clip `first`.
+//   clip-crop k = clip * nc + j holds crop (crops >> 4 j) & 15 of that clip (a crop SUBSET: nc of the ten, ascending, as nibbles
+//     of one argument -- the same arithmetic per pixel, so the row is the ten-crop pass's row clip * 10 + that crop);
+//   frame t of clip w = frames[w * cstride + (t % len_w) * fstep], len_w = min(fpc, ceil((F - w * cstride) / fstep)) (LoopPad: a
+//     short last clip repeats itself); cstride = the distance between clip starts, fstep = the temporal sampling step;
+//   crop j % 5 = the (top, left) window: top-left, top-right, bottom-left, bottom-right, centre (torchvision five_crop order).
+__device__ __forceinline__ CropRow crop_row(const uint8_t* __restrict__ x, const TenCrop& g, long long r, long long first) {
+  const int yo = (int)(r % g.cs);
+  r /= g.cs;
+  const int t = (int)(r % g.fpc);
+  r /= g.fpc;
+  const int c = (int)(r % g.C);
+  r = r / g.C + first;
+  const int clip = (int)(r / g.nc);
+  const int crop = (int)(g.crops >> (4 * (int)(r - (long long)clip * g.nc))) & 15;
+  const int len = min(g.fpc, (g.F - clip * g.cstride + g.fstep - 1) / g.fstep);
+  const int f = clip * g.cstride + (t % len) * g.fstep;
+  const int j = crop % 5;
+  const int top = j == 4 ? g.ctop : ((j >> 1) ? g.H - g.cs : 0), left = j == 4 ? g.cleft : ((j & 1) ? g.W - g.cs : 0);
+  return {x + (((long long)f * g.H + top + yo) * g.W) * g.C + c, f, crop, c, left};
+}
+
+// ---- normaliser policies: by-value kernel arguments.  row(): what one output row needs, looked up once per wave-row (every
+// quantity in it is wave-uniform); apply(): one pixel.  Separately rounded operations throughout: a true division (no reciprocal
+// multiply), and q * r + lo as a multiply and an add.  hipcc contracts that pair into one FMA by default (and its __fmul_rn /
+// __fadd_rn are the plain operators, contracted alike), which changes about a fifth of the outputs at (lo, hi) = (0.1, 0.7):
+// contraction is switched off in apply, and the instructions keep that when it is inlined.
+
 struct RowNorm {
   float sub, div, r, lo;
 };
 
-template <bool MM>
-__device__ __forceinline__ RowNorm row_norm(const NormConsts& k, int mode, const uint8_t* __restrict__ stats, int spitch, int f, int crop,
-                                            int c, int C) {
-  RowNorm n;
-  if constexpr (!MM) {
-    n.sub = k.a[c];
-    n.div = k.b[c];
-    n.r = 0.f;
-    n.lo = 0.f;
-  } else {
-    const uint8_t* s = stats + ((long long)(f / spitch) * 6 + crop_window(crop)) * C * 2;
-    int mn = s[2 * c], mx = s[2 * c + 1];
+__device__ __forceinline__ float standardize(const RowNorm& n, uint8_t px) {
+#pragma clang fp contract(off)
+  return ((float)px - n.sub) / n.div;
+}
+
+// (x - mean) / std with one scalar pair: the reference's own normalisation; any C
+struct ScalarPair {
+  float mean, stdv;
+  __device__ __forceinline__ RowNorm row(const CropRow&, int) const { return {mean, stdv, 0.f, 0.f}; }
+  static __device__ __forceinline__ float apply(const RowNorm& n, uint8_t px) { return standardize(n, px); }
+};
+
+// Per-channel constants as the kernels take them: (mean, std) or (lo, r) of up to three channels
+struct NormConsts {
+  float a[3], b[3];
+};
+
+// (x - mean[c]) / std[c]
+struct PerChannel {
+  NormConsts k;
+  __device__ __forceinline__ RowNorm row(const CropRow& w, int) const { return {k.a[w.c], k.b[w.c], 0.f, 0.f}; }
+  static __device__ __forceinline__ float apply(const RowNorm& n, uint8_t px) { return standardize(n, px); }
+};
+
+// (x - mn) / (mx - mn) * r[c] + lo[c] with (mn, mx) from the statistics table, of channel c (ADVHIP_NORM_CHANNEL_MINMAX) or over
+// all channels (ADVHIP_NORM_PIXEL_MINMAX)
+struct MinMax {
+  NormConsts k;
+  int mode, spitch;
+  const uint8_t* __restrict__ stats;
+  __device__ __forceinline__ RowNorm row(const CropRow& w, int C) const {
+    const uint8_t* s = stats + ((long long)(w.f / spitch) * 6 + crop_window(w.crop)) * C * 2;
+    int mn = s[2 * w.c], mx = s[2 * w.c + 1];
     if (mode == ADVHIP_NORM_PIXEL_MINMAX)
       for (int cc = 0; cc < C; ++cc) {
         mn = min(mn, (int)s[2 * cc]);
         mx = max(mx, (int)s[2 * cc + 1]);
       }
-    n.sub = (float)mn;
-    n.div = (float)mx - (float)mn;  // (exact; 0 for a constant crop / channel: 0 / 0 = NaN, as the reference gives)
-    n.r = k.b[c];
-    n.lo = k.a[c];
+    // (the range is exact; 0 for a constant crop / channel: 0 / 0 = NaN, as the reference gives)
+    return {(float)mn, (float)mx - (float)mn, k.b[w.c], k.a[w.c]};
   }
-  return n;
-}
-
-// Separately rounded operations throughout: a true division (no reciprocal multiply), and q * r + lo as a multiply and an add.
-// hipcc contracts that pair into one FMA by default (and its __fmul_rn / __fadd_rn are the plain operators, contracted alike),
-// which changes about a fifth of the outputs at (lo, hi) = (0.1, 0.7): contraction is switched off for this function, and the
-// instructions keep that when it is inlined.
-template <bool MM>
-__device__ __forceinline__ float apply_norm(const RowNorm& n, uint8_t px) {
+  static __device__ __forceinline__ float apply(const RowNorm& n, uint8_t px) {
 #pragma clang fp contract(off)
-  const float q = ((float)px - n.sub) / n.div;
-  if constexpr (!MM) {
-    return q;
-  } else {
-    const float m = q * n.r;
+    const float m = standardize(n, px) * n.r;
     return m + n.lo;
   }
-}
+};
 
-// tencrop_normalize_u8_kernel (misc.hip) with the mode: the same row decode, LoopPad rule, crop nibbles and frame_step addressing.
-template <int VW, bool MM>
-__global__ __launch_bounds__(256) void tencrop_normalize_u8_modes_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, int F, int H, int W,
-                                                                         int C, int fpc, int cstride, int cs, int ctop, int cleft,
-                                                                         long long rows, int nc, unsigned long long crops, int fstep,
-                                                                         int mode, NormConsts k, const uint8_t* __restrict__ stats,
-                                                                         int spitch) {
+// ---- the two writers ----
+
+// Dense rows y[(clip-crop, c, t, y)][x]: 16-byte stores (VW = 4: cs % 4 == 0 and y 16-byte aligned) or scalar ones.
+template <int VW, class Norm>
+__global__ __launch_bounds__(256) void tencrop_dense_kernel(const uint8_t* __restrict__ x, float* __restrict__ y, TenCrop g, long long rows,
+                                                            Norm norm) {
   const int lane = threadIdx.x & 63;
-  const int csv = cs / VW;
+  const int csv = g.cs / VW;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
-    long long r = r0;  // output order: (clip, crop, c, t, y, x)
-    const int yo = (int)(r % cs);
-    r /= cs;
-    const int t = (int)(r % fpc);
-    r /= fpc;
-    const int c = (int)(r % C);
-    r /= C;
-    const int clip = (int)(r / nc);
-    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;
-    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
-    const int f = clip * cstride + (t % len) * fstep;
-    const int j = crop % 5;
-    const int top = j == 4 ? ctop : ((j >> 1) ? H - cs : 0), left = j == 4 ? cleft : ((j & 1) ? W - cs : 0);
-    const RowNorm n = row_norm<MM>(k, mode, stats, spitch, f, crop, c, C);
-    const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
-    float* out = y + r0 * cs;
+    const CropRow row = crop_row(x, g, r0, 0);
+    const RowNorm n = norm.row(row, g.C);
+    float* out = y + r0 * g.cs;
     for (int q = lane; q < csv; q += 64) {
       float v[VW];
 #pragma unroll
-      for (int e = 0; e < VW; ++e) {
-        const int xo = q * VW + e;
-        const int sx = crop < 5 ? left + xo : W - 1 - (left + xo);
-        v[e] = apply_norm<MM>(n, row[(long long)sx * C]);
-      }
+      for (int e = 0; e < VW; ++e) v[e] = Norm::apply(n, row.at(g, q * VW + e));
       if constexpr (VW == 4) reinterpret_cast<float4*>(out)[q] = make_float4(v[0], v[1], v[2], v[3]);
       else out[q] = v[0];
     }
   }
 }
 
-// tencrop_normalize_planes_u8_kernel (misc.hip) with the mode; the padding columns stay zero.
-template <bool MM>
-__global__ __launch_bounds__(256) void tencrop_normalize_planes_u8_modes_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, int F,
-                                                                                int H, int W, int C, int fpc, int cstride, int cs, int ctop,
-                                                                                int cleft, long long first, long long rows, int WP, int nc,
-                                                                                unsigned long long crops, int fstep, int mode, NormConsts k,
-                                                                                const uint8_t* __restrict__ stats, int spitch) {
+// COLUMN-PARITY PLANES (the operand of the stem's 16-byte gather, advhip_conv3d_s2w_*): crop-clips [first, first + count),
+// xs[(clip-crop, c, t, y)][par][2 + j] = normalised pixel of crop column 2 j + par, zero in the padding columns.  One wave per
+// (row, both planes); the arithmetic per pixel is the dense writer's, so the values are its values.
+template <class Norm>
+__global__ __launch_bounds__(256) void tencrop_planes_kernel(const uint8_t* __restrict__ x, float* __restrict__ xs, TenCrop g, long long first,
+                                                             long long rows, int WP, Norm norm) {
   const int lane = threadIdx.x & 63;
   for (long long r0 = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r0 < rows; r0 += (long long)gridDim.x * 4) {
-    long long r = r0;  // (clip-crop - first, c, t, y)
-    const int yo = (int)(r % cs);
-    r /= cs;
-    const int t = (int)(r % fpc);
-    r /= fpc;
-    const int c = (int)(r % C);
-    r = r / C + first;
-    const int clip = (int)(r / nc);
-    const int crop = (int)(crops >> (4 * (int)(r - (long long)clip * nc))) & 15;
-    const int len = min(fpc, (F - clip * cstride + fstep - 1) / fstep);
-    const int f = clip * cstride + (t % len) * fstep;
-    const int j5 = crop % 5;
-    const int top = j5 == 4 ? ctop : ((j5 >> 1) ? H - cs : 0), left = j5 == 4 ? cleft : ((j5 & 1) ? W - cs : 0);
-    const RowNorm n = row_norm<MM>(k, mode, stats, spitch, f, crop, c, C);
-    const uint8_t* row = x + (((long long)f * H + top + yo) * W) * C + c;
+    const CropRow row = crop_row(x, g, r0, first);
+    const RowNorm n = norm.row(row, g.C);
     float* out = xs + r0 * 2 * WP;
     for (int q = lane; q < 2 * WP; q += 64) {
       const int par = q >= WP, idx = q - par * WP, xo = 2 * (idx - 2) + par;
       float v = 0.f;
-      if (idx >= 2 && xo < cs) {
-        const int sx = crop < 5 ? left + xo : W - 1 - (left + xo);
-        v = apply_norm<MM>(n, row[(long long)sx * C]);
-      }
+      if (idx >= 2 && xo < g.cs) v = Norm::apply(n, row.at(g, xo));
       out[q] = v;
     }
   }
 }
 
-// The checks the two `_modes` passes share beyond the scalar passes' own, and the constants the kernels take.  `a`, `b`: host
-// triples of doubles -- (mean, std) or (lo, hi) per channel, as the caller states them, so that the range is rounded as the
-// reference rounds it: pixel mode r = float(hi - lo) with the subtraction in double, channel mode r = float(hi) - float(lo).
-static int norm_consts(const char* who, int mode, const double* a, const double* b, const uint8_t* stats, int stats_pitch, int C,
-                       const ClipSampling& s, NormConsts* k) {
+// ---- host ----
+
+// The normalisation as an entry point states it: the scalar pair (a == nullptr) or a mode with host triples of doubles `a`, `b`
+// -- (mean, std) or (lo, hi) per channel -- and, for the min-max modes, the statistics table.
+struct NormSpec {
+  float mean, stdv;
+  int mode;
+  const double *a, *b;
+  const uint8_t* stats;
+  int stats_pitch;
+  bool modes;
+};
+
+// The checks of a mode beyond the sampling's own, and the constants the kernels take, rounded as the reference rounds them: pixel
+// mode r = float(hi - lo) with the subtraction in double, channel mode r = float(hi) - float(lo).
+static int norm_consts(const char* who, const NormSpec& n, int C, const ClipSampling& s, NormConsts* k) {
+  const int mode = n.mode;
+  const double *a = n.a, *b = n.b;
   ADVHIP_REQUIRE(mode == ADVHIP_NORM_STANDARDIZE || mode == ADVHIP_NORM_PIXEL_MINMAX || mode == ADVHIP_NORM_CHANNEL_MINMAX,
                  "%s: unknown normalisation mode %d", who, mode);
   ADVHIP_REQUIRE(a && b, "%s: null constants", who);
@@ -283,12 +315,49 @@ static int norm_consts(const char* who, int mode, const double* a, const double*
     k->b[c] = mode == ADVHIP_NORM_PIXEL_MINMAX ? (float)(b[c] - a[c]) : (float)b[c] - (float)a[c];
   }
   ADVHIP_REQUIRE(any, "%s: range: min must be below max in at least one channel", who);
-  ADVHIP_REQUIRE(stats, "%s: the min-max modes need the statistics table", who);
-  ADVHIP_REQUIRE(stats_pitch >= 1, "%s: stats pitch %d", who, stats_pitch);
-  ADVHIP_REQUIRE(s.clip_stride % stats_pitch == 0 && s.frame_step % stats_pitch == 0,
-                 "%s: stats pitch %d does not divide clip stride %d and frame step %d", who, stats_pitch, s.clip_stride, s.frame_step);
+  ADVHIP_REQUIRE(n.stats, "%s: the min-max modes need the statistics table", who);
+  ADVHIP_REQUIRE(n.stats_pitch >= 1, "%s: stats pitch %d", who, n.stats_pitch);
+  ADVHIP_REQUIRE(s.clip_stride % n.stats_pitch == 0 && s.frame_step % n.stats_pitch == 0,
+                 "%s: stats pitch %d does not divide clip stride %d and frame step %d", who, n.stats_pitch, s.clip_stride, s.frame_step);
   return ADVHIP_OK;
 }
+
+// Every TenCrop entry point: the checks, the launch shape (block 256 = four rows, grid capped at 256 x 256) and the launch.
+// `range` = {first crop-clip, count}: the planes writer over those crop-clips; null: the dense writer over the whole video.
+static int tencrop_launch(const char* who, const uint8_t* frames, float* out, int F, int H, int W, int C, const ClipSampling& s, int crop,
+                          const int64_t* range, const NormSpec& n, void* stream) {
+  if (int rc = s.check_crops(who)) return rc;
+  ADVHIP_REQUIRE(frames && out, "%s: null pointer", who);
+  ADVHIP_REQUIRE(F > 0 && C > 0 && s.fpc > 0 && crop > 0 && (!range || crop % 2 == 0), "%s: bad arguments", who);
+  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
+  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
+  NormConsts k;
+  if (n.modes) {
+    if (int rc = norm_consts(who, n, C, s, &k)) return rc;
+  } else {
+    ADVHIP_REQUIRE(n.stdv != 0.f, "%s: std must be non-zero", who);
+  }
+  const long long crop_clips = s.video_windows(F) * s.ncrops;
+  const long long first = range ? range[0] : 0, count = range ? range[1] : crop_clips;
+  ADVHIP_REQUIRE(first >= 0 && count > 0 && first + count <= crop_clips, "%s: crop-clips [%lld, %lld) outside the video's %lld", who, first,
+                 first + count, crop_clips);
+  const TenCrop g{F, H, W, C, s.fpc, s.clip_stride, s.frame_step, crop, half_even(H - crop), half_even(W - crop), s.ncrops, s.crops};
+  const long long rows = count * C * s.fpc * crop;
+  const dim3 grid((unsigned)std::min<long long>((rows + 3) / 4, 256 * 256)), block(256);
+  const bool vec = crop % 4 == 0 && ((uintptr_t)out & 15) == 0;
+  auto launch = [&](auto norm) {
+    using Norm = decltype(norm);
+    if (range) hipLaunchKernelGGL(tencrop_planes_kernel<Norm>, grid, block, 0, (hipStream_t)stream, frames, out, g, first, rows, crop / 2 + 4, norm);
+    else if (vec) hipLaunchKernelGGL((tencrop_dense_kernel<4, Norm>), grid, block, 0, (hipStream_t)stream, frames, out, g, rows, norm);
+    else hipLaunchKernelGGL((tencrop_dense_kernel<1, Norm>), grid, block, 0, (hipStream_t)stream, frames, out, g, rows, norm);
+  };
+  if (!n.modes) launch(ScalarPair{n.mean, n.stdv});
+  else if (n.mode == ADVHIP_NORM_STANDARDIZE) launch(PerChannel{k});
+  else launch(MinMax{k, n.mode, n.stats_pitch, n.stats});
+  return check_launch(who);
+}
+
+static NormSpec scalar_pair(float mean, float stdv) { return {mean, stdv, 0, nullptr, nullptr, nullptr, 0, false}; }
 
 }  // namespace advhip
 
@@ -312,32 +381,76 @@ extern "C" int advhip_crop_minmax_u8(const uint8_t* frames, uint8_t* stats, int3
   return check_launch(who);
 }
 
+// ---- the ten TenCrop names: dense and planes, each plain / _strided / _crops / _sampled (the scalar pair; the shorter names fill
+// in the sampling arguments they lack: back-to-back clips, all ten crops, every frame) and _modes ----
+
+extern "C" int advhip_tencrop_normalize_u8(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                           int32_t frames_per_clip, int32_t crop, float mean, float stdv, void* stream) {
+  return tencrop_launch("tencrop_normalize_u8", frames, y, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, nullptr,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_u8_strided(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t crop, float mean, float stdv,
+                                                   void* stream) {
+  return tencrop_launch("tencrop_normalize_u8", frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, nullptr,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_u8_crops(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                 int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                 uint64_t crops_packed, float mean, float stdv, void* stream) {
+  return tencrop_launch("tencrop_normalize_u8", frames, y, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, nullptr,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_u8_sampled(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                   int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                                   int32_t ncrops, uint64_t crops_packed, float mean, float stdv, void* stream) {
+  return tencrop_launch("tencrop_normalize_u8", frames, y, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, nullptr,
+                        scalar_pair(mean, stdv), stream);
+}
+
 extern "C" int advhip_tencrop_normalize_u8_modes(const uint8_t* frames, float* y, int32_t F, int32_t H, int32_t W, int32_t C,
                                                  int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
                                                  int32_t ncrops, uint64_t crops_packed, int32_t mode, const double* a, const double* b,
                                                  const uint8_t* stats, int32_t stats_pitch, void* stream) {
-  const char* who = "tencrop_normalize_u8_modes";
-  const ClipSampling s{frames_per_clip, clip_stride, frame_step, ncrops, crops_packed};
-  if (int rc = s.check_crops(who)) return rc;
-  ADVHIP_REQUIRE(frames && y, "%s: null pointer", who);
-  ADVHIP_REQUIRE(F > 0 && C > 0 && s.fpc > 0 && crop > 0, "%s: bad arguments", who);
-  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
-  NormConsts k;
-  if (int rc = norm_consts(who, mode, a, b, stats, stats_pitch, C, s, &k)) return rc;
-  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  const bool vec = crop % 4 == 0 && ((uintptr_t)y & 15) == 0, mm = mode != ADVHIP_NORM_STANDARDIZE;
-  const long long rows = s.video_windows(F) * s.ncrops * C * s.fpc * (long long)crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-#define ADVHIP_LAUNCH_MODES(VW, MM)                                                                                                          \
-  hipLaunchKernelGGL((tencrop_normalize_u8_modes_kernel<VW, MM>), dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, y, F, H, W, C, s.fpc, \
-                     s.clip_stride, crop, ctop, cleft, rows, s.ncrops, s.crops, s.frame_step, mode, k, stats, stats_pitch)
-  if (vec && mm) ADVHIP_LAUNCH_MODES(4, true);
-  else if (vec) ADVHIP_LAUNCH_MODES(4, false);
-  else if (mm) ADVHIP_LAUNCH_MODES(1, true);
-  else ADVHIP_LAUNCH_MODES(1, false);
-#undef ADVHIP_LAUNCH_MODES
-  return check_launch(who);
+  return tencrop_launch("tencrop_normalize_u8_modes", frames, y, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop,
+                        nullptr, {0.f, 0.f, mode, a, b, stats, stats_pitch, true}, stream);
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                  int32_t frames_per_clip, int32_t crop, int64_t first_crop_clip, int64_t count, float mean,
+                                                  float stdv, void* stream) {
+  const int64_t range[2] = {first_crop_clip, count};
+  return tencrop_launch("tencrop_normalize_planes_u8", frames, xs, F, H, W, C, {frames_per_clip, frames_per_clip, 1, 10, TENCROP_ALL}, crop, range,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8_strided(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int64_t first_crop_clip,
+                                                          int64_t count, float mean, float stdv, void* stream) {
+  const int64_t range[2] = {first_crop_clip, count};
+  return tencrop_launch("tencrop_normalize_planes_u8", frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, 10, TENCROP_ALL}, crop, range,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8_crops(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                        int32_t frames_per_clip, int32_t clip_stride, int32_t crop, int32_t ncrops,
+                                                        uint64_t crops_packed, int64_t first_crop_clip, int64_t count, float mean,
+                                                        float stdv, void* stream) {
+  const int64_t range[2] = {first_crop_clip, count};
+  return tencrop_launch("tencrop_normalize_planes_u8", frames, xs, F, H, W, C, {frames_per_clip, clip_stride, 1, ncrops, crops_packed}, crop, range,
+                        scalar_pair(mean, stdv), stream);
+}
+
+extern "C" int advhip_tencrop_normalize_planes_u8_sampled(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
+                                                          int32_t frames_per_clip, int32_t clip_stride, int32_t frame_step, int32_t crop,
+                                                          int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
+                                                          float mean, float stdv, void* stream) {
+  const int64_t range[2] = {first_crop_clip, count};
+  return tencrop_launch("tencrop_normalize_planes_u8", frames, xs, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop, range,
+                        scalar_pair(mean, stdv), stream);
 }
 
 extern "C" int advhip_tencrop_normalize_planes_u8_modes(const uint8_t* frames, float* xs, int32_t F, int32_t H, int32_t W, int32_t C,
@@ -345,29 +458,7 @@ extern "C" int advhip_tencrop_normalize_planes_u8_modes(const uint8_t* frames, f
                                                         int32_t ncrops, uint64_t crops_packed, int64_t first_crop_clip, int64_t count,
                                                         int32_t mode, const double* a, const double* b, const uint8_t* stats,
                                                         int32_t stats_pitch, void* stream) {
-  const char* who = "tencrop_normalize_planes_u8_modes";
-  const ClipSampling s{frames_per_clip, clip_stride, frame_step, ncrops, crops_packed};
-  if (int rc = s.check_crops(who)) return rc;
-  ADVHIP_REQUIRE(frames && xs, "%s: null pointer", who);
-  ADVHIP_REQUIRE(F > 0 && C > 0 && s.fpc > 0 && crop > 0 && crop % 2 == 0, "%s: bad arguments", who);
-  if (int rc = s.check_windows(who, 1ll << 31)) return rc;
-  ADVHIP_REQUIRE(H >= crop && W >= crop, "%s: frames (%d x %d) smaller than the %d crop", who, H, W, crop);
-  NormConsts k;
-  if (int rc = norm_consts(who, mode, a, b, stats, stats_pitch, C, s, &k)) return rc;
-  const long long n_clips = s.video_windows(F);
-  ADVHIP_REQUIRE(first_crop_clip >= 0 && count > 0 && first_crop_clip + count <= n_clips * s.ncrops,
-                 "%s: crop-clips [%lld, %lld) outside the video's %lld", who, (long long)first_crop_clip,
-                 (long long)(first_crop_clip + count), n_clips * s.ncrops);
-  const long long rows = (long long)count * C * s.fpc * crop;
-  const int grid = (int)std::min<long long>((rows + 3) / 4, 256 * 256);
-  const int ctop = half_even(H - crop), cleft = half_even(W - crop);
-  if (mode != ADVHIP_NORM_STANDARDIZE)
-    hipLaunchKernelGGL(tencrop_normalize_planes_u8_modes_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C,
-                       s.fpc, s.clip_stride, crop, ctop, cleft, (long long)first_crop_clip, rows, crop / 2 + 4, s.ncrops, s.crops,
-                       s.frame_step, mode, k, stats, stats_pitch);
-  else
-    hipLaunchKernelGGL(tencrop_normalize_planes_u8_modes_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, xs, F, H, W, C,
-                       s.fpc, s.clip_stride, crop, ctop, cleft, (long long)first_crop_clip, rows, crop / 2 + 4, s.ncrops, s.crops,
-                       s.frame_step, mode, k, stats, stats_pitch);
-  return check_launch(who);
+  const int64_t range[2] = {first_crop_clip, count};
+  return tencrop_launch("tencrop_normalize_planes_u8_modes", frames, xs, F, H, W, C, {frames_per_clip, clip_stride, frame_step, ncrops, crops_packed}, crop,
+                        range, {0.f, 0.f, mode, a, b, stats, stats_pitch, true}, stream);
 }

@@ -10,15 +10,14 @@ CUDA tensors only; no fallback.  Reference semantics: modeling_mgfn.py:302-374, 
 """
 from __future__ import annotations
 
-from ctypes import c_float as C_float
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
 from ._lib import check, ptr, require_gpu, stream
-from .ops import (n_windows, normalize_is_default, normalize_launch_args, pack_crops, resolve_clip_stride, resolve_frame_step,
-                  resolve_normalize, resolve_sampling)
+from .ops import resolve_clip_stride, resolve_frame_step
+from .ops import PIXEL_MEAN, PIXEL_STD, normalize_permute_u8, tencrop_normalize_u8  # noqa: F401  (their callers' name for them)
 
 
 class _MilMagnitude(torch.autograd.Function):
@@ -354,63 +353,6 @@ def add_magnitude_np_leaves(C: int):
     n = ctypes.c_int32()
     check(_lib.load().advhip_add_magnitude_np_leaves(int(C), buf, ctypes.byref(n)), "add_magnitude_np_leaves")
     return [(buf[3 * i], buf[3 * i + 1], buf[3 * i + 2]) for i in range(n.value)]
-
-
-PIXEL_MEAN, PIXEL_STD = 114.75, 57.375  # GroupNormalize constants, src/dataset.py:180-181
-
-
-def normalize_permute_u8(frames: torch.Tensor, mean: float = PIXEL_MEAN, std: float = PIXEL_STD) -> torch.Tensor:
-    """uint8 (N, T, C, H, W) -> fp32 (N, C, T, H, W), (x - mean) / std, one HIP pass."""
-    frames = frames.contiguous()
-    require_gpu(frames)
-    if frames.dtype != torch.uint8 or frames.dim() != 5:
-        raise ValueError(f"expected uint8 (N,T,C,H,W), got {frames.dtype} {tuple(frames.shape)}")
-    n, t, c, h, w = frames.shape
-    out = torch.empty((n, c, t, h, w), device=frames.device, dtype=torch.float32)
-    check(_lib.load().advhip_normalize_permute_u8(ptr(frames), ptr(out), n, t, c, h, w, C_float(mean), C_float(std), stream()),
-          "normalize_permute_u8")
-    return out
-
-
-def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
-                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None,
-                         frame_step: Optional[int] = None, normalize=None, crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Resized uint8 frames (F, H, W, C) of one video -> the backbone's input (n_clips * 10, C, frames_per_clip, crop, crop)
-    fp32: TenCrop, float, normalise, LoopPad and the layout permutes of TenCropVideoFrameDataset / _extract
-    (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop.
-    `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = ops.n_windows(F, ...).
-    `crops` (ops.resolve_crops; default all ten): (n_clips * len(crops), ...), row = clip * len(crops) + j holds crop crops[j].
-    `frame_step` d (default 1): sampled frame t of clip w is frames[w * clip_stride + t * d]; a clip spans frames_per_clip * d
-    frames, clip_stride defaults to that span (1 <= clip_stride <= span), and a short last clip of L = ceil((F - w * s) / d)
-    sampled frames repeats them (LoopPad): frame t >= L is frames[w * s + (t % L) * d].  Row w is the row of the call without
-    `frame_step` on those frames as a one-clip video, bit for bit; nothing is gathered.
-    `normalize` (ops.resolve_normalize; default: (x - mean) / std with the two scalars): ("standardize", mean, std) with
-    per-channel lists, "pixel_minmax" / ("pixel_minmax", lo, hi) or "channel_minmax" / ("channel_minmax", lo, hi) -- the
-    reference's three normalisers (src/gtransforms.py:57-112), bit for bit, NaN for a constant crop / channel included.  The
-    min-max kinds read per-(frame, window, channel) statistics: `crop_stats` (ops.crop_minmax_u8 at frame pitch
-    ops.crop_stats_pitch(frames_per_clip, clip_stride, frame_step)), computed here when not given."""
-    s, crops, d = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
-    nc, packed = pack_crops(crops)
-    norm = resolve_normalize(normalize)
-    frames = frames.contiguous()
-    require_gpu(frames)
-    if frames.dtype != torch.uint8 or frames.dim() != 4:
-        raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
-    f, h, w, c = frames.shape
-    if h < crop or w < crop:
-        raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
-    n_clips = n_windows(f, frames_per_clip, s, d)
-    out = torch.empty((n_clips * nc, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
-    if not normalize_is_default(norm):
-        if (mean, std) != (PIXEL_MEAN, PIXEL_STD):
-            raise ValueError("tencrop_normalize_u8: give the constants in `normalize`, not in `mean` / `std` as well")
-        mode, a, b, stats, pitch = normalize_launch_args(norm, frames, crop, frames_per_clip, s, d, crop_stats)
-        check(_lib.load().advhip_tencrop_normalize_u8_modes(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, mode, a, b,
-                                                            ptr(stats), pitch, stream()), "tencrop_normalize_u8_modes")
-        return out
-    check(_lib.load().advhip_tencrop_normalize_u8_sampled(ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
-                                                          C_float(mean), C_float(std), stream()), "tencrop_normalize_u8")
-    return out
 
 
 def frame_scores(scores: torch.Tensor, frames_per_clip: int = 16, clip_stride: Optional[int] = None,

@@ -362,6 +362,25 @@ def active_ktiles(pc: PackedConv, thw: Tuple[int, int, int], ot: int, bk: int = 
     return list(tiles[: n.value])
 
 
+def _pool233_out(pc: PackedConv, d: ConvDesc, what: str, out: Optional[torch.Tensor], dev: torch.device):
+    """What the three fused-stem wrappers share behind their own argument checks: the (2,3,3) / (2,2,2)-pooled output of the conv
+    `d` describes (`out`, checked, or a new tensor) and the launch's workspace -> (y, workspace, its bytes).  `what` names the
+    input in the too-small message."""
+    lib = _lib.load()
+    tp, hp, wp = C.c_int32(), C.c_int32(), C.c_int32()
+    check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wp)), "conv3d_pool_out_dims")
+    shape = (d.B, pc.cout, tp.value, hp.value, wp.value)
+    if min(shape) <= 0:
+        raise ValueError(f"{pc.name}: {what} too small for conv + (2,3,3) pooling")
+    y = out if out is not None else torch.empty(shape, device=dev, dtype=torch.float32)
+    if tuple(y.shape) != shape or y.dtype != torch.float32 or y.device != dev:
+        raise ValueError(f"{pc.name}: out {tuple(y.shape)} != {shape}")
+    need = lib.advhip_conv3d_relu_maxpool233_workspace_bytes(C.byref(d))
+    if need < 0:
+        check(int(need), f"conv3d_relu_maxpool233_workspace_bytes[{pc.name}]")
+    return y, workspace(dev, need), need
+
+
 def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None, border: Optional[bool] = None) -> torch.Tensor:
     """The fused stem on column-parity planes xs (B, Cin, T, H, 2, W/2 + 4) of its input (split_w / tencrop_planes_u8).
     `border` (default STEM_BORDER): split the launch by pool window in t where the geometry allows (ADVHIP_ALGO_STEM_BORDER);
@@ -375,21 +394,10 @@ def conv3d_s2w_bn_relu_maxpool233(xs: torch.Tensor, pc: PackedConv, out: Optiona
     if not s2w_ok(pc, W):
         raise ValueError(f"{pc.name}: the column-parity gather does not apply to W = {W} with k/s/p {pc.kernel[2]}/{pc.stride[2]}/{pc.padding[2]}")
     d = pc.desc(B, T, H, W, True, _lib.ALGO_STEM_BORDER if (STEM_BORDER if border is None else border) else 0, 1)
-    lib = _lib.load()
-    tp, hp, wpo = C.c_int32(), C.c_int32(), C.c_int32()
-    check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wpo)), "conv3d_pool_out_dims")
-    shape = (B, pc.cout, tp.value, hp.value, wpo.value)
-    if min(shape) <= 0:
-        raise ValueError(f"{pc.name}: input too small for conv + (2,3,3) pooling")
-    y = out if out is not None else torch.empty(shape, device=xs.device, dtype=torch.float32)
-    if tuple(y.shape) != shape or y.dtype != torch.float32 or y.device != xs.device:
-        raise ValueError(f"{pc.name}: out {tuple(y.shape)} != {shape}")
-    need = lib.advhip_conv3d_relu_maxpool233_workspace_bytes(C.byref(d))
-    if need < 0:
-        check(int(need), f"conv3d_relu_maxpool233_workspace_bytes[{pc.name}]")
-    ws = workspace(xs.device, need)
-    check(lib.advhip_conv3d_s2w_bn_relu_maxpool233_f32(C.byref(d), ptr(xs), 0, ptr(pc.w_packed), ptr(ensure_ktab_s2w(pc, (T, H, W))), ptr(pc.scale),
-                                                       ptr(pc.shift), ptr(y), batch_stride(y), ptr(ws), need, stream(xs)), f"conv3d s2w+pool233[{pc.name}]")
+    y, ws, need = _pool233_out(pc, d, "input", out, xs.device)
+    check(_lib.load().advhip_conv3d_s2w_bn_relu_maxpool233_f32(C.byref(d), ptr(xs), 0, ptr(pc.w_packed), ptr(ensure_ktab_s2w(pc, (T, H, W))),
+                                                               ptr(pc.scale), ptr(pc.shift), ptr(y), batch_stride(y), ptr(ws), need, stream(xs)),
+          f"conv3d s2w+pool233[{pc.name}]")
     return y
 
 
@@ -505,6 +513,9 @@ def crops_tag(crops) -> str:
     """The file-name tag of a crop subset: "" for all ten, else "_c<digits>" ("_c4", "_c01234")."""
     idx = resolve_crops(crops)
     return "" if len(idx) == 10 else "_c" + "".join(str(c) for c in idx)
+
+
+PIXEL_MEAN, PIXEL_STD = 114.75, 57.375  # GroupNormalize constants, src/dataset.py:180-181
 
 
 class Normalize(NamedTuple):
@@ -653,18 +664,22 @@ def normalize_launch_args(norm: Normalize, frames: torch.Tensor, crop: int, fram
     return mode, a, b, crop_stats, pitch
 
 
-def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = 114.75,
-                      std: float = 57.375, clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None,
-                      normalize=None, crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Resized uint8 frames (F, H, W, C) -> column-parity planes (count, C, frames_per_clip, crop, 2, crop/2 + 4) of crop-clips
-    [first, first + count) (row = clip * 10 + crop): TenCrop, float, normalise, LoopPad and the layout permutes of
-    TenCropVideoFrameDataset / _extract (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass,
-    written as the operand of the stem's 16-byte gather.  Values = mil_ops.tencrop_normalize_u8's.  `clip_stride` (default
-    frames_per_clip): clip w = the window of frames_per_clip frames that starts at frame w * clip_stride.  `crops`
-    (resolve_crops): row = clip * len(crops) + j holds crop crops[j].  `frame_step` (default 1): clip w = frames w * clip_stride +
-    t * frame_step, t in [0, frames_per_clip); clip_stride then defaults to frames_per_clip * frame_step.  `normalize`
-    (resolve_normalize; default: (x - mean) / std with the two scalars): per-channel standardisation or a min-max mode, whose
-    statistics are `crop_stats` (crop_minmax_u8 at frame pitch crop_stats_pitch(...)) or computed here."""
+def normalize_permute_u8(frames: torch.Tensor, mean: float = PIXEL_MEAN, std: float = PIXEL_STD) -> torch.Tensor:
+    """uint8 (N, T, C, H, W) -> fp32 (N, C, T, H, W), (x - mean) / std, one HIP pass."""
+    frames = frames.contiguous()
+    require_gpu(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 5:
+        raise ValueError(f"expected uint8 (N,T,C,H,W), got {frames.dtype} {tuple(frames.shape)}")
+    n, t, c, h, w = frames.shape
+    out = torch.empty((n, c, t, h, w), device=frames.device, dtype=torch.float32)
+    check(_lib.load().advhip_normalize_permute_u8(ptr(frames), ptr(out), n, t, c, h, w, C.c_float(mean), C.c_float(std), stream()),
+          "normalize_permute_u8")
+    return out
+
+
+def _tencrop_call(who: str, frames: torch.Tensor, frames_per_clip: int, mean: float, std: float, clip_stride, crops, frame_step, normalize):
+    """What the two TenCrop passes do before they look at their own arguments: the sampling and the normalisation resolved, the
+    frames checked.  -> (frames, (clip_stride, frame_step, ncrops, packed crops), norm, the video's crop-clips)."""
     s, crops, d = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     nc, packed = pack_crops(crops)
     norm = resolve_normalize(normalize)
@@ -672,23 +687,64 @@ def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_c
     require_gpu(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError(f"expected uint8 (F,H,W,C), got {frames.dtype} {tuple(frames.shape)}")
+    if not normalize_is_default(norm) and (mean, std) != (PIXEL_MEAN, PIXEL_STD):
+        raise ValueError(f"{who}: give the constants in `normalize`, not in `mean` / `std` as well")
+    return frames, (s, d, nc, packed), norm, n_windows(frames.shape[0], frames_per_clip, s, d) * nc
+
+
+def _tencrop_launch(name: str, frames: torch.Tensor, out: torch.Tensor, frames_per_clip: int, crop: int, sampling, window, norm: Normalize,
+                    mean: float, std: float, crop_stats: Optional[torch.Tensor]) -> torch.Tensor:
+    """advhip_<name>_sampled with the scalar pair for the default normalisation, advhip_<name>_modes for any other.  `window`: the
+    arguments between the crop set and the normalisation -- (first, count) of the planes pass, () of the dense one."""
+    lib = _lib.load()
     f, h, w, c = frames.shape
-    n = n_windows(f, frames_per_clip, s, d) * nc
+    s, d, nc, packed = sampling
+    head = (ptr(frames), ptr(out), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, *window)
+    if normalize_is_default(norm):
+        check(getattr(lib, f"advhip_{name}_sampled")(*head, C.c_float(mean), C.c_float(std), stream(frames)), name)
+    else:
+        mode, a, b, stats, pitch = normalize_launch_args(norm, frames, crop, frames_per_clip, s, d, crop_stats)
+        check(getattr(lib, f"advhip_{name}_modes")(*head, mode, a, b, ptr(stats), pitch, stream(frames)), f"{name}_modes")
+    return out
+
+
+def tencrop_normalize_u8(frames: torch.Tensor, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
+                         std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None,
+                         frame_step: Optional[int] = None, normalize=None, crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Resized uint8 frames (F, H, W, C) of one video -> the backbone's input (n_clips * 10, C, frames_per_clip, crop, crop)
+    fp32: TenCrop, float, normalise, LoopPad and the layout permutes of TenCropVideoFrameDataset / _extract
+    (src/dataset.py:175-195, src/gtransforms.py, extract_features.py:83) in one HIP pass.  Row = clip * 10 + crop.
+    `clip_stride` (default frames_per_clip): clip w starts at frame w * clip_stride, n_clips = n_windows(F, ...).
+    `crops` (resolve_crops; default all ten): (n_clips * len(crops), ...), row = clip * len(crops) + j holds crop crops[j].
+    `frame_step` d (default 1): sampled frame t of clip w is frames[w * clip_stride + t * d]; a clip spans frames_per_clip * d
+    frames, clip_stride defaults to that span (1 <= clip_stride <= span), and a short last clip of L = ceil((F - w * s) / d)
+    sampled frames repeats them (LoopPad): frame t >= L is frames[w * s + (t % L) * d].  Row w is the row of the call without
+    `frame_step` on those frames as a one-clip video, bit for bit; nothing is gathered.
+    `normalize` (resolve_normalize; default: (x - mean) / std with the two scalars): ("standardize", mean, std) with
+    per-channel lists, "pixel_minmax" / ("pixel_minmax", lo, hi) or "channel_minmax" / ("channel_minmax", lo, hi) -- the
+    reference's three normalisers (src/gtransforms.py:57-112), bit for bit, NaN for a constant crop / channel included.  The
+    min-max kinds read per-(frame, window, channel) statistics: `crop_stats` (crop_minmax_u8 at frame pitch
+    crop_stats_pitch(frames_per_clip, clip_stride, frame_step)), computed here when not given."""
+    frames, sampling, norm, n = _tencrop_call("tencrop_normalize_u8", frames, frames_per_clip, mean, std, clip_stride, crops, frame_step, normalize)
+    _, h, w, c = frames.shape
+    if h < crop or w < crop:
+        raise ValueError(f"frames {h}x{w} smaller than the {crop} crop")
+    out = torch.empty((n, c, frames_per_clip, crop, crop), device=frames.device, dtype=torch.float32)
+    return _tencrop_launch("tencrop_normalize_u8", frames, out, frames_per_clip, crop, sampling, (), norm, mean, std, crop_stats)
+
+
+def tencrop_planes_u8(frames: torch.Tensor, first: int, count: int, frames_per_clip: int = 16, crop: int = 224, mean: float = PIXEL_MEAN,
+                      std: float = PIXEL_STD, clip_stride: Optional[int] = None, crops=None, frame_step: Optional[int] = None,
+                      normalize=None, crop_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tencrop_normalize_u8's rows [first, first + count) as column-parity planes (count, C, frames_per_clip, crop, 2,
+    crop/2 + 4): the same arguments, the same values, written as the operand of the stem's 16-byte gather with zero padding
+    columns (include/advhip.h: advhip_conv3d_s2w_*)."""
+    frames, sampling, norm, n = _tencrop_call("tencrop_planes_u8", frames, frames_per_clip, mean, std, clip_stride, crops, frame_step, normalize)
+    _, h, w, c = frames.shape
     if h < crop or w < crop or crop % 2 or first < 0 or count <= 0 or first + count > n:
         raise ValueError(f"tencrop_planes_u8: crop-clips [{first},{first + count}) of {n}, frames {h}x{w}, crop {crop}")
     xs = torch.empty((count, c, frames_per_clip, crop, 2, crop // 2 + 4), device=frames.device, dtype=torch.float32)
-    if not normalize_is_default(norm):
-        if (mean, std) != (PIXEL_MEAN, PIXEL_STD):
-            raise ValueError("tencrop_planes_u8: give the constants in `normalize`, not in `mean` / `std` as well")
-        mode, a, b, stats, pitch = normalize_launch_args(norm, frames, crop, frames_per_clip, s, d, crop_stats)
-        check(_lib.load().advhip_tencrop_normalize_planes_u8_modes(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed,
-                                                                   first, count, mode, a, b, ptr(stats), pitch, stream(frames)),
-              "tencrop_normalize_planes_u8_modes")
-        return xs
-    check(_lib.load().advhip_tencrop_normalize_planes_u8_sampled(ptr(frames), ptr(xs), f, h, w, c, frames_per_clip, s, d, crop, nc, packed, first,
-                                                                 count, C.c_float(mean), C.c_float(std), stream(frames)),
-          "tencrop_normalize_planes_u8")
-    return xs
+    return _tencrop_launch("tencrop_normalize_planes_u8", frames, xs, frames_per_clip, crop, sampling, (first, count), norm, mean, std, crop_stats)
 
 
 def conv3d_bn_relu_maxpool233(x: torch.Tensor, pc: PackedConv, out: Optional[torch.Tensor] = None, s2w: Optional[bool] = None,
@@ -702,31 +758,16 @@ def conv3d_bn_relu_maxpool233(x: torch.Tensor, pc: PackedConv, out: Optional[tor
         raise ValueError(f"{pc.name}: expected (B,{pc.cin},T,H,W), got {tuple(x.shape)}")
     B, _, T, H, W = x.shape
     d = pc.desc(B, T, H, W, True, 0, 1)
-    lib = _lib.load()
-    tp, hp, wp = C.c_int32(), C.c_int32(), C.c_int32()
-    check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wp)), "conv3d_pool_out_dims")
-    shape = (B, pc.cout, tp.value, hp.value, wp.value)
-    if min(shape) <= 0:
-        raise ValueError(f"{pc.name}: input {tuple(x.shape)} too small for conv + (2,3,3) pooling")
-    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
-    if tuple(y.shape) != shape or y.dtype != torch.float32 or y.device != x.device:
-        raise ValueError(f"{pc.name}: out {tuple(y.shape)} != {shape}")
+    y, ws, need = _pool233_out(pc, d, f"input {tuple(x.shape)}", out, x.device)
     ktab = ensure_ktab(pc, (T, H, W))
-    need = lib.advhip_conv3d_relu_maxpool233_workspace_bytes(C.byref(d))
-    if need < 0:
-        check(int(need), f"conv3d_relu_maxpool233_workspace_bytes[{pc.name}]")
-    ws = workspace(x.device, need)
     if s2w is None:
         s2w = STEM_S2W
     if s2w and s2w_ok(pc, W) and x.is_contiguous():
         return conv3d_s2w_bn_relu_maxpool233(split_w(x), pc, out=y, border=border)
     xbs, ybs = batch_stride(x), batch_stride(y)
-    check(lib.advhip_conv3d_bn_relu_maxpool233_f32(C.byref(d), ptr(x), xbs, ptr(pc.w_packed), ptr(ktab), ptr(pc.scale), ptr(pc.shift),
-                                                   ptr(y), ybs, ptr(ws), need, stream()), f"conv3d+pool233[{pc.name}]")
+    check(_lib.load().advhip_conv3d_bn_relu_maxpool233_f32(C.byref(d), ptr(x), xbs, ptr(pc.w_packed), ptr(ktab), ptr(pc.scale), ptr(pc.shift),
+                                                           ptr(y), ybs, ptr(ws), need, stream()), f"conv3d+pool233[{pc.name}]")
     return y
-
-
-PIXEL_MEAN, PIXEL_STD = 114.75, 57.375  # GroupNormalize constants, src/dataset.py:180-181
 
 
 # how forward_frames feeds the stem from resized uint8 frames: "planes" (default where the geometry allows): one TenCrop /
@@ -775,49 +816,38 @@ def pad_windows_u8(frames: torch.Tensor, frames_per_clip: int = 16, clip_stride:
     return out
 
 
-def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
-                          frame_step: int = 1):
-    """(`frame_step`: the temporal term of the gather table is frame_step frames per tap -- part of the cache key.)"""
-    key = ("taps", tuple(frame_hw), tuple(clip_thw), float(mean), int(frame_step))
+def _u8_stem_tables(pc: "PackedConv", form: str, frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float, frame_step: int):
+    """The tables of a uint8-frame stem for frames of (FH, FW) and clips of (T, crop, crop), cached on the conv (built on the
+    current stream: callers that fork streams build them first, like the other lazily built tables).  `form` "u8": (gather table,
+    border corrections); "u8_taps": those and the re-laid weights.  `frame_step`: the temporal term of the gather table is
+    frame_step frames per tap -- part of the cache key."""
+    key = (("taps",) if form == "u8_taps" else ()) + (tuple(frame_hw), tuple(clip_thw), float(mean), int(frame_step))
     cache = pc.__dict__.setdefault("_u8_tables", {})
     tabs = cache.get(key)
     if tabs is None:
         d = pc.desc(1, *clip_thw, True, 0, 1)
         lib = _lib.load()
-        nk, nf, nw = C.c_int64(), C.c_int64(), C.c_int64()
-        check(lib.advhip_conv3d_u8_taps_table_sizes(C.byref(d), C.byref(nk), C.byref(nf), C.byref(nw)), "conv3d_u8_taps_table_sizes")
+        sizes = [C.c_int64() for _ in range(3 if form == "u8_taps" else 2)]
+        check(getattr(lib, f"advhip_conv3d_{form}_table_sizes")(C.byref(d), *(C.byref(n) for n in sizes)), f"conv3d_{form}_table_sizes")
         dev = pc.w_packed.device
-        ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
-        corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
-        wt = torch.empty((nw.value,), device=dev, dtype=torch.float32)
-        check(lib.advhip_conv3d_u8_taps_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
-                                                             C.c_float(mean), ptr(ktab), ptr(corr), ptr(wt), stream(dev)),
-              f"conv3d_u8_taps_build_tables[{pc.name}]")
-        tabs = cache[key] = (ktab, corr, wt)
+        tabs = tuple(torch.empty((n.value,), device=dev, dtype=torch.int32 if i == 0 else torch.float32) for i, n in enumerate(sizes))
+        check(getattr(lib, f"advhip_conv3d_{form}_build_tables_sampled")(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
+                                                                         C.c_float(mean), *(ptr(t) for t in tabs), stream(dev)),
+              f"conv3d_{form}_build_tables[{pc.name}]")
+        cache[key] = tabs
     return tabs
+
+
+def ensure_u8_taps_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
+                          frame_step: int = 1):
+    """(ktab, corr, weights) of the whole-pixel ("taps") uint8-frame stem: _u8_stem_tables."""
+    return _u8_stem_tables(pc, "u8_taps", frame_hw, clip_thw, mean, frame_step)
 
 
 def ensure_u8_tables(pc: "PackedConv", frame_hw: Tuple[int, int], clip_thw: Tuple[int, int, int], mean: float = PIXEL_MEAN,
                      frame_step: int = 1):
-    """Gather / border tables of the uint8-frame stem for frames of (FH, FW) and clips of (T, crop, crop); cached on the conv
-    (built on the current stream: callers that fork streams build them first, like the other lazily built tables).  `frame_step`:
-    the temporal term of the gather table is frame_step frames per tap -- part of the cache key."""
-    key = (tuple(frame_hw), tuple(clip_thw), float(mean), int(frame_step))
-    cache = pc.__dict__.setdefault("_u8_tables", {})
-    tabs = cache.get(key)
-    if tabs is None:
-        d = pc.desc(1, *clip_thw, True, 0, 1)
-        lib = _lib.load()
-        nk, nf = C.c_int64(), C.c_int64()
-        check(lib.advhip_conv3d_u8_table_sizes(C.byref(d), C.byref(nk), C.byref(nf)), "conv3d_u8_table_sizes")
-        dev = pc.w_packed.device
-        ktab = torch.empty((nk.value,), device=dev, dtype=torch.int32)
-        corr = torch.empty((nf.value,), device=dev, dtype=torch.float32)
-        check(lib.advhip_conv3d_u8_build_tables_sampled(C.byref(d), frame_hw[0], frame_hw[1], int(frame_step), ptr(pc.w_packed),
-                                                        C.c_float(mean), ptr(ktab), ptr(corr), stream(dev)),
-              f"conv3d_u8_build_tables[{pc.name}]")
-        tabs = cache[key] = (ktab, corr)
-    return tabs
+    """(ktab, corr) of the byte-gather uint8-frame stem: _u8_stem_tables."""
+    return _u8_stem_tables(pc, "u8", frame_hw, clip_thw, mean, frame_step)
 
 
 def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv", first: int, count: int, frames_per_clip: int = 16,
@@ -849,19 +879,8 @@ def conv3d_u8_tencrop_bn_relu_maxpool233(frames: torch.Tensor, pc: "PackedConv",
     if count <= 0 or first < 0 or first + count > n:
         raise ValueError(f"{pc.name}: crop-clips [{first}, {first + count}) outside the video's {n}")
     d = pc.desc(count, frames_per_clip, crop, crop, True, 0, 1)
+    y, ws, need = _pool233_out(pc, d, f"clips of ({frames_per_clip},{crop},{crop})", out, frames.device)
     lib = _lib.load()
-    tp, hp, wp = C.c_int32(), C.c_int32(), C.c_int32()
-    check(lib.advhip_conv3d_pool_out_dims(C.byref(d), 2, 3, 3, 2, 2, 2, C.byref(tp), C.byref(hp), C.byref(wp)), "conv3d_pool_out_dims")
-    shape = (count, pc.cout, tp.value, hp.value, wp.value)
-    if min(shape) <= 0:
-        raise ValueError(f"{pc.name}: clips of ({frames_per_clip},{crop},{crop}) too small for conv + (2,3,3) pooling")
-    y = out if out is not None else torch.empty(shape, device=frames.device, dtype=torch.float32)
-    if tuple(y.shape) != shape or y.dtype != torch.float32 or y.device != frames.device:
-        raise ValueError(f"{pc.name}: out {tuple(y.shape)} != {shape}")
-    need = lib.advhip_conv3d_relu_maxpool233_workspace_bytes(C.byref(d))
-    if need < 0:
-        check(int(need), f"conv3d_relu_maxpool233_workspace_bytes[{pc.name}]")
-    ws = workspace(frames.device, need)
     if U8_STEM_FORM in ("taps", "planes") and pc.cin == 3 and pc.cout == 64:
         frames = with_slack(frames)
         ktab, corr, wt = ensure_u8_taps_tables(pc, (FH, FW), (frames_per_clip, crop, crop), mean, fstep)

@@ -334,3 +334,60 @@ def test_long_video_segments_and_cache_names_with_a_normalisation(tmp_path):
     assert plain["vid"].endswith("vid_i3d_c4.npy") and reads == [(0, 32), (32, 53)]
     assert not np.array_equal(np.load(plain["vid"]), whole)
     assert run(normalize=spec) == {}  # the reference's skip-if-exists rule, per name
+
+
+# ---- 6. the scalar pair at channel counts other than 3 --------------------------------------------------------------------------
+
+def scalar_pair_ref(frames, mean, std, frames_per_clip, crop, clip_stride, frame_step, crops):
+    """tencrop_ref's windows and mirror with the scalar pair: (float32(px) - float32(mean)) / float32(std), any C."""
+    from anomaly_detection_on_video_amd import ops
+    from oracle.host_oracle import ten_crop_clips
+
+    s, crops, d = ops.resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
+    F = frames.shape[0]
+    rows = []
+    for w in range(ops.n_windows(F, frames_per_clip, s, d)):
+        clip = frames[list(ops.window_frame_indices(F, w, frames_per_clip, s, d))]
+        px = ten_crop_clips(clip, frames_per_clip, crop, mean=0.0, std=1.0)[0]  # (10, C, T, crop, crop): the pixels as floats
+        assert px.dtype == np.float32
+        rows.append(((px - np.float32(mean)) / np.float32(std))[list(crops)])
+    return np.concatenate(rows, axis=0)
+
+
+@pytest.mark.parametrize("frame_step", [None, 2])
+@pytest.mark.parametrize("channels", [1, 2, 4])
+def test_scalar_pair_passes_at_other_channel_counts(channels, frame_step):
+    """The scalar pair takes any C (the per-channel triples do not): 9 frames, windows of 4 at stride 3 with a short last window
+    (LoopPad) with and without frame_step, crops (1, 4, 7) -- a corner, the centre, a mirrored corner; crop 32 (16-byte stores) and
+    30 (scalar stores); the default pair and another; planes over a range that starts and ends mid-clip.  Bit for bit."""
+    from anomaly_detection_on_video_amd import mil_ops, ops
+
+    fpc, s, crops = 4, 3, (1, 4, 7)
+    frames = _frames(600 + channels, (9, 33, 35, channels), plant=False)
+    fd = torch.from_numpy(frames).to(_dev())
+    n = ops.n_windows(9, fpc, s, frame_step) * len(crops)
+    assert ops.window_frame_indices(9, n // 3 - 1, fpc, s, frame_step)[3] < ops.window_frame_indices(9, n // 3 - 1, fpc, s, frame_step)[2]  # LoopPad
+    for crop in (32, 30):
+        for pair in ({}, dict(mean=100.5, std=3.0)):
+            want = scalar_pair_ref(frames, pair.get("mean", 114.75), pair.get("std", 57.375), fpc, crop, s, frame_step, crops)
+            assert want.shape == (n, channels, fpc, crop, crop)
+            got = mil_ops.tencrop_normalize_u8(fd, fpc, crop, clip_stride=s, crops=crops, frame_step=frame_step, **pair)
+            assert same(got, want), (crop, pair)
+            for first, count in ((0, n), (1, n - 2)):
+                xs = ops.tencrop_planes_u8(fd, first, count, fpc, crop, clip_stride=s, crops=crops, frame_step=frame_step, **pair)
+                assert same(xs, planes_of(want[first : first + count])), (crop, pair, first, count)
+
+
+def test_modes_passes_refuse_four_channels():
+    """The `_modes` passes take their constants as triples: C = 4 is refused by the entry points, a four-entry parameter by
+    resolve_normalize."""
+    from anomaly_detection_on_video_amd import _lib, mil_ops, ops
+
+    fd = torch.from_numpy(_frames(604, (9, 33, 35, 4), plant=False)).to(_dev())
+    for spec in (MODES["std_channels"], "pixel_minmax", "channel_minmax"):
+        with pytest.raises(_lib.HipExtensionError, match="triples"):
+            mil_ops.tencrop_normalize_u8(fd, 4, 32, clip_stride=3, normalize=spec)
+        with pytest.raises(_lib.HipExtensionError, match="triples"):
+            ops.tencrop_planes_u8(fd, 0, 2, 4, 32, clip_stride=3, normalize=spec)
+    with pytest.raises(ValueError, match="three entries"):
+        ops.resolve_normalize(("standardize", (1.0, 2.0, 3.0, 4.0), 1.0))

@@ -298,3 +298,63 @@ def test_new_entry_points_refuse_before_any_launch():
     assert planes(first=45, count=6) == -1 and b"outside the video's 50" in err()  # 70 frames: 5 windows x 10
     assert planes(first=-1) == -1
     assert planes(count=0) == -1
+
+
+TENCROP_NAMES = [f"tencrop_normalize{p}_u8{k}" for p in ("", "_planes") for k in ("", "_strided", "_crops", "_sampled", "_modes")]
+# what each spelling takes beyond (frames, out, F, H, W, C, frames_per_clip, crop, [first, count,] the normalisation, stream)
+TENCROP_TAKES = {"": (), "_strided": ("s",), "_crops": ("s", "crops"), "_sampled": ("s", "crops", "d"), "_modes": ("s", "crops", "d")}
+
+
+@pytest.mark.parametrize("name", TENCROP_NAMES)
+def test_every_tencrop_name_refuses_before_any_launch(name):
+    """The ten C names of the two TenCrop passes, 70 frames of 256 x 340 x 3 in clips of 16: the refusals they share, and those of
+    the arguments each one takes.  Every call returns ADVHIP_EINVAL (-1) with its message; nothing is launched, the stand-in
+    device pointers are never dereferenced."""
+    _lib, lib = _lib_built()
+    p = C.c_void_p(4096)
+    kind = name.rsplit("u8", 1)[1]
+    takes, is_planes = TENCROP_TAKES[kind], "_planes" in name
+    tri = lambda *v: (C.c_double * 3)(*v)
+
+    def call(**k):
+        assert set(k) <= {"frames", "out", "H", "crop", "std", "first", "count"} | set(takes) | ({"nc"} if "crops" in takes else set()), k
+        args = [k.get("frames", p), k.get("out", p), 70, k.get("H", 256), 340, 3, 16]
+        if "s" in takes:
+            args.append(k.get("s", 16))
+        if "d" in takes:
+            args.append(k.get("d", 1))
+        args.append(k.get("crop", 224))
+        if "crops" in takes:
+            args += [k.get("nc", 10), k.get("crops", 0x9876543210)]
+        if is_planes:
+            args += [k.get("first", 0), k.get("count", 10)]
+        if kind == "_modes":  # per-channel standardisation: the mode whose constants are (mean, std)
+            args += [_lib.NORM_STANDARDIZE, tri(114.75, 114.75, 114.75), tri(57.375, k.get("std", 57.375), 57.375), None, 1]
+        else:
+            args += [C.c_float(114.75), C.c_float(k.get("std", 57.375))]
+        return getattr(lib, "advhip_" + name)(*args, None)
+
+    err = lambda: lib.advhip_last_error()
+    assert call(H=200) == -1 and b"frames (200 x 340) smaller than the 224 crop" in err()
+    assert call(frames=None) == -1
+    assert call(out=None) == -1
+    assert call(crop=0) == -1
+    assert call(crop=-2) == -1
+    assert call(std=0.0) == -1 and b"std must be non-zero" in err()
+    if "d" in takes:
+        assert call(d=0) == -1 and b"frame step 0" in err()
+        assert call(d=2, s=33) == -1 and b"clip stride 33 outside [1, 32]" in err()
+    if "s" in takes:
+        assert call(s=0) == -1 and b"clip stride 0 outside [1, 16]" in err()
+        assert call(s=17) == -1 and b"clip stride 17 outside [1, 16]" in err()
+    if "crops" in takes:
+        assert call(nc=2, crops=0x49) == -1 and b"crop set" in err()    # descending
+        assert call(nc=2, crops=0x44) == -1 and b"crop set" in err()    # a duplicate
+        assert call(nc=1, crops=0xa) == -1 and b"crop set" in err()     # index 10
+        assert call(nc=1, crops=0x14) == -1 and b"crop set" in err()    # bits above the last index
+        assert call(nc=0, crops=0) == -1 and b"crop set" in err()
+        assert call(nc=11) == -1 and b"crop set" in err()
+    if is_planes:
+        assert call(first=45, count=6) == -1 and b"outside the video's 50" in err()  # 70 frames: 5 windows x 10 crops
+        assert call(first=-1) == -1 and b"outside the video's 50" in err()
+        assert call(count=0) == -1 and b"outside the video's 50" in err()
