@@ -264,6 +264,11 @@ SIGNATURES = {
     "advhip_crop_mean_scatter_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     # (src0, idx0, lab0, n0, b0, src1, idx1, lab1, n1, b1, dst, dst_lab0, dst_lab1, R, stream): rows of two stores by index, one launch
     "advhip_gather_batch_f32": (C.c_int, [_P, _P, _P, _L, _I, _P, _P, _P, _L, _I, _P, _P, _P, _L, _P]),
+    # anomaly events from per-frame scores of a ragged batch: (scores, offsets, V, N, window, out, stream)
+    "advhip_smooth_scores_f32": (C.c_int, [_P, _P, _L, _L, _I, _P, _P]),
+    "advhip_score_events_ws_bytes": (_L, [_L, _L]),
+    # (smoothed, offsets, V, N, low, high, merge_gap, min_len, ev_int, ev_f, cap, counts, meta, workspace, workspace_bytes, stream)
+    "advhip_score_events": (C.c_int, [_P, _P, _L, _L, C.c_float, C.c_float, _I, _I, _P, _P, _L, _P, _P, _P, _L, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

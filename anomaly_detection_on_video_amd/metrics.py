@@ -158,7 +158,7 @@ class FrameAucPlan:
     integer counts, the two areas are the host's float64 arithmetic on them.  One synchronisation (roc_counts' read-back) and
     one copy of the compact curve per call.  With clip_stride below the span, compute() first assembles the per-frame scores
     video by video on the device (mil_ops.frame_scores; nothing synchronises).  ValueError: a video whose label count does not
-    fit its windows (by index), and NaN / inf scores at compute()."""
+    fit its windows (by index), and NaN / inf scores at compute().  `events(spec)`: the anomaly events of the same scores."""
 
     def __init__(self, labels_per_video, windows_per_video, frames_per_clip: int = 16, clip_stride: Optional[int] = None,
                  frame_step: Optional[int] = None, device="cuda"):
@@ -175,6 +175,7 @@ class FrameAucPlan:
         self.pos = torch.from_numpy(it.pos).to(self.device)
         self.neg = torch.from_numpy(it.neg).to(self.device)
         self.workspace = mil_ops.roc_counts_workspace(it.pos.size, self.device)
+        self._event_state = None  # events(): (frame scores, smoothed scores, frame offsets, workspace), made on the first call
 
     def __len__(self) -> int:
         return len(self.items.windows)
@@ -208,6 +209,35 @@ class FrameAucPlan:
         _, tps, fps = self._counts()
         tps, fps = torch.stack((tps, fps)).cpu().numpy()  # (one copy of the compact curve)
         return roc_auc_from_counts(tps, fps), pr_auc_from_counts(tps, fps)
+
+    def events(self, spec):
+        """The anomaly events of the whole test set from the scores in the plan's buffer (events.find_events: moving average,
+        two thresholds, gap merge, minimum length) -> events.Events of device tensors, in FRAMES local to each video, equal to
+        events.find_events_host on metrics.frame_scores of the same scores.  The per-frame scores are assembled as for the
+        AUCs (default stride: np.repeat of all the window scores, one launch; clip_stride below the span: mil_ops.frame_scores
+        video by video); the buffers are allocated on the first call.  One synchronisation: the read-back of the number of
+        events."""
+        import torch
+
+        from . import events, mil_ops
+
+        spec = events.resolve_event_spec(spec)
+        if spec is None:
+            raise ValueError("FrameAucPlan.events: no event spec")
+        it = self.items
+        n = int(it.frame_offsets[-1])
+        if self._event_state is None:
+            frames = self.frame_buffer if it.per_frame else torch.empty((n,), device=self.device, dtype=torch.float32)
+            self._event_state = (frames, torch.empty((n,), device=self.device, dtype=torch.float32),
+                                 torch.from_numpy(it.frame_offsets).to(self.device), mil_ops.score_events_workspace(n, len(self), self.device))
+        frames, smoothed, offsets, workspace = self._event_state
+        if it.per_frame:
+            fo = it.frame_offsets
+            for i in range(len(self)):
+                mil_ops.frame_scores(self.slot(i), it.span, it.stride, it.frames[i], out=frames[int(fo[i]):int(fo[i + 1])])
+        else:  # every video has windows * span frames: the repeat of the whole buffer is the videos' repeats back to back
+            mil_ops.frame_scores(self.scores, it.span, it.span, out=frames)
+        return events._find_events_device(frames, offsets, it.frame_offsets, spec, workspace, smoothed)
 
 
 def frame_level_auc_device(preds_per_video, labels_per_video, frames_per_clip: int = 16, clip_stride: Optional[int] = None,

@@ -429,3 +429,104 @@ def roc_counts(scores: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
     if bad:
         raise ValueError(f"roc_counts: {bad} non-finite scores (NaN or inf) among {m}: the curve is undefined")
     return thresholds[:g], tps[:g], fps[:g]
+
+
+def _ragged_checks(what: str, scores: torch.Tensor, offsets: torch.Tensor) -> Tuple[int, int]:
+    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() == 0:
+        raise ValueError(f"{what}: scores must be a non-empty fp32 (N,) tensor, got {scores.dtype} {tuple(scores.shape)}")
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2:
+        raise ValueError(f"{what}: offsets must be an int64 (V + 1,) tensor with V >= 1, got {offsets.dtype} {tuple(offsets.shape)}")
+    if scores.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: {scores.shape[0]} positions, the limit is 2^31 - 1")
+    require_gpu(scores, offsets)
+    return scores.shape[0], offsets.shape[0] - 1
+
+
+def _host_offsets(what: str, offsets: torch.Tensor, offsets_host, n: int):
+    """The offsets as a host int64 array (`offsets_host`, or one read-back of the device tensor), checked: non-decreasing from 0
+    to n."""
+    import numpy as np
+
+    host = offsets.cpu().numpy() if offsets_host is None else np.asarray(offsets_host)
+    if host.dtype.kind not in "iu" or host.shape != (offsets.shape[0],):
+        raise ValueError(f"{what}: the host copy of the offsets must hold {offsets.shape[0]} integers, got {host.dtype} {host.shape}")
+    host = host.astype(np.int64)
+    if host[0] != 0 or host[-1] != n or (np.diff(host) < 0).any():
+        raise ValueError(f"{what}: offsets must be non-decreasing from 0 to N = {n}, got {host[0]} .. {host[-1]}"
+                         + (" with a decreasing step" if (np.diff(host) < 0).any() else ""))
+    return host
+
+
+def smooth_scores(scores: torch.Tensor, offsets: torch.Tensor, window: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Centred moving average of a ragged batch of score curves on the device: `scores` fp32 (N,) holds V videos back to back,
+    video v = scores[offsets[v]:offsets[v + 1]] (`offsets` int64 (V + 1,) on the same device, non-decreasing from 0 to N; a
+    length of 0 is allowed).  `window` w is odd, 1 <= w <= 1023: y[t] = sum(x[max(0, t - h) .. min(L - 1, t + h)]) / count with
+    h = (w - 1) / 2, never across a video boundary; the sum is fp32 in ascending order from +0.0, one division by the count
+    (frame_scores' convention), so w = 1 returns the input's bits (-0.0 becomes +0.0) and NaN / inf propagate as IEEE does.
+    `out`: a contiguous fp32 (N,) tensor on the same device, not `scores` itself.  One launch, nothing synchronises."""
+    n, v = _ragged_checks("smooth_scores", scores, offsets)
+    w = int(window)
+    if w != window or not 1 <= w <= 1023 or w % 2 == 0:
+        raise ValueError(f"smooth_scores: window {window!r} is not an odd integer in [1, 1023]")
+    if out is None:
+        out = torch.empty_like(scores)
+    else:
+        require_gpu(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != (n,) or out.device != scores.device:
+            raise ValueError(f"smooth_scores: out must be fp32 ({n},) on {scores.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if out.data_ptr() == scores.data_ptr():
+            raise ValueError("smooth_scores: out must not be the scores themselves (a frame reads its neighbours)")
+    check(_lib.load().advhip_smooth_scores_f32(ptr(scores), ptr(offsets), v, n, w, ptr(out), stream()), "smooth_scores")
+    return out
+
+
+def score_events_workspace(n: int, v: int, device) -> torch.Tensor:
+    """The scratch buffer `score_events` needs for n positions in v videos (uint8; reusable for that size or smaller ones)."""
+    nbytes = _lib.load().advhip_score_events_ws_bytes(int(n), int(v))
+    if nbytes < 0:
+        check(int(nbytes), "score_events_ws_bytes")
+    return torch.empty((nbytes,), device=device, dtype=torch.uint8)
+
+
+def score_events(smoothed: torch.Tensor, offsets: torch.Tensor, low: float, high: float, merge_gap: int = 0, min_len: int = 1,
+                 workspace: Optional[torch.Tensor] = None, offsets_host=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Events of a ragged batch of (smoothed) score curves on the device, laid out as for `smooth_scores`.  A frame is active iff
+    y >= low and strong iff y >= high (low <= high, finite; a NaN is neither).  Candidates are the maximal runs of active frames,
+    two runs at most `merge_gap` inactive frames apart being one (as a chain); a candidate is an event iff it holds a strong
+    frame and is at least `min_len` frames long.  -> (ev_int int32 (E, 4) = video, start, end, peak_frame; ev_f fp32 (E, 2) =
+    peak, mean; counts int32 (V,)), in (video, start) order, frames local to the video and `end` exclusive; peak = the largest y
+    of the interval (NaN ignored) at its first frame, mean = the float64 sum over [start, end) / length rounded to fp32 (gap
+    frames included: a NaN there shows).  Identical bits in every run.  One read-back of two integers is the only
+    synchronisation.  `offsets_host`: the host copy of the offsets (any integer sequence), from which the wrapper checks them and
+    sizes the event list (sum of ceil(L_v / 2) rows: nothing can overflow); without it the device tensor is read back once more.
+    `workspace`: a buffer from score_events_workspace(n >= N, v >= V, device) to reuse."""
+    import math
+
+    n, v = _ragged_checks("score_events", smoothed, offsets)
+    low, high = float(low), float(high)
+    if not (math.isfinite(low) and math.isfinite(high)) or low > high:
+        raise ValueError(f"score_events: thresholds low = {low}, high = {high}: finite, low <= high")
+    if int(merge_gap) != merge_gap or not 0 <= merge_gap < 1 << 31:
+        raise ValueError(f"score_events: merge_gap {merge_gap!r} is not an integer in [0, 2^31)")
+    if int(min_len) != min_len or not 1 <= min_len < 1 << 31:
+        raise ValueError(f"score_events: min_len {min_len!r} is not an integer in [1, 2^31)")
+    if workspace is not None and (workspace.dtype != torch.uint8 or workspace.dim() != 1):
+        raise ValueError(f"score_events: workspace must be a uint8 (bytes,) tensor, got {workspace.dtype} {tuple(workspace.shape)}")
+    require_gpu(workspace)
+    host = _host_offsets("score_events", offsets, offsets_host, n)
+    lengths = host[1:] - host[:-1]
+    cap = max(1, int(((lengths + 1) // 2).sum()))
+    lib = _lib.load()
+    if workspace is None:
+        workspace = score_events_workspace(n, v, smoothed.device)
+    dev = smoothed.device
+    ev_int = torch.empty((cap, 4), device=dev, dtype=torch.int32)
+    ev_f = torch.empty((cap, 2), device=dev, dtype=torch.float32)
+    counts = torch.empty((v,), device=dev, dtype=torch.int32)
+    meta = torch.empty((2,), device=dev, dtype=torch.int64)
+    check(lib.advhip_score_events(ptr(smoothed), ptr(offsets), v, n, low, high, int(merge_gap), int(min_len), ptr(ev_int), ptr(ev_f), cap,
+                                  ptr(counts), ptr(meta), ptr(workspace), workspace.numel(), stream()), "score_events")
+    found, written = meta.tolist()  # the one synchronisation
+    if found > written:
+        raise _lib.HipExtensionError(f"score_events: {found} events for {cap} rows: the offsets on the device are not the host's")
+    return ev_int[:written], ev_f[:written], counts

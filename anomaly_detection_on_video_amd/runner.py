@@ -49,6 +49,8 @@ class VideoAnomalyDetectionRunner:
         self.auc_plan: Optional[metrics.FrameAucPlan] = None  # data.device_metrics: the validation metrics' device state (setup)
         self.score_plan = None  # data.val_batch_videos > 1: val_batch.ScoreBatchPlan of the resident test set (setup)
         self._val_scores = None  # ... and, without device_metrics, the flat device buffer its passes write
+        self.event_spec = None  # data.events: events.EventSpec of the validation pass's event list (setup)
+        self.last_events = None  # ... and the last validation pass's events.Events (device tensors, frames)
         self.logged: Dict[str, float] = {}
         self.device = torch.device("cpu")
         self.current_epoch = 0  # set by Trainer.fit before every train_dataloader(): what data.shuffle's order is a function of
@@ -136,8 +138,14 @@ class VideoAnomalyDetectionRunner:
                                                       int(self.hparams.data["frames_per_clip"]))
         self.log("valid/rec_auc", rec_auc)
         self.log("valid/pr_auc", pr_auc)
+        out = {"valid/rec_auc": rec_auc, "valid/pr_auc": pr_auc}
+        if self.event_spec is not None and self.auc_plan is not None and not outs:
+            # data.events: the test set's anomaly events from the scores the AUCs were counted on (one more read-back: their number)
+            self.last_events = self.auc_plan.events(self.event_spec)
+            out["valid/n_events"] = len(self.last_events)
+            self.log("valid/n_events", out["valid/n_events"])
         self.validation_step_outputs = []
-        return {"valid/rec_auc": rec_auc, "valid/pr_auc": pr_auc}
+        return out
 
     # runner.py:93-105
     def setup(self, stage: str = "fit") -> None:
@@ -152,6 +160,12 @@ class VideoAnomalyDetectionRunner:
         if device_metrics and not bool(d.get("resident", False)):
             raise ValueError("data.device_metrics=true needs data.resident=true: the validation scores stay on the device only "
                              "when the test set is served from it")
+        from .events import resolve_event_spec
+
+        self.event_spec, self.last_events = resolve_event_spec(d.get("events")), None  # (refuses a bad spec before anything is loaded)
+        if self.event_spec is not None and not device_metrics:
+            raise ValueError("data.events needs data.device_metrics=true: the events are found in the device score buffer of the "
+                             "validation metrics (events.find_events_host is the host path)")
         batch_videos = int(d.get("val_batch_videos", 1))
         if batch_videos < 1:
             raise ValueError(f"data.val_batch_videos={batch_videos} must be at least 1")

@@ -996,6 +996,42 @@ int64_t advhip_roc_counts_ws_bytes(int64_t M);
 int advhip_roc_counts(const float* scores, const int32_t* pos, const int32_t* neg, int64_t M, float* thresholds, int64_t* tps,
                       int64_t* fps, int64_t* meta, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Anomaly events from per-frame scores: smoothing, two thresholds with hysteresis, gap merge, minimum length, event list.
+ * The input is a ragged batch of V videos flattened into N = offsets[V] positions, 1 <= N < 2^31: video v is
+ * [offsets[v], offsets[v + 1]) (offsets: device int64 (V + 1,), non-decreasing from 0 to N; a length of 0 is allowed and gives no
+ * events).  No step looks across a video boundary.  The rule, for a video x of L frames:
+ *   1. smooth   window w odd, 1 <= w <= 1023, h = (w - 1) / 2: y[t] = (sum of x[u], u = max(0, t - h) .. min(L - 1, t + h)) / count,
+ *               the sum in fp32 in ascending u starting from +0.0f, one fp32 division by the count (advhip_frame_scores_f32's
+ *               convention).  w = 1 returns x's bits, except that -0.0 becomes +0.0.  NaN and +-inf propagate as IEEE does.
+ *   2. flags    active[t] = y[t] >= low, strong[t] = y[t] >= high; a NaN is neither, -0.0 >= 0.0 is true.  low <= high, both finite.
+ *   3. candidates  maximal runs of active frames; two runs separated by at most merge_gap frames that are not active are one
+ *               candidate, as a chain (merge_gap >= 0, 0: no merging).  Equivalently: frame t starts a candidate iff it is active
+ *               and no frame of [t - merge_gap - 1, t - 1] inside its video is, and ends one by the mirror image.
+ *   4. keep     a candidate iff it holds a strong frame and end - start >= min_len (min_len >= 1).
+ *   5. record   in (video, start) order: video, start, end (frames local to the video, end exclusive), peak (the largest y of the
+ *               interval, NaN ignored: a copied float), peak_frame (the first frame whose y equals the peak), mean (the float64
+ *               sum of y[start:end] divided by the length, rounded to fp32; the frames of merged gaps are included, so a NaN
+ *               there gives a NaN mean).
+ * advhip_smooth_scores_f32 is step 1: out fp32 (N,), not the scores themselves.  One launch.
+ * advhip_score_events is steps 2 to 5 on the smoothed scores: ev_int int32 (cap, 4) = {video, start, end, peak_frame}, ev_f fp32
+ * (cap, 2) = {peak, mean}, counts int32 (V,) = events per video, meta int64 (2,) = {events found, events written = min(found,
+ * cap)}; rows from meta[1] on are not written.  cap = sum of ceil(L_v / 2) holds every possible result (merge_gap = 0, min_len = 1,
+ * every second frame active).  Every output is an integer, a copied float, or a sum in a fixed order: the same bits in every run
+ * (the float64 sum of an event: 64 strided partial sums in ascending frame order, then a fixed tree over them).
+ * Method: exclusive max-scans of (active ? position : -1) forward and over the reversed order give the nearest active frame on
+ * either side, whose apply step writes the start / end marks; a scan of the marks numbers the candidates; one wave per candidate
+ * reduces it in a loop; a scan of the keep flags compacts the events.  Multi-block scans are reduce / scan of the partials /
+ * apply as separate launches: no workgroup waits on another.  One memset of counts and 5 to 21 launches on `stream` (13 at
+ * N = 2^20); nothing synchronises.  workspace: advhip_score_events_ws_bytes(N, V) bytes (about 16 N), 8-byte aligned, scratch only.
+ * Refused with ADVHIP_EINVAL before anything is launched: null pointers, N outside [1, 2^31), V < 1, an even window or one
+ * outside [1, 1023], low > high or a threshold that is not finite, merge_gap < 0, min_len < 1, cap < 1, a short workspace.  The
+ * offsets are read on the device only; whatever they hold, no access leaves the arrays. */
+int advhip_smooth_scores_f32(const float* scores, const int64_t* offsets, int64_t V, int64_t N, int32_t window, float* out, void* stream);
+int64_t advhip_score_events_ws_bytes(int64_t N, int64_t V);
+int advhip_score_events(const float* smoothed, const int64_t* offsets, int64_t V, int64_t N, float low, float high, int32_t merge_gap,
+                        int32_t min_len, int32_t* ev_int, float* ev_f, int64_t cap, int32_t* counts, int64_t* meta, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
