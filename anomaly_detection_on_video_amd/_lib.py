@@ -269,7 +269,15 @@ SIGNATURES = {
     "advhip_score_events_ws_bytes": (_L, [_L, _L]),
     # (smoothed, offsets, V, N, low, high, merge_gap, min_len, ev_int, ev_f, cap, counts, meta, workspace, workspace_bytes, stream)
     "advhip_score_events": (C.c_int, [_P, _P, _L, _L, C.c_float, C.c_float, _I, _I, _P, _P, _L, _P, _P, _P, _L, _P]),
+    # which kernel form a scorer launch takes: (C, N, aligned16) / (T, aligned16) -> form id (include/advhip.h); nothing is launched
+    "advhip_bn_rows_form": (_I, [_I, _L, _I]),
+    "advhip_chan_layernorm_form": (_I, [_I, _L, _I]),
+    "advhip_head_ln_fc_form": (_I, [_I, _L, _I]),
+    "advhip_dwconv_t_form": (_I, [_I, _I]),
 }
+
+# advhip_bn_rows_form's answers (ADVHIP_BN_ROWS_* of include/advhip.h)
+BN_ROWS_GENERIC, BN_ROWS_REG256X4, BN_ROWS_REG256X12, BN_ROWS_REG1024X4 = 0, 1, 2, 3
 
 _lib: Optional[C.CDLL] = None
 

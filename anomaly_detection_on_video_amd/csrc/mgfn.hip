@@ -357,13 +357,24 @@ __global__ __launch_bounds__(LV_THREADS) void chan_layernorm_fwd_v4_kernel(const
   }
 }
 
-static bool launch_ln_fwd_v4(const float* x, const float* g, const float* b, float* y, float* mu, float* rs, int C, long long N, float eps, hipStream_t st) {
-  if (N % 4 != 0 || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)mu | (uintptr_t)rs) & 15) != 0) return false;
-  const dim3 grid((unsigned)((N + LV_POS - 1) / LV_POS)), block(LV_THREADS);
+// Which kernel a chan_layernorm launch takes (advhip_chan_layernorm_form): 0 = the generic one, else the CPT of the 16-byte form.
+// `aligned16`: every activation-shaped or per-position operand starts on a 16-byte boundary.
+static int ln_form(int C, long long N, bool aligned16) {
+  if (N % 4 != 0 || !aligned16) return 0;
   switch (C) {
-    case 1 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<1>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
-    case 2 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<2>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
-    case 16 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<16>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
+    case 1 * LV_GROUPS: return 1;
+    case 2 * LV_GROUPS: return 2;
+    case 16 * LV_GROUPS: return 16;
+    default: return 0;
+  }
+}
+
+static bool launch_ln_fwd_v4(const float* x, const float* g, const float* b, float* y, float* mu, float* rs, int C, long long N, float eps, hipStream_t st) {
+  const dim3 grid((unsigned)((N + LV_POS - 1) / LV_POS)), block(LV_THREADS);
+  switch (ln_form(C, N, (((uintptr_t)x | (uintptr_t)y | (uintptr_t)mu | (uintptr_t)rs) & 15) == 0)) {
+    case 1: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<1>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
+    case 2: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<2>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
+    case 16: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<16>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
     default: return false;
   }
 }
@@ -371,12 +382,11 @@ static bool launch_ln_fwd_v4(const float* x, const float* g, const float* b, flo
 static bool launch_ln_bwd_v4(const float* dy, const float* x, const float* g, const float* mu, const float* rs, float* dx, float* pg, float* pb, int C,
                              long long N, float eps, const float* add, long long prow, hipStream_t st) {
   static_assert(LV_POS == LN_COLS, "the partial-sum matrices have one row per LN_COLS positions (advhip_chan_layernorm_bwd_partial_rows)");
-  if (N % 4 != 0 || (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mu | (uintptr_t)rs | (uintptr_t)add) & 15) != 0) return false;
   const dim3 grid((unsigned)((N + LV_POS - 1) / LV_POS)), block(LV_THREADS);
-  switch (C) {
-    case 1 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<1>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
-    case 2 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<2>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
-    case 16 * LV_GROUPS: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<16>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
+  switch (ln_form(C, N, (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mu | (uintptr_t)rs | (uintptr_t)add) & 15) == 0)) {
+    case 1: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<1>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
+    case 2: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<2>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
+    case 16: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<16>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
     default: return false;
   }
 }
@@ -447,6 +457,9 @@ __global__ __launch_bounds__(256) void dwconv_t_bwd_kernel(const float* __restri
   if (threadIdx.x <= K)
     partial[(((long long)(c / H) * chunks + chunk) * H + h) * (K + 1) + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
+
+// Which pair of kernels a dwconv_t launch takes (advhip_dwconv_t_form): 1 = the float4 kernels below, 0 = the ones above
+static int dwconv_t_form(int T, bool aligned16) { return T % 4 == 0 && aligned16 ? 1 : 0; }
 
 // The same two kernels with a thread owning FOUR consecutive t of a row (T % 4 == 0, 16-byte accesses, one 64-bit division per
 // quad instead of three per element): the window v[t - K/2 .. t + 3 + K/2] is the quad, its left and its right neighbour quad
@@ -594,9 +607,12 @@ __global__ __launch_bounds__(256) void bn_rows_fwd_kernel(const float* __restric
     q += d * d;
   }
   const float var = block_sum_256(q, red) / (float)N;
-  const float sc = gamma[c] * rsqrtf(var + eps), sh = beta[c] - mean * sc;
+  // (x - mean) * sc + beta, not x * sc + (beta - mean * sc): the latter rounds at the size of mean * sc, far above y's own size
+  // when sc is large (a row of one value, N = 1: sc = gamma / sqrt(eps), where this form gives y = beta exactly and that one
+  // beta +- 2e-4 at |x| ~ 2).  With the mean 40 standard deviations from zero both are bounded by the fp32 mean itself (4e-6).
+  const float sc = gamma[c] * rsqrtf(var + eps), sh = beta[c];
   float* yr = y + (long long)c * N;
-  for (long long i = threadIdx.x; i < N; i += 256) yr[i] = xr[i] * sc + sh;
+  for (long long i = threadIdx.x; i < N; i += 256) yr[i] = (xr[i] - mean) * sc + sh;
   if (threadIdx.x == 0) {
     mean_out[c] = mean;
     var_out[c] = var;
@@ -639,12 +655,12 @@ __global__ __launch_bounds__(NT) void bn_rows_fwd_reg_kernel(const float* __rest
     }
   }
   const float var = block_sum<NT>(q2, red) / (float)N;
-  const float sc = gamma[c] * rsqrtf(var + eps), sh = beta[c] - mean * sc;
+  const float sc = gamma[c] * rsqrtf(var + eps), sh = beta[c];  // (x - mean) * sc + beta, as in bn_rows_fwd_kernel
   float* yr = y + (long long)c * N;
 #pragma unroll
   for (int u = 0; u < BQ; ++u) {
     const long long q = threadIdx.x + (long long)NT * u;
-    if (q < nq) *reinterpret_cast<float4*>(yr + 4 * q) = make_float4(v[u].x * sc + sh, v[u].y * sc + sh, v[u].z * sc + sh, v[u].w * sc + sh);
+    if (q < nq) *reinterpret_cast<float4*>(yr + 4 * q) = make_float4((v[u].x - mean) * sc + sh, (v[u].y - mean) * sc + sh, (v[u].z - mean) * sc + sh, (v[u].w - mean) * sc + sh);
   }
   if (threadIdx.x == 0) {
     mean_out[c] = mean;
@@ -656,18 +672,32 @@ __global__ __launch_bounds__(NT) void bn_rows_fwd_reg_kernel(const float* __rest
   }
 }
 
+// Which kernel a bn_rows launch takes, forward and backward alike (advhip_bn_rows_form): the register forms hold a row of up to
+// NT x 4 x BQ floats; `aligned16`: every activation-shaped operand starts on a 16-byte boundary.
+static int bn_rows_form(int C, long long N, bool aligned16) {
+  const bool vec = N % 4 == 0 && aligned16;
+  if (vec && C < 512 && N <= 1024 * 4 * 4) return ADVHIP_BN_ROWS_REG1024X4;
+  if (vec && N <= 256 * 4 * 4) return ADVHIP_BN_ROWS_REG256X4;
+  if (vec && N <= 256 * 4 * 12) return ADVHIP_BN_ROWS_REG256X12;
+  return ADVHIP_BN_ROWS_GENERIC;
+}
+
 static void launch_bn_rows_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* var, int C, long long N, float eps,
                                float* run_mean, float* run_var, float momentum, hipStream_t st) {
-  const bool vec = N % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
   const dim3 grid((unsigned)C);
-  if (vec && C < 512 && N <= 1024 * 4 * 4)
-    hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-  else if (vec && N <= 256 * 4 * 4)
-    hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-  else if (vec && N <= 256 * 4 * 12)
-    hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-  else
-    hipLaunchKernelGGL(bn_rows_fwd_kernel, grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+  switch (bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)y) & 15) == 0)) {
+    case ADVHIP_BN_ROWS_REG1024X4:
+      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+      break;
+    case ADVHIP_BN_ROWS_REG256X4:
+      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+      break;
+    case ADVHIP_BN_ROWS_REG256X12:
+      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+      break;
+    default:
+      hipLaunchKernelGGL(bn_rows_fwd_kernel, grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+  }
 }
 
 // dx = gamma * rstd * (dy - mean(dy) - xhat * mean(dy * xhat)),  dgamma = sum dy * xhat,  dbeta = sum dy
@@ -812,16 +842,20 @@ __global__ __launch_bounds__(NT) void bn_rows_bwd_reg_kernel(const float* __rest
 
 static void launch_bn_rows_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* var, float* dx, float* dgamma,
                                float* dbeta, int C, long long N, float eps, const float* add, hipStream_t st) {
-  const bool vec = N % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)add) & 15) == 0;
   const dim3 grid((unsigned)C);
-  if (vec && C < 512 && N <= 1024 * 4 * 4)
-    hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-  else if (vec && N <= 256 * 4 * 4)
-    hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-  else if (vec && N <= 256 * 4 * 12)
-    hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-  else
-    hipLaunchKernelGGL(bn_rows_bwd_kernel, grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+  switch (bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)add) & 15) == 0)) {
+    case ADVHIP_BN_ROWS_REG1024X4:
+      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+      break;
+    case ADVHIP_BN_ROWS_REG256X4:
+      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+      break;
+    case ADVHIP_BN_ROWS_REG256X12:
+      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+      break;
+    default:
+      hipLaunchKernelGGL(bn_rows_bwd_kernel, grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+  }
 }
 
 // ---- the scorer's head on the body's layout (modeling_mgfn.py:387-389: permute -> nn.LayerNorm(C) -> Linear(C, 1) -> sigmoid) ----
@@ -977,6 +1011,9 @@ __global__ __launch_bounds__(LN_THREADS) void head_ln_fc_bwd_kernel(const float*
 // value of y resident in registers: ONE read of y in 16-byte accesses; the (C, N) <-> (N, C) transposition through a 32 x 64 LDS tile
 // per 64-channel chunk, rows written / read as 16-byte pieces).  C = 64 * CPT, N % 4 == 0, 16-byte aligned operands.
 constexpr int HV_PAD = LV_GROUPS + 4;  // tile row pitch in floats (16-byte aligned rows)
+
+// Which kernel a head_ln_fc launch takes (advhip_head_ln_fc_form): 1 = this form, 0 = the generic kernel above
+static int head_form(int C, long long N, bool aligned16) { return C == 16 * LV_GROUPS && N % 4 == 0 && aligned16 ? 1 : 0; }
 
 // the lane's four per-position partial sums, over the wave's 8 channel groups (lanes 8 apart) and the block's 8 waves
 __device__ __forceinline__ float4 lv_position_sum(float4 v, float (*part)[LV_POS], int pl, int wave) {
@@ -1801,6 +1838,11 @@ __global__ __launch_bounds__(AMPB_THREADS) void amp_combine_bwd_kernel(const flo
 
 using namespace advhip;
 
+extern "C" int32_t advhip_bn_rows_form(int32_t C, int64_t N, int32_t aligned16) { return bn_rows_form(C, (long long)N, aligned16 != 0); }
+extern "C" int32_t advhip_chan_layernorm_form(int32_t C, int64_t N, int32_t aligned16) { return ln_form(C, (long long)N, aligned16 != 0); }
+extern "C" int32_t advhip_head_ln_fc_form(int32_t C, int64_t N, int32_t aligned16) { return head_form(C, (long long)N, aligned16 != 0); }
+extern "C" int32_t advhip_dwconv_t_form(int32_t T, int32_t aligned16) { return dwconv_t_form(T, aligned16 != 0); }
+
 extern "C" int advhip_bn_rows_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* var,
                                       int32_t C, int64_t N, float eps, void* stream) {
   ADVHIP_REQUIRE(x && gamma && beta && y && mean && var && C > 0 && N > 0, "bn_rows_fwd: bad arguments");
@@ -1892,7 +1934,7 @@ extern "C" int advhip_dwconv_t_fwd_f32(const float* v, const float* w, const flo
   ADVHIP_REQUIRE(K == 5 || K == 3, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
   const long long total = (long long)C * rows * T;
   const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
-  if (T % 4 == 0 && (((uintptr_t)v | (uintptr_t)out) & 15) == 0) {
+  if (dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)out) & 15) == 0) == 1) {
     const int grid4 = (int)std::min<long long>((total / 4 + 255) / 256, 256 * 32);
     if (K == 5) hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<5>, dim3(grid4), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total / 4);
     else hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<3>, dim3(grid4), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total / 4);
@@ -1929,7 +1971,7 @@ extern "C" int advhip_dwconv_t_bwd_f32(const float* dout, const float* v, const 
   const int chunks = advhip_dwconv_t_bwd_chunks(C, rows);
   const long long per_c = (long long)rows * T;
   const dim3 grid((unsigned)((long long)C * chunks));
-  if (T % 4 == 0 && (((uintptr_t)v | (uintptr_t)dout | (uintptr_t)dv) & 15) == 0) {
+  if (dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)dout | (uintptr_t)dv) & 15) == 0) == 1) {
     if (K == 5) hipLaunchKernelGGL(dwconv_t_bwd_v4_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
     else hipLaunchKernelGGL(dwconv_t_bwd_v4_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
     return check_launch("dwconv_t_bwd");
@@ -2029,8 +2071,7 @@ extern "C" int advhip_head_ln_fc_fwd_f32(const float* y, const float* ln_g, cons
   ADVHIP_REQUIRE(y && ln_g && ln_b && fc_w && fc_b && xn && mean && rstd && score && C > 0 && N > 0, "head_ln_fc_fwd: bad arguments");
   const long long blocks = (N + LN_COLS - 1) / LN_COLS;
   ADVHIP_REQUIRE(blocks < (1ll << 31), "head_ln_fc_fwd: too many positions");
-  const bool v4 = C == 16 * LV_GROUPS && N % 4 == 0 &&
-                  (((uintptr_t)y | (uintptr_t)xn | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)score) & 15) == 0;
+  const bool v4 = head_form(C, (long long)N, (((uintptr_t)y | (uintptr_t)xn | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)score) & 15) == 0) == 1;
   if (v4)
     hipLaunchKernelGGL(head_ln_fc_fwd_v4_kernel<16>, dim3((unsigned)blocks), dim3(LV_THREADS), 0, (hipStream_t)stream, y, ln_g, ln_b, fc_w, fc_b, xn, mean,
                        rstd, score, (long long)N, eps);
@@ -2046,8 +2087,8 @@ extern "C" int advhip_head_ln_fc_bwd_f32(const float* d_xn, const float* d_score
   ADVHIP_REQUIRE(y && ln_g && ln_b && fc_w && mean && rstd && score && dy && partial && C > 0 && N > 0, "head_ln_fc_bwd: bad arguments");
   const long long blocks = (N + LN_COLS - 1) / LN_COLS;
   ADVHIP_REQUIRE(blocks < (1ll << 31), "head_ln_fc_bwd: too many positions");
-  const bool v4 = C == 16 * LV_GROUPS && N % 4 == 0 &&
-                  (((uintptr_t)y | (uintptr_t)d_xn | (uintptr_t)d_score | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)score | (uintptr_t)dy) & 15) == 0;
+  const bool v4 = head_form(C, (long long)N, (((uintptr_t)y | (uintptr_t)d_xn | (uintptr_t)d_score | (uintptr_t)mean | (uintptr_t)rstd |
+                                                (uintptr_t)score | (uintptr_t)dy) & 15) == 0) == 1;
   if (v4)
     hipLaunchKernelGGL(head_ln_fc_bwd_v4_kernel<16>, dim3((unsigned)blocks), dim3(LV_THREADS), 0, (hipStream_t)stream, d_xn, d_score, y, ln_g, ln_b, fc_w,
                        mean, rstd, score, dy, partial, (long long)N);

@@ -1032,6 +1032,28 @@ int advhip_score_events(const float* smoothed, const int64_t* offsets, int64_t V
                         int32_t min_len, int32_t* ev_int, float* ev_f, int64_t cap, int32_t* counts, int64_t* meta, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* --- which kernel form a scorer launch takes ---------------------------------------------------------------------------------
+ * The normalisation and depth-wise entry points above each pick one of several kernels from the channel count, the row length
+ * and the alignment of their operands.  These are those rules, as pure host functions that the launchers themselves call: the
+ * answer IS the kernel the launch runs.  Nothing is launched and no pointer is read.  `aligned16` (0 / 1): whether every operand
+ * the launcher looks at starts on a 16-byte boundary --
+ *   bn_rows fwd: x, y;  bwd: dy, x, dx, add
+ *   chan_layernorm fwd: x, y, mu, rs;  bwd: dy, x, dx, mu, rs, add
+ *   head_ln_fc fwd: y, xn, mean, rstd, score;  bwd: y, d_xn, d_score, mean, rstd, score, dy
+ *   dwconv_t fwd: v, out;  bwd: dout, v, dv           (a null operand counts as aligned).
+ * advhip_chan_stats_f32 and advhip_dwconv_t_fwd_lens_f32 have one form each and no query. */
+#define ADVHIP_BN_ROWS_GENERIC 0    /* three reads of the row, any N */
+#define ADVHIP_BN_ROWS_REG256X4 1   /* the row resident in registers: 256 threads x 4 float4, N <= 4 096 */
+#define ADVHIP_BN_ROWS_REG256X12 2  /* 256 threads x 12 float4, N <= 12 288 */
+#define ADVHIP_BN_ROWS_REG1024X4 3  /* 1 024 threads x 4 float4, N <= 16 384, fewer than 512 rows */
+int32_t advhip_bn_rows_form(int32_t C, int64_t N, int32_t aligned16);
+/* 0 = the generic kernel, otherwise the channels per thread of the 16-byte form (1, 2 or 16: C = 64, 128, 1 024) */
+int32_t advhip_chan_layernorm_form(int32_t C, int64_t N, int32_t aligned16);
+/* 0 = the generic kernel, 1 = the 16-byte form (C = 1 024) */
+int32_t advhip_head_ln_fc_form(int32_t C, int64_t N, int32_t aligned16);
+/* 0 = one element per thread, 1 = four consecutive t per thread (T % 4 == 0); the same rule forward and backward, K = 3 and 5 */
+int32_t advhip_dwconv_t_form(int32_t T, int32_t aligned16);
+
 #ifdef __cplusplus
 }
 #endif
