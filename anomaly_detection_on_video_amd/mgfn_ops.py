@@ -153,6 +153,18 @@ def invalidate_caches() -> None:
     _EPOCH += 1
 
 
+def _cached(table: Dict[int, Tuple], owner, params, build, limit: int):
+    """build()'s result, kept in `table` on id(owner) while the owner is the same object and none of `params` has changed
+    (data_ptr / version / shape / the cache epoch).  Past `limit` entries, those of owners that are gone are swept."""
+    stamp = [(p.data_ptr(), p._version, p.shape) for p in params]  # (every inference forward comes through here once per layer: kept cheap)
+    hit = table.get(id(owner))
+    if hit is None or hit[0]() is not owner or hit[1] != stamp or hit[2] != _EPOCH:  # (ids are re-used once an object is gone)
+        if len(table) > limit:
+            for k in [k for k, v in table.items() if v[0]() is None]:  # parameters and layers of discarded models
+                del table[k]
+        hit = table[id(owner)] = (weakref.ref(owner), stamp, _EPOCH, build())
+    return hit[3]
+
 
 def pack_kc_cached(param: torch.Tensor, fresh: bool = False) -> torch.Tensor:
     """pack_kc of a parameter; inference re-uses the packed copy call after call while (data_ptr, version) stay put.
@@ -166,14 +178,7 @@ def pack_kc_cached(param: torch.Tensor, fresh: bool = False) -> torch.Tensor:
         if live is not None and live[0]() is param:
             return live[1]
         return pack_kc(param.detach())
-    hit = _PACKED.get(key)
-    stamp = (param.data_ptr(), param._version, tuple(param.shape), _EPOCH)
-    if hit is None or hit[0]() is not param or hit[1] != stamp:  # (ids are re-used once a tensor is gone: check it is the same object)
-        if len(_PACKED) > 1024:
-            for k in [k for k, v in _PACKED.items() if v[0]() is None]:  # parameters of discarded models
-                del _PACKED[k]
-        hit = _PACKED[key] = (weakref.ref(param), stamp, pack_kc(param.detach()))
-    return hit[2]
+    return _cached(_PACKED, param, (param,), lambda: pack_kc(param.detach()), 1024)
 
 
 # ---- the packed operands of one differentiated forward, all in one launch ------------------------------------------------------
@@ -344,8 +349,7 @@ def colsum_group(items):
 def chan_stats(x: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """(mean, 1 / (std_biased + eps)) over the channels of a contiguous (C, B, T) activation, per position."""
     _lib.require_gpu(x)
-    c = x.shape[0]
-    n = x.numel() // c
+    c, n = x.shape[0], x.numel() // x.shape[0]
     mu = torch.empty((n,), device=x.device, dtype=torch.float32)
     rs = torch.empty_like(mu)
     check(_lib.load().advhip_chan_stats_f32(ptr(x), ptr(mu), ptr(rs), c, n, C.c_float(eps), stream(x)), "chan_stats")
@@ -509,10 +513,15 @@ def _queue_flush() -> None:
         torch.autograd.Variable._execution_engine.queue_callback(_flush_deferred)
 
 
+def _can_defer(params) -> bool:
+    """Column sums that end in these parameters' gradients may wait for the end of the backward pass."""
+    return bool(_DEFER["on"] and params and all(p is not None for p in params))
+
+
 def _defer_colsum(partial: torch.Tensor, targets, period: int = 0) -> bool:
     """Queue the column sums of a (rows, cols) partial-sum matrix; `targets` = [(parameter, lo, hi), ...]: columns [lo, hi) of the
     (de-interleaved, see advhip_colsum_group_f32) sums are that parameter's gradient.  False = the caller sums now."""
-    if not (_DEFER["on"] and targets and all(p is not None for p, _lo, _hi in targets)):
+    if not _can_defer([p for p, _lo, _hi in targets]):
         return False
     _DEFER["colsums"].append((partial, period, targets))
     _queue_flush()
@@ -540,6 +549,227 @@ K3_AS_GEMM = os.environ.get("ADV_MGFN_K3_GEMM", "1") == "1"
 # such a launch is bound by its latency chain, not by the gather's issue rate, so the unfold3(dY) pass in front of the GEMM form
 # is one launch (~5.5 us each, six per step) for nothing
 NARROW_DX_DIRECT = int(os.environ.get("ADV_MGFN_NARROW_DX_DIRECT", "128"))
+
+
+# ---- one launch wrapper per kernel entry point ---------------------------------------------------------------------------------
+# No autograd and no ctx here: each checks its operands, allocates its outputs, makes ONE C call and returns the tensors.  The
+# autograd Functions below are compositions of these and of conv_cn; nothing else in this file calls these entry points.
+def _ln_fwd(x, g, b, eps):
+    """Channel LayerNorm of a contiguous (C, B, T) activation -> (y, mean, 1 / (std + eps) per position, g flattened to (C,))."""
+    _lib.require_gpu(x, g, b, contiguous=False)
+    c, n = x.shape[0], x.numel() // x.shape[0]
+    y = torch.empty_like(x)
+    mu = torch.empty((n,), device=x.device, dtype=torch.float32)
+    rs = torch.empty_like(mu)
+    gf, bf = g.detach().reshape(c).contiguous(), b.detach().reshape(c).contiguous()
+    check(_lib.load().advhip_chan_layernorm_fwd_f32(ptr(x), ptr(gf), ptr(bf), ptr(y), ptr(mu), ptr(rs), c, n, C.c_float(eps), stream(x)),
+          "chan_layernorm_fwd")
+    return y, mu, rs, gf
+
+
+def _ln_bwd(dy, x, gf, mu, rs, eps, add=None, split=False):
+    """-> (dx (+ add: the skip connection's gradient), pgb (rows, 2C): per-block partial sums of dg in columns [0, C), of db in [C, 2C)).
+    `split` (_ChanLayerNorm): the entry point without `add` that writes two matrices -> (dx, pg (rows, C), pb (rows, C))."""
+    c, n = x.shape[0], x.numel() // x.shape[0]
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    pgb = torch.empty((lib.advhip_chan_layernorm_bwd_partial_rows(n), c if split else 2 * c), device=x.device, dtype=torch.float32)
+    if split:
+        pb = torch.empty_like(pgb)
+        check(lib.advhip_chan_layernorm_bwd_f32(ptr(dy), ptr(x), ptr(gf), ptr(mu), ptr(rs), ptr(dx), ptr(pgb), ptr(pb), c, n, C.c_float(eps), stream(x)),
+              "chan_layernorm_bwd")
+        return dx, pgb, pb
+    check(lib.advhip_chan_layernorm_bwd_add_f32(ptr(dy), ptr(x), ptr(gf), ptr(mu), ptr(rs), ptr(add), ptr(dx), ptr(pgb), c, n, C.c_float(eps),
+                                                stream(x)), "chan_layernorm_bwd_add")
+    return dx, pgb
+
+
+def _ln_param_grads(pgb, ln_params, need_g, need_b, gshape):
+    """(dg, db) of a (rows, 2C) partial-sum matrix, summed now -- or (None, None): queued with the other deferred column sums."""
+    c = pgb.shape[1] // 2
+    if need_g and need_b and _defer_colsum(pgb, [(ln_params[0], 0, c), (ln_params[1], c, 2 * c)]):
+        return None, None
+    sums = colsum(pgb)
+    return sums[:c].reshape(gshape), sums[c:].reshape(gshape)
+
+
+def _glance_fwd(qkv, heads, dim_head, scale, keep, lens=None):
+    """The attention core -> (out, aux), aux = what the backward launch needs besides qkv: (softmax,) at T = 32 (the kernel writes it
+    anyway), (out, log-sum-exp) at any other T -- or (), with a null lse pointer, when nothing is kept.  `lens`: the sequences'
+    lengths in a padded batch (no backward pass)."""
+    _lib.require_gpu(qkv)
+    c3, b, t = qkv.shape
+    lib = _lib.load()
+    out = torch.empty((c3 // 3, b, t), device=qkv.device, dtype=torch.float32)
+    if lens is not None:
+        check(lib.advhip_glance_attention_fwd_lens_f32(ptr(qkv), ptr(out), ptr(row_lens(lens, b, t, qkv.device)), heads, b, t, dim_head, C.c_float(scale),
+                                                       stream(qkv)), "glance_attention_fwd_lens")
+        return out, ()
+    if t == 32:
+        p = torch.empty((b, heads, t, t), device=qkv.device, dtype=torch.float32)
+        check(lib.advhip_glance_attention_fwd_f32(ptr(qkv), ptr(out), ptr(p), heads, b, t, dim_head, C.c_float(scale), stream(qkv)), "glance_attention_fwd")
+        return out, (p,)
+    lse = torch.empty((b, heads, t), device=qkv.device, dtype=torch.float32) if keep else None
+    check(lib.advhip_glance_attention_fwd_anyt_f32(ptr(qkv), ptr(out), ptr(lse), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
+          "glance_attention_fwd_anyt")
+    return out, ((out, lse) if keep else ())
+
+
+def _glance_bwd(dout, qkv, aux, heads, dim_head, scale):
+    _, b, t = qkv.shape
+    dqkv = torch.empty_like(qkv)
+    lib = _lib.load()
+    if t == 32:
+        check(lib.advhip_glance_attention_bwd_f32(ptr(dout), ptr(qkv), ptr(aux[0]), ptr(dqkv), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
+              "glance_attention_bwd")
+    else:
+        check(lib.advhip_glance_attention_bwd_anyt_f32(ptr(dout), ptr(qkv), ptr(aux[0]), ptr(aux[1]), ptr(dqkv), heads, b, t, dim_head, C.c_float(scale),
+                                                       stream(qkv)), "glance_attention_bwd_anyt")
+    return dqkv
+
+
+def _dwconv_fwd(v, weight, bias, lens=None):
+    """The per-head depth-wise temporal conv of a contiguous (C, B, T) activation, channel c -> head c % H -> (out, weight as (H, k)).
+    `lens`: the rows' lengths in a padded batch."""
+    _lib.require_gpu(v, weight, bias, contiguous=False)
+    c, b, t = v.shape
+    h, k = weight.shape[0], weight.shape[-1]
+    out = torch.empty_like(v)
+    w2 = weight.detach().reshape(h, k).contiguous()
+    bf = bias.detach().contiguous()
+    if lens is None:
+        check(_lib.load().advhip_dwconv_t_fwd_f32(ptr(v), ptr(w2), ptr(bf), ptr(out), c, h, b, t, k, stream(v)), "dwconv_t_fwd")
+    else:
+        rl = row_lens(lens, b, t, v.device)
+        check(_lib.load().advhip_dwconv_t_fwd_lens_f32(ptr(v), ptr(w2), ptr(bf), ptr(out), c, h, b, t, k, ptr(rl), rl.numel(), stream(v)), "dwconv_t_fwd_lens")
+    return out, w2
+
+
+def _dwconv_bwd(dout, v, w2):
+    """-> (dv, p2): p2 = the partial sums of (dw taps, db) viewed (rows = (c_idx, chunk), heads * (k + 1)); channel = c_idx * H + h_idx."""
+    c, b, t = v.shape
+    h, k = w2.shape
+    lib = _lib.load()
+    chunks = lib.advhip_dwconv_t_bwd_chunks(c, b)
+    dv = torch.empty_like(v)
+    partial = torch.empty((c * chunks, k + 1), device=v.device, dtype=torch.float32)
+    check(lib.advhip_dwconv_t_bwd_f32(ptr(dout), ptr(v), ptr(w2), ptr(dv), ptr(partial), c, h, b, t, k, stream(v)), "dwconv_t_bwd")
+    return dv, partial.view(c // h * chunks, h * (k + 1))
+
+
+def _dwconv_param_grads(p2, wshape, rel_params=None):
+    """(dw, db) of _dwconv_bwd's partial sums, summed now -- or (None, None): queued, de-interleaved with period k + 1, for
+    `rel_params` = the (weight, bias) parameters themselves."""
+    h, k = wshape[0], wshape[-1]
+    if rel_params is not None and _defer_colsum(p2, [(rel_params[0], 0, h * k), (rel_params[1], h * k, h * (k + 1))], period=k + 1):
+        return None, None
+    per_head = colsum(p2).view(h, k + 1)
+    return per_head[:, :k].reshape(wshape), per_head[:, k].contiguous()
+
+
+def _bn_fwd(x, gamma, beta, eps, running=None, momentum=0.0):
+    """Training-mode BatchNorm1d of a (C, B, T) activation -> (y, batch mean, biased batch variance).  `running` = (running_mean,
+    running_var): updated in place inside the launch.  Without it this is advhip_bn_rows_fwd_f32's launch, argument for argument
+    (csrc/mgfn.hip: both entry points call launch_bn_rows_fwd, that one with null pointers and momentum 0)."""
+    _lib.require_gpu(x, gamma, beta, contiguous=False)
+    c, n = x.shape[0], x.numel() // x.shape[0]
+    y = torch.empty_like(x)
+    mean = torch.empty((c,), device=x.device, dtype=torch.float32)
+    var = torch.empty_like(mean)
+    rm, rv = running if running is not None else (None, None)
+    check(_lib.load().advhip_bn_rows_fwd_running_f32(ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(var), ptr(rm), ptr(rv), C.c_float(momentum),
+                                                     c, n, C.c_float(eps), stream(x)), "bn_rows_fwd_running")
+    return y, mean, var
+
+
+def _bn_bwd(dy, x, gamma, mean, var, eps, add=None):
+    """-> (dx (+ add: the skip connection's gradient), dgamma, dbeta).  Without `add` this is advhip_bn_rows_bwd_f32's launch (as above)."""
+    c = x.shape[0]
+    dx = torch.empty_like(x)
+    dg = torch.empty((c,), device=x.device, dtype=torch.float32)
+    db = torch.empty_like(dg)
+    check(_lib.load().advhip_bn_rows_bwd_add_f32(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(var), ptr(add), ptr(dx), ptr(dg), ptr(db), c, x.numel() // c,
+                                                 C.c_float(eps), stream(x)), "bn_rows_bwd_add")
+    return dx, dg, db
+
+
+def _amp_combine_fwd(z, bias, mag, wm, bm, ratio, lens=None):
+    _lib.require_gpu(z, bias, wm, bm)
+    _lib.require_gpu(mag, contiguous=False)
+    _k, o, b, t = z.shape
+    y = torch.empty((o, b, t), device=z.device, dtype=torch.float32)
+    if lens is None:
+        check(_lib.load().advhip_amp_combine_fwd_f32(ptr(z), ptr(bias), ptr(mag), mag.stride(2), ptr(wm), ptr(bm), C.c_float(ratio), ptr(y), o, b, t, stream(z)),
+              "amp_combine_fwd")
+    else:
+        check(_lib.load().advhip_amp_combine_fwd_lens_f32(ptr(z), ptr(bias), ptr(mag), mag.stride(2), ptr(wm), ptr(bm), C.c_float(ratio), ptr(y), o, b, t,
+                                                          ptr(row_lens(lens, b, t, z.device)), stream(z)), "amp_combine_fwd_lens")
+    return y
+
+
+def _ffn_fused_fwd(x, g, b, eps, w1, b1, w2, b2):
+    """The narrow blocks' x + FFN(LN(x)) as ONE launch (csrc/ffn_fused.hip), on the weights as stored -> (y, xh, mu, rs, gf, h, z)."""
+    c, n = x.shape[0], x.numel() // x.shape[0]
+    xh, y = torch.empty_like(x), torch.empty_like(x)
+    mu = torch.empty((n,), device=x.device, dtype=torch.float32)
+    rs = torch.empty_like(mu)
+    gf, bf = g.detach().reshape(c).contiguous(), b.detach().reshape(c).contiguous()
+    h = torch.empty((w1.shape[0],) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+    z = torch.empty_like(h)
+    check(_lib.load().advhip_ffn_block_fwd_f32(ptr(x), ptr(gf), ptr(bf), C.c_float(eps), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(xh), ptr(mu), ptr(rs),
+                                               ptr(h), ptr(z), ptr(y), c, n, stream(x)), "ffn_block_fwd")
+    return y, xh, mu, rs, gf, h, z
+
+
+def _ffn_fused_bwd(dy, x, gf, mu, rs, eps, z, w1p, w2p):
+    """Its backward launch, on the PACKED operands ([C][4C] and [4C][C]) -> (dz, dx, pgb as _ln_bwd's)."""
+    c, n = x.shape[0], x.numel() // x.shape[0]
+    lib = _lib.load()
+    dz, dx = torch.empty_like(z), torch.empty_like(x)
+    pgb = torch.empty((lib.advhip_ffn_block_partial_rows(n), 2 * c), device=x.device, dtype=torch.float32)
+    check(lib.advhip_ffn_block_bwd_f32(ptr(dy), ptr(x), ptr(gf), ptr(mu), ptr(rs), C.c_float(eps), ptr(z), ptr(w2p), ptr(w1p), ptr(dz), ptr(dx), ptr(pgb),
+                                       c, n, stream(x)), "ffn_block_bwd")
+    return dz, dx, pgb
+
+
+def _dw_db(g: torch.Tensor, act: torch.Tensor, want_w: bool, want_b: bool, wparam=None, bparam=None):
+    """dW = g act^T over the positions (1x1 layer), and db = rowsum(g) out of the same launch -- or (None, None) when the pair was
+    queued for the grouped launch at the end of the backward pass (deferred_param_grads; `wparam` / `bparam`: the parameters)."""
+    if want_w:
+        if _defer_dw(g.view(g.shape[0], -1), act.view(act.shape[0], -1), wparam, bparam if want_b else None):
+            return None, None
+        res = ops.gemm_nt(g.view(g.shape[0], -1), act.view(act.shape[0], -1), rowsum=want_b)
+        w, b = res if want_b else (res, None)
+        return w.view(g.shape[0], act.shape[0], 1), b
+    return None, (g.sum(dim=(1, 2)) if want_b else None)
+
+
+def _ffn_pair_fwd(xh, w1, b1, w2, b2, residual, fresh, need_z):
+    """y = W2 GELU(W1 xh + b1) + b2 + residual as two launches -> (y, h, z).  `need_z` (a backward pass will come): z holds
+    GELU'(pre-activation), what that pass multiplies by; else z is None."""
+    hid, dim = w1.shape[0], w1.shape[1]
+    out = conv_cn(xh, pack_kc_cached(w1, fresh), hid, 1, shift=b1.detach(), act=ACT_GELU_D if need_z else ACT_GELU, want_preact=need_z)
+    h, z = out if need_z else (out, None)
+    return conv_cn(h, pack_kc_cached(w2, fresh), dim, 1, shift=b2.detach(), residual=residual), h, z
+
+
+def _ffn_pair_bwd(dy, xh, z, h, w1, w2, params, need, need_x, fork):
+    """Its backward, in this order: dW2 / db2, dz = (W2^T dy) * z, dW1 / db1, dxh -> (dxh, dw1, db1, dw2, db2).  `params` = the
+    parameters (w1, b1, w2, b2) themselves (deferred_param_grads), `need` = which of their gradients are wanted.
+    `fork`: the two dW launches go to the side stream (overlapped_backward), as _LinearCN's do.  _FFNCN passes True; the block
+    Functions pass False and keep theirs on the main stream.  That is how the captured training graph's parallel branches
+    are laid out, not an oversight: keep it so."""
+    hid, dim = w1.shape[0], w1.shape[1]
+    pw1, pb1, pw2, pb2 = params
+    with _Fork(*((dy, h) if fork else ())) as fk:
+        dw2, db2 = _dw_db(dy, h, need[2], need[3], pw2, pb2)
+        fk.out(dw2, db2)
+    dz = conv_cn(dy, w2.detach().view(dim, hid), hid, 1, dact_z=z, act=ACT_MUL)  # (W2^T dY) * GELU'(pre-activation), saved by the forward
+    with _Fork(*((dz, xh) if fork else ())) as fk:
+        dw1, db1 = _dw_db(dz, xh.detach(), need[0], need[1], pw1, pb1)
+        fk.out(dw1, db1)
+    dxh = conv_cn(dz, w1.detach().view(hid, dim), dim, 1) if need_x else None
+    return dxh, dw1, db1, dw2, db2
 
 
 class _LinearCN(torch.autograd.Function):
@@ -585,20 +815,11 @@ class _LinearCN(torch.autograd.Function):
                 wdx = ctx.dx_pack if ctx.dx_pack is not None else pack_dx(weight.detach())
                 dx = conv_cn(dy, wdx, cin, k, residual=dy if fold else None)
         with _Fork(dy, x) as fk:
-            want_db = ctx.has_bias and ctx.needs_input_grad[2]
-            if ctx.needs_input_grad[1]:  # dW = dY X^T, and db = rowsum(dY) out of the same launch
-                if k == 1:
-                    xk = x.detach().view(cin, -1)
-                else:
-                    xk = x.view(3 * cin, -1) if ctx.unfolded else _unfold3(x.detach())
-                if _defer_dw(dy.view(cout, -1), xk, ctx.params[0], ctx.params[1] if want_db else None):
-                    dw = db = None
-                else:
-                    res = ops.gemm_nt(dy.view(cout, -1), xk, rowsum=want_db)
-                    dw, db = res if want_db else (res, None)
-                    dw = dw.view(cout, cin, k)
-            elif want_db:
-                db = dy.sum(dim=(1, 2))
+            xk = None
+            if ctx.needs_input_grad[1]:  # dW = dY X^T, and db = rowsum(dY) out of the same launch; k = 3: X is U = unfold3(x)
+                xk = x.detach().view(cin, -1) if k == 1 else x.view(3 * cin, -1) if ctx.unfolded else _unfold3(x.detach())
+            dw, db = _dw_db(dy, xk, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], *ctx.params)
+            dw = dw.view(cout, cin, k) if dw is not None else None
             fk.out(dw, db)
         return dx, dw, db, (None if fold else (dy if ctx.has_res and ctx.needs_input_grad[3] else None)), None
 
@@ -610,12 +831,8 @@ class _FFNCN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xh, x_res, w1, b1, w2, b2, fresh):
-        hid, dim = w1.shape[0], w1.shape[1]
         need_z = any(ctx.needs_input_grad)
-        # (with a backward pass to come: z holds GELU'(pre-activation), what that pass multiplies by)
-        out = conv_cn(xh, pack_kc_cached(w1, fresh), hid, 1, shift=b1.detach(), act=ACT_GELU_D if need_z else ACT_GELU, want_preact=need_z)
-        h, z = out if need_z else (out, None)
-        y = conv_cn(h, pack_kc_cached(w2, fresh), dim, 1, shift=b2.detach(), residual=x_res.detach().contiguous())
+        y, h, z = _ffn_pair_fwd(xh, w1, b1, w2, b2, x_res.detach().contiguous(), fresh, need_z)
         if need_z:
             ctx.save_for_backward(xh, z, h, w1, w2)
         ctx.params = (w1, b1, w2, b2)
@@ -624,30 +841,10 @@ class _FFNCN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xh, z, h, w1, w2 = ctx.saved_tensors
-        hid, dim = w1.shape[0], w1.shape[1]
+        need = ctx.needs_input_grad
         dy = dy.contiguous()
-        w1p, b1p, w2p, b2p = ctx.params
-        with _Fork(dy, h) as fk:
-            dw2, db2 = _dw_db(dy, h, ctx.needs_input_grad[4], ctx.needs_input_grad[5], w2p, b2p)
-            fk.out(dw2, db2)
-        dz = conv_cn(dy, w2.detach().view(dim, hid), hid, 1, dact_z=z, act=ACT_MUL)  # (W2^T dY) * GELU'(pre-activation), saved by the forward
-        with _Fork(dz, xh) as fk:
-            dw1, db1 = _dw_db(dz, xh.detach(), ctx.needs_input_grad[2], ctx.needs_input_grad[3], w1p, b1p)
-            fk.out(dw1, db1)
-        dxh = conv_cn(dz, w1.detach().view(hid, dim), dim, 1) if ctx.needs_input_grad[0] else None
-        return dxh, (dy if ctx.needs_input_grad[1] else None), dw1, db1, dw2, db2, None
-
-
-def _dw_db(g: torch.Tensor, act: torch.Tensor, want_w: bool, want_b: bool, wparam=None, bparam=None):
-    """dW = g act^T over the positions (1x1 layer), and db = rowsum(g) out of the same launch -- or (None, None) when the pair was
-    queued for the grouped launch at the end of the backward pass (deferred_param_grads; `wparam` / `bparam`: the parameters)."""
-    if want_w:
-        if _defer_dw(g.view(g.shape[0], -1), act.view(act.shape[0], -1), wparam, bparam if want_b else None):
-            return None, None
-        res = ops.gemm_nt(g.view(g.shape[0], -1), act.view(act.shape[0], -1), rowsum=want_b)
-        w, b = res if want_b else (res, None)
-        return w.view(g.shape[0], act.shape[0], 1), b
-    return None, (g.sum(dim=(1, 2)) if want_b else None)
+        dxh, dw1, db1, dw2, db2 = _ffn_pair_bwd(dy, xh, z, h, w1, w2, ctx.params, need[2:6], need[0], fork=True)
+        return dxh, (dy if need[1] else None), dw1, db1, dw2, db2, None
 
 
 class _FFNBlockCN(torch.autograd.Function):
@@ -660,73 +857,39 @@ class _FFNBlockCN(torch.autograd.Function):
     def forward(ctx, x, g, b, eps, w1, b1, w2, b2, fresh):
         _lib.require_gpu(x, g, b, w1, b1, w2, b2, contiguous=False)
         c = x.shape[0]
-        n = x.numel() // c
-        hid = w1.shape[0]
-        xh = torch.empty_like(x)
-        mu = torch.empty((n,), device=x.device, dtype=torch.float32)
-        rs = torch.empty_like(mu)
-        gf, bf = g.detach().reshape(c).contiguous(), b.detach().reshape(c).contiguous()
-        ctx.fused = fused_ffn_ok(c, hid, n, w1, w2)
+        ctx.fused = fused_ffn_ok(c, w1.shape[0], x.numel() // c, w1, w2)
+        ctx.params, ctx.ln_params = (w1, b1, w2, b2), (g, b)
+        ctx.eps, ctx.gshape = eps, g.shape
         if ctx.fused:
             # the narrow blocks (64 / 128 channels): LayerNorm, both GEMMs, GELU and the residual add as ONE launch (csrc/ffn_fused.hip);
             # the packed operands are what the backward launch multiplies by (valid until the next forward, like every step pack)
             w1p, w2p = pack_kc_cached(w1, fresh), pack_kc_cached(w2, fresh)
-            h = torch.empty((hid,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
-            z, y = torch.empty_like(h), torch.empty_like(x)
-            check(_lib.load().advhip_ffn_block_fwd_f32(ptr(x), ptr(gf), ptr(bf), C.c_float(eps), ptr(w1.detach()), ptr(b1.detach()), ptr(w2.detach()),
-                                                       ptr(b2.detach()), ptr(xh), ptr(mu), ptr(rs), ptr(h), ptr(z), ptr(y), c, n, stream(x)), "ffn_block_fwd")
+            y, xh, mu, rs, gf, h, z = _ffn_fused_fwd(x, g, b, eps, w1, b1, w2, b2)
             ctx.save_for_backward(x, gf, mu, rs, xh, z, h, w1p, w2p)
-            ctx.params = (w1, b1, w2, b2)
-            ctx.ln_params = (g, b)
-            ctx.eps, ctx.gshape = eps, g.shape
-            return y
-        check(_lib.load().advhip_chan_layernorm_fwd_f32(ptr(x), ptr(gf), ptr(bf), ptr(xh), ptr(mu), ptr(rs), c, n, C.c_float(eps), stream(x)),
-              "chan_layernorm_fwd")
-        h, z = conv_cn(xh, pack_kc_cached(w1, fresh), hid, 1, shift=b1.detach(), act=ACT_GELU_D, want_preact=True)  # z = GELU'(pre-activation)
-        y = conv_cn(h, pack_kc_cached(w2, fresh), c, 1, shift=b2.detach(), residual=x)
-        ctx.save_for_backward(x, gf, mu, rs, xh, z, h, w1, w2)
-        ctx.params = (w1, b1, w2, b2)
-        ctx.ln_params = (g, b)
-        ctx.eps, ctx.gshape = eps, g.shape
+        else:
+            xh, mu, rs, gf = _ln_fwd(x, g, b, eps)
+            y, h, z = _ffn_pair_fwd(xh, w1, b1, w2, b2, x, fresh, True)
+            ctx.save_for_backward(x, gf, mu, rs, xh, z, h, w1, w2)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, gf, mu, rs, xh, z, h, w1, w2 = ctx.saved_tensors
-        hid, dim = z.shape[0], x.shape[0]
-        n = x.numel() // dim
+        saved = ctx.saved_tensors
+        x, gf, mu, rs, xh, z, h = saved[:7]
         need = ctx.needs_input_grad
         dy = dy.contiguous()
-        w1p, b1p, w2p, b2p = ctx.params
-        if ctx.fused:  # (w1 / w2 of the saved tensors are the PACKED operands here: [C][4C] and [4C][C])
-            lib = _lib.load()
-            rows = lib.advhip_ffn_block_partial_rows(n)
-            dz, dx = torch.empty_like(z), torch.empty_like(x)
-            pgb = torch.empty((rows, 2 * dim), device=x.device, dtype=torch.float32)
-            check(lib.advhip_ffn_block_bwd_f32(ptr(dy), ptr(x), ptr(gf), ptr(mu), ptr(rs), C.c_float(ctx.eps), ptr(z), ptr(w2), ptr(w1), ptr(dz), ptr(dx),
-                                               ptr(pgb), dim, n, stream(x)), "ffn_block_bwd")
-            dw2, db2 = _dw_db(dy, h, need[6], need[7], w2p, b2p)
-            dw1, db1 = _dw_db(dz, xh, need[4], need[5], w1p, b1p)
-            gp, bp = ctx.ln_params
-            if need[1] and need[2] and _defer_colsum(pgb, [(gp, 0, dim), (bp, dim, 2 * dim)]):
-                return dx, None, None, None, dw1, db1, dw2, db2, None
-            sums = colsum(pgb)
-            return dx, sums[:dim].reshape(ctx.gshape), sums[dim:].reshape(ctx.gshape), None, dw1, db1, dw2, db2, None
-        dw2, db2 = _dw_db(dy, h, need[6], need[7], w2p, b2p)
-        dz = conv_cn(dy, w2.detach().view(dim, hid), hid, 1, dact_z=z, act=ACT_MUL)  # (W2^T dY) * GELU'(pre-activation), saved by the forward
-        dw1, db1 = _dw_db(dz, xh, need[4], need[5], w1p, b1p)
-        dxh = conv_cn(dz, w1.detach().view(hid, dim), dim, 1)
-        lib = _lib.load()
-        rows = lib.advhip_chan_layernorm_bwd_partial_rows(n)
-        dx = torch.empty_like(x)
-        pgb = torch.empty((rows, 2 * dim), device=x.device, dtype=torch.float32)
-        check(lib.advhip_chan_layernorm_bwd_add_f32(ptr(dxh), ptr(x), ptr(gf), ptr(mu), ptr(rs), ptr(dy), ptr(dx), ptr(pgb), dim, n,
-                                                    C.c_float(ctx.eps), stream(x)), "chan_layernorm_bwd_add")
-        gp, bp = ctx.ln_params
-        if need[1] and need[2] and _defer_colsum(pgb, [(gp, 0, dim), (bp, dim, 2 * dim)]):
-            return dx, None, None, None, dw1, db1, dw2, db2, None
-        sums = colsum(pgb)
-        return dx, sums[:dim].reshape(ctx.gshape), sums[dim:].reshape(ctx.gshape), None, dw1, db1, dw2, db2, None
+        if ctx.fused:
+            w1p, w2p = saved[7:]  # (the PACKED operands)
+            pw1, pb1, pw2, pb2 = ctx.params
+            dz, dx, pgb = _ffn_fused_bwd(dy, x, gf, mu, rs, ctx.eps, z, w1p, w2p)
+            dw2, db2 = _dw_db(dy, h, need[6], need[7], pw2, pb2)
+            dw1, db1 = _dw_db(dz, xh, need[4], need[5], pw1, pb1)
+        else:
+            w1, w2 = saved[7:]
+            dxh, dw1, db1, dw2, db2 = _ffn_pair_bwd(dy, xh, z, h, w1, w2, ctx.params, need[4:8], True, fork=False)
+            dx, pgb = _ln_bwd(dxh, x, gf, mu, rs, ctx.eps, add=dy)
+        dg, db = _ln_param_grads(pgb, ctx.ln_params, need[1], need[2], ctx.gshape)
+        return dx, dg, db, None, dw1, db1, dw2, db2, None
 
 
 # ADV_MGFN_FUSED_FFN=1 (opt-in): the narrow blocks' `x + FFN(LN(x))` step as ONE launch forward and one backward (csrc/ffn_fused.hip) instead of
@@ -762,61 +925,34 @@ class _FocusAttnBlockCN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bn_w, bn_b, wv, wrel, brel, wo, bo, bn, heads, fresh):
         _lib.require_gpu(x, bn_w, bn_b, wv, wrel, brel, wo, bo, contiguous=False)
-        c, b_, t = x.shape
-        n = b_ * t
-        inner = wv.shape[0]
-        lib = _lib.load()
-        xb = torch.empty_like(x)
-        mean = torch.empty((c,), device=x.device, dtype=torch.float32)
-        var = torch.empty_like(mean)
+        c, inner = x.shape[0], wv.shape[0]
         track = bn.track_running_stats and bn.running_mean is not None
-        check(lib.advhip_bn_rows_fwd_running_f32(ptr(x), ptr(bn_w.detach()), ptr(bn_b.detach()), ptr(xb), ptr(mean), ptr(var),
-                                                 ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                                 C.c_float(bn.momentum if track else 0.0), c, n, C.c_float(bn.eps), stream(x)), "bn_rows_fwd_running")
+        xb, mean, var = _bn_fwd(x, bn_w, bn_b, bn.eps, (bn.running_mean, bn.running_var) if track else None, bn.momentum if track else 0.0)
         if track:
             PENDING_COUNTERS.append(bn.num_batches_tracked)  # += 1 for all the body's BatchNorm layers in one launch (flush_counters)
         v = conv_cn(xb, pack_kc_cached(wv, fresh), inner, 1)
-        k = wrel.shape[-1]
-        w2 = wrel.detach().reshape(heads, k).contiguous()
-        o = torch.empty_like(v)
-        check(lib.advhip_dwconv_t_fwd_f32(ptr(v), ptr(w2), ptr(brel.detach().contiguous()), ptr(o), inner, heads, b_, t, k, stream(x)), "dwconv_t_fwd")
+        o, w2 = _dwconv_fwd(v, wrel, brel)
         y = conv_cn(o, pack_kc_cached(wo, fresh), c, 1, shift=bo.detach(), residual=x)
         ctx.save_for_backward(x, bn_w, mean, var, xb, v, w2, o, wv, wo)
         ctx.params = (wv, wo, bo)
         ctx.rel_params = (wrel, brel)
-        ctx.eps, ctx.heads, ctx.wrel_shape = bn.eps, heads, wrel.shape
+        ctx.eps, ctx.wrel_shape = bn.eps, wrel.shape
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, bn_w, mean, var, xb, v, w2, o, wv, wo = ctx.saved_tensors
-        c, b_, t = x.shape
-        inner, heads = wv.shape[0], ctx.heads
-        k = w2.shape[1]
+        c, inner = x.shape[0], wv.shape[0]
         need = ctx.needs_input_grad
-        lib = _lib.load()
         dy = dy.contiguous()
         wvp, wop, bop = ctx.params
         dwo, dbo = _dw_db(dy, o, need[6], need[7], wop, bop)
         do = conv_cn(dy, wo.detach().view(c, inner), inner, 1)
-        chunks = lib.advhip_dwconv_t_bwd_chunks(inner, b_)
-        dv = torch.empty_like(v)
-        partial = torch.empty((inner * chunks, k + 1), device=x.device, dtype=torch.float32)
-        check(lib.advhip_dwconv_t_bwd_f32(ptr(do), ptr(v), ptr(w2), ptr(dv), ptr(partial), inner, heads, b_, t, k, stream(x)), "dwconv_t_bwd")
-        wrelp, brelp = ctx.rel_params
-        p2 = partial.view(inner // heads * chunks, heads * (k + 1))  # rows = (c_idx, chunk)
-        if need[4] and need[5] and _defer_colsum(p2, [(wrelp, 0, heads * k), (brelp, heads * k, heads * (k + 1))], period=k + 1):
-            dwrel = dbrel = None
-        else:
-            per_head = colsum(p2).view(heads, k + 1)
-            dwrel, dbrel = per_head[:, :k].reshape(ctx.wrel_shape), per_head[:, k].contiguous()
+        dv, p2 = _dwconv_bwd(do, v, w2)
+        dwrel, dbrel = _dwconv_param_grads(p2, ctx.wrel_shape, ctx.rel_params if need[4] and need[5] else None)
         dwv, _ = _dw_db(dv, xb, need[3], False, wvp, None)
         dxb = conv_cn(dv, wv.detach().view(inner, c), c, 1)
-        dx = torch.empty_like(x)
-        dg = torch.empty((c,), device=x.device, dtype=torch.float32)
-        db = torch.empty_like(dg)
-        check(lib.advhip_bn_rows_bwd_add_f32(ptr(dxb), ptr(x), ptr(bn_w.detach()), ptr(mean), ptr(var), ptr(dy), ptr(dx), ptr(dg), ptr(db), c,
-                                             b_ * t, C.c_float(ctx.eps), stream(x)), "bn_rows_bwd_add")
+        dx, dg, db = _bn_bwd(dxb, x, bn_w, mean, var, ctx.eps, add=dy)
         return dx, dg, db, dwv, dwrel, dbrel, dwo, dbo, None, None, None
 
 
@@ -829,42 +965,16 @@ class _GlanceAttnCore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, heads, dim_head, scale):
-        _lib.require_gpu(qkv)
-        c3, b, t = qkv.shape
-        inner = c3 // 3
-        lib = _lib.load()
-        out = torch.empty((inner, b, t), device=qkv.device, dtype=torch.float32)
-        need = any(ctx.needs_input_grad)
-        if t == 32:
-            p = torch.empty((b, heads, t, t), device=qkv.device, dtype=torch.float32)
-            check(lib.advhip_glance_attention_fwd_f32(ptr(qkv), ptr(out), ptr(p), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
-                  "glance_attention_fwd")
-            ctx.save_for_backward(qkv, p)
-        else:
-            lse = torch.empty((b, heads, t), device=qkv.device, dtype=torch.float32) if need else None
-            check(lib.advhip_glance_attention_fwd_anyt_f32(ptr(qkv), ptr(out), ptr(lse), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
-                  "glance_attention_fwd_anyt")
-            if need:
-                ctx.save_for_backward(qkv, out, lse)
+        out, aux = _glance_fwd(qkv, heads, dim_head, scale, keep=any(ctx.needs_input_grad))
+        if aux:
+            ctx.save_for_backward(qkv, *aux)
         ctx.args = (heads, dim_head, scale)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        heads, dim_head, scale = ctx.args
-        qkv = ctx.saved_tensors[0]
-        _, b, t = qkv.shape
-        dqkv = torch.empty_like(qkv)
-        lib = _lib.load()
-        if t == 32:
-            p = ctx.saved_tensors[1]
-            check(lib.advhip_glance_attention_bwd_f32(ptr(dout.contiguous()), ptr(qkv), ptr(p), ptr(dqkv), heads, b, t, dim_head, C.c_float(scale),
-                                                      stream(qkv)), "glance_attention_bwd")
-        else:
-            _qkv, out, lse = ctx.saved_tensors
-            check(lib.advhip_glance_attention_bwd_anyt_f32(ptr(dout.contiguous()), ptr(qkv), ptr(out), ptr(lse), ptr(dqkv), heads, b, t, dim_head,
-                                                           C.c_float(scale), stream(qkv)), "glance_attention_bwd_anyt")
-        return dqkv, None, None, None
+        qkv, *aux = ctx.saved_tensors
+        return _glance_bwd(dout.contiguous(), qkv, aux, *ctx.args), None, None, None
 
 
 class _GlanceAttnBlockCN(torch.autograd.Function):
@@ -876,27 +986,10 @@ class _GlanceAttnBlockCN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, g, b, eps, wqkv, wout, bout, heads, dim_head, scale, fresh):
         _lib.require_gpu(x, g, b, wqkv, wout, bout, contiguous=False)
-        c = x.shape[0]
-        n = x.numel() // c
-        lib = _lib.load()
-        xh = torch.empty_like(x)
-        mu = torch.empty((n,), device=x.device, dtype=torch.float32)
-        rs = torch.empty_like(mu)
-        gf, bf = g.detach().reshape(c).contiguous(), b.detach().reshape(c).contiguous()
-        check(lib.advhip_chan_layernorm_fwd_f32(ptr(x), ptr(gf), ptr(bf), ptr(xh), ptr(mu), ptr(rs), c, n, C.c_float(eps), stream(x)), "chan_layernorm_fwd")
-        inner = heads * dim_head
+        c, inner = x.shape[0], heads * dim_head
+        xh, mu, rs, gf = _ln_fwd(x, g, b, eps)
         qkv = conv_cn(xh, pack_kc_cached(wqkv, fresh), 3 * inner, 1)
-        _c3, bsz, t = qkv.shape
-        core = torch.empty((inner, bsz, t), device=x.device, dtype=torch.float32)
-        if t == 32:
-            p = torch.empty((bsz, heads, t, t), device=x.device, dtype=torch.float32)
-            check(lib.advhip_glance_attention_fwd_f32(ptr(qkv), ptr(core), ptr(p), heads, bsz, t, dim_head, C.c_float(scale), stream(x)), "glance_attention_fwd")
-            aux = (p,)
-        else:
-            lse = torch.empty((bsz, heads, t), device=x.device, dtype=torch.float32)
-            check(lib.advhip_glance_attention_fwd_anyt_f32(ptr(qkv), ptr(core), ptr(lse), heads, bsz, t, dim_head, C.c_float(scale), stream(x)),
-                  "glance_attention_fwd_anyt")
-            aux = (core, lse)
+        core, aux = _glance_fwd(qkv, heads, dim_head, scale, keep=True)
         y = conv_cn(core, pack_kc_cached(wout, fresh), c, 1, shift=bout.detach(), residual=x)
         ctx.save_for_backward(x, gf, mu, rs, xh, qkv, core, wqkv, wout, *aux)
         ctx.params = (wqkv, wout, bout)
@@ -906,38 +999,20 @@ class _GlanceAttnBlockCN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, gf, mu, rs, xh, qkv, core, wqkv, wout = ctx.saved_tensors[:9]
-        aux = ctx.saved_tensors[9:]
+        x, gf, mu, rs, xh, qkv, core, wqkv, wout, *aux = ctx.saved_tensors
         eps, heads, dim_head, scale, gshape = ctx.args
-        c = x.shape[0]
-        n = x.numel() // c
-        inner = heads * dim_head
-        _c3, bsz, t = qkv.shape
+        c, inner = x.shape[0], heads * dim_head
         need = ctx.needs_input_grad
-        lib = _lib.load()
         dy = dy.contiguous()
         wqkvp, woutp, boutp = ctx.params
         dwo, dbo = _dw_db(dy, core, need[5], need[6], woutp, boutp)
         dcore = conv_cn(dy, wout.detach().view(c, inner), inner, 1)
-        dqkv = torch.empty_like(qkv)
-        if t == 32:
-            check(lib.advhip_glance_attention_bwd_f32(ptr(dcore), ptr(qkv), ptr(aux[0]), ptr(dqkv), heads, bsz, t, dim_head, C.c_float(scale), stream(x)),
-                  "glance_attention_bwd")
-        else:
-            check(lib.advhip_glance_attention_bwd_anyt_f32(ptr(dcore), ptr(qkv), ptr(aux[0]), ptr(aux[1]), ptr(dqkv), heads, bsz, t, dim_head, C.c_float(scale),
-                                                           stream(x)), "glance_attention_bwd_anyt")
+        dqkv = _glance_bwd(dcore, qkv, aux, heads, dim_head, scale)
         dwq, _ = _dw_db(dqkv, xh, need[4], False, wqkvp, None)
         dxh = conv_cn(dqkv, wqkv.detach().view(3 * inner, c), c, 1)
-        rows = lib.advhip_chan_layernorm_bwd_partial_rows(n)
-        dx = torch.empty_like(x)
-        pgb = torch.empty((rows, 2 * c), device=x.device, dtype=torch.float32)
-        check(lib.advhip_chan_layernorm_bwd_add_f32(ptr(dxh), ptr(x), ptr(gf), ptr(mu), ptr(rs), ptr(dy), ptr(dx), ptr(pgb), c, n, C.c_float(eps), stream(x)),
-              "chan_layernorm_bwd_add")
-        gp, bp = ctx.ln_params
-        if need[1] and need[2] and _defer_colsum(pgb, [(gp, 0, c), (bp, c, 2 * c)]):
-            return dx, None, None, None, dwq, dwo, dbo, None, None, None, None
-        sums = colsum(pgb)
-        return dx, sums[:c].reshape(gshape), sums[c:].reshape(gshape), None, dwq, dwo, dbo, None, None, None, None
+        dx, pgb = _ln_bwd(dxh, x, gf, mu, rs, eps, add=dy)
+        dg, db = _ln_param_grads(pgb, ctx.ln_params, need[1], need[2], gshape)
+        return dx, dg, db, None, dwq, dwo, dbo, None, None, None, None
 
 
 GLANCE_BLOCK = os.environ.get("ADV_MGFN_GLANCE_BLOCK", "1") == "1"  # (0: LayerNorm, the two GEMMs and the core as separate autograd nodes)
@@ -958,15 +1033,10 @@ def glance_attention_core(qkv: torch.Tensor, heads: int, dim_head: int, scale: f
     if lens is None:
         return _GlanceAttnCore.apply(qkv, heads, dim_head, scale)
     _no_autograd("glance_attention_core")
-    _lib.require_gpu(qkv)
-    c3, b, t = qkv.shape
+    c3 = qkv.shape[0]
     if dim_head != 64 or c3 != 3 * heads * dim_head:
         raise _lib.HipExtensionError(f"glance_attention_core with lens: dim_head = {dim_head}, {c3} rows (the kernel is built for dim_head 64 and 3 * heads * 64 rows)")
-    rl = row_lens(lens, b, t, qkv.device)
-    out = torch.empty((c3 // 3, b, t), device=qkv.device, dtype=torch.float32)
-    check(_lib.load().advhip_glance_attention_fwd_lens_f32(ptr(qkv), ptr(out), ptr(rl), heads, b, t, dim_head, C.c_float(scale), stream(qkv)),
-          "glance_attention_fwd_lens")
-    return out
+    return _glance_fwd(qkv, heads, dim_head, scale, False, lens)[0]
 
 
 # ---- padded batches of sequences of unequal length (inference): the row lengths of a (C, rows, T) activation -------------------
@@ -1113,18 +1183,6 @@ def fold_affine(weight: torch.Tensor, mul: torch.Tensor, add: Optional[torch.Ten
     return pack_kc(wf), bf, rs
 
 
-def _folded(owner, params, build):
-    """Operands derived from `params`, cached on id(owner) until one of them changes (data_ptr / version / the cache epoch)."""
-    stamp = tuple((p.data_ptr(), p._version) for p in params) + (_EPOCH,)
-    hit = _FOLDED.get(id(owner))
-    if hit is None or hit[0]() is not owner or hit[1] != stamp:
-        if len(_FOLDED) > 256:
-            for k in [k for k, v in _FOLDED.items() if v[0]() is None]:
-                del _FOLDED[k]
-        hit = _FOLDED[id(owner)] = (weakref.ref(owner), stamp) + tuple(build())
-    return hit[2:]
-
-
 @torch.no_grad()
 def ffn_cn_folded_ln(x: torch.Tensor, norm, in_conv: torch.nn.Conv1d, out_conv: torch.nn.Conv1d) -> torch.Tensor:
     """Inference form of `ffn(x) + x` with the channel LayerNorm folded into the first GEMM: W1.LN(x) = (W1.diag(g)) x_raw
@@ -1132,9 +1190,9 @@ def ffn_cn_folded_ln(x: torch.Tensor, norm, in_conv: torch.nn.Conv1d, out_conv: 
     The folded operands are cached until one of the four parameters changes."""
     x = x.contiguous()
     hid, dim = in_conv.weight.shape[0], in_conv.weight.shape[1]
-    wg_packed, shift, u = _folded(in_conv, (in_conv.weight, in_conv.bias, norm.g, norm.b),
+    wg_packed, shift, u = _cached(_FOLDED, in_conv, (in_conv.weight, in_conv.bias, norm.g, norm.b),
                                   lambda: fold_affine(in_conv.weight, norm.g.detach().reshape(dim).contiguous(), norm.b.detach().reshape(dim).contiguous(),
-                                                      in_conv.bias.detach(), want_rowsum=True))
+                                                      in_conv.bias.detach(), want_rowsum=True), 256)
     mu, rs = chan_stats(x, norm.eps)
     h = conv_cn(x, wg_packed, hid, 1, shift=shift, act=ACT_GELU, ln=(u, mu, rs))
     return conv_cn(h, pack_kc_cached(out_conv.weight), dim, 1, shift=out_conv.bias, residual=x)
@@ -1158,7 +1216,7 @@ def to_v_folded_bn(x: torch.Tensor, bn: torch.nn.BatchNorm1d, to_v: torch.nn.Con
         return wp, bf
 
     params = (to_v.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) + ((to_v.bias,) if to_v.bias is not None else ())
-    wp, bf = _folded(to_v, params, build)
+    wp, bf = _cached(_FOLDED, to_v, params, build, 256)
     return conv_cn(x.contiguous(), wp, inner, 1, shift=bf)
 
 
@@ -1168,15 +1226,7 @@ class _ChanLayerNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, g, b, eps):
-        _lib.require_gpu(x, g, b, contiguous=False)
-        c = x.shape[0]
-        n = x.numel() // c
-        y = torch.empty_like(x)
-        mu = torch.empty((n,), device=x.device, dtype=torch.float32)
-        rs = torch.empty_like(mu)
-        gf, bf = g.detach().reshape(c).contiguous(), b.detach().reshape(c).contiguous()
-        check(_lib.load().advhip_chan_layernorm_fwd_f32(ptr(x), ptr(gf), ptr(bf), ptr(y), ptr(mu), ptr(rs), c, n, C.c_float(eps), stream(x)),
-              "chan_layernorm_fwd")
+        y, mu, rs, gf = _ln_fwd(x, g, b, eps)
         ctx.save_for_backward(x, gf, mu, rs)
         ctx.eps, ctx.gshape = eps, g.shape
         ctx.ln_params = (g, b)
@@ -1186,17 +1236,11 @@ class _ChanLayerNorm(torch.autograd.Function):
     def backward(ctx, dy):
         x, gf, mu, rs = ctx.saved_tensors
         c = x.shape[0]
-        n = x.numel() // c
-        dy = dy.contiguous()
-        lib = _lib.load()
-        rows = lib.advhip_chan_layernorm_bwd_partial_rows(n)
-        dx = torch.empty_like(x)
-        pg = torch.empty((rows, c), device=x.device, dtype=torch.float32)
-        pb = torch.empty_like(pg)
-        check(lib.advhip_chan_layernorm_bwd_f32(ptr(dy), ptr(x), ptr(gf), ptr(mu), ptr(rs), ptr(dx), ptr(pg), ptr(pb), c, n,
-                                                C.c_float(ctx.eps), stream(x)), "chan_layernorm_bwd")
+        dx, pg, pb = _ln_bwd(dy.contiguous(), x, gf, mu, rs, ctx.eps, split=True)
         gp, bp = ctx.ln_params
-        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _defer_colsum(pg, [(gp, 0, c)]) and _defer_colsum(pb, [(bp, 0, c)]):
+        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _can_defer((gp, bp)):  # (decided for both before either is queued)
+            _defer_colsum(pg, [(gp, 0, c)])
+            _defer_colsum(pb, [(bp, 0, c)])
             return dx, None, None, None
         return dx, colsum(pg).view(ctx.gshape), colsum(pb).view(ctx.gshape), None
 
@@ -1206,12 +1250,7 @@ class _DWConvT(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, v, weight, bias):
-        _lib.require_gpu(v, weight, bias, contiguous=False)
-        c, b, t = v.shape
-        h, _, k = weight.shape
-        out = torch.empty_like(v)
-        w2 = weight.detach().reshape(h, k).contiguous()
-        check(_lib.load().advhip_dwconv_t_fwd_f32(ptr(v), ptr(w2), ptr(bias.detach().contiguous()), ptr(out), c, h, b, t, k, stream(v)), "dwconv_t_fwd")
+        out, w2 = _dwconv_fwd(v, weight, bias)
         ctx.save_for_backward(v, w2)
         ctx.wshape = weight.shape
         return out
@@ -1219,16 +1258,8 @@ class _DWConvT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         v, w2 = ctx.saved_tensors
-        c, b, t = v.shape
-        h, k = w2.shape
-        dout = dout.contiguous()
-        lib = _lib.load()
-        chunks = lib.advhip_dwconv_t_bwd_chunks(c, b)
-        dv = torch.empty_like(v)
-        partial = torch.empty((c * chunks, k + 1), device=v.device, dtype=torch.float32)
-        check(lib.advhip_dwconv_t_bwd_f32(ptr(dout), ptr(v), ptr(w2), ptr(dv), ptr(partial), c, h, b, t, k, stream(v)), "dwconv_t_bwd")
-        per_head = colsum(partial.view(c // h * chunks, h * (k + 1))).view(h, k + 1)  # rows = (c_idx, chunk), channel = c_idx * H + h_idx
-        return dv, per_head[:, :k].reshape(ctx.wshape), per_head[:, k].contiguous()
+        dv, p2 = _dwconv_bwd(dout.contiguous(), v, w2)
+        return (dv,) + _dwconv_param_grads(p2, ctx.wshape)
 
 
 class _TokenTaps(torch.autograd.Function):
@@ -1271,14 +1302,8 @@ class _AmpCombine(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bias, mag, wm, bm, ratio):
-        _lib.require_gpu(z, bias, wm, bm)
-        _lib.require_gpu(mag, contiguous=False)
-        k, o, b, t = z.shape
-        y = torch.empty((o, b, t), device=z.device, dtype=torch.float32)
-        check(_lib.load().advhip_amp_combine_fwd_f32(ptr(z), ptr(bias.detach()), ptr(mag), mag.stride(2), ptr(wm.detach()), ptr(bm.detach()),
-                                                     C.c_float(ratio), ptr(y), o, b, t, stream(z)), "amp_combine_fwd")
         ctx.mag, ctx.ratio = mag, ratio
-        return y
+        return _amp_combine_fwd(z, bias, mag, wm, bm, ratio)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1306,14 +1331,7 @@ def amp_combine(z, conv, to_mag, mag, ratio: float, lens=None) -> torch.Tensor:
     if lens is None:
         return _AmpCombine.apply(z, conv.bias, mag, to_mag.weight, to_mag.bias, float(ratio))
     _no_autograd("amp_combine")
-    bias, wm, bm = conv.bias.detach(), to_mag.weight.detach(), to_mag.bias.detach()
-    _lib.require_gpu(z, bias, wm, bm)
-    _lib.require_gpu(mag, contiguous=False)
-    k, o, b, t = z.shape
-    y = torch.empty((o, b, t), device=z.device, dtype=torch.float32)
-    check(_lib.load().advhip_amp_combine_fwd_lens_f32(ptr(z), ptr(bias), ptr(mag), mag.stride(2), ptr(wm), ptr(bm), C.c_float(float(ratio)), ptr(y), o, b, t,
-                                                      ptr(row_lens(lens, b, t, z.device)), stream(z)), "amp_combine_fwd_lens")
-    return y
+    return _amp_combine_fwd(z, conv.bias, mag, to_mag.weight, to_mag.bias, float(ratio), lens)
 
 
 def fused_ok(x: torch.Tensor) -> bool:
@@ -1329,15 +1347,7 @@ def dwconv_t(v: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, lens=Non
     if lens is None:
         return _DWConvT.apply(v.contiguous(), weight, bias)
     _no_autograd("dwconv_t")
-    v = v.contiguous()
-    _lib.require_gpu(v, weight, bias, contiguous=False)
-    c, b, t = v.shape
-    h, _, k = weight.shape
-    out = torch.empty_like(v)
-    rl = row_lens(lens, b, t, v.device)
-    check(_lib.load().advhip_dwconv_t_fwd_lens_f32(ptr(v), ptr(weight.detach().reshape(h, k).contiguous()), ptr(bias.detach().contiguous()), ptr(out), c, h, b, t, k,
-                                                   ptr(rl), rl.numel(), stream(v)), "dwconv_t_fwd_lens")
-    return out
+    return _dwconv_fwd(v.contiguous(), weight, bias, lens)[0]
 
 
 class _BNRowsTrain(torch.autograd.Function):
@@ -1346,14 +1356,7 @@ class _BNRowsTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        _lib.require_gpu(x, gamma, beta, contiguous=False)
-        c = x.shape[0]
-        n = x.numel() // c
-        y = torch.empty_like(x)
-        mean = torch.empty((c,), device=x.device, dtype=torch.float32)
-        var = torch.empty_like(mean)
-        check(_lib.load().advhip_bn_rows_fwd_f32(ptr(x), ptr(gamma.detach()), ptr(beta.detach()), ptr(y), ptr(mean), ptr(var), c, n,
-                                                 C.c_float(eps), stream(x)), "bn_rows_fwd")
+        y, mean, var = _bn_fwd(x, gamma, beta, eps)
         ctx.save_for_backward(x, gamma, mean, var)
         ctx.eps = eps
         ctx.mark_non_differentiable(mean, var)
@@ -1362,14 +1365,7 @@ class _BNRowsTrain(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dm, _dv):
         x, gamma, mean, var = ctx.saved_tensors
-        c = x.shape[0]
-        n = x.numel() // c
-        dx = torch.empty_like(x)
-        dg = torch.empty((c,), device=x.device, dtype=torch.float32)
-        db = torch.empty_like(dg)
-        check(_lib.load().advhip_bn_rows_bwd_f32(ptr(dy.contiguous()), ptr(x), ptr(gamma.detach()), ptr(mean), ptr(var), ptr(dx), ptr(dg),
-                                                 ptr(db), c, n, C.c_float(ctx.eps), stream(x)), "bn_rows_bwd")
-        return dx, dg, db, None
+        return _bn_bwd(dy.contiguous(), x, gamma, mean, var, ctx.eps) + (None,)
 
 
 def bn_rows_train(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float):

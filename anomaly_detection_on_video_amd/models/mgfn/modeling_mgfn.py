@@ -260,19 +260,8 @@ class FocusAttention(nn.Module):
 
     def _batch_norm(self, x):  # nn.BatchNorm1d semantics on a (C, B, T) tensor
         bn = self.norm
-        if bn.training and mgfn_ops.fused_ok(x):  # batch statistics + normalisation: one HIP launch (fwd) / one (bwd)
-            y, mean, var = mgfn_ops.bn_rows_train(x, bn.weight, bn.bias, bn.eps)
-            if bn.track_running_stats:
-                with torch.no_grad():
-                    n = x.shape[1] * x.shape[2]
-                    mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked + 1)
-                    bn.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
-                    bn.running_var.mul_(1 - mom).add_(var * (n / max(n - 1, 1)), alpha=mom)
-                    bn.num_batches_tracked += 1
-            return y
-        mgfn_ops.torch_path(x, "BatchNorm1d (batch statistics off the fused kernel, or running statistics with autograd)")
-        if bn.training:
-            var, mean = torch.var_mean(x, dim=(1, 2), unbiased=False)
+
+        def track(mean, var):  # the running statistics' update from the batch mean and the biased batch variance
             if bn.track_running_stats:
                 with torch.no_grad():
                     n = x.shape[1] * x.shape[2]
@@ -280,6 +269,15 @@ class FocusAttention(nn.Module):
                     bn.running_mean.mul_(1 - mom).add_(mean.detach(), alpha=mom)
                     bn.running_var.mul_(1 - mom).add_(var.detach() * (n / max(n - 1, 1)), alpha=mom)
                     bn.num_batches_tracked += 1
+
+        if bn.training and mgfn_ops.fused_ok(x):  # batch statistics + normalisation: one HIP launch (fwd) / one (bwd)
+            y, mean, var = mgfn_ops.bn_rows_train(x, bn.weight, bn.bias, bn.eps)
+            track(mean, var)
+            return y
+        mgfn_ops.torch_path(x, "BatchNorm1d (batch statistics off the fused kernel, or running statistics with autograd)")
+        if bn.training:
+            var, mean = torch.var_mean(x, dim=(1, 2), unbiased=False)
+            track(mean, var)
         else:
             mean, var = bn.running_mean, bn.running_var
         scale = bn.weight * torch.rsqrt(var + bn.eps)
