@@ -269,6 +269,11 @@ SIGNATURES = {
     "advhip_score_events_ws_bytes": (_L, [_L, _L]),
     # (smoothed, offsets, V, N, low, high, merge_gap, min_len, ev_int, ev_f, cap, counts, meta, workspace, workspace_bytes, stream)
     "advhip_score_events": (C.c_int, [_P, _P, _L, _L, C.c_float, C.c_float, _I, _I, _P, _P, _L, _P, _P, _P, _L, _P]),
+    # live scoring: (feats, cam_ids, ring, counts, n, n_cam, ncrops, W, C, stream) / (ring, counts, cam_ids, dst, nb, n_cam, ncrops, W, Tmax, C1, stream)
+    # / (scores, lens, cam_ids, latest, nb, ncrops, Tmax, stream)
+    "advhip_ring_push_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "advhip_ring_windows_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "advhip_crop_mean_last_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     # which kernel form a scorer launch takes: (C, N, aligned16) / (T, aligned16) -> form id (include/advhip.h); nothing is launched
     "advhip_bn_rows_form": (_I, [_I, _L, _I]),
     "advhip_chan_layernorm_form": (_I, [_I, _L, _I]),

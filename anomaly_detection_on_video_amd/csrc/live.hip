@@ -1,0 +1,112 @@
+// Live scoring: the state in front of the padded scorer pass and the read-out behind it (include/advhip.h: "live scoring").
+// Every camera keeps its last W clips of features, magnitude channel included, in a ring on the device; the clip pushed at count k
+// lies in slot k % W.  Three entry points, each a copy or a sum in an order the library has already stated: no atomics, no
+// workgroup waits on another, the same bits in every run.
+#include "pw_sum.h"
+
+namespace advhip {
+
+// One wavefront (= one workgroup) per pushed row (i, k): the slot from the camera's count, the row and its magnitude by
+// pw_row_magnitude.  The count is only read here: ring_advance_kernel, launched behind this one, moves it.
+__global__ __launch_bounds__(64) void ring_push_kernel(const float* __restrict__ feats, const int* __restrict__ cam_ids, float* __restrict__ ring,
+                                                       const long long* __restrict__ counts, int n_cam, int ncrops, int W, int C, PwLeaves tab) {
+  extern __shared__ float pw_lds[];
+  const int i = blockIdx.x / ncrops, k = blockIdx.x % ncrops;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;  // (the whole workgroup: nothing waits at a barrier)
+  const long long count = counts[c];
+  if (count < 0) return;
+  const long long slot = count % W;
+  pw_row_magnitude(feats + (long long)blockIdx.x * C, ring + (((long long)c * ncrops + k) * W + slot) * (C + 1), C, tab, pw_lds);
+}
+
+__global__ __launch_bounds__(256) void ring_advance_kernel(const int* __restrict__ cam_ids, long long* __restrict__ counts, int n, int n_cam) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = cam_ids[i];
+  if (c >= 0 && c < n_cam) counts[c] += 1;  // ids are distinct: one thread per count
+}
+
+// One workgroup per dst row (v, k, t), as pack_padded_kernel: dword copies of C1 floats, every lane's loads issued before its
+// stores.  Rows of the ring and of dst start at 4-byte boundaries only (C1 is odd at the trained width), and the slot a row comes
+// from moves by one with every push, so source and destination share a 16-byte phase in one step of four: there is no wider form.
+constexpr int RW_UNROLL = 4;
+__global__ __launch_bounds__(256) void ring_windows_kernel(const float* __restrict__ ring, const long long* __restrict__ counts,
+                                                           const int* __restrict__ cam_ids, float* __restrict__ dst, int n_cam, int ncrops, int W,
+                                                           int Tmax, int C1) {
+  const long long row = blockIdx.x;  // (v * ncrops + k) * Tmax + t
+  const int t = (int)(row % Tmax);
+  const long long vk = row / Tmax;
+  const int v = (int)(vk / ncrops), k = (int)(vk % ncrops);
+  const int c = cam_ids[v];
+  if (c < 0 || c >= n_cam) return;
+  const long long count = counts[c];
+  const long long len = min(min(count, (long long)W), (long long)Tmax);
+  if (t >= len) return;  // (count <= 0: len <= 0, nothing is written)
+  const long long slot = (count - len + t) % W;
+  const unsigned* __restrict__ s = (const unsigned*)ring + (((long long)c * ncrops + k) * W + slot) * C1;
+  unsigned* __restrict__ d = (unsigned*)dst + row * C1;
+  int i = threadIdx.x;
+  for (; i + 256 * (RW_UNROLL - 1) < C1; i += 256 * RW_UNROLL) {
+    unsigned r[RW_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RW_UNROLL; ++u) r[u] = s[i + 256 * u];
+#pragma unroll
+    for (int u = 0; u < RW_UNROLL; ++u) d[i + 256 * u] = r[u];
+  }
+  for (; i < C1; i += 256) d[i] = s[i];
+}
+
+// crop_mean_scatter_kernel's sum (mil.hip: crop order from 0.f, one division) at the newest clip of every listed camera
+__global__ __launch_bounds__(256) void crop_mean_last_kernel(const float* __restrict__ scores, const int* __restrict__ lens,
+                                                             const int* __restrict__ cam_ids, float* __restrict__ latest, int nb, int ncrops, int Tmax) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= nb) return;
+  const int L = lens[v];
+  if (L < 1 || L > Tmax) return;
+  float s = 0.f;
+  for (int k = 0; k < ncrops; ++k) s += scores[((size_t)v * ncrops + k) * Tmax + (L - 1)];
+  latest[cam_ids[v]] = s / (float)ncrops;
+}
+
+}  // namespace advhip
+
+using namespace advhip;
+
+extern "C" int advhip_ring_push_f32(const float* feats, const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam,
+                                    int32_t ncrops, int32_t W, int32_t C, void* stream) {
+  ADVHIP_REQUIRE(feats && cam_ids && ring && counts, "ring_push: null pointer");
+  ADVHIP_REQUIRE(n > 0 && n_cam > 0 && ncrops > 0 && W > 0 && C > 0, "ring_push: bad shape");
+  ADVHIP_REQUIRE(C <= PW_MAX_C, "ring_push: C=%d above %d: numpy sums in chunks of %d elements, the order of its adds changes there", C,
+                 PW_MAX_C, PW_MAX_C);
+  const long long rows = (long long)n * ncrops;
+  ADVHIP_REQUIRE(rows < (1ll << 31), "ring_push: %lld rows is outside the launch grid", rows);
+  const PwLeaves& tab = pw_leaves(C);
+  hipLaunchKernelGGL(ring_push_kernel, dim3((unsigned)rows), dim3(64), pw_lds_bytes(C, tab), (hipStream_t)stream, feats, (const int*)cam_ids, ring,
+                     (const long long*)counts, (int)n_cam, (int)ncrops, (int)W, (int)C, tab);
+  const int rc = check_launch("ring_push");
+  if (rc != ADVHIP_OK) return rc;
+  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (long long*)counts,
+                     (int)n, (int)n_cam);
+  return check_launch("ring_push (counts)");
+}
+
+extern "C" int advhip_ring_windows_f32(const float* ring, const int64_t* counts, const int32_t* cam_ids, float* dst, int32_t nb, int32_t n_cam,
+                                       int32_t ncrops, int32_t W, int32_t Tmax, int32_t C1, void* stream) {
+  ADVHIP_REQUIRE(ring && counts && cam_ids && dst, "ring_windows: null pointer");
+  ADVHIP_REQUIRE(nb > 0 && n_cam > 0 && ncrops > 0 && W > 0 && Tmax > 0 && C1 > 0, "ring_windows: bad shape");
+  const long long rows = (long long)nb * ncrops * Tmax;
+  ADVHIP_REQUIRE(rows < (1ll << 31), "ring_windows: %lld rows is outside the launch grid", rows);
+  hipLaunchKernelGGL(ring_windows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, ring, (const long long*)counts,
+                     (const int*)cam_ids, dst, (int)n_cam, (int)ncrops, (int)W, (int)Tmax, (int)C1);
+  return check_launch("ring_windows");
+}
+
+extern "C" int advhip_crop_mean_last_f32(const float* scores, const int32_t* lens, const int32_t* cam_ids, float* latest, int32_t nb,
+                                         int32_t ncrops, int32_t Tmax, void* stream) {
+  ADVHIP_REQUIRE(scores && lens && cam_ids && latest, "crop_mean_last: null pointer");
+  ADVHIP_REQUIRE(nb > 0 && ncrops > 0 && Tmax > 0, "crop_mean_last: bad shape");
+  hipLaunchKernelGGL(crop_mean_last_kernel, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, (hipStream_t)stream, scores, (const int*)lens,
+                     (const int*)cam_ids, latest, (int)nb, (int)ncrops, (int)Tmax);
+  return check_launch("crop_mean_last");
+}

@@ -235,6 +235,83 @@ def pack_padded(store: torch.Tensor, src_offsets: torch.Tensor, lens: torch.Tens
     return dst
 
 
+def _live_arg(t, dtype, shape, what: str, name: str, dev=None) -> torch.Tensor:
+    """One argument of the live-scoring launches: a contiguous `dtype` tensor on the GPU (on `dev`, the device of the arguments
+    before it) of `shape`, where None stands for any extent."""
+    if (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and (dev is None or t.device == dev) and t.dim() == len(shape) and t.numel() > 0
+            and all(s is None or s == d for s, d in zip(shape, t.shape)) and t.is_contiguous()):
+        return t
+    err = _lib.HipExtensionError  # which of them it was, in the order a caller would fix them
+    want = "(" + ", ".join("*" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+    if not torch.is_tensor(t):
+        raise err(f"{what}: {name} must be a {dtype} tensor {want} on the GPU, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise err(f"{what}: {name} is on '{t.device}': this op runs only as a HIP kernel on the GPU (there is no CPU fallback)")
+    if dev is not None and t.device != dev:
+        raise err(f"{what}: {name} is on {t.device}, the arguments before it are on {dev}")
+    if t.dtype != dtype:
+        raise err(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous() and t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)):
+        raise err(f"{what}: {name} must be contiguous")
+    raise err(f"{what}: {name} must be {want}, got {tuple(t.shape)}")
+
+
+def ring_push(feats: torch.Tensor, cam_ids: torch.Tensor, ring: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """One new clip for each of n distinct cameras into their rings (include/advhip.h: live scoring): feats (n, ncrops, C) fp32,
+    cam_ids int32 (n,), ring (n_cam, ncrops, W, C + 1) fp32, counts int64 (n_cam,), all on the device.  Camera c = cam_ids[i]
+    gets ring[c, :, counts[c] % W, :C] = feats[i] and, in the last channel, the clips' L2 magnitudes with numpy's bits
+    (`add_magnitude_np`'s rule, C <= 8192); then counts[c] += 1.  An id outside [0, n_cam) writes nothing; the ids' values are
+    the caller's (nothing is read back): the same id twice is an error this wrapper cannot see.  Two launches, no autograd."""
+    what = "ring_push"
+    ring = _live_arg(ring, torch.float32, (None, None, None, None), what, "ring")
+    n_cam, ncrops, W, C1 = ring.shape
+    if C1 < 2:
+        raise _lib.HipExtensionError(f"{what}: ring must be (n_cam, ncrops, W, C + 1) with C >= 1, got {tuple(ring.shape)}")
+    feats = _live_arg(feats, torch.float32, (None, ncrops, C1 - 1), what, "feats", ring.device)
+    cam_ids = _live_arg(cam_ids, torch.int32, (feats.shape[0],), what, "cam_ids", ring.device)
+    counts = _live_arg(counts, torch.int64, (n_cam,), what, "counts", ring.device)
+    require_gpu(ring)  # (the current device)
+    check(_lib.load().advhip_ring_push_f32(ptr(feats), ptr(cam_ids), ptr(ring), ptr(counts), feats.shape[0], n_cam, ncrops, W, C1 - 1, stream()), what)
+    return ring
+
+
+def ring_windows(ring: torch.Tensor, counts: torch.Tensor, cam_ids: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """The windows of the listed cameras as a padded batch, one launch: dst (nb, ncrops, Tmax, C + 1) fp32, cam_ids int32 (nb,);
+    dst[v, :, t] for t < len = min(counts[c], W, Tmax), c = cam_ids[v], is the camera's last len clips, oldest first (entry t in
+    slot (counts[c] - len + t) % W); the rows behind stay as they are (`pack_padded`'s contract), a camera at count 0 writes
+    nothing.  A copy of bits.  No autograd."""
+    what = "ring_windows"
+    ring = _live_arg(ring, torch.float32, (None, None, None, None), what, "ring")
+    n_cam, ncrops, W, C1 = ring.shape
+    counts = _live_arg(counts, torch.int64, (n_cam,), what, "counts", ring.device)
+    dst = _live_arg(dst, torch.float32, (None, ncrops, None, C1), what, "dst", ring.device)
+    cam_ids = _live_arg(cam_ids, torch.int32, (dst.shape[0],), what, "cam_ids", ring.device)
+    require_gpu(ring)
+    check(_lib.load().advhip_ring_windows_f32(ptr(ring), ptr(counts), ptr(cam_ids), ptr(dst), dst.shape[0], n_cam, ncrops, W, dst.shape[2], C1, stream()), what)
+    return dst
+
+
+def crop_mean_last(scores: torch.Tensor, lens: torch.Tensor, cam_ids: torch.Tensor, latest: torch.Tensor, ncrops: int) -> torch.Tensor:
+    """latest[cam_ids[v]] = the crop mean of the per-crop scores (nb * ncrops, Tmax[, 1]) at clip lens[v] - 1 of listed camera v --
+    `crop_mean_scatter`'s bits at the newest clip.  lens and cam_ids are device int32 (nb,) vectors whose values the caller has
+    validated (1 .. Tmax; distinct indices of `latest`); nothing else of latest (fp32, one entry per camera) is written."""
+    what = "crop_mean_last"
+    lens = _live_arg(lens, torch.int32, (None,), what, "lens")
+    nb = lens.shape[0]
+    if isinstance(ncrops, bool) or int(ncrops) != ncrops or ncrops < 1:
+        raise _lib.HipExtensionError(f"{what}: ncrops {ncrops!r} is not a positive integer")
+    if not torch.is_tensor(scores) or scores.numel() == 0 or scores.numel() % (nb * int(ncrops)) or scores.dim() < 2 or scores.shape[0] != nb * int(ncrops):
+        raise _lib.HipExtensionError(f"{what}: scores must be ({nb * int(ncrops)}, Tmax) for {nb} cameras x {ncrops} crops, got "
+                                     f"{tuple(getattr(scores, 'shape', ()))}")
+    tmax = scores.numel() // (nb * int(ncrops))
+    scores = _live_arg(scores, torch.float32, (nb * int(ncrops), tmax) + (1,) * (scores.dim() - 2), what, "scores", lens.device)
+    cam_ids = _live_arg(cam_ids, torch.int32, (nb,), what, "cam_ids", lens.device)
+    latest = _live_arg(latest, torch.float32, (None,), what, "latest", lens.device)
+    require_gpu(scores)
+    check(_lib.load().advhip_crop_mean_last_f32(ptr(scores), ptr(lens), ptr(cam_ids), ptr(latest), nb, int(ncrops), tmax, stream()), what)
+    return latest
+
+
 def _gather_side(store, idx, labels, dst_labels, what: str):
     """Checks of one store of `gather_batch` -> (n, R, b)."""
     err = _lib.HipExtensionError

@@ -804,6 +804,31 @@ int advhip_add_magnitude_np_f32(const float* feats, float* out, int64_t a, int32
  * that block's sum is known (the tree of `+` walked with a stack).  This is the table the kernel sums by. */
 int advhip_add_magnitude_np_leaves(int32_t C, int32_t* leaves, int32_t* n_leaves);
 
+/* --- live scoring: per-camera feature rings -------------------------------------------------------
+ * State owned by the caller, all on the device: ring fp32 (n_cam, ncrops, W, C + 1), counts int64 (n_cam,) = the clips pushed
+ * so far per camera, latest fp32 (n_cam,).
+ * THE SLOT RULE: the clip pushed when a camera's count is k lies in slot k % W.  A camera at count k therefore holds its last
+ * len = min(k, W) clips, and entry t of that window (oldest first, t < len) lies in slot (k - len + t) % W.
+ *
+ * One new clip for each of n DISTINCT cameras: feats (n, ncrops, C) fp32, cam_ids int32 (n,) on the device.  For c = cam_ids[i]
+ * and slot = counts[c] % W: ring[c, k, slot, :C] = feats[i, k] bit for bit and ring[c, k, slot, C] = the row's L2 magnitude by
+ * advhip_add_magnitude_np_f32's rule (numpy's bits; C <= 8192, a larger C is refused); a second launch of the same call then
+ * does counts[c] += 1.  An id outside [0, n_cam) writes nothing and advances nothing (the kernels check it).  The same id twice
+ * in one call is the caller's error: the two clips land in one slot and the count advances by one. */
+int advhip_ring_push_f32(const float* feats, const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam,
+                         int32_t ncrops, int32_t W, int32_t C, void* stream);
+/* The windows of the nb listed cameras as a padded batch: for c = cam_ids[v] and len = min(counts[c], W, Tmax),
+ * dst[v, k, t, :] = the camera's entry t of its last len (the slot rule) for t < len, dst (nb, ncrops, Tmax, C1) fp32 with
+ * C1 = C + 1.  Rows t >= len are left as they are (advhip_pack_padded_f32's contract); a camera at count 0 or an id outside
+ * [0, n_cam) writes nothing.  A copy of bits by 4-byte accesses: rows of C1 = 2049 floats start at 4-byte boundaries only. */
+int advhip_ring_windows_f32(const float* ring, const int64_t* counts, const int32_t* cam_ids, float* dst, int32_t nb, int32_t n_cam,
+                            int32_t ncrops, int32_t W, int32_t Tmax, int32_t C1, void* stream);
+/* latest[cam_ids[v]] = (sum_k scores[(v * ncrops + k) * Tmax + lens[v] - 1]) / ncrops: the crop mean of the newest clip of
+ * listed camera v, by advhip_crop_mean_scatter_f32's rule (crop order from 0.f, one division: its bits).  lens int32 (nb,) in
+ * 1 .. Tmax and cam_ids int32 (nb,), distinct, index `latest`: the caller has validated both.  Nothing else of latest is written. */
+int advhip_crop_mean_last_f32(const float* scores, const int32_t* lens, const int32_t* cam_ids, float* latest, int32_t nb,
+                              int32_t ncrops, int32_t Tmax, void* stream);
+
 /* Clip pre-processing on the device: uint8 frames (N, T, C, H, W) -> fp32 (N, C, T, H, W) with
  * y = (x - mean) / std.  Replaces PILToTensor().float() + GroupNormalize(114.75, 57.375)
  * (src/dataset.py:175-183) and the permute of extract_features.py:83, so that only uint8 pixels
