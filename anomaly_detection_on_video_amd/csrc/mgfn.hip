@@ -1591,21 +1591,22 @@ __global__ __launch_bounds__(256) void glance_attn_bwd_anyt_kernel(const float* 
       ga_load_tile(k, qkv, inner + row0, N, col0, jb, T, tid);
       ga_load_tile(v, qkv, 2ll * inner + row0, N, col0, jb, T, tid);
     }
-    if (!role_q || ob == 0) {  // the query-side tiles: q, dout, dout * out, lse
+    if (!role_q || ob == 0) {  // the query-side tiles: q, dout, out, lse
       ga_load_tile(q, qkv, row0, N, col0, ib, T, tid);
       for (int e = tid; e < GA_D * GA_T; e += 256) {
         const int d = e / GA_T, t = e % GA_T, tt = ib + t;
         const long long o = (row0 + d) * N + col0 + tt;
-        const float gv = tt < T ? dout[o] : 0.f;
-        g[d][t] = gv;
-        go[d][t] = tt < T ? gv * out[o] : 0.f;
+        g[d][t] = tt < T ? dout[o] : 0.f;
+        go[d][t] = tt < T ? out[o] : 0.f;
       }
       if (tid < GA_T) L_s[tid] = ib + tid < T ? lse[(long long)bh * T + ib + tid] : 0.f;
     }
     __syncthreads();
     if ((!role_q || ob == 0) && tid < GA_T) {
+      // D and dp are the SAME chain (fmaf over d = 0 .. 63 from 0): where a row's softmax is one-hot, out is that key's v and
+      // dp - D cancels to exactly 0 instead of to the difference of two roundings (T = 1: dq = dk = 0, not 1e-7)
       float dsum = 0.f;
-      for (int d = 0; d < GA_D; ++d) dsum += go[d][tid];
+      for (int d = 0; d < GA_D; ++d) dsum = fmaf(g[d][tid], go[d][tid], dsum);
       D_s[tid] = dsum;
     }
     float s[4] = {0.f, 0.f, 0.f, 0.f}, dp[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1614,7 +1615,7 @@ __global__ __launch_bounds__(256) void glance_attn_bwd_anyt_kernel(const float* 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         s[e] += qi * k[d][j0 + e];
-        dp[e] += gi * v[d][j0 + e];
+        dp[e] = fmaf(gi, v[d][j0 + e], dp[e]);
       }
     }
     __syncthreads();  // D_s
