@@ -1,31 +1,62 @@
 // Fused element-wise / reduction kernels of the MGFN scorer body on (C, N) activations (channels outermost, N = B*T
 // positions contiguous), forward and backward -- the work between the GEMM-shaped layers that the torch formulation
 // spends ~10 passes over the activation on:
-//   chan_layernorm   MGFNLayerNorm over channels, (x - mean) / (sqrt(var_biased) + eps) * g + b
-//                    (/root/reference/src/models/mgfn/modeling_mgfn.py:36-46)
+//   chan_layernorm   MGFNLayerNorm over channels, (x - mean) / (sqrt(var_biased) + eps) * g + b  (modeling_mgfn.py:36-46)
 //   dwconv_t         FocusAttention.rel_pos: per-head depth-wise temporal Conv1d(heads, heads, k, padding=k/2, groups=heads)
 //                    applied to "b (c h) n -> (b c) h n" (modeling_mgfn.py:169-171, 176-178): channel c uses filter c % heads
+//   bn_rows, head_ln_fc, glance_attention, amp_combine: the sections below
+// and the operand-build and padded-batch utilities of the same layout (fold_affine, pack_weights_multi, unfold3, colsum,
+// mask_tail, pack_padded).  The optimizer step is csrc/optim.hip.
 // All reductions are deterministic (fixed-order partial sums, no atomics).
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
+#include "quad.h"
 
 namespace advhip {
 
-// A block = LN_COLS positions x LN_GROUPS channel groups (512 threads): lanes run along n (128-byte row pieces), the channel
-// groups split C and combine through LDS.  N = 10240 positions give 320 blocks (64-position blocks: 160 for 256 CUs) and
-// the channel loops are unrolled eight-fold -- these kernels live on bytes in flight (round 2: 42 / 68 us fwd / bwd at
-// 1024 x 10240 with 64 positions x 4 waves, ~2 TB/s).
+// One of the compile-time values Vs picked by a run-time v: f(std::integral_constant<int, V>{}) runs for the V that equals v, and
+// a launcher instantiates its kernel template on CVAL(that argument); false if v is none of them.
+#define CVAL(c) decltype(c)::value
+template <int... Vs, class F>
+static bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// ---- the generic LayerNorm core: a block = LN_COLS positions x LN_GROUPS channel groups (512 threads).  Lanes run along n
+// (128-byte row pieces), the channel groups split C and combine through LDS.  N = 10240 positions give 320 blocks (64-position
+// blocks: 160 for 256 CUs) and the channel loops are unrolled eight-fold -- these kernels live on bytes in flight (round 2:
+// 42 / 68 us fwd / bwd at 1024 x 10240 with 64 positions x 4 waves, ~2 TB/s).
 #ifndef ADV_LN_COLS
 #define ADV_LN_COLS 32
 #endif
 constexpr int LN_COLS = ADV_LN_COLS, LN_GROUPS = 512 / LN_COLS, LN_THREADS = LN_COLS * LN_GROUPS, LN_UNROLL = 8;
 
-// per-position mean and 1 / (std_biased + eps) of x[:, n] in one read: sums of d = x - x[0, n] and d^2 (the shift keeps
-// s2 / C - (s1 / C)^2 free of cancellation: d is of the order of the spread, whatever the mean)
-__device__ __forceinline__ void ln_stats(const float* __restrict__ x, int Cc, long long N, long long n, bool ok, int p, int grp,
-                                         float (*part)[LN_GROUPS][LN_COLS], float eps, float& mean, float& r) {
-  const float x0 = ok ? x[n] : 0.f;
+// init + the LN_GROUPS partial sums of position p, in group order (fixed: deterministic)
+__device__ __forceinline__ float ln_group_sum(const float (*part)[LN_COLS], int p, float init) {
+  float t = init;
+#pragma unroll
+  for (int gI = 0; gI < LN_GROUPS; ++gI) t += part[gI][p];
+  return t;
+}
+
+// a position's two per-group partial sums s1, s2 -> its sums t1, t2 over all channel groups (one barrier: `part` is not in use)
+__device__ __forceinline__ void ln_group_combine(float (*part)[LN_GROUPS][LN_COLS], int grp, int p, float s1, float s2, float& t1, float& t2) {
+  part[0][grp][p] = s1;
+  part[1][grp][p] = s2;
+  __syncthreads();
+  t1 = ln_group_sum(part[0], p, 0.f);
+  t2 = ln_group_sum(part[1], p, 0.f);
+}
+
+// The one-pass statistics of x[:, n]: x0 = x[0, n] and the sums over c of d = x[c, n] - x0 and of d^2, then (ln_moments)
+// mean = x0 + t1 / C and var_biased = t2 / C - (t1 / C)^2.  The shift keeps the variance free of cancellation: d is of the
+// order of the spread, whatever the mean.  What a kernel makes of var -- 1 / (sqrt(var) + eps) for MGFNLayerNorm, rsqrt(var + eps)
+// for the head's nn.LayerNorm -- is its own last step.
+__device__ __forceinline__ void ln_shifted_sums(const float* __restrict__ x, int Cc, long long N, long long n, bool ok, int p, int grp,
+                                                float (*part)[LN_GROUPS][LN_COLS], float& x0, float& t1, float& t2) {
+  x0 = ok ? x[n] : 0.f;
   float s1 = 0.f, s2 = 0.f;
   if (ok) {
     int c = grp;
@@ -46,18 +77,20 @@ __device__ __forceinline__ void ln_stats(const float* __restrict__ x, int Cc, lo
       s2 += d * d;
     }
   }
-  part[0][grp][p] = s1;
-  part[1][grp][p] = s2;
-  __syncthreads();
-  float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int gI = 0; gI < LN_GROUPS; ++gI) {  // fixed order: deterministic
-    t1 += part[0][gI][p];
-    t2 += part[1][gI][p];
-  }
+  ln_group_combine(part, grp, p, s1, s2, t1, t2);
+}
+__device__ __forceinline__ void ln_moments(float x0, float t1, float t2, int Cc, float& mean, float& var) {
   const float m1 = t1 / (float)Cc;
   mean = x0 + m1;
-  const float var = fmaxf(t2 / (float)Cc - m1 * m1, 0.f);
+  var = fmaxf(t2 / (float)Cc - m1 * m1, 0.f);
+}
+
+// per-position mean and 1 / (std_biased + eps) of x[:, n] in one read
+__device__ __forceinline__ void ln_stats(const float* __restrict__ x, int Cc, long long N, long long n, bool ok, int p, int grp,
+                                         float (*part)[LN_GROUPS][LN_COLS], float eps, float& mean, float& r) {
+  float x0, t1, t2, var;
+  ln_shifted_sums(x, Cc, N, n, ok, p, grp, part, x0, t1, t2);
+  ln_moments(x0, t1, t2, Cc, mean, var);
   r = 1.f / (sqrtf(var) + eps);
 }
 
@@ -135,28 +168,17 @@ __global__ __launch_bounds__(LN_THREADS) void chan_layernorm_bwd_kernel(const fl
       s1 += dyg;
       s2 += dyg * xc[u];
       // per-channel sums over the block's 32 positions: a half-wave reduction in fixed order
-      float a = d[u] * xc[u] * r, bsum = d[u];
-#pragma unroll
-      for (int off = LN_COLS / 2; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        bsum += __shfl_xor(bsum, off, 64);
-      }
+      float cs[2] = {d[u] * xc[u] * r, d[u]};
+      lane_group_sums<LN_COLS>(cs);
       if (p == 0) {
-        pg[(long long)blockIdx.x * prow + c] = a;
-        pb[(long long)blockIdx.x * prow + c] = bsum;
+        pg[(long long)blockIdx.x * prow + c] = cs[0];
+        pb[(long long)blockIdx.x * prow + c] = cs[1];
       }
     }
   }
-  part[0][grp][p] = s1;
-  part[1][grp][p] = s2;
-  __syncthreads();
+  float t1, t2;
+  ln_group_combine(part, grp, p, s1, s2, t1, t2);
   if (!ok) return;
-  float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int gI = 0; gI < LN_GROUPS; ++gI) {
-    t1 += part[0][gI][p];
-    t2 += part[1][gI][p];
-  }
   const float m1 = t1 / (float)Cc, m2 = t2 / (float)Cc;
   const float sigma = 1.f / r - eps;
   const float k2 = sigma > 0.f ? r * r / sigma * m2 : 0.f;
@@ -184,17 +206,76 @@ __global__ __launch_bounds__(LN_THREADS) void chan_layernorm_bwd_kernel(const fl
   }
 }
 
-// The same backward for the shapes the scorer has (C = 64 / 128 / 1024, N a multiple of 4), re-blocked around what bounds it.  The
-// kernel above gives every lane ONE position and a 16th of the channels: a dword per lane and access (the texture addresser takes
-// 16 cycles per 256-byte wave-instruction: ~17 us per 512-KB block whatever HBM does), ten cross-lane shuffles per channel and
-// thread for the per-channel sums, and dy / x read twice.  Here a lane owns FOUR consecutive positions (16-byte accesses: a
-// quarter of the wave-instructions) and a 64th of the channels, with every value resident in registers between the statistics
-// and the output (CPT = C / 64 float4 pairs per thread: 128 VGPRs at C = 1 024; a block has its CU to itself at N / 32 = 320
-// blocks on 256 CUs), the per-channel sums fold the lane's four positions first (three shuffle steps over 8 lanes instead of five
-// over 32), the per-position sums fold across the wave's 8 channel groups by shuffles and across the 8 waves through LDS.
-// Same formulas; the sums associate differently from the kernel above (1e-7 relative).  Stage-2 launch (1 024 x 10 240, + skip
-// gradient): profiles/r05_mgfn_passes.md.
-constexpr int LV_POS = 32, LV_PL = 8, LV_GROUPS = 64, LV_THREADS = LV_PL * LV_GROUPS;  // 8 position quads x 64 channel groups
+// ---- the quad LayerNorm core: the same kernels for the shapes the scorer has (C = 64 / 128 / 1024, N a multiple of 4, 16-byte
+// aligned operands), re-blocked around what bounds them.  The generic kernels give every lane ONE position and a 16th of the
+// channels: a dword per lane and access (the texture addresser takes 16 cycles per 256-byte wave-instruction: ~17 us per 512-KB
+// block whatever HBM does), ten cross-lane shuffles per channel and thread for the per-channel sums, and the activations read
+// twice.  Here a block is LV_PL = 8 position quads x LV_GROUPS = 64 channel groups: a lane owns FOUR consecutive positions
+// (16-byte accesses: a quarter of the wave-instructions) and a 64th of the channels -- channel grp + 64 u for u < CPT = C / 64 --
+// with every value resident in registers between the statistics and the output (the LayerNorm backward: CPT float4 pairs, 128
+// VGPRs at C = 1 024; a block has its CU to itself at N / 32 = 320 blocks on 256 CUs).  Per-channel sums fold the lane's four
+// positions first, then the 8 lanes of the channel group (three shuffle steps instead of five over 32); per-position sums fold
+// across the wave's 8 channel groups by shuffles and across the 8 waves through LDS.  Same formulas as the generic kernels; the
+// sums associate differently (1e-7 relative).  Stage-2 launch (1 024 x 10 240, + skip gradient): profiles/r05_mgfn_passes.md.
+constexpr int LV_POS = 32, LV_PL = 8, LV_GROUPS = 64, LV_THREADS = LV_PL * LV_GROUPS, LV_WAVES = LV_THREADS / 64;
+
+// v[u] = the thread's quad (positions n .. n + 3) of channel grp + 64 u of t (C, N).  N % 4 == 0: a quad is inside the tensor or
+// past it, and a thread whose quad is past it keeps the zeros its arrays start with -- the callers put ONE branch around all
+// their loads (a branch, not a select between addresses: the loads stay 16-byte global loads).
+template <int CPT>
+__device__ __forceinline__ void lv_load(const float* __restrict__ t, int grp, long long N, long long n, float4 (&v)[CPT]) {
+  const float* tp = t + (long long)grp * N + n;
+#pragma unroll
+  for (int u = 0; u < CPT; ++u, tp += LV_GROUPS * N) v[u] = q4_load(tp);  // (a running pointer: one 64-bit add per load)
+}
+
+// The lane's per-position partial sums v[0 .. NV) -> the sums over all channels: the wave's 8 channel groups by shuffles (lanes 8
+// apart), the block's 8 waves through part[i] in wave order.  One barrier for all NV; `part` is not in use (a caller that has
+// just read it puts a barrier in front).  Every thread calls.
+template <int NV>
+__device__ __forceinline__ void lv_position_sums(float4 (&v)[NV], float (*part)[LV_WAVES][LV_POS]) {
+  const int pl = threadIdx.x % LV_PL, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = LV_PL; off < 64; off <<= 1)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = q4_shfl_xor_add(v[i], off);
+  if ((threadIdx.x & 63) < LV_PL)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) q4_store(&part[i][wave][4 * pl], v[i]);
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = q4_splat(0.f);
+#pragma unroll
+  for (int w = 0; w < LV_WAVES; ++w)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = q4_add(v[i], q4_load(&part[i][w][4 * pl]));
+}
+__device__ __forceinline__ float4 lv_position_sum(float4 v, float (*part)[LV_WAVES][LV_POS]) {
+  float4 a[1] = {v};
+  lv_position_sums(a, part);
+  return a[0];
+}
+
+// ln_shifted_sums / ln_moments in this blocking: s[0] = the thread's sum of d = v - x0 over its channels, s[1] = of d^2; then,
+// from the position sums t1 / t2, mean = x0 + t1 / C and var_biased.  The kernel's own last step turns var into its 1 / std.
+template <int CPT>
+__device__ __forceinline__ void lv_shifted_sums(const float4 (&v)[CPT], float4 x0, float4 (&s)[2]) {
+  s[0] = s[1] = q4_splat(0.f);
+#pragma unroll
+  for (int u = 0; u < CPT; ++u) {
+    const float4 d = q4_sub(v[u], x0);
+    s[0] = q4_add(s[0], d);
+    s[1] = q4_madd(s[1], d, d);
+  }
+}
+__device__ __forceinline__ void lv_moments(float4 x0, float4 t1, float4 t2, int Cc, float4& mean, float4& var) {
+  const float inv = 1.f / (float)Cc;
+  const float4 m1 = q4_scale(t1, inv);
+  mean = q4_add(x0, m1);
+  var = q4_map([inv](float t, float m) { return fmaxf(t * inv - m * m, 0.f); }, t2, m1);
+}
+
+// chan_layernorm_bwd_kernel in the quad blocking (dy and x are read once)
 template <int CPT>
 __global__ __launch_bounds__(LV_THREADS) void chan_layernorm_bwd_v4_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                            const float* __restrict__ g, const float* __restrict__ mu,
@@ -202,193 +283,112 @@ __global__ __launch_bounds__(LV_THREADS) void chan_layernorm_bwd_v4_kernel(const
                                                                            float* __restrict__ pg, float* __restrict__ pb, long long N,
                                                                            float eps, const float* __restrict__ add, long long prow) {
   constexpr int Cc = CPT * LV_GROUPS;
-  __shared__ float part[2][LV_THREADS / 64][LV_POS];
-  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL, wave = threadIdx.x >> 6;
-  const long long n = blockIdx.x * (long long)LV_POS + 4 * pl;  // N % 4 == 0: a quad is inside the tensor or past it
+  __shared__ float part[2][LV_WAVES][LV_POS];
+  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL;
+  const long long n = blockIdx.x * (long long)LV_POS + 4 * pl;
   const bool ok = n < N;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 mean = zero4, r = zero4, d[CPT], xc[CPT];
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) d[u] = xc[u] = zero4;
-  if (ok) {  // (a branch, not a select between addresses: the loads stay 16-byte global loads)
-    mean = *reinterpret_cast<const float4*>(mu + n);
-    r = *reinterpret_cast<const float4*>(rs + n);
-    const float* dyp = dy + (long long)grp * N + n;
-    const float* xp = x + (long long)grp * N + n;
-#pragma unroll
-    for (int u = 0; u < CPT; ++u) {
-      d[u] = *reinterpret_cast<const float4*>(dyp + (long long)u * LV_GROUPS * N);
-      xc[u] = *reinterpret_cast<const float4*>(xp + (long long)u * LV_GROUPS * N);
-    }
+  float4 mean = q4_splat(0.f), r = mean, d[CPT] = {}, xc[CPT] = {};
+  if (ok) {
+    mean = q4_load(mu + n);
+    r = q4_load(rs + n);
+    lv_load(dy, grp, N, n, d);
+    lv_load(x, grp, N, n, xc);
   }
-  float4 s1 = zero4, s2 = zero4;
+  float4 s[2] = {q4_splat(0.f), q4_splat(0.f)};
 #pragma unroll
   for (int u = 0; u < CPT; ++u) {
     const int c = grp + u * LV_GROUPS;
     const float gc = g[c];
-    if (ok) { xc[u].x -= mean.x; xc[u].y -= mean.y; xc[u].z -= mean.z; xc[u].w -= mean.w; }
-    const float4 dyg = make_float4(d[u].x * gc, d[u].y * gc, d[u].z * gc, d[u].w * gc);
-    s1.x += dyg.x; s1.y += dyg.y; s1.z += dyg.z; s1.w += dyg.w;
-    s2.x += dyg.x * xc[u].x; s2.y += dyg.y * xc[u].y; s2.z += dyg.z * xc[u].z; s2.w += dyg.w * xc[u].w;
+    if (ok) xc[u] = q4_sub(xc[u], mean);
+    const float4 dyg = q4_scale(d[u], gc);
+    s[0] = q4_add(s[0], dyg);
+    s[1] = q4_madd(s[1], dyg, xc[u]);
     // dg / db of channel c over the block's 32 positions: the lane's four, then the 8 lanes of the channel group
-    float a = ((d[u].x * xc[u].x * r.x + d[u].y * xc[u].y * r.y) + d[u].z * xc[u].z * r.z) + d[u].w * xc[u].w * r.w;
-    float bsum = ((d[u].x + d[u].y) + d[u].z) + d[u].w;
-#pragma unroll
-    for (int off = LV_PL / 2; off > 0; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      bsum += __shfl_xor(bsum, off, 64);
-    }
+    float cs[2] = {q4_sum_seq(q4_mul(q4_mul(d[u], xc[u]), r)), q4_sum_seq(d[u])};
+    lane_group_sums<LV_PL>(cs);
     if (pl == 0) {
-      pg[(long long)blockIdx.x * prow + c] = a;
-      pb[(long long)blockIdx.x * prow + c] = bsum;
+      pg[(long long)blockIdx.x * prow + c] = cs[0];
+      pb[(long long)blockIdx.x * prow + c] = cs[1];
     }
   }
-  // per-position sums over the channels: the wave's 8 channel groups by shuffles (lanes 8 apart), the 8 waves through LDS
-#pragma unroll
-  for (int off = LV_PL; off < 64; off <<= 1) {
-    s1.x += __shfl_xor(s1.x, off, 64); s1.y += __shfl_xor(s1.y, off, 64); s1.z += __shfl_xor(s1.z, off, 64); s1.w += __shfl_xor(s1.w, off, 64);
-    s2.x += __shfl_xor(s2.x, off, 64); s2.y += __shfl_xor(s2.y, off, 64); s2.z += __shfl_xor(s2.z, off, 64); s2.w += __shfl_xor(s2.w, off, 64);
-  }
-  if ((threadIdx.x & 63) < LV_PL) {
-    *reinterpret_cast<float4*>(&part[0][wave][4 * pl]) = s1;
-    *reinterpret_cast<float4*>(&part[1][wave][4 * pl]) = s2;
-  }
-  __syncthreads();
+  lv_position_sums(s, part);
   if (!ok) return;
-  float4 t1 = zero4, t2 = zero4;
-#pragma unroll
-  for (int w = 0; w < LV_THREADS / 64; ++w) {
-    const float4 a1 = *reinterpret_cast<const float4*>(&part[0][w][4 * pl]), a2 = *reinterpret_cast<const float4*>(&part[1][w][4 * pl]);
-    t1.x += a1.x; t1.y += a1.y; t1.z += a1.z; t1.w += a1.w;
-    t2.x += a2.x; t2.y += a2.y; t2.z += a2.z; t2.w += a2.w;
-  }
   const float inv = 1.f / (float)Cc;
-  const float4 m1 = make_float4(t1.x * inv, t1.y * inv, t1.z * inv, t1.w * inv);
-  float4 k2;
-  {
-    const float sx = 1.f / r.x - eps, sy = 1.f / r.y - eps, sz = 1.f / r.z - eps, sw = 1.f / r.w - eps;
-    k2.x = sx > 0.f ? r.x * r.x / sx * (t2.x * inv) : 0.f;
-    k2.y = sy > 0.f ? r.y * r.y / sy * (t2.y * inv) : 0.f;
-    k2.z = sz > 0.f ? r.z * r.z / sz * (t2.z * inv) : 0.f;
-    k2.w = sw > 0.f ? r.w * r.w / sw * (t2.w * inv) : 0.f;
-  }
+  const float4 m1 = q4_scale(s[0], inv);
+  const float4 k2 = q4_map([=](float rr, float t2) {
+    const float sigma = 1.f / rr - eps;
+    return sigma > 0.f ? rr * rr / sigma * (t2 * inv) : 0.f;
+  }, r, s[1]);
   constexpr int AB = CPT < 2 ? CPT : 2;  // `add` quads fetched per batch
 #pragma unroll
   for (int u0 = 0; u0 < CPT; u0 += AB) {
     float4 av[AB];
 #pragma unroll
     for (int u = 0; u < AB; ++u) {
-      av[u] = zero4;
-      if (add != nullptr) av[u] = *reinterpret_cast<const float4*>(add + (long long)(grp + (u0 + u) * LV_GROUPS) * N + n);
+      av[u] = q4_splat(0.f);
+      if (add != nullptr) av[u] = q4_load(add + (long long)(grp + (u0 + u) * LV_GROUPS) * N + n);
     }
 #pragma unroll
     for (int u = 0; u < AB; ++u) {
       const int cc = grp + (u0 + u) * LV_GROUPS;
       const float gc = g[cc];
-      const float4 dd = d[u0 + u], xx = xc[u0 + u];
-      *reinterpret_cast<float4*>(dx + (long long)cc * N + n) =
-          make_float4(r.x * (dd.x * gc - m1.x) - k2.x * xx.x + av[u].x, r.y * (dd.y * gc - m1.y) - k2.y * xx.y + av[u].y,
-                      r.z * (dd.z * gc - m1.z) - k2.z * xx.z + av[u].z, r.w * (dd.w * gc - m1.w) - k2.w * xx.w + av[u].w);
+      q4_store(dx + (long long)cc * N + n, q4_map([gc](float rr, float dd, float m, float k, float xx, float a) { return rr * (dd * gc - m) - k * xx + a; },
+                                                  r, d[u0 + u], m1, k2, xc[u0 + u], av[u]));
     }
   }
 }
 
-// forward in the same blocking: y = (x - mu) * rs * g + b with the one-pass shifted statistics of ln_stats, x resident in registers
+// forward in the same blocking: y = (x - mu) * rs * g + b, x resident in registers
 template <int CPT>
 __global__ __launch_bounds__(LV_THREADS) void chan_layernorm_fwd_v4_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
                                                                            float* __restrict__ y, float* __restrict__ mu, float* __restrict__ rs, long long N,
                                                                            float eps) {
   constexpr int Cc = CPT * LV_GROUPS;
-  __shared__ float part[2][LV_THREADS / 64][LV_POS];
-  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL, wave = threadIdx.x >> 6;
+  __shared__ float part[2][LV_WAVES][LV_POS];
+  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL;
   const long long n = blockIdx.x * (long long)LV_POS + 4 * pl;
   const bool ok = n < N;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v[CPT], x0 = zero4;
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) v[u] = zero4;
+  float4 v[CPT] = {}, x0 = q4_splat(0.f), s[2], mean, var;
   if (ok) {
-    x0 = *reinterpret_cast<const float4*>(x + n);
-    const float* xp = x + (long long)grp * N + n;
-#pragma unroll
-    for (int u = 0; u < CPT; ++u) v[u] = *reinterpret_cast<const float4*>(xp + (long long)u * LV_GROUPS * N);
+    x0 = q4_load(x + n);  // channel 0: the shift of the one-pass statistics
+    lv_load(x, grp, N, n, v);
   }
-  float4 s1 = zero4, s2 = zero4;
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) {
-    const float4 d = make_float4(v[u].x - x0.x, v[u].y - x0.y, v[u].z - x0.z, v[u].w - x0.w);
-    s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-    s2.x += d.x * d.x; s2.y += d.y * d.y; s2.z += d.z * d.z; s2.w += d.w * d.w;
-  }
-#pragma unroll
-  for (int off = LV_PL; off < 64; off <<= 1) {
-    s1.x += __shfl_xor(s1.x, off, 64); s1.y += __shfl_xor(s1.y, off, 64); s1.z += __shfl_xor(s1.z, off, 64); s1.w += __shfl_xor(s1.w, off, 64);
-    s2.x += __shfl_xor(s2.x, off, 64); s2.y += __shfl_xor(s2.y, off, 64); s2.z += __shfl_xor(s2.z, off, 64); s2.w += __shfl_xor(s2.w, off, 64);
-  }
-  if ((threadIdx.x & 63) < LV_PL) {
-    *reinterpret_cast<float4*>(&part[0][wave][4 * pl]) = s1;
-    *reinterpret_cast<float4*>(&part[1][wave][4 * pl]) = s2;
-  }
-  __syncthreads();
+  lv_shifted_sums(v, x0, s);
+  lv_position_sums(s, part);
   if (!ok) return;
-  float4 t1 = zero4, t2 = zero4;
-#pragma unroll
-  for (int w = 0; w < LV_THREADS / 64; ++w) {
-    const float4 a1 = *reinterpret_cast<const float4*>(&part[0][w][4 * pl]), a2 = *reinterpret_cast<const float4*>(&part[1][w][4 * pl]);
-    t1.x += a1.x; t1.y += a1.y; t1.z += a1.z; t1.w += a1.w;
-    t2.x += a2.x; t2.y += a2.y; t2.z += a2.z; t2.w += a2.w;
-  }
-  const float inv = 1.f / (float)Cc;
-  const float4 m1 = make_float4(t1.x * inv, t1.y * inv, t1.z * inv, t1.w * inv);
-  const float4 mean = make_float4(x0.x + m1.x, x0.y + m1.y, x0.z + m1.z, x0.w + m1.w);
-  const float4 r = make_float4(1.f / (sqrtf(fmaxf(t2.x * inv - m1.x * m1.x, 0.f)) + eps), 1.f / (sqrtf(fmaxf(t2.y * inv - m1.y * m1.y, 0.f)) + eps),
-                               1.f / (sqrtf(fmaxf(t2.z * inv - m1.z * m1.z, 0.f)) + eps), 1.f / (sqrtf(fmaxf(t2.w * inv - m1.w * m1.w, 0.f)) + eps));
+  lv_moments(x0, s[0], s[1], Cc, mean, var);
+  const float4 r = q4_map([eps](float vv) { return 1.f / (sqrtf(vv) + eps); }, var);
   if (grp == 0) {
-    *reinterpret_cast<float4*>(mu + n) = mean;
-    *reinterpret_cast<float4*>(rs + n) = r;
+    q4_store(mu + n, mean);
+    q4_store(rs + n, r);
   }
   float* yp = y + (long long)grp * N + n;
 #pragma unroll
   for (int u = 0; u < CPT; ++u) {
     const int c = grp + u * LV_GROUPS;
     const float gc = g[c], bc = b[c];
-    *reinterpret_cast<float4*>(yp + (long long)u * LV_GROUPS * N) =
-        make_float4((v[u].x - mean.x) * r.x * gc + bc, (v[u].y - mean.y) * r.y * gc + bc, (v[u].z - mean.z) * r.z * gc + bc, (v[u].w - mean.w) * r.w * gc + bc);
+    q4_store(yp + (long long)u * LV_GROUPS * N, q4_map([gc, bc](float xv, float m, float rr) { return (xv - m) * rr * gc + bc; }, v[u], mean, r));
   }
 }
 
-// Which kernel a chan_layernorm launch takes (advhip_chan_layernorm_form): 0 = the generic one, else the CPT of the 16-byte form.
+// Which kernel a chan_layernorm launch takes (advhip_chan_layernorm_form): 0 = the generic one, else the CPT of the quad form.
 // `aligned16`: every activation-shaped or per-position operand starts on a 16-byte boundary.
+// The CPTs that are instantiated, in one place: f(CPT as an integral_constant) for a quad form, false for any other number.
+template <class F>
+static bool ln_dispatch_quad(int form, F&& f) { return dispatch_int<1, 2, 16>(form, f); }
 static int ln_form(int C, long long N, bool aligned16) {
-  if (N % 4 != 0 || !aligned16) return 0;
-  switch (C) {
-    case 1 * LV_GROUPS: return 1;
-    case 2 * LV_GROUPS: return 2;
-    case 16 * LV_GROUPS: return 16;
-    default: return 0;
-  }
+  if (N % 4 != 0 || !aligned16 || C % LV_GROUPS != 0) return 0;
+  return ln_dispatch_quad(C / LV_GROUPS, [](auto) {}) ? C / LV_GROUPS : 0;
 }
 
-static bool launch_ln_fwd_v4(const float* x, const float* g, const float* b, float* y, float* mu, float* rs, int C, long long N, float eps, hipStream_t st) {
-  const dim3 grid((unsigned)((N + LV_POS - 1) / LV_POS)), block(LV_THREADS);
-  switch (ln_form(C, N, (((uintptr_t)x | (uintptr_t)y | (uintptr_t)mu | (uintptr_t)rs) & 15) == 0)) {
-    case 1: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<1>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
-    case 2: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<2>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
-    case 16: hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<16>, grid, block, 0, st, x, g, b, y, mu, rs, N, eps); return true;
-    default: return false;
-  }
-}
-
-static bool launch_ln_bwd_v4(const float* dy, const float* x, const float* g, const float* mu, const float* rs, float* dx, float* pg, float* pb, int C,
-                             long long N, float eps, const float* add, long long prow, hipStream_t st) {
-  static_assert(LV_POS == LN_COLS, "the partial-sum matrices have one row per LN_COLS positions (advhip_chan_layernorm_bwd_partial_rows)");
-  const dim3 grid((unsigned)((N + LV_POS - 1) / LV_POS)), block(LV_THREADS);
-  switch (ln_form(C, N, (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mu | (uintptr_t)rs | (uintptr_t)add) & 15) == 0)) {
-    case 1: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<1>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
-    case 2: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<2>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
-    case 16: hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<16>, grid, block, 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow); return true;
-    default: return false;
-  }
+// The launch grid of every LayerNorm-shaped kernel, generic or quad: one block per LN_COLS = LV_POS positions (also the rows of
+// the backward passes' partial-sum matrices)
+static_assert(LV_POS == LN_COLS, "the partial-sum matrices have one row per LN_COLS positions (advhip_chan_layernorm_bwd_partial_rows)");
+static long long ln_blocks(long long N) { return (N + LN_COLS - 1) / LN_COLS; }
+static int ln_grid(const char* who, long long N, dim3* grid) {
+  ADVHIP_REQUIRE(ln_blocks(N) < (1ll << 31), "%s: too many positions", who);
+  *grid = dim3((unsigned)ln_blocks(N));
+  return ADVHIP_OK;
 }
 
 // out[c, b, t] = bias[c % H] + sum_j w[c % H][j] * v[c, b, t + j - K/2]   (zero outside [0, T)); one thread per element
@@ -465,10 +465,10 @@ static int dwconv_t_form(int T, bool aligned16) { return T % 4 == 0 && aligned16
 // quad instead of three per element): the window v[t - K/2 .. t + 3 + K/2] is the quad, its left and its right neighbour quad
 // (zero outside the row).  Same sums per output; the per-block partial sums of the backward associate differently (1e-7).
 __device__ __forceinline__ void dw_window(const float* __restrict__ p, long long e, int t, int T, float (&win)[12]) {
-  const float4 c = *reinterpret_cast<const float4*>(p + e);
-  float4 l = make_float4(0.f, 0.f, 0.f, 0.f), r = l;
-  if (t > 0) l = *reinterpret_cast<const float4*>(p + e - 4);
-  if (t + 4 < T) r = *reinterpret_cast<const float4*>(p + e + 4);
+  const float4 c = q4_load(p + e);
+  float4 l = q4_splat(0.f), r = l;
+  if (t > 0) l = q4_load(p + e - 4);
+  if (t + 4 < T) r = q4_load(p + e + 4);
   win[0] = l.x; win[1] = l.y; win[2] = l.z; win[3] = l.w;
   win[4] = c.x; win[5] = c.y; win[6] = c.z; win[7] = c.w;
   win[8] = r.x; win[9] = r.y; win[10] = r.z; win[11] = r.w;
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void dwconv_t_fwd_v4_kernel(const float* __res
       for (int j = 0; j < K; ++j) acc += wk[j] * win[4 + q + j - K / 2];  // (zero outside the row: the same sum as the scalar kernel's taps in range)
       o[q] = acc;
     }
-    *reinterpret_cast<float4*>(out + e) = make_float4(o[0], o[1], o[2], o[3]);
+    q4_store(out + e, make_float4(o[0], o[1], o[2], o[3]));
   }
 }
 
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void dwconv_t_bwd_v4_kernel(const float* __res
       acc[K] += dw[4 + q];
       g[q] = gq;
     }
-    *reinterpret_cast<float4*>(dv + i) = make_float4(g[0], g[1], g[2], g[3]);
+    q4_store(dv + i, make_float4(g[0], g[1], g[2], g[3]));
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
@@ -552,40 +552,16 @@ __global__ __launch_bounds__(256) void unfold3_kernel(const float* __restrict__ 
     const long long e = i * 4;               // first element of this float4 (T % 4 == 0: a float4 never straddles a row)
     const long long c = e / per_c, w = e - c * per_c;
     const int t = (int)(w % T);
-    const float4 v = *reinterpret_cast<const float4*>(x + e);
+    const float4 v = q4_load(x + e);
     const float l = t > 0 ? x[e - 1] : 0.f, r = t + 4 < T ? x[e + 4] : 0.f;
     float* o = u + (c * 3) * per_c + w;
-    *reinterpret_cast<float4*>(o) = make_float4(l, v.x, v.y, v.z);                 // tap 0: x[t - 1]
-    *reinterpret_cast<float4*>(o + per_c) = v;                                     // tap 1
-    *reinterpret_cast<float4*>(o + 2 * per_c) = make_float4(v.y, v.z, v.w, r);     // tap 2: x[t + 1]
+    q4_store(o, make_float4(l, v.x, v.y, v.z));                 // tap 0: x[t - 1]
+    q4_store(o + per_c, v);                                     // tap 1
+    q4_store(o + 2 * per_c, make_float4(v.y, v.z, v.w, r));     // tap 2: x[t + 1]
   }
 }
 
 // ---- BatchNorm1d over the rows of a (C, N) activation (FocusAttention.norm, modeling_mgfn.py:162, 174) -------------------
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) t += red[i];
-  return t;
-}
-
 // training mode: batch statistics per channel (one block per channel row); y = (x - mean) * rstd * gamma + beta;
 // mean / biased var are returned (running-statistics update and backward)
 __global__ __launch_bounds__(256) void bn_rows_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -600,13 +576,13 @@ __global__ __launch_bounds__(256) void bn_rows_fwd_kernel(const float* __restric
   const float* xr = x + (long long)c * N;
   float s = 0.f;
   for (long long i = threadIdx.x; i < N; i += 256) s += xr[i];
-  const float mean = block_sum_256(s, red) / (float)N;
+  const float mean = block_sum<256>(s, red) / (float)N;
   float q = 0.f;
   for (long long i = threadIdx.x; i < N; i += 256) {
     const float d = xr[i] - mean;
     q += d * d;
   }
-  const float var = block_sum_256(q, red) / (float)N;
+  const float var = block_sum<256>(q, red) / (float)N;
   // (x - mean) * sc + beta, not x * sc + (beta - mean * sc): the latter rounds at the size of mean * sc, far above y's own size
   // when sc is large (a row of one value, N = 1: sc = gamma / sqrt(eps), where this form gives y = beta exactly and that one
   // beta +- 2e-4 at |x| ~ 2).  With the mean 40 standard deviations from zero both are bounded by the fp32 mean itself (4e-6).
@@ -635,32 +611,27 @@ __global__ __launch_bounds__(NT) void bn_rows_fwd_reg_kernel(const float* __rest
   const int c = blockIdx.x;
   const float* xr = x + (long long)c * N;
   const long long nq = N / 4;
-  float4 v[BQ];
+  float4 v[BQ] = {};
 #pragma unroll
   for (int u = 0; u < BQ; ++u) {
-    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     const long long q = threadIdx.x + (long long)NT * u;
-    if (q < nq) v[u] = *reinterpret_cast<const float4*>(xr + 4 * q);
+    if (q < nq) v[u] = q4_load(xr + 4 * q);
   }
   float s = 0.f;
 #pragma unroll
-  for (int u = 0; u < BQ; ++u) s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
+  for (int u = 0; u < BQ; ++u) s += q4_sum_pairs(v[u]);
   const float mean = block_sum<NT>(s, red) / (float)N;
   float q2 = 0.f;
 #pragma unroll
-  for (int u = 0; u < BQ; ++u) {
-    if (threadIdx.x + (long long)NT * u < nq) {
-      const float d0 = v[u].x - mean, d1 = v[u].y - mean, d2 = v[u].z - mean, d3 = v[u].w - mean;
-      q2 += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    }
-  }
+  for (int u = 0; u < BQ; ++u)
+    if (threadIdx.x + (long long)NT * u < nq) q2 += q4_sum_pairs(q4_map([mean](float xv) { return (xv - mean) * (xv - mean); }, v[u]));
   const float var = block_sum<NT>(q2, red) / (float)N;
   const float sc = gamma[c] * rsqrtf(var + eps), sh = beta[c];  // (x - mean) * sc + beta, as in bn_rows_fwd_kernel
   float* yr = y + (long long)c * N;
 #pragma unroll
   for (int u = 0; u < BQ; ++u) {
     const long long q = threadIdx.x + (long long)NT * u;
-    if (q < nq) *reinterpret_cast<float4*>(yr + 4 * q) = make_float4((v[u].x - mean) * sc + sh, (v[u].y - mean) * sc + sh, (v[u].z - mean) * sc + sh, (v[u].w - mean) * sc + sh);
+    if (q < nq) q4_store(yr + 4 * q, q4_map([=](float xv) { return (xv - mean) * sc + sh; }, v[u]));
   }
   if (threadIdx.x == 0) {
     mean_out[c] = mean;
@@ -681,23 +652,24 @@ static int bn_rows_form(int C, long long N, bool aligned16) {
   if (vec && N <= 256 * 4 * 12) return ADVHIP_BN_ROWS_REG256X12;
   return ADVHIP_BN_ROWS_GENERIC;
 }
+// f(NT, BQ) for a register form, false for the generic one
+template <class F>
+static bool bn_dispatch_reg(int form, F&& f) {
+  switch (form) {
+    case ADVHIP_BN_ROWS_REG1024X4: f(std::integral_constant<int, 1024>{}, std::integral_constant<int, 4>{}); return true;
+    case ADVHIP_BN_ROWS_REG256X4: f(std::integral_constant<int, 256>{}, std::integral_constant<int, 4>{}); return true;
+    case ADVHIP_BN_ROWS_REG256X12: f(std::integral_constant<int, 256>{}, std::integral_constant<int, 12>{}); return true;
+    default: return false;
+  }
+}
 
 static void launch_bn_rows_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* var, int C, long long N, float eps,
                                float* run_mean, float* run_var, float momentum, hipStream_t st) {
   const dim3 grid((unsigned)C);
-  switch (bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)y) & 15) == 0)) {
-    case ADVHIP_BN_ROWS_REG1024X4:
-      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-      break;
-    case ADVHIP_BN_ROWS_REG256X4:
-      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-      break;
-    case ADVHIP_BN_ROWS_REG256X12:
-      hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-      break;
-    default:
-      hipLaunchKernelGGL(bn_rows_fwd_kernel, grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
-  }
+  if (!bn_dispatch_reg(bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)y) & 15) == 0), [&](auto nt, auto bq) {
+        hipLaunchKernelGGL((bn_rows_fwd_reg_kernel<CVAL(nt), CVAL(bq)>), grid, dim3(CVAL(nt)), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
+      }))
+    hipLaunchKernelGGL(bn_rows_fwd_kernel, grid, dim3(256), 0, st, x, gamma, beta, y, mean, var, N, eps, run_mean, run_var, momentum);
 }
 
 // dx = gamma * rstd * (dy - mean(dy) - xhat * mean(dy * xhat)),  dgamma = sum dy * xhat,  dbeta = sum dy
@@ -718,8 +690,8 @@ __global__ __launch_bounds__(256) void bn_rows_bwd_kernel(const float* __restric
     s1 += d;
     s2 += d * (xr[i] - mu) * rstd;
   }
-  const float sum_dy = block_sum_256(s1, red);
-  const float sum_dyx = block_sum_256(s2, red);
+  const float sum_dy = block_sum<256>(s1, red);
+  const float sum_dyx = block_sum<256>(s2, red);
   const float k = gamma[c] * rstd, m1 = sum_dy / (float)N, m2 = sum_dyx / (float)N;
   float* o = dx + (long long)c * N;
   const float* ar = add ? add + (long long)c * N : nullptr;
@@ -801,23 +773,22 @@ __global__ __launch_bounds__(NT) void bn_rows_bwd_reg_kernel(const float* __rest
   const float* dr = dy + (long long)c * N;
   const long long nq = N / 4;
   const float mu = mean[c], rstd = rsqrtf(var[c] + eps);
-  float4 d[BQ], h[BQ];
+  float4 d[BQ] = {}, h[BQ] = {};
 #pragma unroll
   for (int u = 0; u < BQ; ++u) {
-    d[u] = h[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     const long long q = threadIdx.x + (long long)NT * u;
     if (q < nq) {
-      d[u] = *reinterpret_cast<const float4*>(dr + 4 * q);
-      h[u] = *reinterpret_cast<const float4*>(xr + 4 * q);
+      d[u] = q4_load(dr + 4 * q);
+      h[u] = q4_load(xr + 4 * q);
     }
   }
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int u = 0; u < BQ; ++u) {
     if (threadIdx.x + (long long)NT * u < nq) {
-      h[u] = make_float4((h[u].x - mu) * rstd, (h[u].y - mu) * rstd, (h[u].z - mu) * rstd, (h[u].w - mu) * rstd);
-      s1 += (d[u].x + d[u].y) + (d[u].z + d[u].w);
-      s2 += (d[u].x * h[u].x + d[u].y * h[u].y) + (d[u].z * h[u].z + d[u].w * h[u].w);
+      h[u] = q4_map([=](float xv) { return (xv - mu) * rstd; }, h[u]);
+      s1 += q4_sum_pairs(d[u]);
+      s2 += q4_sum_pairs(q4_mul(d[u], h[u]));
     }
   }
   const float sum_dy = block_sum<NT>(s1, red);
@@ -828,10 +799,9 @@ __global__ __launch_bounds__(NT) void bn_rows_bwd_reg_kernel(const float* __rest
   for (int u = 0; u < BQ; ++u) {
     const long long q = threadIdx.x + (long long)NT * u;
     if (q < nq) {
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (add != nullptr) a = *reinterpret_cast<const float4*>(add + (long long)c * N + 4 * q);
-      *reinterpret_cast<float4*>(o + 4 * q) = make_float4(k * (d[u].x - m1 - h[u].x * m2) + a.x, k * (d[u].y - m1 - h[u].y * m2) + a.y,
-                                                          k * (d[u].z - m1 - h[u].z * m2) + a.z, k * (d[u].w - m1 - h[u].w * m2) + a.w);
+      float4 a = q4_splat(0.f);
+      if (add != nullptr) a = q4_load(add + (long long)c * N + 4 * q);
+      q4_store(o + 4 * q, q4_map([=](float dd, float hh, float aa) { return k * (dd - m1 - hh * m2) + aa; }, d[u], h[u], a));
     }
   }
   if (threadIdx.x == 0) {
@@ -843,19 +813,10 @@ __global__ __launch_bounds__(NT) void bn_rows_bwd_reg_kernel(const float* __rest
 static void launch_bn_rows_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* var, float* dx, float* dgamma,
                                float* dbeta, int C, long long N, float eps, const float* add, hipStream_t st) {
   const dim3 grid((unsigned)C);
-  switch (bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)add) & 15) == 0)) {
-    case ADVHIP_BN_ROWS_REG1024X4:
-      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<1024, 4>), grid, dim3(1024), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-      break;
-    case ADVHIP_BN_ROWS_REG256X4:
-      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 4>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-      break;
-    case ADVHIP_BN_ROWS_REG256X12:
-      hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<256, 12>), grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-      break;
-    default:
-      hipLaunchKernelGGL(bn_rows_bwd_kernel, grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
-  }
+  if (!bn_dispatch_reg(bn_rows_form(C, N, (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)add) & 15) == 0), [&](auto nt, auto bq) {
+        hipLaunchKernelGGL((bn_rows_bwd_reg_kernel<CVAL(nt), CVAL(bq)>), grid, dim3(CVAL(nt)), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
+      }))
+    hipLaunchKernelGGL(bn_rows_bwd_kernel, grid, dim3(256), 0, st, dy, x, gamma, mean, var, dx, dgamma, dbeta, N, eps, add);
 }
 
 // ---- the scorer's head on the body's layout (modeling_mgfn.py:387-389: permute -> nn.LayerNorm(C) -> Linear(C, 1) -> sigmoid) ----
@@ -872,23 +833,10 @@ __global__ __launch_bounds__(LN_THREADS) void head_ln_fc_fwd_kernel(const float*
   const int p = threadIdx.x % LN_COLS, grp = threadIdx.x / LN_COLS;
   const long long n0 = blockIdx.x * (long long)LN_COLS, n = n0 + p;
   const bool ok = n < N;
-  // statistics in one read, shifted by the first channel's value (as ln_stats), nn.LayerNorm's rsqrt(var + eps)
-  const float x0 = ok ? x[n] : 0.f;
-  float s1 = 0.f, s2 = 0.f;
-  if (ok)
-    for (int c = grp; c < Cc; c += LN_GROUPS) {
-      const float d = x[(long long)c * N + n] - x0;
-      s1 += d;
-      s2 += d * d;
-    }
-  part[0][grp][p] = s1;
-  part[1][grp][p] = s2;
-  __syncthreads();
-  float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int gI = 0; gI < LN_GROUPS; ++gI) { t1 += part[0][gI][p]; t2 += part[1][gI][p]; }
-  const float m1 = t1 / (float)Cc, mean = x0 + m1;
-  const float r = rsqrtf(fmaxf(t2 / (float)Cc - m1 * m1, 0.f) + eps);
+  float x0, t1, t2, mean, var;
+  ln_shifted_sums(x, Cc, N, n, ok, p, grp, part, x0, t1, t2);
+  ln_moments(x0, t1, t2, Cc, mean, var);
+  const float r = rsqrtf(var + eps);  // nn.LayerNorm's
   if (ok && grp == 0) { mean_out[n] = mean; rstd_out[n] = r; }
   float dot = 0.f;
   for (int c0 = 0; c0 < Cc; c0 += HD_CHUNK) {
@@ -911,12 +859,7 @@ __global__ __launch_bounds__(LN_THREADS) void head_ln_fc_fwd_kernel(const float*
   }
   part[0][grp][p] = dot;
   __syncthreads();
-  if (ok && grp == 0) {
-    float z = b0[0];
-#pragma unroll
-    for (int gI = 0; gI < LN_GROUPS; ++gI) z += part[0][gI][p];
-    score[n] = 1.f / (1.f + expf(-z));
-  }
+  if (ok && grp == 0) score[n] = 1.f / (1.f + expf(-ln_group_sum(part[0], p, b0[0])));
 }
 
 // backward: dy[n][c] = dxn[n][c] + dscore[n] s (1 - s) w[c];  dx = r (dy g - mean_c(dy g) - xhat mean_c(dy g xhat));
@@ -962,33 +905,23 @@ __global__ __launch_bounds__(LN_THREADS) void head_ln_fc_bwd_kernel(const float*
       const float dyg = dy * g[c];
       s1 += dyg;
       s2 += dyg * xh;
-      float a = dy * xh, bs = dy, cw = dwv;  // per-channel sums over the block's 32 positions: a half-wave reduction
-#pragma unroll
-      for (int off = LN_COLS / 2; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        bs += __shfl_xor(bs, off, 64);
-        cw += __shfl_xor(cw, off, 64);
-      }
+      float cs[3] = {dy * xh, dy, dwv};  // per-channel sums over the block's 32 positions: a half-wave reduction
+      lane_group_sums<LN_COLS>(cs);
       if (p == 0) {
-        prow[c] = a;
-        prow[Cc + c] = bs;
-        prow[2 * Cc + c] = cw;
+        prow[c] = cs[0];
+        prow[Cc + c] = cs[1];
+        prow[2 * Cc + c] = cs[2];
       }
     }
     __syncthreads();
   }
   if (grp == 0) {  // db0: sum of dlogit over the block's positions
-    float t = dl;
-#pragma unroll
-    for (int off = LN_COLS / 2; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (p == 0) prow[3 * Cc] = t;
+    float t[1] = {dl};
+    lane_group_sums<LN_COLS>(t);
+    if (p == 0) prow[3 * Cc] = t[0];
   }
-  part[0][grp][p] = s1;
-  part[1][grp][p] = s2;
-  __syncthreads();
-  float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-  for (int gI = 0; gI < LN_GROUPS; ++gI) { t1 += part[0][gI][p]; t2 += part[1][gI][p]; }
+  float t1, t2;
+  ln_group_combine(part, grp, p, s1, s2, t1, t2);
   const float m1 = t1 / (float)Cc, m2 = t2 / (float)Cc;
   for (int c0 = 0; c0 < Cc; c0 += HD_CHUNK) {
     __syncthreads();
@@ -1007,31 +940,12 @@ __global__ __launch_bounds__(LN_THREADS) void head_ln_fc_bwd_kernel(const float*
   }
 }
 
-// ---- the head, re-blocked like chan_layernorm_bwd_v4_kernel (a lane owns four consecutive positions and C / 64 channels, every
-// value of y resident in registers: ONE read of y in 16-byte accesses; the (C, N) <-> (N, C) transposition through a 32 x 64 LDS tile
-// per 64-channel chunk, rows written / read as 16-byte pieces).  C = 64 * CPT, N % 4 == 0, 16-byte aligned operands.
+// ---- the head on the quad LayerNorm core (ONE read of y in 16-byte accesses); the (C, N) <-> (N, C) transposition goes through
+// a 32 x 64 LDS tile per 64-channel chunk, rows written / read as 16-byte pieces.  C = 64 * CPT, N % 4 == 0, 16-byte aligned operands.
 constexpr int HV_PAD = LV_GROUPS + 4;  // tile row pitch in floats (16-byte aligned rows)
 
 // Which kernel a head_ln_fc launch takes (advhip_head_ln_fc_form): 1 = this form, 0 = the generic kernel above
 static int head_form(int C, long long N, bool aligned16) { return C == 16 * LV_GROUPS && N % 4 == 0 && aligned16 ? 1 : 0; }
-
-// the lane's four per-position partial sums, over the wave's 8 channel groups (lanes 8 apart) and the block's 8 waves
-__device__ __forceinline__ float4 lv_position_sum(float4 v, float (*part)[LV_POS], int pl, int wave) {
-#pragma unroll
-  for (int off = LV_PL; off < 64; off <<= 1) {
-    v.x += __shfl_xor(v.x, off, 64); v.y += __shfl_xor(v.y, off, 64); v.z += __shfl_xor(v.z, off, 64); v.w += __shfl_xor(v.w, off, 64);
-  }
-  __syncthreads();  // (part may still be read from a previous call)
-  if ((threadIdx.x & 63) < LV_PL) *reinterpret_cast<float4*>(&part[wave][4 * pl]) = v;
-  __syncthreads();
-  float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int w = 0; w < LV_THREADS / 64; ++w) {
-    const float4 a = *reinterpret_cast<const float4*>(&part[w][4 * pl]);
-    t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w;
-  }
-  return t;
-}
 
 template <int CPT>
 __global__ __launch_bounds__(LV_THREADS) void head_ln_fc_fwd_v4_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
@@ -1039,60 +953,46 @@ __global__ __launch_bounds__(LV_THREADS) void head_ln_fc_fwd_v4_kernel(const flo
                                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                                        float* __restrict__ score, long long N, float eps) {
   constexpr int Cc = CPT * LV_GROUPS;
-  __shared__ float part[LV_THREADS / 64][LV_POS];
+  __shared__ float part[1][LV_WAVES][LV_POS];  // (one value at a time: the room of a second one goes to the tile)
   __shared__ __attribute__((aligned(16))) float tile[LV_POS][HV_PAD];
-  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL, wave = threadIdx.x >> 6;
+  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL;
   const long long n0 = blockIdx.x * (long long)LV_POS, n = n0 + 4 * pl;
   const bool ok = n < N;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 v[CPT], x0 = zero4;
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) v[u] = zero4;
+  float4 v[CPT] = {}, x0 = q4_splat(0.f), s[2], mean, var;
   if (ok) {
-    x0 = *reinterpret_cast<const float4*>(x + n);  // channel 0: the shift of the one-pass statistics (as ln_stats)
-    const float* xp = x + (long long)grp * N + n;
-#pragma unroll
-    for (int u = 0; u < CPT; ++u) v[u] = *reinterpret_cast<const float4*>(xp + (long long)u * LV_GROUPS * N);
+    x0 = q4_load(x + n);  // channel 0: the shift of the one-pass statistics
+    lv_load(x, grp, N, n, v);
   }
-  float4 s1 = zero4, s2 = zero4;
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) {
-    const float4 d = make_float4(v[u].x - x0.x, v[u].y - x0.y, v[u].z - x0.z, v[u].w - x0.w);
-    s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-    s2.x += d.x * d.x; s2.y += d.y * d.y; s2.z += d.z * d.z; s2.w += d.w * d.w;
-  }
-  const float4 t1 = lv_position_sum(s1, part, pl, wave), t2 = lv_position_sum(s2, part, pl, wave);
-  const float inv = 1.f / (float)Cc;
-  const float4 m1 = make_float4(t1.x * inv, t1.y * inv, t1.z * inv, t1.w * inv);
-  const float4 mean = make_float4(x0.x + m1.x, x0.y + m1.y, x0.z + m1.z, x0.w + m1.w);
-  const float4 r = make_float4(rsqrtf(fmaxf(t2.x * inv - m1.x * m1.x, 0.f) + eps), rsqrtf(fmaxf(t2.y * inv - m1.y * m1.y, 0.f) + eps),
-                               rsqrtf(fmaxf(t2.z * inv - m1.z * m1.z, 0.f) + eps), rsqrtf(fmaxf(t2.w * inv - m1.w * m1.w, 0.f) + eps));
+  lv_shifted_sums(v, x0, s);
+  const float4 t1 = lv_position_sum(s[0], part);
+  __syncthreads();
+  const float4 t2 = lv_position_sum(s[1], part);
+  lv_moments(x0, t1, t2, Cc, mean, var);
+  const float4 r = q4_map([eps](float vv) { return rsqrtf(vv + eps); }, var);  // nn.LayerNorm's
   if (ok && grp == 0) {
-    *reinterpret_cast<float4*>(mean_out + n) = mean;
-    *reinterpret_cast<float4*>(rstd_out + n) = r;
+    q4_store(mean_out + n, mean);
+    q4_store(rstd_out + n, r);
   }
-  float4 dot = zero4;
+  float4 dot = q4_splat(0.f);
   const int orow = threadIdx.x / 16, ocol = (threadIdx.x % 16) * 4;  // this thread's 16-byte piece of the 32 x 64 tile on the way out
 #pragma unroll
   for (int u = 0; u < CPT; ++u) {
     const int c = grp + u * LV_GROUPS;
     const float gc = g[c], bc = b[c], wc = w[c];
-    const float4 o = make_float4((v[u].x - mean.x) * r.x * gc + bc, (v[u].y - mean.y) * r.y * gc + bc, (v[u].z - mean.z) * r.z * gc + bc,
-                                 (v[u].w - mean.w) * r.w * gc + bc);
-    if (ok) { dot.x += o.x * wc; dot.y += o.y * wc; dot.z += o.z * wc; dot.w += o.w * wc; }
+    const float4 o = q4_map([gc, bc](float xv, float m, float rr) { return (xv - m) * rr * gc + bc; }, v[u], mean, r);
+    if (ok) dot = q4_madd(dot, o, q4_splat(wc));
     __syncthreads();  // (the previous chunk's readers are done)
     tile[4 * pl + 0][grp] = o.x;
     tile[4 * pl + 1][grp] = o.y;
     tile[4 * pl + 2][grp] = o.z;
     tile[4 * pl + 3][grp] = o.w;
     __syncthreads();
-    if (n0 + orow < N) *reinterpret_cast<float4*>(xn + (n0 + orow) * Cc + u * LV_GROUPS + ocol) = *reinterpret_cast<const float4*>(&tile[orow][ocol]);
+    if (n0 + orow < N) q4_store(xn + (n0 + orow) * Cc + u * LV_GROUPS + ocol, q4_load(&tile[orow][ocol]));
   }
-  const float4 z = lv_position_sum(dot, part, pl, wave);
+  const float4 z = lv_position_sum(dot, part);  // (the chunk loop's barriers lie between this and the last reader of part)
   if (ok && grp == 0) {
     const float bb = b0[0];
-    *reinterpret_cast<float4*>(score + n) = make_float4(1.f / (1.f + expf(-(z.x + bb))), 1.f / (1.f + expf(-(z.y + bb))), 1.f / (1.f + expf(-(z.z + bb))),
-                                                        1.f / (1.f + expf(-(z.w + bb))));
+    q4_store(score + n, q4_map([bb](float zz) { return 1.f / (1.f + expf(-(zz + bb))); }, z));
   }
 }
 
@@ -1103,25 +1003,18 @@ __global__ __launch_bounds__(LV_THREADS) void head_ln_fc_bwd_v4_kernel(const flo
                                                                        const float* __restrict__ rstd_in, const float* __restrict__ score,
                                                                        float* __restrict__ dx, float* __restrict__ partial, long long N) {
   constexpr int Cc = CPT * LV_GROUPS;
-  __shared__ float part[LV_THREADS / 64][LV_POS];
+  __shared__ float part[1][LV_WAVES][LV_POS];
   __shared__ __attribute__((aligned(16))) float tile[LV_POS][HV_PAD];
-  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL, wave = threadIdx.x >> 6;
+  const int pl = threadIdx.x % LV_PL, grp = threadIdx.x / LV_PL;
   const long long n0 = blockIdx.x * (long long)LV_POS, n = n0 + 4 * pl;
   const bool ok = n < N;
-  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 mean = zero4, r = zero4, dl = zero4, xh[CPT], dy[CPT];
-#pragma unroll
-  for (int u = 0; u < CPT; ++u) xh[u] = dy[u] = zero4;
+  const float4 zero4 = q4_splat(0.f);
+  float4 mean = zero4, r = zero4, dl = zero4, xh[CPT] = {}, dy[CPT];
   if (ok) {
-    mean = *reinterpret_cast<const float4*>(mean_in + n);
-    r = *reinterpret_cast<const float4*>(rstd_in + n);
-    if (dscore != nullptr) {
-      const float4 sg = *reinterpret_cast<const float4*>(score + n), ds = *reinterpret_cast<const float4*>(dscore + n);
-      dl = make_float4(ds.x * sg.x * (1.f - sg.x), ds.y * sg.y * (1.f - sg.y), ds.z * sg.z * (1.f - sg.z), ds.w * sg.w * (1.f - sg.w));
-    }
-    const float* xp = x + (long long)grp * N + n;
-#pragma unroll
-    for (int u = 0; u < CPT; ++u) xh[u] = *reinterpret_cast<const float4*>(xp + (long long)u * LV_GROUPS * N);
+    mean = q4_load(mean_in + n);
+    r = q4_load(rstd_in + n);
+    if (dscore != nullptr) dl = q4_map([](float ds, float sg) { return ds * sg * (1.f - sg); }, q4_load(dscore + n), q4_load(score + n));
+    lv_load(x, grp, N, n, xh);
   }
   float* prow = partial + (long long)blockIdx.x * (3 * Cc + 1);
   const int irow = threadIdx.x / 16, icol = (threadIdx.x % 16) * 4;  // this thread's 16-byte piece of the 32 x 64 tile on the way in
@@ -1134,51 +1027,47 @@ __global__ __launch_bounds__(LV_THREADS) void head_ln_fc_bwd_v4_kernel(const flo
     if (dxn != nullptr) {  // d_xn (N, C) -> the lane's (channel, four positions) through the tile
       __syncthreads();
       float4 piece = zero4;
-      if (n0 + irow < N) piece = *reinterpret_cast<const float4*>(dxn + (n0 + irow) * Cc + u * LV_GROUPS + icol);
-      *reinterpret_cast<float4*>(&tile[irow][icol]) = piece;
+      if (n0 + irow < N) piece = q4_load(dxn + (n0 + irow) * Cc + u * LV_GROUPS + icol);
+      q4_store(&tile[irow][icol], piece);
       __syncthreads();
       din = make_float4(tile[4 * pl + 0][grp], tile[4 * pl + 1][grp], tile[4 * pl + 2][grp], tile[4 * pl + 3][grp]);
     }
     float4 h = zero4, d = zero4, cw4 = zero4;
     if (ok) {
-      h = make_float4((xh[u].x - mean.x) * r.x, (xh[u].y - mean.y) * r.y, (xh[u].z - mean.z) * r.z, (xh[u].w - mean.w) * r.w);
-      d = make_float4(din.x + dl.x * wc, din.y + dl.y * wc, din.z + dl.z * wc, din.w + dl.w * wc);
-      cw4 = make_float4(dl.x * (h.x * gc + bc), dl.y * (h.y * gc + bc), dl.z * (h.z * gc + bc), dl.w * (h.w * gc + bc));
+      h = q4_map([](float xv, float m, float rr) { return (xv - m) * rr; }, xh[u], mean, r);
+      d = q4_madd(din, dl, q4_splat(wc));
+      cw4 = q4_map([gc, bc](float l, float hh) { return l * (hh * gc + bc); }, dl, h);
     }
     xh[u] = h;
     dy[u] = d;
-    s1.x += d.x * gc; s1.y += d.y * gc; s1.z += d.z * gc; s1.w += d.w * gc;
-    s2.x += d.x * gc * h.x; s2.y += d.y * gc * h.y; s2.z += d.z * gc * h.z; s2.w += d.w * gc * h.w;
-    float a = ((d.x * h.x + d.y * h.y) + d.z * h.z) + d.w * h.w, bs = ((d.x + d.y) + d.z) + d.w, cw = ((cw4.x + cw4.y) + cw4.z) + cw4.w;
-#pragma unroll
-    for (int off = LV_PL / 2; off > 0; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      bs += __shfl_xor(bs, off, 64);
-      cw += __shfl_xor(cw, off, 64);
-    }
+    const float4 dg = q4_scale(d, gc);
+    s1 = q4_add(s1, dg);
+    s2 = q4_madd(s2, dg, h);
+    float cs[3] = {q4_sum_seq(q4_mul(d, h)), q4_sum_seq(d), q4_sum_seq(cw4)};
+    lane_group_sums<LV_PL>(cs);
     if (pl == 0) {
-      prow[c] = a;
-      prow[Cc + c] = bs;
-      prow[2 * Cc + c] = cw;
+      prow[c] = cs[0];
+      prow[Cc + c] = cs[1];
+      prow[2 * Cc + c] = cs[2];
     }
   }
   if (grp == 0) {  // db0: the block's sum of dlogit
-    float t = ((dl.x + dl.y) + dl.z) + dl.w;
-#pragma unroll
-    for (int off = LV_PL / 2; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (pl == 0) prow[3 * Cc] = t;
+    float t[1] = {q4_sum_seq(dl)};
+    lane_group_sums<LV_PL>(t);
+    if (pl == 0) prow[3 * Cc] = t[0];
   }
-  const float4 t1 = lv_position_sum(s1, part, pl, wave), t2 = lv_position_sum(s2, part, pl, wave);
+  const float4 t1 = lv_position_sum(s1, part);
+  __syncthreads();
+  const float4 t2 = lv_position_sum(s2, part);
   if (!ok) return;
   const float inv = 1.f / (float)Cc;
-  const float4 m1 = make_float4(t1.x * inv, t1.y * inv, t1.z * inv, t1.w * inv), m2 = make_float4(t2.x * inv, t2.y * inv, t2.z * inv, t2.w * inv);
+  const float4 m1 = q4_scale(t1, inv), m2 = q4_scale(t2, inv);
   float* dxp = dx + (long long)grp * N + n;
 #pragma unroll
   for (int u = 0; u < CPT; ++u) {
     const float gc = g[grp + u * LV_GROUPS];
-    *reinterpret_cast<float4*>(dxp + (long long)u * LV_GROUPS * N) =
-        make_float4(r.x * (dy[u].x * gc - m1.x - xh[u].x * m2.x), r.y * (dy[u].y * gc - m1.y - xh[u].y * m2.y),
-                    r.z * (dy[u].z * gc - m1.z - xh[u].z * m2.z), r.w * (dy[u].w * gc - m1.w - xh[u].w * m2.w));
+    q4_store(dxp + (long long)u * LV_GROUPS * N,
+             q4_map([gc](float rr, float dd, float a1, float hh, float a2) { return rr * (dd * gc - a1 - hh * a2); }, r, dy[u], m1, xh[u], m2));
   }
 }
 
@@ -1299,13 +1188,16 @@ __global__ __launch_bounds__(256) void glance_attn_bwd_kernel(const float* __res
 }
 
 // ---- GlanceAttention core for ANY T (dim_head = 64): the validation pass scores a whole video, T = n_clips
-// (/root/reference/src/runner.py:42-50 feeds modeling_mgfn.py:107-123 with T = 50..500+).  One workgroup per (32-query tile,
+// (the reference's src/runner.py:42-50 feeds modeling_mgfn.py:107-123 with T = 50..500+).  One workgroup per (32-query tile,
 // sequence, head); key / value tiles of 32 clips run through LDS with an online softmax (running row maximum m, running sum l,
 // the accumulator rescaled by exp(m_old - m_new) per tile): T x T never exists in memory.  lse[i] = m + log(l) (nullable) is
 // what the backward pass needs instead of the T x T softmax.  Same thread -> element maps as the T = 32 kernel above.
 constexpr float GA_NEG = -3.0e38f;  // "minus infinity" that stays finite under subtraction
 
-__device__ __forceinline__ void ga_load_tile(float (*dst)[GA_T + 1], const float* __restrict__ src, long long row0, long long N, long long col0,
+// dst[d][t] = src[row0 + d][col0 + t_base + t] for the GA_D rows of a head and a tile of GA_T clips, 0 from clip T on; P = the
+// LDS row pitch
+template <int P>
+__device__ __forceinline__ void ga_load_tile(float (*dst)[P], const float* __restrict__ src, long long row0, long long N, long long col0,
                                              int t_base, int T, int tid) {
   for (int e = tid; e < GA_D * GA_T; e += 256) {
     const int d = e / GA_T, t = e % GA_T, tt = t_base + t;
@@ -1313,16 +1205,19 @@ __device__ __forceinline__ void ga_load_tile(float (*dst)[GA_T + 1], const float
   }
 }
 
+// out[row0 + d][col0 + t] = 0 for the GA_D rows of a head and the clips t of a TILE-wide query tile at t_base that lie below T:
+// what a LENS workgroup whose tile starts behind its sequence's length stores before it leaves
+template <int TILE>
+__device__ __forceinline__ void ga_zero_tile(float* __restrict__ out, long long row0, long long N, long long col0, int t_base, int T, int tid) {
+  for (int e = tid; e < GA_D * TILE; e += 256) {
+    const int d = e / TILE, t = t_base + e % TILE;
+    if (t < T) out[(row0 + d) * N + col0 + t] = 0.f;
+  }
+}
+
 // (LDS images with 16-byte aligned rows, pitch GA_P: the inner loops read k and the transposed softmax tile as float4 -- a third
 // of the LDS instructions of the one-dword form, which is what a workgroup's ~10 sequential key tiles at T = 290 spend their time on)
 constexpr int GA_P = GA_T + 4;
-__device__ __forceinline__ void ga_load_tile_p(float (*dst)[GA_P], const float* __restrict__ src, long long row0, long long N, long long col0,
-                                               int t_base, int T, int tid) {
-  for (int e = tid; e < GA_D * GA_T; e += 256) {
-    const int d = e / GA_T, t = e % GA_T, tt = t_base + t;
-    dst[d][t] = tt < T ? src[(row0 + d) * N + col0 + tt] : 0.f;
-  }
-}
 
 // LENS (padded batches of sequences of unequal length, inference): sequence b still starts at column b * T but holds only
 // L = row_lens[b] (clamped to T) clips -- L takes T's place in the key loop and in every mask, so nothing behind L is read, a
@@ -1339,13 +1234,10 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
   const long long col0 = (long long)b * T, row0 = (long long)h * GA_D;
   const int L = LENS ? min(row_lens[b], T) : T;
   if (LENS && i_base >= L) {  // (the same for the whole workgroup: nobody waits at a barrier)
-    for (int e = tid; e < GA_D * GA_T; e += 256) {
-      const int d = e / GA_T, t = i_base + e % GA_T;
-      if (t < T) out[(row0 + d) * N + col0 + t] = 0.f;
-    }
+    ga_zero_tile<GA_T>(out, row0, N, col0, i_base, T, tid);
     return;
   }
-  ga_load_tile_p(q, qkv, row0, N, col0, i_base, L, tid);
+  ga_load_tile(q, qkv, row0, N, col0, i_base, L, tid);
   const int i = tid >> 3, j0 = (tid & 7) * 4;   // sim: row i, columns j0 .. j0 + 3
   const int d2 = tid >> 2, i0 = (tid & 3) * 8;  // out: channel d2, queries i0 .. i0 + 7
   float m = GA_NEG, l = 0.f, o[8];
@@ -1353,14 +1245,13 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
   for (int jb = 0; jb < L; jb += GA_T) {
     __syncthreads();  // (the previous tile's readers of k, v, pT, alpha_s are done; first pass: q is complete)
-    ga_load_tile_p(k, qkv, inner + row0, N, col0, jb, L, tid);
-    ga_load_tile_p(v, qkv, 2ll * inner + row0, N, col0, jb, L, tid);
+    ga_load_tile(k, qkv, inner + row0, N, col0, jb, L, tid);
+    ga_load_tile(v, qkv, 2ll * inner + row0, N, col0, jb, L, tid);
     __syncthreads();
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     for (int d = 0; d < GA_D; ++d) {
       const float qi = q[d][i];
-      const float4 kv = *reinterpret_cast<const float4*>(&k[d][j0]);
-      s[0] += qi * kv.x; s[1] += qi * kv.y; s[2] += qi * kv.z; s[3] += qi * kv.w;
+      q4_axpy(s, qi, q4_load(&k[d][j0]));
     }
     float mx = GA_NEG;
 #pragma unroll
@@ -1389,9 +1280,8 @@ __global__ __launch_bounds__(256) void glance_attn_fwd_anyt_kernel(const float* 
     for (int e = 0; e < 8; ++e) o[e] *= alpha_s[i0 + e];
     for (int j = 0; j < GA_T; ++j) {
       const float vj = v[d2][j];
-      const float4 p0 = *reinterpret_cast<const float4*>(&pT[j][i0]), p1 = *reinterpret_cast<const float4*>(&pT[j][i0 + 4]);
-      o[0] += vj * p0.x; o[1] += vj * p0.y; o[2] += vj * p0.z; o[3] += vj * p0.w;
-      o[4] += vj * p1.x; o[5] += vj * p1.y; o[6] += vj * p1.z; o[7] += vj * p1.w;
+      q4_axpy(o, vj, q4_load(&pT[j][i0]));
+      q4_axpy(o + 4, vj, q4_load(&pT[j][i0 + 4]));
     }
   }
   if ((tid & 7) == 0) {
@@ -1435,10 +1325,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   const float* __restrict__ vp = qkv + (2ll * inner + row0) * N + col0;
   const int L = LENS ? min(row_lens[b], T) : T;
   if (LENS && (int)(blockIdx.x * GM_Q) >= L) {  // (the same for the whole workgroup: nobody waits at a barrier)
-    for (int e = tid; e < GA_D * GM_Q; e += 256) {
-      const int d = e / GM_Q, t = blockIdx.x * GM_Q + e % GM_Q;
-      if (t < T) out[(row0 + d) * N + col0 + t] = 0.f;
-    }
+    ga_zero_tile<GM_Q>(out, row0, N, col0, blockIdx.x * GM_Q, T, tid);
     return;
   }
   const int qi = blockIdx.x * GM_Q + wave * 16 + li;  // this lane's query (a column of every fragment)
@@ -1877,47 +1764,53 @@ extern "C" int advhip_bn_rows_bwd_add_f32(const float* dy, const float* x, const
 
 extern "C" int advhip_chan_stats_f32(const float* x, float* mu, float* rs, int32_t C, int64_t N, float eps, void* stream) {
   ADVHIP_REQUIRE(x && mu && rs && C > 0 && N > 0, "chan_stats: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "chan_stats: too many positions");
-  hipLaunchKernelGGL(chan_stats_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, x, mu, rs, C, (long long)N, eps);
+  dim3 grid;
+  if (int rc = ln_grid("chan_stats", N, &grid)) return rc;
+  hipLaunchKernelGGL(chan_stats_kernel, grid, dim3(LN_THREADS), 0, (hipStream_t)stream, x, mu, rs, C, (long long)N, eps);
   return check_launch("chan_stats");
 }
 
 extern "C" int advhip_chan_layernorm_fwd_f32(const float* x, const float* g, const float* b, float* y, float* mu, float* rs,
                                              int32_t C, int64_t N, float eps, void* stream) {
   ADVHIP_REQUIRE(x && g && b && y && mu && rs && C > 0 && N > 0, "chan_layernorm_fwd: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "chan_layernorm_fwd: too many positions");
-  if (!launch_ln_fwd_v4(x, g, b, y, mu, rs, C, (long long)N, eps, (hipStream_t)stream))
-    hipLaunchKernelGGL(chan_layernorm_fwd_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, x, g, b, y, mu, rs, C,
-                       (long long)N, eps);
+  dim3 grid;
+  if (int rc = ln_grid("chan_layernorm_fwd", N, &grid)) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const int form = ln_form(C, (long long)N, (((uintptr_t)x | (uintptr_t)y | (uintptr_t)mu | (uintptr_t)rs) & 15) == 0);
+  if (!ln_dispatch_quad(form, [&](auto cpt) {
+        hipLaunchKernelGGL(chan_layernorm_fwd_v4_kernel<CVAL(cpt)>, grid, dim3(LV_THREADS), 0, st, x, g, b, y, mu, rs, (long long)N, eps);
+      }))
+    hipLaunchKernelGGL(chan_layernorm_fwd_kernel, grid, dim3(LN_THREADS), 0, st, x, g, b, y, mu, rs, C, (long long)N, eps);
   return check_launch("chan_layernorm_fwd");
 }
 
-extern "C" int64_t advhip_chan_layernorm_bwd_partial_rows(int64_t N) { return (N + LN_COLS - 1) / LN_COLS; }
+extern "C" int64_t advhip_chan_layernorm_bwd_partial_rows(int64_t N) { return ln_blocks(N); }
+
+// pg / pb: the partial-sum matrices of dg / db, rows `prow` floats apart; `add` (nullable): the skip connection's gradient
+static int launch_ln_bwd(const char* who, const float* dy, const float* x, const float* g, const float* mu, const float* rs, float* dx, float* pg,
+                         float* pb, int C, long long N, float eps, const float* add, long long prow, hipStream_t st) {
+  dim3 grid;
+  if (int rc = ln_grid(who, N, &grid)) return rc;
+  const int form = ln_form(C, N, (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx | (uintptr_t)mu | (uintptr_t)rs | (uintptr_t)add) & 15) == 0);
+  if (!ln_dispatch_quad(form, [&](auto cpt) {
+        hipLaunchKernelGGL(chan_layernorm_bwd_v4_kernel<CVAL(cpt)>, grid, dim3(LV_THREADS), 0, st, dy, x, g, mu, rs, dx, pg, pb, N, eps, add, prow);
+      }))
+    hipLaunchKernelGGL(chan_layernorm_bwd_kernel, grid, dim3(LN_THREADS), 0, st, dy, x, g, mu, rs, dx, pg, pb, C, N, eps, add, prow);
+  return check_launch(who);
+}
 
 extern "C" int advhip_chan_layernorm_bwd_f32(const float* dy, const float* x, const float* g, const float* mu, const float* rs,
                                              float* dx, float* dg_partial, float* db_partial, int32_t C, int64_t N, float eps,
                                              void* stream) {
   ADVHIP_REQUIRE(dy && x && g && mu && rs && dx && dg_partial && db_partial && C > 0 && N > 0, "chan_layernorm_bwd: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "chan_layernorm_bwd: too many positions");
-  if (!launch_ln_bwd_v4(dy, x, g, mu, rs, dx, dg_partial, db_partial, C, (long long)N, eps, nullptr, (long long)C, (hipStream_t)stream))
-    hipLaunchKernelGGL(chan_layernorm_bwd_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, dy, x, g, mu, rs, dx,
-                       dg_partial, db_partial, C, (long long)N, eps, (const float*)nullptr, (long long)C);
-  return check_launch("chan_layernorm_bwd");
+  return launch_ln_bwd("chan_layernorm_bwd", dy, x, g, mu, rs, dx, dg_partial, db_partial, C, (long long)N, eps, nullptr, (long long)C, (hipStream_t)stream);
 }
 
 extern "C" int advhip_chan_layernorm_bwd_add_f32(const float* dy, const float* x, const float* g, const float* mu, const float* rs,
                                                  const float* add, float* dx, float* dgb_partial, int32_t C, int64_t N, float eps,
                                                  void* stream) {
   ADVHIP_REQUIRE(dy && x && g && mu && rs && dx && dgb_partial && C > 0 && N > 0, "chan_layernorm_bwd_add: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "chan_layernorm_bwd_add: too many positions");
-  if (!launch_ln_bwd_v4(dy, x, g, mu, rs, dx, dgb_partial, dgb_partial + C, C, (long long)N, eps, add, 2ll * C, (hipStream_t)stream))
-    hipLaunchKernelGGL(chan_layernorm_bwd_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, dy, x, g, mu, rs, dx,
-                       dgb_partial, dgb_partial + C, C, (long long)N, eps, add, 2ll * C);
-  return check_launch("chan_layernorm_bwd_add");
+  return launch_ln_bwd("chan_layernorm_bwd_add", dy, x, g, mu, rs, dx, dgb_partial, dgb_partial + C, C, (long long)N, eps, add, 2ll * C, (hipStream_t)stream);
 }
 
 extern "C" int advhip_unfold3_f32(const float* x, float* u, int32_t C, int64_t rows, int32_t T, void* stream) {
@@ -1929,33 +1822,40 @@ extern "C" int advhip_unfold3_f32(const float* x, float* u, int32_t C, int64_t r
   return check_launch("unfold3");
 }
 
+// f(K) for an instantiated filter length, else the error of every dwconv_t entry point
+template <class F>
+static int dwconv_t_dispatch(int K, F&& f) {
+  const bool launched = dispatch_int<3, 5>(K, f);
+  ADVHIP_REQUIRE(launched, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
+  return ADVHIP_OK;
+}
+
+// forward, with row lengths (LENS: the scalar kernel alone) or without
+template <bool LENS>
+static int launch_dwconv_t_fwd(const char* who, const float* v, const float* w, const float* bias, float* out, int C, int H, long long rows, int T, int K,
+                               const int* row_lens, hipStream_t st) {
+  const long long total = (long long)C * rows * T;
+  const bool quad = !LENS && dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)out) & 15) == 0) == 1;
+  const dim3 grid((unsigned)std::min<long long>(((quad ? total / 4 : total) + 255) / 256, 256 * 32));
+  if (int rc = dwconv_t_dispatch(K, [&](auto k) {
+        if (quad) hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<CVAL(k)>, grid, dim3(256), 0, st, v, w, bias, out, H, T, rows, total / 4);
+        else hipLaunchKernelGGL((dwconv_t_fwd_kernel<CVAL(k), LENS>), grid, dim3(256), 0, st, v, w, bias, out, H, T, rows, total, row_lens);
+      }))
+    return rc;
+  return check_launch(who);
+}
+
 extern "C" int advhip_dwconv_t_fwd_f32(const float* v, const float* w, const float* bias, float* out, int32_t C, int32_t H,
                                        int64_t rows, int32_t T, int32_t K, void* stream) {
   ADVHIP_REQUIRE(v && w && bias && out && C > 0 && H > 0 && rows > 0 && T > 0 && C % H == 0, "dwconv_t_fwd: bad arguments");
-  ADVHIP_REQUIRE(K == 5 || K == 3, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
-  const long long total = (long long)C * rows * T;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
-  if (dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)out) & 15) == 0) == 1) {
-    const int grid4 = (int)std::min<long long>((total / 4 + 255) / 256, 256 * 32);
-    if (K == 5) hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<5>, dim3(grid4), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total / 4);
-    else hipLaunchKernelGGL(dwconv_t_fwd_v4_kernel<3>, dim3(grid4), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total / 4);
-    return check_launch("dwconv_t_fwd");
-  }
-  if (K == 5) hipLaunchKernelGGL((dwconv_t_fwd_kernel<5, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)nullptr);
-  else hipLaunchKernelGGL((dwconv_t_fwd_kernel<3, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)nullptr);
-  return check_launch("dwconv_t_fwd");
+  return launch_dwconv_t_fwd<false>("dwconv_t_fwd", v, w, bias, out, C, H, (long long)rows, T, K, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int advhip_dwconv_t_fwd_lens_f32(const float* v, const float* w, const float* bias, float* out, int32_t C, int32_t H,
                                             int64_t rows, int32_t T, int32_t K, const int32_t* row_lens_per_row, int64_t n_rows, void* stream) {
   ADVHIP_REQUIRE(v && w && bias && out && row_lens_per_row && C > 0 && H > 0 && rows > 0 && T > 0 && C % H == 0, "dwconv_t_fwd_lens: bad arguments");
   ADVHIP_REQUIRE(n_rows == rows, "dwconv_t_fwd_lens: %lld lengths for %lld rows", (long long)n_rows, (long long)rows);
-  ADVHIP_REQUIRE(K == 5 || K == 3, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
-  const long long total = (long long)C * rows * T;
-  const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
-  if (K == 5) hipLaunchKernelGGL((dwconv_t_fwd_kernel<5, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)row_lens_per_row);
-  else hipLaunchKernelGGL((dwconv_t_fwd_kernel<3, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, v, w, bias, out, H, T, (long long)rows, total, (const int*)row_lens_per_row);
-  return check_launch("dwconv_t_fwd_lens");
+  return launch_dwconv_t_fwd<true>("dwconv_t_fwd_lens", v, w, bias, out, C, H, (long long)rows, T, K, (const int*)row_lens_per_row, (hipStream_t)stream);
 }
 
 extern "C" int32_t advhip_dwconv_t_bwd_chunks(int32_t C, int64_t rows) {
@@ -1968,17 +1868,15 @@ extern "C" int32_t advhip_dwconv_t_bwd_chunks(int32_t C, int64_t rows) {
 extern "C" int advhip_dwconv_t_bwd_f32(const float* dout, const float* v, const float* w, float* dv, float* partial, int32_t C,
                                        int32_t H, int64_t rows, int32_t T, int32_t K, void* stream) {
   ADVHIP_REQUIRE(dout && v && w && dv && partial && C > 0 && H > 0 && rows > 0 && T > 0 && C % H == 0, "dwconv_t_bwd: bad arguments");
-  ADVHIP_REQUIRE(K == 5 || K == 3, "dwconv_t: kernel size %d (3 and 5 are instantiated)", K);
   const int chunks = advhip_dwconv_t_bwd_chunks(C, rows);
   const long long per_c = (long long)rows * T;
   const dim3 grid((unsigned)((long long)C * chunks));
-  if (dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)dout | (uintptr_t)dv) & 15) == 0) == 1) {
-    if (K == 5) hipLaunchKernelGGL(dwconv_t_bwd_v4_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
-    else hipLaunchKernelGGL(dwconv_t_bwd_v4_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
-    return check_launch("dwconv_t_bwd");
-  }
-  if (K == 5) hipLaunchKernelGGL(dwconv_t_bwd_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
-  else hipLaunchKernelGGL(dwconv_t_bwd_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
+  const bool quad = dwconv_t_form(T, (((uintptr_t)v | (uintptr_t)dout | (uintptr_t)dv) & 15) == 0) == 1;
+  if (int rc = dwconv_t_dispatch(K, [&](auto k) {
+        if (quad) hipLaunchKernelGGL(dwconv_t_bwd_v4_kernel<CVAL(k)>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
+        else hipLaunchKernelGGL(dwconv_t_bwd_kernel<CVAL(k)>, grid, dim3(256), 0, (hipStream_t)stream, dout, v, w, dv, partial, H, T, per_c, chunks);
+      }))
+    return rc;
   return check_launch("dwconv_t_bwd");
 }
 
@@ -2002,46 +1900,38 @@ extern "C" int advhip_glance_attention_bwd_f32(const float* dout, const float* q
   return check_launch("glance_attention_bwd");
 }
 
+// The any-T forward, with per-sequence lengths (LENS) or without.  `who` names the entry point in its errors.
 constexpr int GLANCE_MFMA_MIN_T = 256;
-extern "C" int advhip_glance_attention_fwd_anyt_f32(const float* qkv, float* out, float* lse, int32_t heads, int64_t B, int32_t T, int32_t dim_head,
-                                                    float scale, void* stream) {
-  ADVHIP_REQUIRE(qkv && out && heads > 0 && B > 0 && T > 0, "glance_attention_fwd_anyt: bad arguments");
-  ADVHIP_REQUIRE(dim_head == GA_D, "glance_attention_anyt: dim_head = %d (the kernel is built for %d)", dim_head, GA_D);
-  ADVHIP_REQUIRE(B * heads < (1ll << 31), "glance_attention_anyt: too many (sequence, head) pairs");
+template <bool LENS>
+static int launch_glance_fwd(const char* who, const float* qkv, float* out, float* lse, const int* row_lens, int heads, long long B, int T, int dim_head,
+                             float scale, hipStream_t st) {
+  ADVHIP_REQUIRE(dim_head == GA_D, "%s: dim_head = %d (the kernel is built for %d)", who, dim_head, GA_D);
+  ADVHIP_REQUIRE(B * heads < (1ll << 31), "%s: too many (sequence, head) pairs", who);
   // the matrix-pipe form from GLANCE_MFMA_MIN_T clips on (below it a pass is a few dozen workgroups of a handful of key tiles: the
-  // 32-query tiles of the vector kernel give the chip more of them).  A compile-time constant: the library reads no environment
-  // (the A/B of profiles/r06_studies.md section 4 was a study build)
+  // 32-query tiles of the vector kernel give the chip more of them); with LENS per launch, from the padded length.  A compile-time
+  // constant: the library reads no environment (the A/B of profiles/r06_studies.md section 4 was a study build)
   const bool mfma = T >= GLANCE_MFMA_MIN_T;
   const unsigned tiles = mfma ? (unsigned)((T + GM_Q - 1) / GM_Q) : (unsigned)((T + GA_T - 1) / GA_T);
   for (long long bh0 = 0; bh0 < B * heads; bh0 += 32768) {  // (grid.y is 16 bits wide)
     const unsigned ny = (unsigned)std::min<long long>(32768, B * heads - bh0);
     if (mfma)
-      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel<false>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
-                         (long long)B * T, scale, (int)bh0, (const int*)nullptr);
+      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel<LENS>, dim3(tiles, ny), dim3(256), 0, st, qkv, out, lse, heads * GA_D, heads, T, B * T, scale, (int)bh0, row_lens);
     else
-      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel<false>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, lse, heads * GA_D, heads, T,
-                         (long long)B * T, scale, (int)bh0, (const int*)nullptr);
+      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel<LENS>, dim3(tiles, ny), dim3(256), 0, st, qkv, out, lse, heads * GA_D, heads, T, B * T, scale, (int)bh0, row_lens);
   }
-  return check_launch("glance_attention_fwd_anyt");
+  return check_launch(who);
+}
+
+extern "C" int advhip_glance_attention_fwd_anyt_f32(const float* qkv, float* out, float* lse, int32_t heads, int64_t B, int32_t T, int32_t dim_head,
+                                                    float scale, void* stream) {
+  ADVHIP_REQUIRE(qkv && out && heads > 0 && B > 0 && T > 0, "glance_attention_fwd_anyt: bad arguments");
+  return launch_glance_fwd<false>("glance_attention_fwd_anyt", qkv, out, lse, nullptr, heads, (long long)B, T, dim_head, scale, (hipStream_t)stream);
 }
 
 extern "C" int advhip_glance_attention_fwd_lens_f32(const float* qkv, float* out, const int32_t* row_lens, int32_t heads, int64_t B, int32_t T,
                                                     int32_t dim_head, float scale, void* stream) {
   ADVHIP_REQUIRE(qkv && out && row_lens && heads > 0 && B > 0 && T > 0, "glance_attention_fwd_lens: bad arguments");
-  ADVHIP_REQUIRE(dim_head == GA_D, "glance_attention_lens: dim_head = %d (the kernel is built for %d)", dim_head, GA_D);
-  ADVHIP_REQUIRE(B * heads < (1ll << 31), "glance_attention_lens: too many (sequence, head) pairs");
-  const bool mfma = T >= GLANCE_MFMA_MIN_T;  // (per launch, from the padded length: the rule of advhip_glance_attention_fwd_anyt_f32)
-  const unsigned tiles = mfma ? (unsigned)((T + GM_Q - 1) / GM_Q) : (unsigned)((T + GA_T - 1) / GA_T);
-  for (long long bh0 = 0; bh0 < B * heads; bh0 += 32768) {
-    const unsigned ny = (unsigned)std::min<long long>(32768, B * heads - bh0);
-    if (mfma)
-      hipLaunchKernelGGL(glance_attn_fwd_mfma_kernel<true>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, (float*)nullptr, heads * GA_D, heads,
-                         T, (long long)B * T, scale, (int)bh0, (const int*)row_lens);
-    else
-      hipLaunchKernelGGL(glance_attn_fwd_anyt_kernel<true>, dim3(tiles, ny), dim3(256), 0, (hipStream_t)stream, qkv, out, (float*)nullptr, heads * GA_D, heads,
-                         T, (long long)B * T, scale, (int)bh0, (const int*)row_lens);
-  }
-  return check_launch("glance_attention_fwd_lens");
+  return launch_glance_fwd<true>("glance_attention_fwd_lens", qkv, out, nullptr, (const int*)row_lens, heads, (long long)B, T, dim_head, scale, (hipStream_t)stream);
 }
 
 extern "C" int advhip_glance_attention_bwd_anyt_f32(const float* dout, const float* qkv, const float* out, const float* lse, float* dqkv, int32_t heads,
@@ -2065,19 +1955,19 @@ extern "C" int advhip_fold_affine_f32(const float* W, const float* mul, const fl
   return check_launch("fold_affine");
 }
 
-extern "C" int64_t advhip_head_ln_fc_partial_rows(int64_t N) { return (N + LN_COLS - 1) / LN_COLS; }
+extern "C" int64_t advhip_head_ln_fc_partial_rows(int64_t N) { return ln_blocks(N); }
 
 extern "C" int advhip_head_ln_fc_fwd_f32(const float* y, const float* ln_g, const float* ln_b, const float* fc_w, const float* fc_b, float* xn,
                                          float* mean, float* rstd, float* score, int32_t C, int64_t N, float eps, void* stream) {
   ADVHIP_REQUIRE(y && ln_g && ln_b && fc_w && fc_b && xn && mean && rstd && score && C > 0 && N > 0, "head_ln_fc_fwd: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "head_ln_fc_fwd: too many positions");
+  dim3 grid;
+  if (int rc = ln_grid("head_ln_fc_fwd", N, &grid)) return rc;
   const bool v4 = head_form(C, (long long)N, (((uintptr_t)y | (uintptr_t)xn | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)score) & 15) == 0) == 1;
   if (v4)
-    hipLaunchKernelGGL(head_ln_fc_fwd_v4_kernel<16>, dim3((unsigned)blocks), dim3(LV_THREADS), 0, (hipStream_t)stream, y, ln_g, ln_b, fc_w, fc_b, xn, mean,
+    hipLaunchKernelGGL(head_ln_fc_fwd_v4_kernel<16>, grid, dim3(LV_THREADS), 0, (hipStream_t)stream, y, ln_g, ln_b, fc_w, fc_b, xn, mean,
                        rstd, score, (long long)N, eps);
   else
-    hipLaunchKernelGGL(head_ln_fc_fwd_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, y, ln_g, ln_b, fc_w, fc_b, xn, mean, rstd,
+    hipLaunchKernelGGL(head_ln_fc_fwd_kernel, grid, dim3(LN_THREADS), 0, (hipStream_t)stream, y, ln_g, ln_b, fc_w, fc_b, xn, mean, rstd,
                        score, C, (long long)N, eps);
   return check_launch("head_ln_fc_fwd");
 }
@@ -2086,15 +1976,15 @@ extern "C" int advhip_head_ln_fc_bwd_f32(const float* d_xn, const float* d_score
                                          const float* fc_w, const float* mean, const float* rstd, const float* score, float* dy, float* partial,
                                          int32_t C, int64_t N, void* stream) {
   ADVHIP_REQUIRE(y && ln_g && ln_b && fc_w && mean && rstd && score && dy && partial && C > 0 && N > 0, "head_ln_fc_bwd: bad arguments");
-  const long long blocks = (N + LN_COLS - 1) / LN_COLS;
-  ADVHIP_REQUIRE(blocks < (1ll << 31), "head_ln_fc_bwd: too many positions");
+  dim3 grid;
+  if (int rc = ln_grid("head_ln_fc_bwd", N, &grid)) return rc;
   const bool v4 = head_form(C, (long long)N, (((uintptr_t)y | (uintptr_t)d_xn | (uintptr_t)d_score | (uintptr_t)mean | (uintptr_t)rstd |
                                                 (uintptr_t)score | (uintptr_t)dy) & 15) == 0) == 1;
   if (v4)
-    hipLaunchKernelGGL(head_ln_fc_bwd_v4_kernel<16>, dim3((unsigned)blocks), dim3(LV_THREADS), 0, (hipStream_t)stream, d_xn, d_score, y, ln_g, ln_b, fc_w,
+    hipLaunchKernelGGL(head_ln_fc_bwd_v4_kernel<16>, grid, dim3(LV_THREADS), 0, (hipStream_t)stream, d_xn, d_score, y, ln_g, ln_b, fc_w,
                        mean, rstd, score, dy, partial, (long long)N);
   else
-    hipLaunchKernelGGL(head_ln_fc_bwd_kernel, dim3((unsigned)blocks), dim3(LN_THREADS), 0, (hipStream_t)stream, d_xn, d_score, y, ln_g, ln_b, fc_w, mean,
+    hipLaunchKernelGGL(head_ln_fc_bwd_kernel, grid, dim3(LN_THREADS), 0, (hipStream_t)stream, d_xn, d_score, y, ln_g, ln_b, fc_w, mean,
                        rstd, score, dy, partial, C, (long long)N);
   return check_launch("head_ln_fc_bwd");
 }
@@ -2136,219 +2026,6 @@ extern "C" int advhip_colsum_group_f32(const advhip_colsum_item* items, int32_t 
     if (int rc = check_launch("colsum_group")) return rc;
   }
   return ADVHIP_OK;
-}
-
-// ---- Adam with L2-in-gradient weight decay over many parameter tensors in one launch (torch.optim.Adam's update rule,
-// /root/reference/src/runner.py:53-59; torch/optim/adam.py) -------------------------------------------------------------------
-//   g' = g + wd * p;  m = m + (1 - b1) (g' - m);  v = b2 v + (1 - b2) g'^2;  p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-// t = *step (a device-side counter the caller has already incremented for this step; fp32 as torch's capturable Adam keeps it).
-// The item table travels in the kernel arguments (a launch inside a captured HIP graph replays it as is); a workgroup finds its
-// item by a scalar scan and updates ADAM_PER_BLOCK consecutive elements of it, 16 bytes per lane and access.
-constexpr int ADAM_MAX_ITEMS = 80, ADAM_PER_BLOCK = 4096;
-struct AdamItem {
-  float* p;
-  const float* g;
-  float* m;
-  float* v;
-  const float* step;
-  int n;
-  int block_begin;
-};
-struct AdamArgs {
-  AdamItem it[ADAM_MAX_ITEMS];
-  int n;
-  double lr, b1, b2;  // (doubles: 1 - beta and lr / (1 - beta^t) are formed in double and rounded once, as torch does in Python)
-  float eps, wd;
-};
-// The update of one workgroup's ADAM_PER_BLOCK elements, shared by the by-value launch and the device-scalar one.  SCALED: every
-// gradient element is first multiplied by `scale` as ONE separately rounded fp32 product (torch's in-place `g.mul_(coef)`;
-// __fmul_rn is never contracted into the weight-decay FMA behind it); what follows is the same instruction sequence either way.
-template <bool SCALED>
-__device__ __forceinline__ void adam_update_block(const AdamArgs& aa, const double lr, const float scale) {
-  int i = 0;
-  while (i + 1 < aa.n && (int)blockIdx.x >= aa.it[i + 1].block_begin) ++i;
-  const AdamItem& t = aa.it[i];
-  const int base = ((int)blockIdx.x - t.block_begin) * ADAM_PER_BLOCK;
-  const double st = (double)*t.step;
-  const float step_size = (float)(lr / (1.0 - pow(aa.b1, st)));
-  const float bc2_sqrt = (float)sqrt(1.0 - pow(aa.b2, st));
-  const float omb1 = (float)(1.0 - aa.b1), b2 = (float)aa.b2, omb2 = (float)(1.0 - aa.b2), eps = aa.eps, wd = aa.wd;
-  auto upd = [&](float& p, float g, float& m, float& v) {
-    if constexpr (SCALED) g = __fmul_rn(g, scale);
-    g = g + wd * p;
-    m = m + omb1 * (g - m);
-    v = b2 * v + omb2 * g * g;
-    p = p - step_size * m / (sqrtf(v) / bc2_sqrt + eps);
-  };
-  const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0);
-#pragma unroll
-  for (int u = 0; u < ADAM_PER_BLOCK / 1024; ++u) {
-    const int e = base + u * 1024 + (int)threadIdx.x * 4;
-    if (e >= t.n) break;
-    if (vec && e + 4 <= t.n) {
-      float4 p = *reinterpret_cast<const float4*>(t.p + e), m = *reinterpret_cast<const float4*>(t.m + e), v = *reinterpret_cast<const float4*>(t.v + e);
-      const float4 g = *reinterpret_cast<const float4*>(t.g + e);
-      upd(p.x, g.x, m.x, v.x); upd(p.y, g.y, m.y, v.y); upd(p.z, g.z, m.z, v.z); upd(p.w, g.w, m.w, v.w);
-      *reinterpret_cast<float4*>(t.p + e) = p;
-      *reinterpret_cast<float4*>(t.m + e) = m;
-      *reinterpret_cast<float4*>(t.v + e) = v;
-    } else {
-      for (int k = e; k < e + 4 && k < t.n; ++k) {
-        float p = t.p[k], m = t.m[k], v = t.v[k];
-        upd(p, t.g[k], m, v);
-        t.p[k] = p; t.m[k] = m; t.v[k] = v;
-      }
-    }
-  }
-}
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamArgs aa) { adam_update_block<false>(aa, aa.lr, 1.0f); }
-// lr (a double: lr / (1 - b1^t) is still formed in double and rounded once) and the gradient scale are read from device memory, so
-// a captured launch sees the values of the replay, not of the capture.  Both loads are uniform: one scalar load per workgroup.
-__global__ __launch_bounds__(256) void adam_multi_dev_kernel(const AdamArgs aa, const double* __restrict__ lr_dev, const float* __restrict__ scale_dev) {
-  const double lr = *lr_dev;
-  if (scale_dev) adam_update_block<true>(aa, lr, *scale_dev);
-  else adam_update_block<false>(aa, lr, 1.0f);
-}
-
-static int adam_multi_launch(const char* what, const advhip_adam_item* items, int32_t n_items, double lr, const double* lr_dev, const float* scale_dev,
-                             double beta1, double beta2, double eps, double weight_decay, void* stream) {
-  ADVHIP_REQUIRE(items && n_items > 0, "%s: bad arguments", what);
-  ADVHIP_REQUIRE(lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. && weight_decay >= 0.,
-                 "%s: bad hyper-parameters (lr %g, betas %g %g, eps %g, weight_decay %g)", what, lr, beta1, beta2, eps, weight_decay);
-  for (int base = 0; base < n_items; base += ADAM_MAX_ITEMS) {
-    AdamArgs aa;
-    aa.n = std::min(ADAM_MAX_ITEMS, n_items - base);
-    aa.lr = lr; aa.b1 = beta1; aa.b2 = beta2; aa.eps = (float)eps; aa.wd = (float)weight_decay;
-    long long blocks = 0;
-    for (int i = 0; i < aa.n; ++i) {
-      const advhip_adam_item& s = items[base + i];
-      ADVHIP_REQUIRE(s.param && s.grad && s.exp_avg && s.exp_avg_sq && s.step && s.n > 0 && s.n < (1ll << 31), "%s: item %d: bad arguments", what, base + i);
-      aa.it[i] = AdamItem{s.param, s.grad, s.exp_avg, s.exp_avg_sq, s.step, (int)s.n, (int)blocks};
-      blocks += (s.n + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK;
-      ADVHIP_REQUIRE(blocks < (1ll << 31), "%s: too many elements", what);
-    }
-    for (int i = aa.n; i < ADAM_MAX_ITEMS; ++i) aa.it[i] = AdamItem{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0x7FFFFFFF};
-    if (lr_dev) hipLaunchKernelGGL(adam_multi_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, aa, lr_dev, scale_dev);
-    else hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, aa);
-    if (int rc = check_launch(what)) return rc;
-  }
-  return ADVHIP_OK;
-}
-
-extern "C" int advhip_adam_multi_f32(const advhip_adam_item* items, int32_t n_items, double lr, double beta1, double beta2, double eps,
-                                     double weight_decay, void* stream) {
-  return adam_multi_launch("adam_multi", items, n_items, lr, nullptr, nullptr, beta1, beta2, eps, weight_decay, stream);
-}
-
-extern "C" int advhip_adam_multi_dev_f32(const advhip_adam_item* items, int32_t n_items, const double* lr_dev, const float* grad_scale_dev, double beta1,
-                                         double beta2, double eps, double weight_decay, void* stream) {
-  ADVHIP_REQUIRE(lr_dev, "adam_multi_dev: lr_dev is null");
-  return adam_multi_launch("adam_multi_dev", items, n_items, 0., lr_dev, grad_scale_dev, beta1, beta2, eps, weight_decay, stream);
-}
-
-// ---- global L2 norm of many gradient tensors and the clip factor (torch.nn.utils.clip_grad_norm_), for advhip_adam_multi_dev_f32 ----
-// Stage 1: one workgroup per NORM_PER_BLOCK consecutive elements of one tensor (found by the scalar scan Adam uses, in two strides): every lane adds
-// the squares of its elements, formed in double, in index order; the 64 lanes of a wave are added by a shuffle tree, the four waves in
-// wave order; the sum goes to partials[first + blockIdx.x].  Stage 2: ONE workgroup adds the partials -- lane l takes l, l + 256, ...
-// in that order, then the same tree -- and writes the norm and the factor.  Every order is fixed and no atomic is used: same bits
-// every run.
-constexpr int NORM_MAX_ITEMS = 240, NORM_PER_BLOCK = 4096;
-struct NormItem {
-  const float* g;
-  int n;
-  int block_begin;
-};
-struct NormArgs {
-  NormItem it[NORM_MAX_ITEMS];
-  int n;
-  double* partials;  // (this launch's first slot)
-};
-__device__ __forceinline__ double block_sum_256(double s, double* lds4) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];  // (read by every lane; lane 0's copy is the one stored)
-}
-__global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(const NormArgs na) {
-  __shared__ double lds4[4];
-  // the scalar scan of the Adam launch in two strides (16 items, then 1): every step is a dependent scalar load, and a table of 240
-  // items scanned one by one costs the late workgroups more than their 16 KiB of gradient
-  int i = 0;
-  while (i + 16 < na.n && (int)blockIdx.x >= na.it[i + 16].block_begin) i += 16;
-  while (i + 1 < na.n && (int)blockIdx.x >= na.it[i + 1].block_begin) ++i;
-  const NormItem& t = na.it[i];
-  const int base = ((int)blockIdx.x - t.block_begin) * NORM_PER_BLOCK;
-  const bool vec = (((uintptr_t)t.g & 15) == 0);
-  double s = 0.0;
-  auto add4 = [&](const float4 g) {
-    s += (double)g.x * (double)g.x; s += (double)g.y * (double)g.y; s += (double)g.z * (double)g.z; s += (double)g.w * (double)g.w;
-  };
-  if (vec && base + NORM_PER_BLOCK <= t.n) {
-    // a whole block of an aligned tensor: the four loads are issued together, the sum keeps the order of the general path below
-    const float4* g4 = reinterpret_cast<const float4*>(t.g + base) + threadIdx.x;
-    const float4 g0 = g4[0], g1 = g4[256], g2 = g4[512], g3 = g4[768];
-    add4(g0); add4(g1); add4(g2); add4(g3);
-  } else {
-#pragma unroll
-    for (int u = 0; u < NORM_PER_BLOCK / 1024; ++u) {
-      const int e = base + u * 1024 + (int)threadIdx.x * 4;
-      if (e < t.n) {
-        if (vec && e + 4 <= t.n) {
-          add4(*reinterpret_cast<const float4*>(t.g + e));
-        } else {
-          for (int k = e; k < e + 4 && k < t.n; ++k) s += (double)t.g[k] * (double)t.g[k];
-        }
-      }
-    }
-  }
-  s = block_sum_256(s, lds4);
-  if (threadIdx.x == 0) na.partials[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, long long n, float max_norm, float* __restrict__ norm_out,
-                                                               float* __restrict__ scale_out) {
-  __shared__ double lds4[4];
-  double s = 0.0;
-  for (long long k = threadIdx.x; k < n; k += 256) s += partials[k];
-  s = block_sum_256(s, lds4);
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(s);
-    // torch: clamp(max_norm / (norm + 1e-6), max=1.0) on an fp32 tensor; `number / tensor` is tensor.reciprocal() * number there
-    const float coef = __fmul_rn(__fdiv_rn(1.0f, __fadd_rn(norm, 1e-6f)), max_norm);
-    *norm_out = norm;
-    *scale_out = coef > 1.0f ? 1.0f : coef;  // (a NaN fails the comparison and stays, as under torch.clamp)
-  }
-}
-
-extern "C" int advhip_grad_norm_multi_f32(const advhip_norm_item* items, int32_t n_items, double max_norm, double* partials, int64_t n_partials,
-                                          float* norm_out, float* scale_out, void* stream) {
-  ADVHIP_REQUIRE(items && n_items > 0 && partials && norm_out && scale_out, "grad_norm_multi: bad arguments");
-  ADVHIP_REQUIRE(max_norm > 0. && std::isfinite(max_norm), "grad_norm_multi: max_norm %g is not a finite number > 0", max_norm);
-  long long total = 0;  // (every item is checked, and the partials' room, before the first launch)
-  for (int i = 0; i < n_items; ++i) {
-    ADVHIP_REQUIRE(items[i].grad && items[i].n > 0 && items[i].n < (1ll << 31), "grad_norm_multi: item %d: bad arguments", i);
-    total += (items[i].n + NORM_PER_BLOCK - 1) / NORM_PER_BLOCK;
-  }
-  ADVHIP_REQUIRE(total <= n_partials, "grad_norm_multi: %lld partial sums needed, room for %lld", total, (long long)n_partials);
-  long long first = 0;
-  for (int base = 0; base < n_items; base += NORM_MAX_ITEMS) {
-    NormArgs na;
-    na.n = std::min(NORM_MAX_ITEMS, n_items - base);
-    na.partials = partials + first;
-    long long blocks = 0;
-    for (int i = 0; i < na.n; ++i) {
-      const advhip_norm_item& s = items[base + i];
-      na.it[i] = NormItem{s.grad, (int)s.n, (int)blocks};
-      blocks += (s.n + NORM_PER_BLOCK - 1) / NORM_PER_BLOCK;
-      ADVHIP_REQUIRE(blocks < (1ll << 31), "grad_norm_multi: too many elements");
-    }
-    for (int i = na.n; i < NORM_MAX_ITEMS; ++i) na.it[i] = NormItem{nullptr, 0, 0x7FFFFFFF};
-    hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, na);
-    if (int rc = check_launch("grad_norm_multi")) return rc;
-    first += blocks;
-  }
-  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, total, (float)max_norm, norm_out, scale_out);
-  return check_launch("grad_norm_finish");
 }
 
 extern "C" int advhip_amp_combine_fwd_f32(const float* z, const float* bias, const float* mag, int64_t mag_stride, const float* wm, const float* bm,
