@@ -274,12 +274,18 @@ SIGNATURES = {
     "advhip_ring_push_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "advhip_ring_windows_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "advhip_crop_mean_last_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    # live events: (scores, cam_ids, ring, samples, cand_int, cand_peak, cand_sum, alert, open_start, log_int, log_f, emitted, nb, n_cam, K,
+    # smooth, low, high, merge_gap, min_len, by_camera, mode, stream)
+    "advhip_live_events_update_f32": (C.c_int, [_P] * 12 + [_I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _I, _P]),
     # which kernel form a scorer launch takes: (C, N, aligned16) / (T, aligned16) -> form id (include/advhip.h); nothing is launched
     "advhip_bn_rows_form": (_I, [_I, _L, _I]),
     "advhip_chan_layernorm_form": (_I, [_I, _L, _I]),
     "advhip_head_ln_fc_form": (_I, [_I, _L, _I]),
     "advhip_dwconv_t_form": (_I, [_I, _I]),
 }
+
+# advhip_live_events_update_f32: the modes and the width of cand_int (ADVHIP_LIVE_EVENTS_* of include/advhip.h)
+LIVE_EVENTS_UPDATE, LIVE_EVENTS_FINISH, LIVE_EVENTS_RESET, LIVE_EVENTS_CAND_INTS = 0, 1, 2, 5
 
 # advhip_bn_rows_form's answers (ADVHIP_BN_ROWS_* of include/advhip.h)
 BN_ROWS_GENERIC, BN_ROWS_REG256X4, BN_ROWS_REG256X12, BN_ROWS_REG1024X4 = 0, 1, 2, 3

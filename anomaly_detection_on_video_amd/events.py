@@ -16,12 +16,14 @@ The rule (this package's definition; include/advhip.h restates it for the kernel
 from __future__ import annotations
 
 import math
+from collections import OrderedDict
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 MAX_SMOOTH = 1023
+LIVE_CACHE_ENTRIES = 64  # camera sets a LiveEventTracker keeps on the device (least recently used out first)
 
 
 @dataclass(frozen=True)
@@ -256,6 +258,169 @@ def _find_events_device(scores, offsets, offsets_host, spec: EventSpec, workspac
     y = mil_ops.smooth_scores(scores, offsets, spec.smooth, out=smoothed)
     return Events(*mil_ops.score_events(y, offsets, spec.low, spec.high, spec.merge_gap, spec.min_len, workspace=workspace,
                                         offsets_host=offsets_host))
+
+
+def live_emission_count(end: int, spec) -> int:
+    """The sample count at which a live camera emits the event that ends (exclusive) at `end`: end + merge_gap + h + 1 with
+    h = (smooth - 1) / 2.  The candidate closes at the first final y more than merge_gap behind its last active sample, position
+    end + merge_gap, and y[t] is final once sample t + h has been fed.  An event still open at `finish` is emitted there."""
+    spec = resolve_event_spec(spec)
+    if spec is None:
+        raise ValueError("live_emission_count: no event spec")
+    end = _integer("end", end)
+    if end < 1:
+        raise ValueError(f"events: end={end} below 1 (an event holds a sample)")
+    return end + spec.merge_gap + (spec.smooth - 1) // 2 + 1
+
+
+MAX_LIVE_SAMPLES = (1 << 31) - 1  # positions are int32: a camera is finished or reset before it has fed this many samples
+
+
+class LiveDrain(NamedTuple):
+    events: Events          # the events emitted since the previous drain, per camera and in emission order; video = the camera id
+    generation: object      # int32 (E,): the camera's generation when each event was emitted (finish and reset add one)
+    lost: np.ndarray        # int64 (n_cameras,): events of each camera overwritten in its log before they were drained
+
+
+class LiveEventTracker:
+    """The event rule, streaming, for `n_cameras` independent score series on the device (include/advhip.h: live events; one
+    launch of mil_ops.live_events_update per call).  The events a camera emits while it runs plus what `finish` closes are
+    `find_events_host`'s events of its whole series, and the event [s, e) is emitted by the update that brings the camera's sample
+    count to `live_emission_count(e, spec)`.  `log`: the events kept per camera between two drains.
+
+    `alert` (1 iff a candidate is open, strong and at least min_len long), `open_start` (its start, or -1), `emitted` and
+    `samples` are device tensors; `samples_host` is the host's mirror of the last.  Camera-id tensors are cached by tuple: a
+    repeated camera set uploads nothing.  CUDA only; no fallback."""
+
+    def __init__(self, spec, n_cameras: int, log: int = 64, device="cuda:0"):
+        import torch
+
+        from . import mil_ops
+        from ._lib import HipExtensionError
+
+        try:
+            self.spec = resolve_event_spec(spec)
+        except ValueError as e:
+            raise HipExtensionError(f"LiveEventTracker: {e}") from None
+        if self.spec is None:
+            raise HipExtensionError("LiveEventTracker: no event spec")
+        for name, v in (("n_cameras", n_cameras), ("log", log)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < 1 << 31:
+                raise HipExtensionError(f"LiveEventTracker: {name} = {v!r} is not an integer in [1, 2^31)")
+        self.n_cameras, self.log = int(n_cameras), int(log)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise HipExtensionError(f"LiveEventTracker: device '{self.device}': the state lives on the GPU (there is no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.state = mil_ops.live_events_state(self.n_cameras, self.spec.smooth, self.log, self.device)
+        self._host = [0] * self.n_cameras
+        self._drained = np.zeros(self.n_cameras, dtype=np.int64)
+        self._ids: "OrderedDict[tuple, object]" = OrderedDict()
+
+    alert = property(lambda self: self.state["alert"])
+    open_start = property(lambda self: self.state["open_start"])
+    emitted = property(lambda self: self.state["emitted"])
+    samples = property(lambda self: self.state["samples"])
+
+    @property
+    def samples_host(self) -> tuple:
+        """Samples fed per camera since its last finish / reset, kept by update / finish / reset: nothing is read back."""
+        return tuple(self._host)
+
+    def _cams(self, cams, what: str):
+        """-> (the checked tuple, its int32 device tensor)"""
+        import torch
+
+        from ._lib import HipExtensionError
+
+        if type(cams) is tuple and cams in self._ids and all(type(c) is int for c in cams):
+            self._ids.move_to_end(cams)
+            return cams, self._ids[cams]  # (a camera set seen before was checked then)
+        if torch.is_tensor(cams) or isinstance(cams, np.ndarray):
+            raise HipExtensionError(f"{what}: cams must be a sequence of host integers, got a {type(cams).__name__} (the ids are checked on the host)")
+        try:
+            cams = tuple(cams)
+        except TypeError:
+            raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
+        if not cams:
+            raise HipExtensionError(f"{what}: an empty list of cameras")
+        for c in cams:
+            if isinstance(c, bool) or torch.is_tensor(c) or not isinstance(c, (int, float, np.integer, np.floating)) or int(c) != c:
+                raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
+            if not 0 <= int(c) < self.n_cameras:
+                raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {self.n_cameras})")
+        cams = tuple(int(c) for c in cams)
+        if len(set(cams)) != len(cams):
+            dup = sorted(c for c in set(cams) if cams.count(c) > 1)
+            raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one sample per camera and call")
+        ids = self._ids[cams] = torch.tensor(cams, dtype=torch.int32).to(self.device)
+        if len(self._ids) > LIVE_CACHE_ENTRIES:
+            self._ids.popitem(last=False)
+        return cams, ids
+
+    def _launch(self, ids, scores, by_camera: bool, mode: int) -> None:
+        from . import mil_ops
+
+        s = self.spec
+        mil_ops.live_events_update(scores, ids, self.state, s.low, s.high, s.smooth, s.merge_gap, s.min_len, by_camera, mode)
+
+    def update(self, cams, scores, by_camera: bool = False) -> None:
+        """One new sample for each camera of `cams` (distinct host ints): scores fp32 on the device, (len(cams),) in `cams` order,
+        or with by_camera (n_cameras,) indexed by camera id (LiveScorer.latest as it is)."""
+        from ._lib import LIVE_EVENTS_UPDATE, HipExtensionError
+
+        cams, ids = self._cams(cams, "LiveEventTracker.update")
+        full = [c for c in cams if self._host[c] >= MAX_LIVE_SAMPLES]
+        if full:
+            raise HipExtensionError(f"LiveEventTracker.update: cameras {full} have fed 2^31 - 1 samples (positions are int32): finish or reset them")
+        self._launch(ids, scores, bool(by_camera), LIVE_EVENTS_UPDATE)
+        for c in cams:
+            self._host[c] += 1
+
+    def finish(self, cams) -> None:
+        """The listed cameras' series end here: their pending (smooth - 1) / 2 samples are finalised as at a video's end, an open
+        event is closed and emitted if it qualifies, then the cameras start over (samples 0, generation + 1)."""
+        from ._lib import LIVE_EVENTS_FINISH
+
+        self._clear(cams, "LiveEventTracker.finish", LIVE_EVENTS_FINISH)
+
+    def reset(self, cams) -> None:
+        """The listed cameras start over without emitting: samples 0, generation + 1, an open candidate is dropped."""
+        from ._lib import LIVE_EVENTS_RESET
+
+        self._clear(cams, "LiveEventTracker.reset", LIVE_EVENTS_RESET)
+
+    def _clear(self, cams, what: str, mode: int) -> None:
+        cams, ids = self._cams(cams, what)
+        self._launch(ids, None, False, mode)
+        for c in cams:
+            self._host[c] = 0
+
+    def drain(self) -> LiveDrain:
+        """The events emitted since the previous drain: ONE read-back (of `emitted`), then one gather of their log rows on the
+        device.  -> LiveDrain(events, generation, lost): `events` an Events of device tensors, camera by camera in emission
+        order, video = the camera id, counts int32 (n_cameras,); `generation` int32 (E,) on the device; `lost` int64
+        (n_cameras,) on the host: how many of a camera's events were overwritten in its log (more than `log` since the
+        previous drain) and are not among `events`."""
+        import torch
+
+        emitted = self.state["emitted"].cpu().numpy()
+        new = emitted - self._drained
+        lost = np.maximum(new - self.log, 0)
+        kept = (new - lost).astype(np.int64)
+        cam = np.repeat(np.arange(self.n_cameras, dtype=np.int64), kept)
+        first = np.repeat(emitted - kept, kept)                                    # the number of each camera's oldest kept event
+        within = np.arange(int(kept.sum()), dtype=np.int64) - np.repeat(np.cumsum(kept) - kept, kept)
+        rows = cam * self.log + (first + within) % self.log
+        self._drained = emitted.copy()
+        counts = torch.from_numpy(kept.astype(np.int32)).to(self.device)
+        idx = torch.from_numpy(np.stack([rows, cam])).to(self.device)
+        ev_int = self.state["log_int"].view(-1, 4).index_select(0, idx[0])
+        ev_f = self.state["log_f"].view(-1, 2).index_select(0, idx[0])
+        generation = ev_int[:, 0].clone()
+        ev_int[:, 0] = idx[1].to(torch.int32)
+        return LiveDrain(Events(ev_int, ev_f, counts), generation, lost)
 
 
 def video_events(window_scores, spec, frames_per_clip: int = 16, clip_stride: Optional[int] = None, frame_step: Optional[int] = None,

@@ -10,7 +10,14 @@ mil_ops.ring_push; `score` is mil_ops.ring_windows into one preallocated padded 
 (MGFNForVideoAnomalyDetection._score_padded_rows), mil_ops.crop_mean_scatter and mil_ops.crop_mean_last.  A host mirror of the
 counts supplies the lengths, and the device vectors of camera ids and lengths are cached by their tuples: once every listed
 camera has `window` clips and the calls repeat a camera set, a push + score uploads nothing, synchronises nothing and dispatches
-no torch arithmetic.  CUDA tensors only; no fallback."""
+no torch arithmetic.  CUDA tensors only; no fallback.
+
+    live = LiveScorer(scorer, n_cameras, events=EventSpec(low=0.5, high=0.8, smooth=9, merge_gap=2, min_len=4))
+    live.score(); live.events.alert; live.events.drain()
+
+With `events=` every score also feeds each listed camera's newest clip score to an events.LiveEventTracker (`live.events`: the
+streaming form of events.find_events' rule, one more small launch on `latest` as it is); the steady step still uploads nothing,
+synchronises nothing and dispatches no torch arithmetic."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -49,13 +56,25 @@ class _Lru:
 class LiveScorer:
     """`scorer`: an MGFNForVideoAnomalyDetection in eval mode on `device`.  `window`: the clips a camera's score looks back over
     (default 32, the T the scorer is trained at).  `max_rows`: the scorer's row limit (val_batch.DEFAULT_MAX_ROWS), which the
-    whole state -- n_cameras * ncrops * window rows, one pass when every camera is listed -- has to fit."""
+    whole state -- n_cameras * ncrops * window rows, one pass when every camera is listed -- has to fit.  `events`: None (nothing
+    is built or launched for events), or an event spec (events.resolve_event_spec) for `self.events`, an events.LiveEventTracker
+    with a log of `event_log` events per camera: `score` feeds it the newest clip score of every listed camera that has exactly
+    one clip more than the tracker has samples of it (a camera scored again without a push is not fed again; one that was pushed
+    twice between two scores is refused, its series would miss a sample)."""
 
     def __init__(self, scorer, n_cameras: int, window: int = 32, ncrops: int = 10, channels: int = 2048, device="cuda:0",
-                 max_rows: int = DEFAULT_MAX_ROWS):
+                 max_rows: int = DEFAULT_MAX_ROWS, events=None, event_log: int = 64):
         for name, v in (("n_cameras", n_cameras), ("window", window), ("ncrops", ncrops), ("channels", channels)):
             if isinstance(v, bool) or int(v) != v or int(v) < 1:
                 raise HipExtensionError(f"LiveScorer: {name} = {v!r} is not an integer >= 1 (window < 1 holds no clip)")
+        from .events import resolve_event_spec
+
+        try:
+            spec = resolve_event_spec(events)
+        except ValueError as e:
+            raise HipExtensionError(f"LiveScorer: {e}") from None
+        if spec is not None and (isinstance(event_log, bool) or not isinstance(event_log, int) or event_log < 1):
+            raise HipExtensionError(f"LiveScorer: event_log = {event_log!r} is not an integer >= 1")
         self.scorer = scorer
         self.n_cameras, self.window, self.ncrops, self.channels = int(n_cameras), int(window), int(ncrops), int(channels)
         if self.channels > mil_ops.ADD_MAGNITUDE_NP_MAX_C:
@@ -79,6 +98,11 @@ class LiveScorer:
         self._iota = torch.arange(self.n_cameras, dtype=torch.int32).to(self.device)
         self._ids = _Lru(lambda cams: torch.tensor(cams, dtype=torch.int32).to(self.device))  # keyed by checked tuples only
         self._lens = _Lru(self._make_lens)
+        self.events = None
+        if spec is not None:
+            from .events import LiveEventTracker
+
+            self.events = LiveEventTracker(spec, self.n_cameras, log=event_log, device=self.device)
 
     def _make_lens(self, key):
         from .models.mgfn.modeling_mgfn import PaddedLens
@@ -147,6 +171,14 @@ class LiveScorer:
             empty = [c for c in cams if self._host[c] == 0]
             if empty:
                 raise HipExtensionError(f"LiveScorer.score: cameras {empty} have no clip yet")
+        feed = None
+        if self.events is not None:  # which of the listed cameras have a new clip for the tracker: decided before anything is launched
+            fed = self.events._host
+            ahead = [c for c in cams if self._host[c] > fed[c] + 1]
+            if ahead:
+                raise HipExtensionError(f"LiveScorer.score: cameras {ahead} are more than one clip ahead of their event series (pushed twice, scored "
+                                        f"once): every clip's score is a sample; score after every push, or reset the cameras")
+            feed = tuple(c for c in cams if self._host[c] == fed[c] + 1)
         lens = tuple(min(self._host[c], self.window) for c in cams)
         nb, tmax = len(cams), max(lens)
         ids, pl = self._ids(cams), self._lens((lens, tmax))
@@ -156,6 +188,8 @@ class LiveScorer:
         scores = torch.zeros((nb, tmax), dtype=torch.float32, device=self.device)
         mil_ops.crop_mean_scatter(rows, pl.video_lens, pl.dense_offsets, scores, nb, self.ncrops)
         mil_ops.crop_mean_last(rows, pl.video_lens, ids, self.latest, self.ncrops)
+        if feed:
+            self.events.update(feed, self.latest, by_camera=True)
         if min(lens) == tmax:  # the newest clips are one column of the scores (the same sum, the same bits): a view of it
             latest = scores[:, tmax - 1]
         else:
@@ -163,8 +197,11 @@ class LiveScorer:
         return LiveScores(cams, lens, scores, latest)
 
     def reset(self, cams: Sequence[int]) -> None:
-        """The listed cameras start over: count 0, latest NaN (their rings' old clips can no longer be reached)."""
+        """The listed cameras start over: count 0, latest NaN (their rings' old clips can no longer be reached).  With `events`
+        their event series start over too, an open event is dropped: call `self.events.finish(cams)` first to keep it."""
         cams = self._check_cams(cams, "LiveScorer.reset")
+        if self.events is not None:
+            self.events.reset(cams)
         idx = self._ids(cams).long()
         self._counts[idx] = 0
         self.latest[idx] = float("nan")

@@ -312,6 +312,63 @@ def crop_mean_last(scores: torch.Tensor, lens: torch.Tensor, cam_ids: torch.Tens
     return latest
 
 
+LIVE_EVENTS_STATE = ("ring", "samples", "cand_int", "cand_peak", "cand_sum", "alert", "open_start", "log_int", "log_f", "emitted")
+
+
+def live_events_state(n_cam: int, smooth: int, log: int, device) -> dict:
+    """The per-camera state of `live_events_update` for n_cam cameras, a window of `smooth` samples and a log of `log` events per
+    camera, as include/advhip.h ("live events") lays it out: nothing fed, nothing open, generation 0."""
+    dev, z = torch.device(device), torch.zeros
+    cand_int = z((n_cam, _lib.LIVE_EVENTS_CAND_INTS), dtype=torch.int32)
+    cand_int[:, :3] = -1
+    return {"ring": z((n_cam, smooth), dtype=torch.float32, device=dev), "samples": z((n_cam,), dtype=torch.int64, device=dev),
+            "cand_int": cand_int.to(dev), "cand_peak": z((n_cam,), dtype=torch.float32, device=dev),
+            "cand_sum": z((n_cam, 2), dtype=torch.float64, device=dev), "alert": z((n_cam,), dtype=torch.int32, device=dev),
+            "open_start": torch.full((n_cam,), -1, dtype=torch.int32).to(dev), "log_int": z((n_cam, log, 4), dtype=torch.int32, device=dev),
+            "log_f": z((n_cam, log, 2), dtype=torch.float32, device=dev), "emitted": z((n_cam,), dtype=torch.int64, device=dev)}
+
+
+def live_events_update(scores: Optional[torch.Tensor], cam_ids: torch.Tensor, state: dict, low: float, high: float, smooth: int = 1,
+                       merge_gap: int = 0, min_len: int = 1, by_camera: bool = False, mode: int = _lib.LIVE_EVENTS_UPDATE) -> dict:
+    """One launch of the streaming event rule (include/advhip.h: live events) for the nb distinct cameras of cam_ids (int32 (nb,)
+    on the device).  `state`: the tensors of `live_events_state` (ring (n_cam, smooth) fp32, samples int64, cand_int int32
+    (n_cam, 5), cand_peak fp32, cand_sum float64 (n_cam, 2), alert and open_start int32, log_int int32 (n_cam, K, 4), log_f fp32
+    (n_cam, K, 2), emitted int64), written in place for the listed cameras only.  mode LIVE_EVENTS_UPDATE feeds one sample each:
+    scores[cam_ids[v]] of an fp32 (n_cam,) tensor with by_camera (LiveScorer.latest as it is), else scores[v] of an fp32 (nb,)
+    one.  LIVE_EVENTS_FINISH / LIVE_EVENTS_RESET take scores = None.  The ids' values are the caller's (nothing is read back):
+    an id outside [0, n_cam) writes nothing, the same id twice is an error this wrapper cannot see.  No autograd."""
+    what, err = "live_events_update", _lib.HipExtensionError
+    if not isinstance(state, dict) or sorted(state) != sorted(LIVE_EVENTS_STATE):
+        raise err(f"{what}: state must be a dict of the tensors {list(LIVE_EVENTS_STATE)} (mil_ops.live_events_state)")
+    ring = _live_arg(state["ring"], torch.float32, (None, None), what, "ring")
+    n_cam, dev = ring.shape[0], ring.device
+    if isinstance(smooth, bool) or int(smooth) != smooth or int(smooth) != ring.shape[1]:
+        raise err(f"{what}: ring must be (n_cam, smooth = {smooth!r}), got {tuple(ring.shape)}")
+    log_int = _live_arg(state["log_int"], torch.int32, (n_cam, None, 4), what, "log_int", dev)
+    K = log_int.shape[1]
+    rest = [_live_arg(state[name], dtype, shape, what, name, dev) for name, dtype, shape in (
+        ("samples", torch.int64, (n_cam,)), ("cand_int", torch.int32, (n_cam, _lib.LIVE_EVENTS_CAND_INTS)), ("cand_peak", torch.float32, (n_cam,)),
+        ("cand_sum", torch.float64, (n_cam, 2)), ("alert", torch.int32, (n_cam,)), ("open_start", torch.int32, (n_cam,)))]
+    log_f = _live_arg(state["log_f"], torch.float32, (n_cam, K, 2), what, "log_f", dev)
+    emitted = _live_arg(state["emitted"], torch.int64, (n_cam,), what, "emitted", dev)
+    cam_ids = _live_arg(cam_ids, torch.int32, (None,), what, "cam_ids", dev)
+    nb = cam_ids.shape[0]
+    if mode not in (_lib.LIVE_EVENTS_UPDATE, _lib.LIVE_EVENTS_FINISH, _lib.LIVE_EVENTS_RESET):
+        raise err(f"{what}: mode {mode!r} is not LIVE_EVENTS_UPDATE, LIVE_EVENTS_FINISH or LIVE_EVENTS_RESET")
+    if mode == _lib.LIVE_EVENTS_UPDATE:
+        scores = _live_arg(scores, torch.float32, (n_cam if by_camera else nb,), what, "scores", dev)
+    elif scores is not None:
+        raise err(f"{what}: finish and reset feed no sample: scores must be None")
+    for name, v, lo in (("merge_gap", merge_gap, 0), ("min_len", min_len, 1)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) < 1 << 31:
+            raise err(f"{what}: {name} {v!r} is not an integer in [{lo}, 2^31)")
+    require_gpu(ring)  # (the current device)
+    check(_lib.load().advhip_live_events_update_f32(ptr(scores), ptr(cam_ids), ptr(ring), *(ptr(t) for t in rest), ptr(log_int), ptr(log_f), ptr(emitted),
+                                                    nb, n_cam, K, int(smooth), float(low), float(high), int(merge_gap), int(min_len),
+                                                    1 if by_camera else 0, int(mode), stream()), what)
+    return state
+
+
 def _gather_side(store, idx, labels, dst_labels, what: str):
     """Checks of one store of `gather_batch` -> (n, R, b)."""
     err = _lib.HipExtensionError

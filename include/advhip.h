@@ -1057,6 +1057,53 @@ int advhip_score_events(const float* smoothed, const int64_t* offsets, int64_t V
                         int32_t min_len, int32_t* ev_int, float* ev_f, int64_t cap, int32_t* counts, int64_t* meta, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* --- live events: the rule above, streaming, with state per camera ----------------------------------------------------------
+ * A camera's series x[0 .. n) holds one sample per call that lists it (a clip score of live scoring: advhip_crop_mean_last_f32's
+ * `latest`).  With h = (smooth - 1) / 2, y[t] is final once sample t + h has been fed, and is step 1's y[t] of any longer series
+ * (the window [max(0, t - h), t + h], fp32 ascending from +0.0f, one division); every update finalises at most one y.  Over the
+ * final y in order: an active sample (y >= low) opens a candidate or extends the open one; an inactive sample at t closes it when
+ * t - last_active > merge_gap; a NaN is neither active nor strong.  In an open candidate: strong = any y >= high; peak = the
+ * largest y of an active sample and peak_frame its first position; a float64 running sum of every final y since start (gap
+ * samples included, ascending from 0.0) is copied at each active sample.  On close: end = last_active + 1, mean = (float)(copy /
+ * (double)(end - start)); a closed candidate that is strong with end - start >= min_len is an event, steps 4 and 5 of the rule.
+ * THE EMISSION RULE: the event [s, e) is written by the update that brings the camera's sample count to e + merge_gap + h + 1; a
+ * camera emits at most one event per update.  Emitted events plus what finish closes are the offline rule's events of the whole
+ * series: integers and peak bits equal, the mean the ascending float64 sum (within one fp32 ulp of advhip_score_events').
+ *
+ * State, all on the device, owned and zero-initialised by the caller except where stated:
+ *   ring        fp32  (n_cam, smooth)   the last `smooth` samples, sample k in slot k % smooth
+ *   samples     int64 (n_cam,)          samples fed since the last finish / reset (below 2^31: positions are int32)
+ *   cand_int    int32 (n_cam, 5)        {start (-1: no candidate is open; initialise to -1), last_active, peak_frame, strong,
+ *                                        generation}; the three fields in the middle are -1, -1, 0 while nothing is open
+ *   cand_peak   fp32  (n_cam,)          the open candidate's peak (0 while nothing is open)
+ *   cand_sum    fp64  (n_cam, 2)        {running sum, its copy at last_active} (0 while nothing is open)
+ *   alert       int32 (n_cam,)          1 iff a candidate is open, strong, and last_active + 1 - start >= min_len
+ *   open_start  int32 (n_cam,)          the open candidate's start, or -1 (initialise to -1)
+ *   log_int     int32 (n_cam, K, 4)     {generation, start, end, peak_frame}; event number j of a camera lies in slot j % K
+ *   log_f       fp32  (n_cam, K, 2)     {peak, mean}
+ *   emitted     int64 (n_cam,)          events written so far (never reset: the log keeps the last K)
+ * alert and open_start describe the final part of the curve: they trail the newest sample by h (smooth = 1: no delay).
+ *
+ * One launch for nb DISTINCT listed cameras (cam_ids int32 (nb,) on the device), one wavefront per camera (the ring row staged in
+ * LDS, one lane runs the ordered sum and the state machine): no atomics, no workgroup waits on another, the same bits in every
+ * run.  mode ADVHIP_LIVE_EVENTS_UPDATE: one new sample each, scores[cam_ids[v]] when by_camera is 1 (scores fp32 (n_cam,)), else
+ * scores[v] (scores fp32 (nb,)).  ADVHIP_LIVE_EVENTS_FINISH: the pending min(h, n) samples are finalised with windows clipped at
+ * n - 1 (a loop of at most h steps), the open candidate is closed and emitted if it qualifies, then the camera is cleared: samples
+ * 0, generation + 1, nothing open.  ADVHIP_LIVE_EVENTS_RESET: cleared the same way without finalising or emitting.  scores is
+ * not read by the last two (it may be null).  Only the listed cameras' state is written; an id outside [0, n_cam), or a camera
+ * whose samples lie outside [0, 2^31 - 1) (finish / reset: [0, 2^31 - 1]) or whose emitted is negative, writes nothing; every log
+ * index is bounded by K.  The same id twice in one call is the caller's error.
+ * Refused with ADVHIP_EINVAL before anything is launched: null pointers, an unknown mode, nb < 1, n_cam < 1, K < 1, an even smooth
+ * or one outside [1, 1023], merge_gap < 0, min_len < 1, a threshold that is not finite, low > high, by_camera not 0 or 1. */
+#define ADVHIP_LIVE_EVENTS_CAND_INTS 5
+#define ADVHIP_LIVE_EVENTS_UPDATE 0
+#define ADVHIP_LIVE_EVENTS_FINISH 1
+#define ADVHIP_LIVE_EVENTS_RESET 2
+int advhip_live_events_update_f32(const float* scores, const int32_t* cam_ids, float* ring, int64_t* samples, int32_t* cand_int,
+                                  float* cand_peak, double* cand_sum, int32_t* alert, int32_t* open_start, int32_t* log_int,
+                                  float* log_f, int64_t* emitted, int32_t nb, int32_t n_cam, int32_t K, int32_t smooth, float low,
+                                  float high, int32_t merge_gap, int32_t min_len, int32_t by_camera, int32_t mode, void* stream);
+
 /* --- which kernel form a scorer launch takes ---------------------------------------------------------------------------------
  * The normalisation and depth-wise entry points above each pick one of several kernels from the channel count, the row length
  * and the alignment of their operands.  These are those rules, as pure host functions that the launchers themselves call: the
