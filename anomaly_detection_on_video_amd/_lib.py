@@ -53,28 +53,19 @@ def is_tfold(algo: int) -> bool:
     return ALGO_TFOLD_BASE <= algo < ALGO_TFOLD_BASE + 16
 
 
+FAMILIES = ("generic", "fast", "dma3", "dma4", "bf16x3", "dma2", "tspan", "mixed", "persist")  # ADVHIP_FAMILY_* of include/advhip.h, by value
+
+
+def algo_info(algo: int):
+    """(family name, BM, BN, BK) of an implicit-GEMM algorithm id: advhip_conv3d_algo_info (a TFOLD id reports its folded DMA2 launch)."""
+    out = [C.c_int32() for _ in range(4)]
+    check(load().advhip_conv3d_algo_info(algo, *(C.byref(o) for o in out)), "conv3d_algo_info")
+    return (FAMILIES[out[0].value],) + tuple(o.value for o in out[1:])
+
+
 def algo_tile(algo: int):
-    """(BM, BN, BK) of an implicit-GEMM algorithm id."""
-    if is_tfold(algo):  # the folded launch is the 2-deep LDS-DMA kernel of the same tile id
-        algo += ALGO_DMA2_BASE - ALGO_TFOLD_BASE
-    if algo in (ALGO_TSPAN_128x64, ALGO_MIXED_128x64):
-        return (128, 64, 16)
-    if ALGO_PERSIST_BASE <= algo < ALGO_PERSIST_BASE + 32:
-        return (128 if (algo - ALGO_PERSIST_BASE) & 7 == 2 else 64, 64, 16)
-    if algo == ALGO_DMA2_BASE + ALGO_IGEMM_256x64:
-        return (256, 64, 16)
-    if algo >= ALGO_DMA2_BASE:
-        algo -= ALGO_DMA2_BASE
-    if algo >= ALGO_BF16X3_BASE:
-        algo -= ALGO_BF16X3_BASE
-    if algo >= ALGO_DMA4_BASE:
-        algo -= ALGO_DMA4_BASE
-    if algo >= ALGO_DMA_BASE:
-        algo -= ALGO_DMA_BASE
-    if algo >= ALGO_FAST_BASE:
-        algo -= ALGO_FAST_BASE
-    t = (algo - 1) & 3
-    return (128 if t in (0, 1) else 64, 128 if t in (0, 3) else 64, 32 if algo >= 5 else 16)
+    """(BM, BN, BK) of an implicit-GEMM algorithm id, as the library's own table has it (raises for an id without a kernel)."""
+    return algo_info(algo)[1:]
 
 
 class HipExtensionError(RuntimeError):
@@ -127,6 +118,7 @@ SIGNATURES = {
     "advhip_target_arch": (C.c_char_p, []),
     "advhip_conv3d_out_dims": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "advhip_conv3d_packed_rows": (C.c_int, [C.POINTER(ConvDesc)]),
+    "advhip_conv3d_algo_info": (C.c_int, [_I] + [C.POINTER(_I)] * 4),
     "advhip_conv3d_pack_weight_f32": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
     "advhip_conv3d_pack_weight_bf16x3": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P]),
     "advhip_conv3d_build_ktab": (C.c_int, [C.POINTER(ConvDesc), _P, _P]),

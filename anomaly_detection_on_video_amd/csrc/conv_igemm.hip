@@ -3038,46 +3038,158 @@ extern "C" int advhip_bn_fold_f32(const float* gamma, const float* beta, const f
 }
 
 namespace advhip {
-struct Choice {
-  int algo;    // ADVHIP_ALGO_IGEMM_*
-  int splits;  // >= 1
+// ---- the one table of algorithm ids -------------------------------------------------------------------------------------------
+// What an id means -- its family, its tile, how it splits K, which kernel it launches -- is stated in ALGO_TABLE below and nowhere
+// else: an id without a row has no kernel and is refused (algo_row() == nullptr), and a row cannot exist without a launch.
+enum AlgoFamily : int32_t {
+  FAM_GENERIC = ADVHIP_FAMILY_GENERIC, FAM_FAST = ADVHIP_FAMILY_FAST, FAM_DMA3 = ADVHIP_FAMILY_DMA3, FAM_DMA4 = ADVHIP_FAMILY_DMA4,
+  FAM_BF16X3 = ADVHIP_FAMILY_BF16X3, FAM_DMA2 = ADVHIP_FAMILY_DMA2, FAM_TSPAN = ADVHIP_FAMILY_TSPAN, FAM_MIXED = ADVHIP_FAMILY_MIXED,
+  FAM_PERSIST = ADVHIP_FAMILY_PERSIST
+};
+// nocheck: every tap of every output position lies inside the input (is_nocheck); s16: 16-byte gather pieces of a (kt,1,1) conv
+using AlgoLaunch = void (*)(const ConvArgs& a, dim3 grid, hipStream_t st, bool nocheck, bool s16);
+struct AlgoRow {
+  int id;
+  AlgoFamily family;
+  int BM, BN, BK;
+  bool reduces_in_kernel;  // split-K partials are reduced inside the launch (the LDS-DMA kernels), not by a second kernel
+  bool needs_fast_ok;      // 32-bit byte offsets and tap masks: fast_ok() must hold for the descriptor
+  bool pads_rows;          // eligible for the virtual row padding (padded_rows)
+  int wgs_per_cu;          // FAM_PERSIST: resident workgroups per compute unit (0 elsewhere)
+  AlgoLaunch launch;
 };
 
-// persistent family: id = ADVHIP_ALGO_PERSIST_BASE + tile (2: 128 x 64, 3: 64 x 64) + 8 * (workgroups per CU - 1)
-static bool is_persist(int algo) { return algo >= ADVHIP_ALGO_PERSIST_BASE && algo < ADVHIP_ALGO_PERSIST_BASE + 32; }
-static int persist_tile(int algo) { return (algo - ADVHIP_ALGO_PERSIST_BASE) & 7; }
-static int persist_wgs_per_cu(int algo) { return ((algo - ADVHIP_ALGO_PERSIST_BASE) >> 3) + 1; }
-
-static void tile_of(int algo, int* BM, int* BN, int* BK) {
-  if (algo == ADVHIP_ALGO_TSPAN_128x64 || algo == ADVHIP_ALGO_MIXED_128x64) { *BM = 128; *BN = 64; *BK = 16; return; }
-  if (is_persist(algo)) { *BM = persist_tile(algo) == ADVHIP_ALGO_IGEMM_128x64 ? 128 : 64; *BN = 64; *BK = 16; return; }
-  if (algo == ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_256x64) { *BM = 256; *BN = 64; *BK = 16; return; }
-  if (algo >= ADVHIP_ALGO_DMA2_BASE) algo -= ADVHIP_ALGO_DMA2_BASE;
-  if (algo >= ADVHIP_ALGO_BF16X3_BASE) algo -= ADVHIP_ALGO_BF16X3_BASE;
-  if (algo >= ADVHIP_ALGO_DMA4_BASE) algo -= ADVHIP_ALGO_DMA4_BASE;
-  if (algo >= ADVHIP_ALGO_DMA_BASE) algo -= ADVHIP_ALGO_DMA_BASE;
-  if (algo >= ADVHIP_ALGO_FAST_BASE) algo -= ADVHIP_ALGO_FAST_BASE;
-  const int t = (algo - 1) & 3;
-  *BM = (t == 0 || t == 1) ? 128 : 64;
-  *BN = (t == 0 || t == 3) ? 128 : 64;
-  *BK = algo >= ADVHIP_ALGO_IGEMM_128x128x32 ? 32 : 16;
+template <int BM, int BN, int BK>
+constexpr AlgoRow generic_row(int tile) {
+  return {tile, FAM_GENERIC, BM, BN, BK, false, false, false, 0, [](const ConvArgs& a, dim3 grid, hipStream_t st, bool, bool) {
+            hipLaunchKernelGGL((conv3d_igemm_f32_kernel<BM, BN, BK>), grid, dim3(256), 0, st, a);
+          }};
+}
+template <int BM, int BN, int BK>
+constexpr AlgoRow fast_row(int tile) {
+  return {ADVHIP_ALGO_FAST_BASE + tile, FAM_FAST, BM, BN, BK, false, true, false, 0, [](const ConvArgs& a, dim3 grid, hipStream_t st, bool nocheck, bool) {
+            if (nocheck) hipLaunchKernelGGL((conv3d_igemm_fast_kernel<BM, BN, BK, false>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((conv3d_igemm_fast_kernel<BM, BN, BK, true>), grid, dim3(256), 0, st, a);
+          }};
+}
+// the LDS-DMA kernel on a ring of NS = 3 or 4 stages
+template <int NS, int BM, int BN, int BK>
+constexpr AlgoRow dma_row(int tile) {
+  return {(NS == 3 ? ADVHIP_ALGO_DMA_BASE : ADVHIP_ALGO_DMA4_BASE) + tile, NS == 3 ? FAM_DMA3 : FAM_DMA4, BM, BN, BK, true, true, false, 0,
+          [](const ConvArgs& a, dim3 grid, hipStream_t st, bool nocheck, bool) {
+            if (nocheck) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM, BN, BK, false, NS>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM, BN, BK, true, NS>), grid, dim3(256), 0, st, a);
+          }};
+}
+template <int BN>
+constexpr AlgoRow bf16x3_row(int tile) {
+  return {ADVHIP_ALGO_BF16X3_BASE + tile, FAM_BF16X3, 128, BN, 32, false, true, false, 0, [](const ConvArgs& a, dim3 grid, hipStream_t st, bool nocheck, bool) {
+            if (nocheck) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<BN, false>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<BN, true>), grid, dim3(256), 0, st, a);
+          }};
 }
 
-// Which (family, tile) ids have a kernel in this library.  Ids inside a family's range without an instantiation
-// (e.g. DMA_BASE + 5) are rejected up front: a launch switch that fell through would return OK with y unwritten.
-static bool instantiated(int algo) {
-  if (algo == ADVHIP_ALGO_TSPAN_128x64 || algo == ADVHIP_ALGO_MIXED_128x64) return true;
-  if (algo >= ADVHIP_ALGO_PERSIST_BASE) return is_persist(algo) && (persist_tile(algo) == ADVHIP_ALGO_IGEMM_128x64 || persist_tile(algo) == ADVHIP_ALGO_IGEMM_64x64) && persist_wgs_per_cu(algo) <= 3;
-  auto tile_in = [](int t, unsigned mask) { return t >= 1 && t <= 8 && ((mask >> t) & 1u); };
-  constexpr unsigned ALL = 0x1FEu, NO5 = ALL & ~(1u << 5);
-  if (algo == ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_256x64) return true;
-  if (algo >= ADVHIP_ALGO_DMA2_BASE) return tile_in(algo - ADVHIP_ALGO_DMA2_BASE, NO5);
-  if (algo >= ADVHIP_ALGO_BF16X3_BASE) return tile_in(algo - ADVHIP_ALGO_BF16X3_BASE, (1u << 5) | (1u << 6));
-  if (algo >= ADVHIP_ALGO_DMA4_BASE) return tile_in(algo - ADVHIP_ALGO_DMA4_BASE, (1u << 2) | (1u << 3) | (1u << 4));
-  if (algo >= ADVHIP_ALGO_DMA_BASE) return tile_in(algo - ADVHIP_ALGO_DMA_BASE, NO5);
-  if (algo >= ADVHIP_ALGO_FAST_BASE) return tile_in(algo - ADVHIP_ALGO_FAST_BASE, ALL);
-  return tile_in(algo, ALL);
+// the 2-deep-ring LDS-DMA kernel of a tile: unchecked (1x1x1, no padding), 16-byte gather pieces ((kt,1,1) stride-1 convs on
+// planes of a multiple of 4 positions, 16-deep k-tiles), or the 4-byte gather
+// ADVHIP_EXTRA_LDS (study builds only, default 0): unused dynamic LDS per workgroup of the 2-deep-ring kernels -- fewer workgroups of
+// one launch per CU, so that launches of different lanes share a CU (profiles/r05_studies.md section 5)
+#ifndef ADVHIP_EXTRA_LDS
+#define ADVHIP_EXTRA_LDS 0
+#endif
+template <int BM_, int BN_, int BK_>
+static void launch_dma2(const ConvArgs& a, dim3 grid, hipStream_t st, bool nocheck, bool s16) {
+  constexpr unsigned XL = ADVHIP_EXTRA_LDS;
+  if (nocheck) {
+    if (a.a16) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false, 2, EPI_STD, false, 2>), grid, dim3(256), XL, st, a);
+    else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false, 2>), grid, dim3(256), XL, st, a);
+    return;
+  }
+  if constexpr (BK_ == 16) {
+    if (s16) {
+      hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true, 2, EPI_STD, false, 1>), grid, dim3(256), XL, st, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true, 2>), grid, dim3(256), XL, st, a);
 }
+template <int BM, int BN, int BK>
+constexpr AlgoRow dma2_row(int tile) {
+  return {ADVHIP_ALGO_DMA2_BASE + tile, FAM_DMA2, BM, BN, BK, true, true, true, 0, launch_dma2<BM, BN, BK>};
+}
+// persistent family: id = ADVHIP_ALGO_PERSIST_BASE + tile (2: 128 x 64, 3: 64 x 64) + 8 * (workgroups per CU - 1); `grid` is the
+// resident workgroups (launch_persist), eight waves each
+template <int BM>
+constexpr AlgoRow persist_row(int tile, int wgs_per_cu) {
+  return {ADVHIP_ALGO_PERSIST_BASE + tile + 8 * (wgs_per_cu - 1), FAM_PERSIST, BM, 64, 16, true, true, true, wgs_per_cu,
+          [](const ConvArgs& a, dim3 grid, hipStream_t st, bool, bool) {
+            hipLaunchKernelGGL((conv1x1_persist_kernel<BM, 64, 2>), grid, dim3(512), 0, st, a, GFX950_XCDS);
+          }};
+}
+
+// conv + global mean in one launch (advhip_conv3d_epilogue::avgpool_out; no id of its own): the 128 x 64 tile of the 2-deep ring
+// (a.a16 is always set here -- the rows are padded in the M index space -- so the compile-time a16 form applies)
+static int launch_avg(const ConvArgs& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_AVG, false, 2>), grid, dim3(256), 0, st, a);
+  return check_launch("conv3d + mean");
+}
+
+// One row per id that has a kernel.  (The order of the rows is the order in which the kernel templates are instantiated, and so
+// the order of the kernels in the code object.)  ADVHIP_ALGO_TFOLD_BASE ids are no rows: they redirect to the folded descriptor's
+// FAM_DMA2 id (is_tfold).  To add an id: one row here and one literal in _lib.py's *_ALGOS; tests/test_conv_algo_table.py says
+// which of the two was forgotten.
+constexpr AlgoRow ALGO_TABLE[] = {
+    // the plain launch of the mixed family (launch_mixed: nothing to cut) is the a16 form of FAM_DMA2's 128 x 64 kernel
+    {ADVHIP_ALGO_MIXED_128x64, FAM_MIXED, 128, 64, 16, true, true, true, 0, [](const ConvArgs& a, dim3 grid, hipStream_t st, bool, bool) {
+       hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_STD, false, 2>), grid, dim3(256), 0, st, a);
+     }},
+    persist_row<128>(ADVHIP_ALGO_IGEMM_128x64, 1), persist_row<64>(ADVHIP_ALGO_IGEMM_64x64, 1),
+    persist_row<128>(ADVHIP_ALGO_IGEMM_128x64, 2), persist_row<64>(ADVHIP_ALGO_IGEMM_64x64, 2),
+    persist_row<128>(ADVHIP_ALGO_IGEMM_128x64, 3), persist_row<64>(ADVHIP_ALGO_IGEMM_64x64, 3),
+    // m-tiles of 4 frames (T % 4 == 0) or 2 frames x flattened spatial positions (launch_tspan)
+    {ADVHIP_ALGO_TSPAN_128x64, FAM_TSPAN, 128, 64, 16, true, true, false, 0, [](const ConvArgs& a, dim3 grid, hipStream_t st, bool, bool) {
+       if (a.To % 4 == 0) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_TSPAN4, false, 1>), grid, dim3(256), 0, st, a);
+       else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_TSPAN2, false, 1>), grid, dim3(256), 0, st, a);
+     }},
+    dma2_row<128, 128, 16>(ADVHIP_ALGO_IGEMM_128x128), dma2_row<128, 64, 16>(ADVHIP_ALGO_IGEMM_128x64),
+    dma2_row<256, 64, 16>(ADVHIP_ALGO_IGEMM_256x64), dma2_row<64, 64, 16>(ADVHIP_ALGO_IGEMM_64x64),
+    dma2_row<64, 128, 16>(ADVHIP_ALGO_IGEMM_64x128), dma2_row<128, 64, 32>(ADVHIP_ALGO_IGEMM_128x64x32),
+    dma2_row<64, 64, 32>(ADVHIP_ALGO_IGEMM_64x64x32), dma2_row<64, 128, 32>(ADVHIP_ALGO_IGEMM_64x128x32),
+    bf16x3_row<128>(ADVHIP_ALGO_IGEMM_128x128x32), bf16x3_row<64>(ADVHIP_ALGO_IGEMM_128x64x32),
+    dma_row<4, 128, 64, 16>(ADVHIP_ALGO_IGEMM_128x64), dma_row<4, 64, 64, 16>(ADVHIP_ALGO_IGEMM_64x64),
+    dma_row<4, 64, 128, 16>(ADVHIP_ALGO_IGEMM_64x128),
+    dma_row<3, 128, 128, 16>(ADVHIP_ALGO_IGEMM_128x128), dma_row<3, 128, 64, 16>(ADVHIP_ALGO_IGEMM_128x64),
+    dma_row<3, 64, 64, 16>(ADVHIP_ALGO_IGEMM_64x64), dma_row<3, 64, 128, 16>(ADVHIP_ALGO_IGEMM_64x128),
+    dma_row<3, 128, 64, 32>(ADVHIP_ALGO_IGEMM_128x64x32), dma_row<3, 64, 64, 32>(ADVHIP_ALGO_IGEMM_64x64x32),
+    dma_row<3, 64, 128, 32>(ADVHIP_ALGO_IGEMM_64x128x32),
+    fast_row<128, 128, 16>(ADVHIP_ALGO_IGEMM_128x128), fast_row<128, 64, 16>(ADVHIP_ALGO_IGEMM_128x64),
+    fast_row<64, 64, 16>(ADVHIP_ALGO_IGEMM_64x64), fast_row<64, 128, 16>(ADVHIP_ALGO_IGEMM_64x128),
+    fast_row<128, 128, 32>(ADVHIP_ALGO_IGEMM_128x128x32), fast_row<128, 64, 32>(ADVHIP_ALGO_IGEMM_128x64x32),
+    fast_row<64, 64, 32>(ADVHIP_ALGO_IGEMM_64x64x32), fast_row<64, 128, 32>(ADVHIP_ALGO_IGEMM_64x128x32),
+    generic_row<128, 128, 16>(ADVHIP_ALGO_IGEMM_128x128), generic_row<128, 64, 16>(ADVHIP_ALGO_IGEMM_128x64),
+    generic_row<64, 64, 16>(ADVHIP_ALGO_IGEMM_64x64), generic_row<64, 128, 16>(ADVHIP_ALGO_IGEMM_64x128),
+    generic_row<128, 128, 32>(ADVHIP_ALGO_IGEMM_128x128x32), generic_row<128, 64, 32>(ADVHIP_ALGO_IGEMM_128x64x32),
+    generic_row<64, 64, 32>(ADVHIP_ALGO_IGEMM_64x64x32), generic_row<64, 128, 32>(ADVHIP_ALGO_IGEMM_64x128x32),
+};
+constexpr bool algo_table_ok() {
+  for (const AlgoRow& r : ALGO_TABLE)
+    for (const AlgoRow& q : ALGO_TABLE)
+      if (r.launch == nullptr || (&q != &r && q.id == r.id)) return false;
+  return true;
+}
+static_assert(algo_table_ok(), "every row of ALGO_TABLE has a launch, and no id has two rows");
+
+// the row of an id, nullptr for one without a kernel (ADVHIP_ALGO_AUTO and the TFOLD ids included: resolve those first)
+static const AlgoRow* algo_row(int algo) {
+  for (const AlgoRow& r : ALGO_TABLE)
+    if (r.id == algo) return &r;
+  return nullptr;
+}
+
+struct Choice {
+  int algo;            // ADVHIP_ALGO_IGEMM_*
+  int splits;          // >= 1
+  const AlgoRow* row;  // algo's row of ALGO_TABLE; nullptr: no kernel for that id, and the caller refuses it
+};
 
 // the fast kernel covers kernels up to 10x10x10 on tensors addressable by 32-bit byte offsets
 static bool fast_ok(const advhip_conv3d_desc* d, long long in_elems, long long w_elems) {
@@ -3089,7 +3201,7 @@ static bool fast_ok(const advhip_conv3d_desc* d, long long in_elems, long long w
 // from a measured table).  Goal: >= ~3 workgroups per CU; big tiles when M*N is plentiful, split-K
 // when it is not and K is long.
 static Choice choose(const advhip_conv3d_desc* d, long long M, int Kpad) {
-  Choice c{d->algo, d->splits};
+  Choice c{d->algo, d->splits, nullptr};
   const int N = d->Cout;
   if (c.algo == ADVHIP_ALGO_AUTO) {
     // what the measured table (tuned/gfx950.json) picks almost everywhere: 64x64x16 tiles -- many
@@ -3098,11 +3210,10 @@ static Choice choose(const advhip_conv3d_desc* d, long long M, int Kpad) {
     c.algo = ADVHIP_ALGO_IGEMM_64x64;
     if (fast_ok(d, in_elems, (long long)Kpad * N)) c.algo += ADVHIP_ALGO_DMA_BASE;
   }
-  if (c.splits <= 0) {
-    int BM, BN, BK;
-    tile_of(c.algo, &BM, &BN, &BK);
-    const long long tiles = ((M + BM - 1) / BM) * (N / BN);
-    const int nk = Kpad / BK;
+  c.row = algo_row(c.algo);
+  if (c.splits <= 0 && c.row != nullptr) {
+    const long long tiles = ((M + c.row->BM - 1) / c.row->BM) * (N / c.row->BN);
+    const int nk = Kpad / c.row->BK;
     int s = 1;
     while (tiles * s < 1024 && s < 9 && nk / (s + 1) >= 8) ++s;
     c.splits = s;
@@ -3128,11 +3239,6 @@ static Geometry geometry(const advhip_conv3d_desc* d) {
 }  // namespace advhip
 
 namespace advhip {
-// the LDS-DMA kernel families reduce split-K partials inside the launch (no second kernel)
-static bool reduces_in_kernel(int algo) {
-  return (algo >= ADVHIP_ALGO_DMA_BASE && algo < ADVHIP_ALGO_BF16X3_BASE) || algo >= ADVHIP_ALGO_DMA2_BASE;
-}
-
 // compute units of the current device (the persistent kernels size their grid from it)
 static int device_cus() {
   static int cached[64] = {0};
@@ -3154,9 +3260,8 @@ struct SplitLayout {
 // `Mv`: rows of the launch's M index space -- g.M, or the virtually padded count (padded_rows below) that its m-tiles cover.
 static SplitLayout split_layout(const advhip_conv3d_desc* d, const Geometry& g, const Choice& c, long long Mv) {
   if (c.splits <= 1) return {0, 0};
-  if (!reduces_in_kernel(c.algo)) return {0, (int64_t)c.splits * g.M * d->Cout * (int64_t)sizeof(float)};
-  int BM, BN, BK;
-  tile_of(c.algo, &BM, &BN, &BK);
+  if (!c.row->reduces_in_kernel) return {0, (int64_t)c.splits * g.M * d->Cout * (int64_t)sizeof(float)};
+  const int BM = c.row->BM, BN = c.row->BN;
   const int64_t tiles = ((Mv + BM - 1) / BM) * (d->Cout / BN);
   return {(tiles * 4 + 255) / 256 * 256, tiles * c.splits * BM * BN * (int64_t)sizeof(float)};
 }
@@ -3174,7 +3279,7 @@ static bool is_nocheck(const advhip_conv3d_desc* d, const Geometry& g) {
 static long long padded_rows(const advhip_conv3d_desc* d, const Geometry& g, const Choice& c) {
   const long long thw = (long long)g.To * g.Ho * g.Wo;
   if (!(is_nocheck(d, g) && d->st == 1 && d->sh == 1 && d->sw == 1 && thw % 4 != 0)) return 0;
-  if (!((c.algo > ADVHIP_ALGO_DMA2_BASE && c.algo <= ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_256x64) || c.algo == ADVHIP_ALGO_MIXED_128x64 || is_persist(c.algo))) return 0;
+  if (!c.row->pads_rows) return 0;
   const long long Mv = (long long)d->B * ((thw + 3) / 4 * 4);
   return Mv < (1ll << 31) ? Mv : 0;
 }
@@ -3183,33 +3288,15 @@ static long long padded_rows(const advhip_conv3d_desc* d, const Geometry& g, con
 static bool is_tfold(int algo) { return algo >= ADVHIP_ALGO_TFOLD_BASE && algo < ADVHIP_ALGO_TFOLD_BASE + 16; }
 }  // namespace advhip
 
-namespace advhip {
-static void set_bricks(ConvArgs& a, int nbt, int nbh, int nbw);  // defined with the pooling launchers below
-
-// the 2-deep-ring LDS-DMA kernel of a tile: unchecked (1x1x1, no padding), 16-byte gather pieces ((kt,1,1) stride-1 convs on
-// planes of a multiple of 4 positions, 16-deep k-tiles), or the 4-byte gather
-// ADVHIP_EXTRA_LDS (study builds only, default 0): unused dynamic LDS per workgroup of the 2-deep-ring kernels -- fewer workgroups of
-// one launch per CU, so that launches of different lanes share a CU (profiles/r05_studies.md section 5)
-#ifndef ADVHIP_EXTRA_LDS
-#define ADVHIP_EXTRA_LDS 0
-#endif
-template <int BM_, int BN_, int BK_>
-static void launch_dma2(bool nocheck, bool s16, dim3 grid, hipStream_t st, const ConvArgs& a) {
-  constexpr unsigned XL = ADVHIP_EXTRA_LDS;
-  if (nocheck) {
-    if (a.a16) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false, 2, EPI_STD, false, 2>), grid, dim3(256), XL, st, a);
-    else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false, 2>), grid, dim3(256), XL, st, a);
-    return;
-  }
-  if constexpr (BK_ == 16) {
-    if (s16) {
-      hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true, 2, EPI_STD, false, 1>), grid, dim3(256), XL, st, a);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true, 2>), grid, dim3(256), XL, st, a);
-}
-
+extern "C" int advhip_conv3d_algo_info(int32_t algo, int32_t* family, int32_t* BM, int32_t* BN, int32_t* BK) {
+  // (ADVHIP_ALGO_AUTO: its first choice, as choose() makes it; the generic kernel it falls back to has the same tile)
+  const AlgoRow* r = algo_row(algo == ADVHIP_ALGO_AUTO ? ADVHIP_ALGO_DMA_BASE + ADVHIP_ALGO_IGEMM_64x64
+                              : is_tfold(algo)         ? algo - ADVHIP_ALGO_TFOLD_BASE + ADVHIP_ALGO_DMA2_BASE
+                                                       : algo);
+  ADVHIP_REQUIRE(r != nullptr, "conv3d: algo %d is not instantiated in this library", algo);
+  if (family) *family = r->family;
+  if (BM) *BM = r->BM;  if (BN) *BN = r->BN;  if (BK) *BK = r->BK;
+  return ADVHIP_OK;
 }
 
 extern "C" int64_t advhip_conv3d_workspace_bytes(const advhip_conv3d_desc* d) {
@@ -3220,7 +3307,7 @@ extern "C" int64_t advhip_conv3d_workspace_bytes(const advhip_conv3d_desc* d) {
   }
   const Geometry g = geometry(d);
   const Choice c = choose(d, g.M, g.Kpad);
-  if (!instantiated(c.algo)) {
+  if (c.row == nullptr) {
     set_error("conv3d: algo %d is not instantiated in this library", c.algo);
     return -1;
   }
@@ -3228,6 +3315,264 @@ extern "C" int64_t advhip_conv3d_workspace_bytes(const advhip_conv3d_desc* d) {
   const long long Mp = padded_rows(d, g, c);
   return split_layout(d, g, c, Mp > g.M ? Mp : g.M).total();
 }
+
+// ---- the steps of advhip_conv3d_bn_act_ex_f32, in the order it takes them -----------------------------------------------------------
+namespace advhip {
+static void set_bricks(ConvArgs& a, int nbt, int nbh, int nbw);  // defined with the pooling launchers below
+
+// x as a launch addresses it: one dense sample, the batch stride, and the span in elements (the last sample is not padded out to the stride)
+struct XSpan { long long dense, bstride, elems; };
+static XSpan x_span(const advhip_conv3d_desc* d, int64_t x_batch_stride) {
+  const long long dense = (long long)d->Cin * d->T * d->H * d->W, bstride = x_batch_stride > 0 ? x_batch_stride : dense;
+  return {dense, bstride, (long long)(d->B - 1) * bstride + dense};
+}
+
+// What every conv launcher puts into ConvArgs the same way (`a` arrives value-initialised: what no step sets is zero).  The caller
+// has checked x_span's range; kt_ ... w_bytes are read by the families whose rows say needs_fast_ok only.
+static void fill_conv_args(ConvArgs& a, const advhip_conv3d_desc* d, const Geometry& g, const float* x, int64_t x_batch_stride, const float* w_packed,
+                           const int32_t* ktab, const float* scale, const float* shift) {
+  const XSpan xs = x_span(d, x_batch_stride);
+  a.x = x; a.w = w_packed; a.ktab = reinterpret_cast<const int4*>(ktab);
+  a.scale = scale; a.shift = shift;
+  a.B = d->B; a.Cin = d->Cin; a.T = d->T; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
+  a.st = d->st; a.sh = d->sh; a.sw = d->sw; a.pt = d->pt; a.ph = d->ph; a.pw = d->pw;
+  a.To = g.To; a.Ho = g.Ho; a.Wo = g.Wo;
+  a.M = (int)g.M; a.x_bstride = (int)xs.bstride; a.Kpad = g.Kpad;
+  a.HWo = a.Ho * a.Wo; a.THWo = a.To * a.HWo;
+  a.HW = d->H * d->W; a.THW = d->T * a.HW;
+  a.relu = d->relu; a.MP = a.THWo;
+  a.dTHWo = FastDiv::make((unsigned)a.THWo); a.dHWo = FastDiv::make((unsigned)a.HWo); a.dWo = FastDiv::make((unsigned)a.Wo);
+  a.kt_ = d->kt; a.kh_ = d->kh; a.kw_ = d->kw;
+  a.pad_off = d->pt * d->H * d->W + d->ph * d->W + d->pw;
+  a.x_bytes = (unsigned)((xs.elems + a.pad_off) * 4);
+  a.w_bytes = (unsigned)((long long)g.Kpad * d->Cout * 4);
+}
+
+// One call as its steps see it: the caller's arguments and what follows from the descriptor alone
+struct ConvCall {
+  const advhip_conv3d_desc* d;
+  Geometry g;
+  XSpan xs;
+  long long y_dense, ybs;  // one dense sample of y, and its batch stride
+  const float *x, *residual;
+  float* y;
+  const advhip_conv3d_epilogue* ep;  // nullable; the next line is its operands, null / false without it
+  float* y_preact; const float* dact_z; float* avg_out; bool ln;
+  void* workspace; int64_t workspace_bytes;
+  hipStream_t st;
+  bool plain_epilogue() const { return !ln && y_preact == nullptr && dact_z == nullptr; }  // none of the MGFN epilogue operands
+};
+// What plan_conv decides: the id's row and the split count, the rows of the launch's M index space, the split-K layout, the gather forms
+struct ConvPlan { Choice c; long long Mv; SplitLayout lay; bool nocheck, s16; };
+static dim3 conv_grid(const ConvArgs& a) { return dim3((unsigned)(a.tiles_m * a.tiles_n * a.splits)); }
+
+// step 1: what the activation code and the epilogue need, the operands nobody may leave out (`tables`: w_packed, ktab, scale and
+// shift are all there), batch strides that hold a sample, tensors that 32-bit indices reach
+static int check_call(const ConvCall& k, bool tables) {
+  const advhip_conv3d_desc* d = k.d;
+  const advhip_conv3d_epilogue* ep = k.ep;
+  ADVHIP_REQUIRE(!ep || (!ep->ln_u == !ep->ln_mu && !ep->ln_u == !ep->ln_rs), "conv3d: the LayerNorm fold needs ln_u, ln_mu and ln_rs together");
+  ADVHIP_REQUIRE(d->relu >= 0 && d->relu <= ACT_MUL, "conv3d: unknown activation code %d (0 none, 1 ReLU, 2 GELU, 3 GELU + GELU' output, 4 multiplier)", d->relu);
+  ADVHIP_REQUIRE(d->relu != ACT_GELU_D || (ep && ep->y_preact), "conv3d: activation code 3 writes GELU'(pre-activation) to the epilogue's second output: y_preact is null");
+  ADVHIP_REQUIRE(d->relu != ACT_MUL || (ep && ep->dact_z && k.residual == nullptr), "conv3d: activation code 4 multiplies by the epilogue's dact_z tensor (no residual): it is null");
+  ADVHIP_REQUIRE(k.x && tables && (k.y || k.avg_out), "conv3d: null pointer");
+  ADVHIP_REQUIRE(k.xs.bstride >= k.xs.dense && k.ybs >= k.y_dense, "conv3d: batch strides (%lld, %lld) smaller than one sample (%lld, %lld)", k.xs.bstride, k.ybs,
+                 k.xs.dense, k.y_dense);
+  if (k.xs.elems >= (1ll << 31) || (long long)d->B * k.ybs >= (1ll << 32) || k.g.M * d->Cout >= (1ll << 32) || k.g.M >= (1ll << 31)) {
+    set_error("conv3d: tensor too large for 32-bit indexing (in=%lld, out=%lld elements)", k.xs.elems, k.g.M * d->Cout);
+    return ADVHIP_ERANGE;
+  }
+  return ADVHIP_OK;
+}
+
+// step 2 (after fill_conv_args): the outputs and the epilogue operands
+static void fill_epilogue_args(ConvArgs& a, const ConvCall& k) {
+  a.res = k.residual; a.y = k.y;
+  a.y2 = k.y_preact; a.dact = k.dact_z;
+  if (k.ln) { a.ln_u = k.ep->ln_u; a.ln_mu = k.ep->ln_mu; a.ln_rs = k.ep->ln_rs; }
+  a.y_bstride = (int)k.ybs;
+  // widest epilogue vector (floats) the output rows, the batch stride and the pointers are all aligned to
+  auto aligned_to = [&](int v) {
+    const uintptr_t bytes = (uintptr_t)v * sizeof(float);
+    return a.THWo % v == 0 && k.ybs % v == 0 && (uintptr_t)k.y % bytes == 0 && (uintptr_t)k.residual % bytes == 0 &&
+           (uintptr_t)k.workspace % bytes == 0 && (uintptr_t)k.y_preact % bytes == 0 && (uintptr_t)k.dact_z % bytes == 0 &&
+           (uintptr_t)a.ln_mu % bytes == 0 && (uintptr_t)a.ln_rs % bytes == 0;
+  };
+  a.vw = aligned_to(4) ? 4 : (aligned_to(2) ? 2 : 1);
+}
+
+// step 3: the id and the split count (choose, or what the fused mean forces), what that id requires of the call, the virtual row
+// padding, the split-K layout in the workspace, the tiles and the gather forms.  Every check of the plain families is in here.
+static int plan_conv(const ConvCall& k, ConvArgs& a, ConvPlan& p) {
+  const advhip_conv3d_desc* d = k.d;
+  const Geometry& g = k.g;
+  Choice& c = p.c = choose(d, g.M, g.Kpad);
+  if (k.avg_out != nullptr) {  // conv + global mean in one launch: one sample per 128-row tile of the 2-deep LDS-DMA kernel, unsplit
+    ADVHIP_REQUIRE(d->kt == 1 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 &&
+                       g.K == g.Kpad && a.THWo <= 128 && d->Cout % 64 == 0 && ((uintptr_t)k.x & 15) == 0 && k.plain_epilogue() && a.relu <= 1,
+                   "conv3d: avgpool_out needs a 1x1x1 stride-1 conv on <= 128 positions per sample (%d), Cin %% 16 == 0, Cout %% 64 == 0, x 16-byte aligned, "
+                   "no other epilogue operand, activation none or ReLU", a.THWo);
+    c = Choice{ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_128x64, 1, algo_row(ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_128x64)};
+  }
+  ADVHIP_REQUIRE(c.row != nullptr, "conv3d: algo %d is not instantiated in this library", c.algo);
+  const AlgoRow& row = *c.row;
+  if (k.ybs != k.y_dense && !row.reduces_in_kernel) c.splits = 1;  // the separate split-K reduce pass writes a dense y
+  ADVHIP_REQUIRE(!k.ln || (d->kt == 1 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0),
+                 "conv3d: the LayerNorm fold applies to 1x1x1 stride-1 convs (per-position statistics of the input)");
+  ADVHIP_REQUIRE(k.plain_epilogue() || c.splits == 1 || row.reduces_in_kernel,
+                 "conv3d: pre-activation output / GELU-backward multiplier need a fused epilogue (algo %d with %d splits reduces in a second launch)", c.algo, c.splits);
+  ADVHIP_REQUIRE(!row.needs_fast_ok || fast_ok(d, k.xs.elems, (long long)g.Kpad * d->Cout),
+                 "conv3d: fast kernel needs kernel extents <= 10 and < 3.75 GiB operands (k=%d,%d,%d)", d->kt, d->kh, d->kw);
+  const int BM = row.BM, BN = row.BN, BK = row.BK;
+  ADVHIP_REQUIRE(d->Cout % BN == 0, "conv3d: Cout=%d not a multiple of the %d-wide N tile", d->Cout, BN);
+  ADVHIP_REQUIRE(g.Kpad % BK == 0 || BK == 16, "conv3d: internal: Kpad");
+  a.splits = c.splits;
+  a.slab = g.M * d->Cout;
+  const int nk = (g.Kpad + BK - 1) / BK;
+  ADVHIP_REQUIRE(c.splits >= 1 && c.splits <= nk && c.splits <= 64, "conv3d: bad split count %d (k-tiles %d)", c.splits, nk);
+  p.nocheck = is_nocheck(d, g);
+  // rows padded to a multiple of 4 in the M index space (padded_rows): a group of 4 positions never straddles two samples; the last
+  // group of a row reads on into the next channel's row -- or past the tensor, where the buffer range check returns zeros -- for
+  // positions nobody stores.  Split launches too: the partial tiles and the arrival counters are per tile of the padded M.
+  p.Mv = g.M;
+  bool a16pad = false;
+  if (const long long Mp = padded_rows(d, g, c); Mp > 0 && ((uintptr_t)k.x & 15) == 0 && k.plain_epilogue()) {
+    a.MP = (a.THWo + 3) / 4 * 4;
+    p.Mv = Mp;
+    a16pad = true;
+  }
+  p.lay = split_layout(d, g, c, p.Mv);
+  if (c.splits > 1) {
+    ADVHIP_REQUIRE(k.workspace != nullptr && k.workspace_bytes >= p.lay.total(),
+                   "conv3d: split-K needs a %lld-byte workspace (got %lld); query advhip_conv3d_workspace_bytes",
+                   (long long)p.lay.total(), (long long)k.workspace_bytes);
+    if (row.reduces_in_kernel) {
+      ADVHIP_REQUIRE(p.lay.part_bytes < 0xF0000000ll && (uintptr_t)k.workspace % 16 == 0,
+                     "conv3d: split-K partial tiles need a 16-byte aligned workspace below 3.75 GiB (%lld bytes)", (long long)p.lay.part_bytes);
+      a.cnt = reinterpret_cast<unsigned*>(k.workspace);
+      a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(k.workspace) + p.lay.cnt_bytes);
+      a.part_bytes = (unsigned)p.lay.part_bytes;
+    } else {
+      a.y = reinterpret_cast<float*>(k.workspace);
+    }
+  }
+  if (k.avg_out != nullptr) {  // (the same virtual padding, to the whole tile: the last groups of a sample read on into rows nobody adds up)
+    a.MP = 128;
+    p.Mv = (long long)d->B * a.MP;
+    ADVHIP_REQUIRE(p.Mv < (1ll << 31), "conv3d: too many samples for the fused mean");
+    a16pad = true;
+    a.avg_out = k.avg_out;
+  }
+  if (a16pad) {
+    a.M = (int)p.Mv;
+    a.dTHWo = FastDiv::make((unsigned)a.MP);
+  }
+  a.tiles_m = (int)((p.Mv + BM - 1) / BM);
+  a.tiles_n = d->Cout / BN;
+  a.dTilesN = FastDiv::make((unsigned)a.tiles_n);
+  a.dSplits = FastDiv::make((unsigned)c.splits);
+  // BK = 32 needs Kpad % 32 == 0: the packed weights are padded to 16 rows only, but the k-table
+  // marks rows >= K invalid and the weight rows read beyond Kpad must exist -> require it.
+  if (BK == 32) ADVHIP_REQUIRE(g.Kpad % 32 == 0, "conv3d: BK=32 variants need K padded to 32 (K=%d)", g.K);
+  // (kt,1,1) stride-1 conv whose planes are a multiple of 4 positions long: a group of 4 consecutive m is 16 contiguous bytes for
+  // every tap (all inside or all padding) -- 16-byte gather pieces, offsets from the conv's own compact table
+  p.s16 = !p.nocheck && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && a.HW % 4 == 0 &&
+          d->kt <= 10 && g.K % 4 == 0;
+  if (p.s16) a.ktab_s2w = reinterpret_cast<const int2*>(a.ktab + g.Kpad);
+  // ... and rows of 4 consecutive positions contiguous and 16-byte aligned in x: 16-byte LDS-DMA pieces for A
+  a.a16 = (a16pad || (p.nocheck && d->st == 1 && d->sh == 1 && d->sw == 1 && a.THW % 4 == 0 && k.xs.bstride % 4 == 0 && ((uintptr_t)k.x & 15) == 0)) ? 1 : 0;
+  return ADVHIP_OK;
+}
+
+// step 4, FAM_TSPAN: m-tiles that span T -- (kt,1,1) stride-1 "same" convs only; the spatial plane is presented as one flattened row
+static int launch_tspan(const ConvCall& k, const ConvPlan& p, ConvArgs& a) {
+  const advhip_conv3d_desc* d = k.d;
+  const Geometry& g = k.g;  // (a.To == g.To: the row's launch picks its kernel by the same bt rule)
+  ADVHIP_REQUIRE(d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && 2 * d->pt + 1 == d->kt,
+                 "conv3d: ADVHIP_ALGO_TSPAN needs a (kt,1,1) stride-1 conv with padding kt/2 (k=%d,%d,%d)", d->kt, d->kh, d->kw);
+  ADVHIP_REQUIRE(p.c.splits == 1 && g.To % 2 == 0 && k.plain_epilogue(),
+                 "conv3d: ADVHIP_ALGO_TSPAN runs unsplit on an even number of frames (T=%d, splits=%d) without the MGFN epilogue operands", g.To, p.c.splits);
+  const int bt = g.To % 4 == 0 ? 4 : 2;  // frames per m-tile
+  a.H = 1; a.W = a.HW; a.Ho = 1; a.Wo = a.HWo; a.kh_ = 1; a.kw_ = 1;
+  set_bricks(a, g.To / bt, 1, (a.Wo + 128 / bt - 1) / (128 / bt));
+  // 16-byte gather pieces: a tile row segment is BW consecutive positions of one flattened plane, tap dt of a k-row reads
+  // the same segment one plane on -- four consecutive positions are four consecutive floats (at a 4-byte aligned address:
+  // LDS-DMA takes it, tools/probe/), so a lane fetches a 4-position group and a wave-instruction two whole k-rows, offsets
+  // from the conv's own compact table {(ci*T + dt)*HW*4, tap bits}
+  a.ktab_s2w = reinterpret_cast<const int2*>(a.ktab + g.Kpad);
+  a.s2w_rowp = a.W;
+  p.c.row->launch(a, conv_grid(a), k.st, p.nocheck, p.s16);
+  return check_launch("conv3d_igemm");
+}
+
+// step 4, FAM_MIXED: 128-row m-tiles, and the last ones cut into 64-row tiles
+static int launch_mixed(const ConvCall& k, const ConvPlan& p, ConvArgs& a) {
+  ADVHIP_REQUIRE(a.a16 != 0 && p.c.splits == 1 && k.plain_epilogue(),
+                 "conv3d: ADVHIP_ALGO_MIXED_128x64 takes unsplit 1x1x1 stride-1 convs on 16-byte aligned rows without the MGFN epilogue operands "
+                 "(k=%d,%d,%d, splits=%d)", k.d->kt, k.d->kh, k.d->kw, p.c.splits);
+  // how many of the last 128-row m-tile rows to cut: all the workgroups past the last whole round of
+  // resident slots (6 per CU) must be short ones -- cutting `c` tall m-tile rows adds c * tiles_n workgroups, so c >= rem / tiles_n.
+  // A launch that is below one round, on a round boundary or far into a round is the plain 128 x 64 launch.
+  const long long mt = (p.Mv + 127) / 128, tn = a.tiles_n, slots = 6ll * device_cus();
+  const long long rem = (mt * tn) % slots;
+  long long cut = (mt * tn > slots && rem > 0 && rem * 4 <= slots) ? (rem + tn - 1) / tn : 0;
+  if (cut > mt) cut = mt;
+  if (cut == 0) {
+    p.c.row->launch(a, conv_grid(a), k.st, p.nocheck, p.s16);
+    return check_launch("conv3d mixed (plain)");
+  }
+  const long long big_rows = (mt - cut) * 128, small_mt = (p.Mv - big_rows + 63) / 64;
+  a.mix_big = (int)((mt - cut) * tn);
+  a.mix_small = (int)(small_mt * tn);
+  a.mix_mbase = (int)big_rows;
+  hipLaunchKernelGGL(conv1x1_mixed_tail_kernel, dim3((unsigned)(a.mix_big + a.mix_small)), dim3(256), 0, k.st, a);
+  return check_launch("conv3d mixed tail");
+}
+
+// step 4, FAM_PERSIST: workgroups that stay -- `wgs_per_cu` per compute unit (a multiple of 8 in all, at most one per tile), each
+// walking its share of the tiles
+static int launch_persist(const ConvCall& k, const ConvPlan& p, const ConvArgs& a) {
+  ADVHIP_REQUIRE(k.g.Kpad >= 16 * PERSIST_MIN_NK, "conv3d: the persistent kernels need K >= %d (%d k-tiles per output tile), got %d", 16 * PERSIST_MIN_NK,
+                 PERSIST_MIN_NK, k.g.K);
+  ADVHIP_REQUIRE(a.a16 != 0 && p.c.splits == 1 && !k.ln && k.dact_z == nullptr,
+                 "conv3d: the persistent kernels (algo %d) take unsplit 1x1x1 stride-1 convs on 16-byte aligned rows without the LayerNorm fold / "
+                 "GELU-backward operands (k=%d,%d,%d, splits=%d)", p.c.algo, k.d->kt, k.d->kh, k.d->kw, p.c.splits);
+  const long long nt = (long long)a.tiles_m * a.tiles_n;
+  long long wgs = (long long)p.c.row->wgs_per_cu * device_cus();
+  if (wgs > nt) wgs = nt;
+  wgs = wgs / GFX950_XCDS * GFX950_XCDS;
+  if (wgs < GFX950_XCDS) wgs = GFX950_XCDS;
+  p.c.row->launch(a, dim3((unsigned)wgs), k.st, p.nocheck, p.s16);
+  return check_launch("conv3d persistent");
+}
+
+// step 4, every other family: the arrival counters of an in-kernel split-K reduction, the row's kernel, and the reduce pass of the
+// families that leave their K slices in slabs
+static int launch_row(const ConvCall& k, const ConvPlan& p, ConvArgs& a) {
+  if (a.cnt != nullptr) {
+    const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
+    if (k.ep && k.ep->splitk_counters && k.ep->splitk_counter_bytes >= tiles * 4) {
+      // the caller's counter block: zero when allocated, and every launch leaves it zero (the last arriver of a tile resets its word)
+      ADVHIP_REQUIRE((uintptr_t)k.ep->splitk_counters % 4 == 0, "conv3d: misaligned split-K counter block");
+      a.cnt = reinterpret_cast<unsigned*>(k.ep->splitk_counters);
+    } else if (hipMemsetAsync(a.cnt, 0, (size_t)p.lay.cnt_bytes, k.st) != hipSuccess) {  // (a memset node: graph-capturable, replayed first)
+      return check_launch("conv3d split-K counters");
+    }
+  }
+  p.c.row->launch(a, conv_grid(a), k.st, p.nocheck, p.s16);
+  if (int rc = check_launch("conv3d_igemm")) return rc;
+  if (p.c.splits > 1 && a.part == nullptr) {
+    const long long total = a.slab;
+    const int vec4 = a.vw == 4 ? 1 : 0;  // rows, slabs, residual and y all 16-byte aligned
+    const long long work = vec4 ? total / 4 : total;
+    const int rgrid = (int)std::min<long long>((work + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rgrid), dim3(256), 0, k.st, reinterpret_cast<const float*>(k.workspace), a.scale,
+                       a.shift, k.residual, k.y, total, a.THWo, k.d->Cout, p.c.splits, k.d->relu, vec4);
+    return check_launch("splitk_reduce");
+  }
+  return ADVHIP_OK;
+}
+}  // namespace advhip
 
 extern "C" int advhip_conv3d_bn_act_f32(const advhip_conv3d_desc* d, const float* x, const float* w_packed,
                                         const int32_t* ktab, const float* scale, const float* shift,
@@ -3261,296 +3606,24 @@ extern "C" int advhip_conv3d_bn_act_ex_f32(const advhip_conv3d_desc* d, const fl
     return advhip_conv3d_bn_act_ex_f32(&f, x, x_batch_stride, w_packed, ktab, scale, shift, residual, y, y_batch_stride, ep, workspace,
                                        workspace_bytes, stream);
   }
-  float* y_preact = ep ? ep->y_preact : nullptr;
-  const float* dact_z = ep ? ep->dact_z : nullptr;
-  float* avg_out = ep ? ep->avgpool_out : nullptr;
-  const bool ln = ep && ep->ln_u;
-  ADVHIP_REQUIRE(!ep || (!ep->ln_u == !ep->ln_mu && !ep->ln_u == !ep->ln_rs), "conv3d: the LayerNorm fold needs ln_u, ln_mu and ln_rs together");
-  ADVHIP_REQUIRE(d->relu >= 0 && d->relu <= ACT_MUL, "conv3d: unknown activation code %d (0 none, 1 ReLU, 2 GELU, 3 GELU + GELU' output, 4 multiplier)", d->relu);
-  ADVHIP_REQUIRE(d->relu != ACT_GELU_D || (ep && ep->y_preact), "conv3d: activation code 3 writes GELU'(pre-activation) to the epilogue's second output: y_preact is null");
-  ADVHIP_REQUIRE(d->relu != ACT_MUL || (ep && ep->dact_z && residual == nullptr), "conv3d: activation code 4 multiplies by the epilogue's dact_z tensor (no residual): it is null");
-  ADVHIP_REQUIRE(x && w_packed && ktab && scale && shift && (y || avg_out), "conv3d: null pointer");
   const Geometry g = geometry(d);
-  ConvArgs a;
-  a.x = x; a.w = w_packed; a.ktab = reinterpret_cast<const int4*>(ktab);
-  a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
-  a.y2 = y_preact; a.dact = dact_z;
-  a.ln_u = ln ? ep->ln_u : nullptr; a.ln_mu = ln ? ep->ln_mu : nullptr; a.ln_rs = ln ? ep->ln_rs : nullptr;
-  a.B = d->B; a.Cin = d->Cin; a.T = d->T; a.H = d->H; a.W = d->W; a.Cout = d->Cout;
-  a.st = d->st; a.sh = d->sh; a.sw = d->sw; a.pt = d->pt; a.ph = d->ph; a.pw = d->pw;
-  a.To = g.To; a.Ho = g.Ho; a.Wo = g.Wo;
-  const long long x_dense = (long long)d->Cin * d->T * d->H * d->W, y_dense = (long long)d->Cout * g.To * g.Ho * g.Wo;
-  const long long xbs = x_batch_stride > 0 ? x_batch_stride : x_dense, ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
-  ADVHIP_REQUIRE(xbs >= x_dense && ybs >= y_dense, "conv3d: batch strides (%lld, %lld) smaller than one sample (%lld, %lld)", xbs, ybs, x_dense, y_dense);
-  // span of x in elements (the last sample is not padded out to the stride)
-  const long long in_elems = (long long)(d->B - 1) * xbs + x_dense;
-  const long long M = g.M;
-  if (in_elems >= (1ll << 31) || (long long)d->B * ybs >= (1ll << 32) || M * d->Cout >= (1ll << 32) || M >= (1ll << 31)) {
-    set_error("conv3d: tensor too large for 32-bit indexing (in=%lld, out=%lld elements)", in_elems, M * d->Cout);
-    return ADVHIP_ERANGE;
+  const long long y_dense = (long long)d->Cout * g.To * g.Ho * g.Wo;
+  const ConvCall k{d, g, x_span(d, x_batch_stride), y_dense, y_batch_stride > 0 ? y_batch_stride : y_dense, x, residual, y, ep,
+                   ep ? ep->y_preact : nullptr, ep ? ep->dact_z : nullptr, ep ? ep->avgpool_out : nullptr, ep && ep->ln_u,
+                   workspace, workspace_bytes, (hipStream_t)stream};
+  if (int rc = check_call(k, w_packed && ktab && scale && shift)) return rc;
+  ConvArgs a{};
+  fill_conv_args(a, d, g, x, x_batch_stride, w_packed, ktab, scale, shift);
+  fill_epilogue_args(a, k);
+  ConvPlan p;
+  if (int rc = plan_conv(k, a, p)) return rc;
+  if (k.avg_out != nullptr) return launch_avg(a, conv_grid(a), k.st);
+  switch (p.c.row->family) {
+    case FAM_TSPAN: return launch_tspan(k, p, a);
+    case FAM_MIXED: return launch_mixed(k, p, a);
+    case FAM_PERSIST: return launch_persist(k, p, a);
+    default: return launch_row(k, p, a);
   }
-  a.M = (int)M;
-  a.x_bstride = (int)xbs;
-  a.y_bstride = (int)ybs;
-  a.Kpad = g.Kpad;
-  a.HWo = a.Ho * a.Wo; a.THWo = a.To * a.HWo;
-  a.HW = d->H * d->W; a.THW = d->T * a.HW;
-  a.relu = d->relu;
-  a.MP = a.THWo;
-  a.dTHWo = FastDiv::make((unsigned)a.THWo);
-  a.dHWo = FastDiv::make((unsigned)a.HWo);
-  a.dWo = FastDiv::make((unsigned)a.Wo);
-  // widest epilogue vector (floats) the output rows, the batch stride and the pointers are all aligned to
-  auto aligned_to = [&](int v) {
-    const uintptr_t bytes = (uintptr_t)v * sizeof(float);
-    return a.THWo % v == 0 && ybs % v == 0 && (uintptr_t)y % bytes == 0 && (uintptr_t)residual % bytes == 0 &&
-           (uintptr_t)workspace % bytes == 0 && (uintptr_t)y_preact % bytes == 0 && (uintptr_t)dact_z % bytes == 0 &&
-           (uintptr_t)a.ln_mu % bytes == 0 && (uintptr_t)a.ln_rs % bytes == 0;
-  };
-  a.vw = aligned_to(4) ? 4 : (aligned_to(2) ? 2 : 1);
-
-  Choice c = choose(d, M, g.Kpad);
-  if (avg_out != nullptr) {  // conv + global mean in one launch: one sample per 128-row tile of the 2-deep LDS-DMA kernel, unsplit
-    ADVHIP_REQUIRE(d->kt == 1 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 &&
-                       g.K == g.Kpad && a.THWo <= 128 && d->Cout % 64 == 0 && ((uintptr_t)x & 15) == 0 && !ln && y_preact == nullptr && dact_z == nullptr && a.relu <= 1,
-                   "conv3d: avgpool_out needs a 1x1x1 stride-1 conv on <= 128 positions per sample (%d), Cin %% 16 == 0, Cout %% 64 == 0, x 16-byte aligned, "
-                   "no other epilogue operand, activation none or ReLU", a.THWo);
-    c.algo = ADVHIP_ALGO_DMA2_BASE + ADVHIP_ALGO_IGEMM_128x64;
-    c.splits = 1;
-  }
-  if (ybs != y_dense && !reduces_in_kernel(c.algo)) c.splits = 1;  // the separate split-K reduce pass writes a dense y
-  ADVHIP_REQUIRE(!ln || (d->kt == 1 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0),
-                 "conv3d: the LayerNorm fold applies to 1x1x1 stride-1 convs (per-position statistics of the input)");
-  ADVHIP_REQUIRE((y_preact == nullptr && dact_z == nullptr && !ln) || c.splits == 1 || reduces_in_kernel(c.algo),
-                 "conv3d: pre-activation output / GELU-backward multiplier need a fused epilogue (algo %d with %d splits reduces in a second launch)", c.algo, c.splits);
-  int BM, BN, BK;
-  tile_of(c.algo, &BM, &BN, &BK);
-  ADVHIP_REQUIRE(instantiated(c.algo), "conv3d: algo %d is not instantiated in this library", c.algo);
-  const bool fast = c.algo >= ADVHIP_ALGO_FAST_BASE;  // includes the LDS-DMA and split-bf16 ids
-  if (fast) {
-    ADVHIP_REQUIRE(fast_ok(d, in_elems, (long long)g.Kpad * d->Cout),
-                   "conv3d: fast kernel needs kernel extents <= 10 and < 3.75 GiB operands (k=%d,%d,%d)", d->kt, d->kh, d->kw);
-    a.kt_ = d->kt; a.kh_ = d->kh; a.kw_ = d->kw;
-    a.pad_off = d->pt * d->H * d->W + d->ph * d->W + d->pw;
-    a.x_bytes = (unsigned)((in_elems + a.pad_off) * 4);
-    a.w_bytes = (unsigned)((long long)g.Kpad * d->Cout * 4);
-  }
-  ADVHIP_REQUIRE(d->Cout % BN == 0, "conv3d: Cout=%d not a multiple of the %d-wide N tile", d->Cout, BN);
-  ADVHIP_REQUIRE(g.Kpad % BK == 0 || BK == 16, "conv3d: internal: Kpad");
-  a.splits = c.splits;
-  a.slab = M * d->Cout;
-  const int nk = (g.Kpad + BK - 1) / BK;
-  ADVHIP_REQUIRE(c.splits >= 1 && c.splits <= nk && c.splits <= 64, "conv3d: bad split count %d (k-tiles %d)", c.splits, nk);
-  a.part = nullptr; a.cnt = nullptr; a.part_bytes = 0;
-  a.mix_big = a.mix_small = a.mix_mbase = 0;
-  const bool nocheck = is_nocheck(d, g);
-  // rows padded to a multiple of 4 in the M index space (padded_rows): a group of 4 positions never straddles two samples; the last
-  // group of a row reads on into the next channel's row -- or past the tensor, where the buffer range check returns zeros -- for
-  // positions nobody stores.  Split launches too: the partial tiles and the arrival counters are per tile of the padded M.
-  long long Mv = M;
-  bool a16pad = false;
-  if (const long long Mp = padded_rows(d, g, c); Mp > 0 && ((uintptr_t)x & 15) == 0 && !ln && y_preact == nullptr && dact_z == nullptr) {
-    a.MP = (a.THWo + 3) / 4 * 4;
-    Mv = Mp;
-    a16pad = true;
-    a.M = (int)Mv;
-    a.dTHWo = FastDiv::make((unsigned)a.MP);
-  }
-  const SplitLayout lay = split_layout(d, g, c, Mv);
-  if (c.splits > 1) {
-    ADVHIP_REQUIRE(workspace != nullptr && workspace_bytes >= lay.total(),
-                   "conv3d: split-K needs a %lld-byte workspace (got %lld); query advhip_conv3d_workspace_bytes",
-                   (long long)lay.total(), (long long)workspace_bytes);
-    if (reduces_in_kernel(c.algo)) {
-      ADVHIP_REQUIRE(lay.part_bytes < 0xF0000000ll && (uintptr_t)workspace % 16 == 0,
-                     "conv3d: split-K partial tiles need a 16-byte aligned workspace below 3.75 GiB (%lld bytes)", (long long)lay.part_bytes);
-      a.cnt = reinterpret_cast<unsigned*>(workspace);
-      a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + lay.cnt_bytes);
-      a.part_bytes = (unsigned)lay.part_bytes;
-    } else {
-      a.y = reinterpret_cast<float*>(workspace);
-    }
-  }
-  if (avg_out != nullptr) {  // (the same virtual padding, to the whole tile: the last groups of a sample read on into rows nobody adds up)
-    a.MP = 128;
-    Mv = (long long)d->B * a.MP;
-    ADVHIP_REQUIRE(Mv < (1ll << 31), "conv3d: too many samples for the fused mean");
-    a16pad = true;
-    a.M = (int)Mv;
-    a.dTHWo = FastDiv::make((unsigned)a.MP);
-    a.avg_out = avg_out;
-  }
-  a.tiles_m = (int)((Mv + BM - 1) / BM);
-  a.tiles_n = d->Cout / BN;
-  a.dTilesN = FastDiv::make((unsigned)a.tiles_n);
-  a.dSplits = FastDiv::make((unsigned)c.splits);
-  int tspan_bt = 0;
-  if (c.algo == ADVHIP_ALGO_TSPAN_128x64) {
-    // m-tiles that span T: (kt,1,1) stride-1 "same" convs only; the spatial plane is presented as one flattened row
-    ADVHIP_REQUIRE(d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && 2 * d->pt + 1 == d->kt,
-                   "conv3d: ADVHIP_ALGO_TSPAN needs a (kt,1,1) stride-1 conv with padding kt/2 (k=%d,%d,%d)", d->kt, d->kh, d->kw);
-    ADVHIP_REQUIRE(c.splits == 1 && g.To % 2 == 0 && y_preact == nullptr && dact_z == nullptr && !ln,
-                   "conv3d: ADVHIP_ALGO_TSPAN runs unsplit on an even number of frames (T=%d, splits=%d) without the MGFN epilogue operands", g.To, c.splits);
-    tspan_bt = g.To % 4 == 0 ? 4 : 2;
-    a.H = 1; a.W = d->H * d->W; a.Ho = 1; a.Wo = a.HWo;
-    a.kh_ = 1; a.kw_ = 1;
-    set_bricks(a, g.To / tspan_bt, 1, (a.Wo + 128 / tspan_bt - 1) / (128 / tspan_bt));
-    a.Tp = 0;
-    // 16-byte gather pieces: a tile row segment is BW consecutive positions of one flattened plane, tap dt of a k-row reads
-    // the same segment one plane on -- four consecutive positions are four consecutive floats (at a 4-byte aligned address:
-    // LDS-DMA takes it, tools/probe/), so a lane fetches a 4-position group and a wave-instruction two whole k-rows, offsets
-    // from the conv's own compact table {(ci*T + dt)*HW*4, tap bits}
-    a.ktab_s2w = reinterpret_cast<const int2*>(a.ktab + g.Kpad);
-    a.s2w_rowp = a.W;
-  }
-  dim3 grid((unsigned)(a.tiles_m * a.tiles_n * c.splits));
-  hipStream_t st = (hipStream_t)stream;
-  if (a.cnt != nullptr) {
-    const int64_t tiles = (int64_t)a.tiles_m * a.tiles_n;
-    if (ep && ep->splitk_counters && ep->splitk_counter_bytes >= tiles * 4) {
-      // the caller's counter block: zero when allocated, and every launch leaves it zero (the last arriver of a tile resets its word)
-      ADVHIP_REQUIRE((uintptr_t)ep->splitk_counters % 4 == 0, "conv3d: misaligned split-K counter block");
-      a.cnt = reinterpret_cast<unsigned*>(ep->splitk_counters);
-    } else if (hipMemsetAsync(a.cnt, 0, (size_t)lay.cnt_bytes, st) != hipSuccess) {  // (a memset node: graph-capturable, replayed first)
-      return check_launch("conv3d split-K counters");
-    }
-  }
-  // BK = 32 needs Kpad % 32 == 0: the packed weights are padded to 16 rows only, but the k-table
-  // marks rows >= K invalid and the weight rows read beyond Kpad must exist -> require it.
-  if (BK == 32) ADVHIP_REQUIRE(g.Kpad % 32 == 0, "conv3d: BK=32 variants need K padded to 32 (K=%d)", g.K);
-  // (kt,1,1) stride-1 conv whose planes are a multiple of 4 positions long: a group of 4 consecutive m is 16 contiguous bytes for
-  // every tap (all inside or all padding) -- 16-byte gather pieces, offsets from the conv's own compact table
-  const bool s16 = !nocheck && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->ph == 0 && d->pw == 0 && a.HW % 4 == 0 &&
-                   d->kt <= 10 && g.K % 4 == 0;
-  if (s16) a.ktab_s2w = reinterpret_cast<const int2*>(a.ktab + g.Kpad);
-  // ... and rows of 4 consecutive positions contiguous and 16-byte aligned in x: 16-byte LDS-DMA pieces for A
-  a.a16 = (a16pad || (nocheck && d->st == 1 && d->sh == 1 && d->sw == 1 && a.THW % 4 == 0 && xbs % 4 == 0 && ((uintptr_t)x & 15) == 0)) ? 1 : 0;
-#define ADVHIP_FAST_CASE(ID, BM_, BN_, BK_)                                                                         \
-  case ADVHIP_ALGO_FAST_BASE + ID:                                                                                  \
-    if (nocheck) hipLaunchKernelGGL((conv3d_igemm_fast_kernel<BM_, BN_, BK_, false>), grid, dim3(256), 0, st, a);   \
-    else hipLaunchKernelGGL((conv3d_igemm_fast_kernel<BM_, BN_, BK_, true>), grid, dim3(256), 0, st, a);            \
-    break;
-#define ADVHIP_DMA_CASE(ID, BM_, BN_, BK_)                                                                        \
-  case ADVHIP_ALGO_DMA_BASE + ID:                                                                                 \
-    if (nocheck) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false>), grid, dim3(256), 0, st, a);  \
-    else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true>), grid, dim3(256), 0, st, a);           \
-    break;
-#define ADVHIP_DMA4_CASE(ID, BM_, BN_, BK_)                                                                          \
-  case ADVHIP_ALGO_DMA4_BASE + ID:                                                                                   \
-    if (nocheck) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, false, 4>), grid, dim3(256), 0, st, a);  \
-    else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<BM_, BN_, BK_, true, 4>), grid, dim3(256), 0, st, a);           \
-    break;
-#define ADVHIP_DMA2_CASE(ID, BM_, BN_, BK_)                                   \
-  case ADVHIP_ALGO_DMA2_BASE + ID:                                            \
-    launch_dma2<BM_, BN_, BK_>(nocheck, s16, grid, st, a);                    \
-    break;
-#define ADVHIP_BF16X3_CASE(ID, BN_)                                                                               \
-  case ADVHIP_ALGO_BF16X3_BASE + ID:                                                                               \
-    if (nocheck) hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<BN_, false>), grid, dim3(256), 0, st, a);          \
-    else hipLaunchKernelGGL((conv3d_igemm_bf16x3_kernel<BN_, true>), grid, dim3(256), 0, st, a);                   \
-    break;
-  if (avg_out != nullptr) {
-    // (a.a16 is always set here -- the rows are padded in the M index space -- so the compile-time a16 form applies)
-    hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_AVG, false, 2>), grid, dim3(256), 0, st, a);
-    return check_launch("conv3d + mean");
-  }
-  if (c.algo == ADVHIP_ALGO_MIXED_128x64) {
-    ADVHIP_REQUIRE(a.a16 != 0 && c.splits == 1 && !ln && dact_z == nullptr && y_preact == nullptr,
-                   "conv3d: ADVHIP_ALGO_MIXED_128x64 takes unsplit 1x1x1 stride-1 convs on 16-byte aligned rows without the MGFN epilogue operands "
-                   "(k=%d,%d,%d, splits=%d)", d->kt, d->kh, d->kw, c.splits);
-    // 128-row m-tiles, and how many of the last ones to cut into 64-row tiles: all the workgroups past the last whole round of
-    // resident slots (6 per CU) must be short ones -- cutting `c` tall m-tile rows adds c * tiles_n workgroups, so c >= rem / tiles_n.
-    // A launch that is below one round, on a round boundary or far into a round is the plain 128 x 64 launch.
-    const long long mt = (Mv + 127) / 128, tn = a.tiles_n, slots = 6ll * device_cus();
-    const long long rem = (mt * tn) % slots;
-    long long cut = (mt * tn > slots && rem > 0 && rem * 4 <= slots) ? (rem + tn - 1) / tn : 0;
-    if (cut > mt) cut = mt;
-    if (cut == 0) {
-      hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, false, 2, EPI_STD, false, 2>), grid, dim3(256), 0, st, a);
-      return check_launch("conv3d mixed (plain)");
-    }
-    const long long big_rows = (mt - cut) * 128, small_mt = (Mv - big_rows + 63) / 64;
-    a.mix_big = (int)((mt - cut) * tn);
-    a.mix_small = (int)(small_mt * tn);
-    a.mix_mbase = (int)big_rows;
-    hipLaunchKernelGGL(conv1x1_mixed_tail_kernel, dim3((unsigned)(a.mix_big + a.mix_small)), dim3(256), 0, st, a);
-    return check_launch("conv3d mixed tail");
-  }
-  if (is_persist(c.algo)) {
-    // workgroups that stay: `wgs_per_cu` per compute unit (a multiple of 8 in all, at most one per tile), each walking its share of the tiles
-    ADVHIP_REQUIRE(g.Kpad >= 16 * PERSIST_MIN_NK, "conv3d: the persistent kernels need K >= %d (%d k-tiles per output tile), got %d", 16 * PERSIST_MIN_NK,
-                   PERSIST_MIN_NK, g.K);
-    ADVHIP_REQUIRE(a.a16 != 0 && c.splits == 1 && !ln && dact_z == nullptr,
-                   "conv3d: the persistent kernels (algo %d) take unsplit 1x1x1 stride-1 convs on 16-byte aligned rows without the LayerNorm fold / "
-                   "GELU-backward operands (k=%d,%d,%d, splits=%d)", c.algo, d->kt, d->kh, d->kw, c.splits);
-    const long long nt = (long long)a.tiles_m * a.tiles_n;
-    long long g = (long long)persist_wgs_per_cu(c.algo) * device_cus();
-    if (g > nt) g = nt;
-    g = g / GFX950_XCDS * GFX950_XCDS;
-    if (g < GFX950_XCDS) g = GFX950_XCDS;
-    const dim3 pgrid((unsigned)g);
-    switch (persist_tile(c.algo)) {
-      case ADVHIP_ALGO_IGEMM_128x64: hipLaunchKernelGGL((conv1x1_persist_kernel<128, 64, 2>), pgrid, dim3(512), 0, st, a, GFX950_XCDS); break;
-      default: hipLaunchKernelGGL((conv1x1_persist_kernel<64, 64, 2>), pgrid, dim3(512), 0, st, a, GFX950_XCDS); break;
-    }
-    return check_launch("conv3d persistent");
-  }
-  switch (c.algo) {
-    case ADVHIP_ALGO_TSPAN_128x64:
-      if (tspan_bt == 4) hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_TSPAN4, false, 1>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((conv3d_igemm_dma_kernel<128, 64, 16, true, 2, EPI_TSPAN2, false, 1>), grid, dim3(256), 0, st, a);
-      break;
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_128x128, 128, 128, 16)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_128x64, 128, 64, 16)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_256x64, 256, 64, 16)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_64x64, 64, 64, 16)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_64x128, 64, 128, 16)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_128x64x32, 128, 64, 32)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_64x64x32, 64, 64, 32)
-    ADVHIP_DMA2_CASE(ADVHIP_ALGO_IGEMM_64x128x32, 64, 128, 32)
-    ADVHIP_BF16X3_CASE(ADVHIP_ALGO_IGEMM_128x128x32, 128)
-    ADVHIP_BF16X3_CASE(ADVHIP_ALGO_IGEMM_128x64x32, 64)
-    ADVHIP_DMA4_CASE(ADVHIP_ALGO_IGEMM_128x64, 128, 64, 16)
-    ADVHIP_DMA4_CASE(ADVHIP_ALGO_IGEMM_64x64, 64, 64, 16)
-    ADVHIP_DMA4_CASE(ADVHIP_ALGO_IGEMM_64x128, 64, 128, 16)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_128x128, 128, 128, 16)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_128x64, 128, 64, 16)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_64x64, 64, 64, 16)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_64x128, 64, 128, 16)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_128x64x32, 128, 64, 32)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_64x64x32, 64, 64, 32)
-    ADVHIP_DMA_CASE(ADVHIP_ALGO_IGEMM_64x128x32, 64, 128, 32)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_128x128, 128, 128, 16)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_128x64, 128, 64, 16)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_64x64, 64, 64, 16)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_64x128, 64, 128, 16)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_128x128x32, 128, 128, 32)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_128x64x32, 128, 64, 32)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_64x64x32, 64, 64, 32)
-    ADVHIP_FAST_CASE(ADVHIP_ALGO_IGEMM_64x128x32, 64, 128, 32)
-    case ADVHIP_ALGO_IGEMM_128x128: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<128, 128, 16>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_128x64: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<128, 64, 16>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_64x64: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<64, 64, 16>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_64x128: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<64, 128, 16>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_128x128x32: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<128, 128, 32>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_128x64x32: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<128, 64, 32>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_64x64x32: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<64, 64, 32>), grid, dim3(256), 0, st, a); break;
-    case ADVHIP_ALGO_IGEMM_64x128x32: hipLaunchKernelGGL((conv3d_igemm_f32_kernel<64, 128, 32>), grid, dim3(256), 0, st, a); break;
-    default:
-      set_error("conv3d: algo %d is not instantiated in this library", c.algo);
-      return ADVHIP_EINVAL;
-  }
-  if (int rc = check_launch("conv3d_igemm")) return rc;
-  if (c.splits > 1 && a.part == nullptr) {
-    const long long total = a.slab;
-    const int vec4 = a.vw == 4 ? 1 : 0;  // rows, slabs, residual and y all 16-byte aligned
-    const long long work = vec4 ? total / 4 : total;
-    const int rgrid = (int)std::min<long long>((work + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rgrid), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), scale,
-                       shift, residual, y, total, a.THWo, d->Cout, c.splits, d->relu, vec4);
-    return check_launch("splitk_reduce");
-  }
-  return ADVHIP_OK;
 }
 
 // ---- conv + max-pool in one launch (brick-ordered LDS-DMA kernel) ----------------------------------------------------
@@ -3560,39 +3633,16 @@ static int pool_out(int n, int k, int s) { return n >= k ? (n - k) / s + 1 : 0; 
 // shared argument set-up of the two pooling forms; `flat_hw`: present the (1x1x1, stride 1) conv as H = 1, W = H*W
 static int fill_pool_args(ConvArgs& a, const advhip_conv3d_desc* d, const Geometry& g, const float* x, int64_t x_batch_stride,
                           const float* w_packed, const int32_t* ktab, const float* scale, const float* shift, bool flat_hw) {
-  a.x = x; a.w = w_packed; a.ktab = reinterpret_cast<const int4*>(ktab);
-  a.scale = scale; a.shift = shift; a.res = nullptr; a.y = nullptr; a.y2 = nullptr; a.dact = nullptr;
-  a.ln_u = nullptr; a.ln_mu = nullptr; a.ln_rs = nullptr;
-  a.B = d->B; a.Cin = d->Cin; a.T = d->T; a.Cout = d->Cout;
-  a.H = flat_hw ? 1 : d->H; a.W = flat_hw ? d->H * d->W : d->W;
-  a.st = d->st; a.sh = d->sh; a.sw = d->sw; a.pt = d->pt; a.ph = d->ph; a.pw = d->pw;
-  a.To = g.To; a.Ho = flat_hw ? 1 : g.Ho; a.Wo = flat_hw ? g.Ho * g.Wo : g.Wo;
-  const long long x_dense = (long long)d->Cin * d->T * d->H * d->W;
-  const long long xbs = x_batch_stride > 0 ? x_batch_stride : x_dense;
-  ADVHIP_REQUIRE(xbs >= x_dense, "conv3d+pool: x batch stride %lld smaller than one sample (%lld)", xbs, x_dense);
-  const long long in_elems = (long long)(d->B - 1) * xbs + x_dense;
-  ADVHIP_REQUIRE(fast_ok(d, in_elems, (long long)g.Kpad * d->Cout) && g.M * d->Cout < (1ll << 32) && in_elems < (1ll << 31),
+  const XSpan xs = x_span(d, x_batch_stride);
+  ADVHIP_REQUIRE(xs.bstride >= xs.dense, "conv3d+pool: x batch stride %lld smaller than one sample (%lld)", xs.bstride, xs.dense);
+  ADVHIP_REQUIRE(fast_ok(d, xs.elems, (long long)g.Kpad * d->Cout) && g.M * d->Cout < (1ll << 32) && xs.elems < (1ll << 31),
                  "conv3d+pool: tensor too large for 32-bit offsets");
-  a.M = (int)g.M;
-  a.x_bstride = (int)xbs;
-  a.Kpad = g.Kpad;
-  a.HWo = g.Ho * g.Wo; a.THWo = g.To * a.HWo;
-  a.HW = d->H * d->W; a.THW = d->T * a.HW;
-  a.relu = d->relu;
-  a.vw = 1;
-  a.a16 = 0;
-  a.MP = a.THWo;
-  a.dTHWo = FastDiv::make((unsigned)a.THWo); a.dHWo = FastDiv::make((unsigned)a.HWo); a.dWo = FastDiv::make((unsigned)a.Wo);
-  a.kt_ = d->kt; a.kh_ = d->kh; a.kw_ = d->kw;
-  a.pad_off = d->pt * d->H * d->W + d->ph * d->W + d->pw;
-  a.x_bytes = (unsigned)((in_elems + a.pad_off) * 4);
-  a.w_bytes = (unsigned)((long long)g.Kpad * d->Cout * 4);
-  a.splits = 1; a.slab = 0; a.part = nullptr; a.cnt = nullptr; a.part_bytes = 0;
+  fill_conv_args(a, d, g, x, x_batch_stride, w_packed, ktab, scale, shift);
+  if (flat_hw) { a.H = 1; a.W = a.HW; a.Ho = 1; a.Wo = a.HWo; a.dWo = FastDiv::make((unsigned)a.Wo); }
+  a.vw = 1; a.splits = 1;
   a.tiles_n = d->Cout / 64;
   a.dTilesN = FastDiv::make((unsigned)a.tiles_n);
   a.dSplits = FastDiv::make(1u);
-  a.bt_off = 0; a.ws_nbh = 0; a.fr_n0 = 0; a.fr_skip = 0; a.ws_frame1 = 0; a.ws_nbwin = 0;
-  for (unsigned long long& m : a.fr_ktiles) m = 0;
   return ADVHIP_OK;
 }
 
@@ -3712,7 +3762,7 @@ static int conv_pool233(const char* who, const advhip_conv3d_desc* d, const Geom
   const long long y_dense = (long long)d->Cout * Tp * Hp * Wp;
   const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
   ADVHIP_REQUIRE(ybs >= y_dense, "%s: y batch stride %lld smaller than one pooled sample (%lld)", who, ybs, y_dense);
-  ConvArgs a;
+  ConvArgs a{};
   if (int rc = fill(a)) return rc;
   a.y = reinterpret_cast<float*>(workspace);
   a.y_bstride = 0; a.Tp = Tp; a.relu = 1;
@@ -4093,7 +4143,7 @@ extern "C" int advhip_conv3d_bn_act_maxpool211_f32(const advhip_conv3d_desc* d, 
   const long long y_dense = (long long)d->Cout * Tp * g.Ho * g.Wo;
   const long long ybs = y_batch_stride > 0 ? y_batch_stride : y_dense;
   ADVHIP_REQUIRE(ybs >= y_dense && (long long)d->B * ybs < (1ll << 32), "conv3d+pool211: bad y batch stride %lld (one pooled sample: %lld)", ybs, y_dense);
-  ConvArgs a;
+  ConvArgs a{};
   if (int rc = fill_pool_args(a, d, g, x, x_batch_stride, w_packed, ktab, scale, shift, true)) return rc;
   a.res = residual; a.y = y; a.y_bstride = (int)ybs; a.Tp = Tp;
   set_bricks(a, Tp, 1, (a.Wo + 63) / 64);
@@ -4127,7 +4177,7 @@ static int gemm_nt_launch(const float* A, const float* B, float* C, int32_t M, i
   ADVHIP_REQUIRE(splits >= 1 && splits <= K / 16 && (splits == 1 || workspace != nullptr || slab_stride >= (long long)(M - 1) * ldc + N),
                  "gemm_nt: bad split count %d", splits);
   ADVHIP_REQUIRE(tile >= 0 && tile <= 3, "gemm_nt: tile id %d (0 auto, 1 64x64, 2 128x64, 3 128x128)", tile);
-  GemmKKArgs g;
+  GemmKKArgs g{};
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
   g.lda = (int)lda; g.ldb = (int)ldb; g.ldc = (int)ldc;
   g.a_bytes = (unsigned)a_bytes; g.b_bytes = (unsigned)b_bytes;
@@ -4206,7 +4256,7 @@ extern "C" int advhip_gemm_nt_group_slabs_f32(const advhip_nt_item* items, int32
   using namespace advhip;
   ADVHIP_REQUIRE(items && n_items > 0 && K > 0 && K % 16 == 0 && splits >= 1 && splits <= K / 16, "gemm_nt_group: bad arguments (K=%d, splits=%d)", K, splits);
   for (int base = 0; base < n_items; base += NT_GROUP_MAX) {
-    NtGroupArgs ga;
+    NtGroupArgs ga{};
     ga.n = std::min(NT_GROUP_MAX, n_items - base);
     ga.K = K; ga.splits = splits; ga.pad = 0; ga.slab = slab_stride;
     long long wg = 0;

@@ -94,6 +94,16 @@ extern "C" {
  * product is 0 * w).  Applies to kt = 5, pt = 2, st = 2, an even output T and an even number of 4-row bricks along h; any other
  * geometry runs the single launch.  Any other algo value on that entry point: the single launch. */
 #define ADVHIP_ALGO_STEM_BORDER 256
+/* Kernel families, as advhip_conv3d_algo_info reports them (DMA3 is ADVHIP_ALGO_DMA_BASE's 3-deep ring). */
+#define ADVHIP_FAMILY_GENERIC 0
+#define ADVHIP_FAMILY_FAST 1
+#define ADVHIP_FAMILY_DMA3 2
+#define ADVHIP_FAMILY_DMA4 3
+#define ADVHIP_FAMILY_BF16X3 4
+#define ADVHIP_FAMILY_DMA2 5
+#define ADVHIP_FAMILY_TSPAN 6
+#define ADVHIP_FAMILY_MIXED 7
+#define ADVHIP_FAMILY_PERSIST 8
 
 typedef struct advhip_conv3d_desc {
   int32_t B, Cin, T, H, W;    /* input  (B, Cin, T, H, W) */
@@ -120,6 +130,11 @@ int advhip_conv3d_out_dims(const advhip_conv3d_desc* d, int32_t* To, int32_t* Ho
 
 /* Rows of the packed weight matrix: K = Cin*kt*kh*kw rounded up to a multiple of 32. */
 int advhip_conv3d_packed_rows(const advhip_conv3d_desc* d);
+
+/* What an implicit-GEMM algorithm id means: its kernel family (ADVHIP_FAMILY_*) and its block tile BM x BN x BK (outputs may be
+ * NULL).  ADVHIP_EINVAL ("not instantiated") for an id this library has no kernel for.  An ADVHIP_ALGO_TFOLD_BASE id reports
+ * the ADVHIP_ALGO_DMA2_BASE kernel its folded launch runs, ADVHIP_ALGO_AUTO the LDS-DMA 64 x 64 x 16 kernel it prefers.  Host only. */
+int advhip_conv3d_algo_info(int32_t algo, int32_t* family, int32_t* BM, int32_t* BN, int32_t* BK);
 
 /* Pack torch-layout weights w[Cout][Cin][kt][kh][kw] into the kernels' [Kpad][Cout] layout
  * (row k = ((ci*kt+dt)*kh+dh)*kw+dw, zero rows above K).  Done once per layer at load time: the
