@@ -69,9 +69,127 @@ __global__ __launch_bounds__(256) void crop_mean_last_kernel(const float* __rest
   latest[cam_ids[v]] = s / (float)ncrops;
 }
 
+// ---- live frames (include/advhip.h: "live frames"): per-camera rings of the last R resized uint8 frames.  Two copies of bits in
+// gather_batch_kernel's form (mil.hip): a frame is cut into chunks of FRAME_CHUNK elements of V, blockIdx.x = chunk, blockIdx.y =
+// frame row; every lane issues its FRAME_UNROLL loads before its first store; all byte offsets are 64-bit.  V is u32x4 when both
+// pointers and frame_bytes are multiples of 16 (the working frame, 256 x 340 x 3 = 261 120 bytes, is), one dword when they are
+// multiples of 4, else one byte -- the host decides, so every frame and every ring slot starts at a multiple of sizeof(V): never
+// an unaligned wide access.
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+constexpr int FRAME_UNROLL = 4;
+constexpr int FRAME_CHUNK = 256 * FRAME_UNROLL;
+
+template <typename V>
+__device__ __forceinline__ void frame_copy_chunk(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, long long frame_bytes) {
+  const long long nv = frame_bytes / (long long)sizeof(V);  // a frame in elements of V
+  const V* __restrict__ s = reinterpret_cast<const V*>(src);
+  V* __restrict__ d = reinterpret_cast<V*>(dst);
+  const long long e0 = (long long)blockIdx.x * FRAME_CHUNK + threadIdx.x;
+  V v[FRAME_UNROLL] = {};
+#pragma unroll
+  for (int u = 0; u < FRAME_UNROLL; ++u) {
+    const long long e = e0 + u * 256;
+    if (e < nv) v[u] = s[e];
+  }
+#pragma unroll
+  for (int u = 0; u < FRAME_UNROLL; ++u) {
+    const long long e = e0 + u * 256;
+    if (e < nv) d[e] = v[u];
+  }
+}
+
+// Frame i into slot counts[c] % R of camera c = cam_ids[i].  The count is only read here: ring_advance_kernel moves it.
+template <typename V>
+__global__ __launch_bounds__(256) void frame_ring_push_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ cam_ids,
+                                                              unsigned char* __restrict__ ring, const long long* __restrict__ counts, int n_cam, int R,
+                                                              long long frame_bytes) {
+  const long long i = blockIdx.y;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;
+  const long long count = counts[c];
+  if (count < 0) return;
+  frame_copy_chunk<V>(frames + i * frame_bytes, ring + ((long long)c * R + count % R) * frame_bytes, frame_bytes);
+}
+
+// dst row v * fpc + t = entry t of listed camera v's window: the frame in slot (count + t * frame_step) % R.
+template <typename V>
+__global__ __launch_bounds__(256) void frame_ring_windows_kernel(const unsigned char* __restrict__ ring, const long long* __restrict__ counts,
+                                                                 const int* __restrict__ cam_ids, unsigned char* __restrict__ dst, int n_cam, int R,
+                                                                 long long frame_bytes, int fpc, int frame_step) {
+  const long long row = blockIdx.y;
+  const int v = (int)(row / fpc), t = (int)(row % fpc);
+  const int c = cam_ids[v];
+  if (c < 0 || c >= n_cam) return;
+  const long long count = counts[c];
+  if (count < R) return;  // no window yet: its rows stay as they are
+  const long long slot = (count + (long long)t * frame_step) % R;
+  frame_copy_chunk<V>(ring + ((long long)c * R + slot) * frame_bytes, dst + row * frame_bytes, frame_bytes);
+}
+
+// The access width of a frame copy from everything that enters an address: 16, 4 or 1 bytes.
+inline int frame_access_bytes(const void* a, const void* b, long long frame_bytes) {
+  const unsigned long long bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (unsigned long long)frame_bytes;
+  return (bits & 15) == 0 ? 16 : (bits & 3) == 0 ? 4 : 1;
+}
+
 }  // namespace advhip
 
 using namespace advhip;
+
+extern "C" int advhip_frame_ring_push_u8(const uint8_t* frames, const int32_t* cam_ids, uint8_t* ring, int64_t* counts, int32_t n, int32_t n_cam,
+                                         int32_t R, int64_t frame_bytes, void* stream) {
+  ADVHIP_REQUIRE(frames && cam_ids && ring && counts, "frame_ring_push: null pointer");
+  ADVHIP_REQUIRE(n > 0 && n_cam > 0 && R > 0 && frame_bytes > 0, "frame_ring_push: bad shape (n=%d n_cam=%d R=%d frame_bytes=%lld)", n, n_cam, R,
+                 (long long)frame_bytes);
+  const int width = frame_access_bytes(frames, ring, frame_bytes);
+  const long long chunks = (frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK;
+  ADVHIP_REQUIRE(n <= 65535 && chunks * n * 256 < (1ll << 32), "frame_ring_push: %d rows of %lld bytes are outside the launch grid", n,
+                 (long long)frame_bytes);
+  const dim3 grid((unsigned)chunks, (unsigned)n);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, frames, (const int*)cam_ids, ring, (const long long*)counts, (int)n_cam, (int)R,
+                       (long long)frame_bytes);
+  };
+  if (width == 16)
+    launch(frame_ring_push_kernel<u32x4>);
+  else if (width == 4)
+    launch(frame_ring_push_kernel<unsigned>);
+  else
+    launch(frame_ring_push_kernel<unsigned char>);
+  const int rc = check_launch("frame_ring_push");
+  if (rc != ADVHIP_OK) return rc;
+  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (long long*)counts,
+                     (int)n, (int)n_cam);
+  return check_launch("frame_ring_push (counts)");
+}
+
+extern "C" int advhip_frame_ring_windows_u8(const uint8_t* ring, const int64_t* counts, const int32_t* cam_ids, uint8_t* dst, int32_t nb,
+                                            int32_t n_cam, int32_t R, int64_t frame_bytes, int32_t frames_per_clip, int32_t frame_step,
+                                            void* stream) {
+  ADVHIP_REQUIRE(ring && counts && cam_ids && dst, "frame_ring_windows: null pointer");
+  ADVHIP_REQUIRE(nb > 0 && n_cam > 0 && R > 0 && frame_bytes > 0 && frames_per_clip > 0 && frame_step > 0,
+                 "frame_ring_windows: bad shape (nb=%d n_cam=%d R=%d frame_bytes=%lld frames_per_clip=%d frame_step=%d)", nb, n_cam, R,
+                 (long long)frame_bytes, frames_per_clip, frame_step);
+  ADVHIP_REQUIRE((long long)frames_per_clip * frame_step == R, "frame_ring_windows: R=%d is not frames_per_clip * frame_step = %d * %d", R,
+                 frames_per_clip, frame_step);
+  const long long rows = (long long)nb * frames_per_clip;
+  const int width = frame_access_bytes(ring, dst, frame_bytes);
+  const long long chunks = (frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK;
+  ADVHIP_REQUIRE(rows <= 65535 && chunks * rows * 256 < (1ll << 32), "frame_ring_windows: %lld rows of %lld bytes are outside the launch grid", rows,
+                 (long long)frame_bytes);
+  const dim3 grid((unsigned)chunks, (unsigned)rows);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, ring, (const long long*)counts, (const int*)cam_ids, dst, (int)n_cam, (int)R,
+                       (long long)frame_bytes, (int)frames_per_clip, (int)frame_step);
+  };
+  if (width == 16)
+    launch(frame_ring_windows_kernel<u32x4>);
+  else if (width == 4)
+    launch(frame_ring_windows_kernel<unsigned>);
+  else
+    launch(frame_ring_windows_kernel<unsigned char>);
+  return check_launch("frame_ring_windows");
+}
 
 extern "C" int advhip_ring_push_f32(const float* feats, const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam,
                                     int32_t ncrops, int32_t W, int32_t C, void* stream) {

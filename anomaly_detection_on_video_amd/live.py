@@ -17,7 +17,14 @@ no torch arithmetic.  CUDA tensors only; no fallback.
 
 With `events=` every score also feeds each listed camera's newest clip score to an events.LiveEventTracker (`live.events`: the
 streaming form of events.find_events' rule, one more small launch on `latest` as it is); the steady step still uploads nothing,
-synchronises nothing and dispatches no torch arithmetic."""
+synchronises nothing and dispatches no torch arithmetic.
+
+    lf = LiveFrames(n_cameras, frame_hw=(256, 340), frames_per_clip=16, clip_stride=8)
+    live.step_camera_frames(backbone, lf, cams, frames, resize=256, crops="center_flip")   # None until a clip is due
+
+`LiveFrames` is the front end: per-camera rings of the last `span` resized uint8 frames, one decoded frame per camera and push,
+and the clips that are due gathered in one launch into the buffer I3Res50.forward_frames reads -- each one window w of the
+camera's frames as an offline video, byte for byte."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -51,6 +58,164 @@ class _Lru:
         if len(self.items) > self.entries:
             self.items.popitem(last=False)
         return val
+
+
+def _checked_cams(cams, what: str, n_cameras: int, seen, unit: str) -> Tuple[int, ...]:
+    """`cams` as a tuple of distinct host ints in [0, n_cameras); `seen` holds the tuples checked before (the id cache's keys)."""
+    if type(cams) is tuple and all(type(c) is int for c in cams) and cams in seen:
+        return cams  # (a camera set seen before was checked then)
+    try:
+        cams = tuple(cams)
+    except TypeError:
+        raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
+    if not cams:
+        raise HipExtensionError(f"{what}: an empty list of cameras")
+    for c in cams:
+        if isinstance(c, bool) or torch.is_tensor(c) or int(c) != c:
+            raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
+        if not 0 <= int(c) < n_cameras:
+            raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {n_cameras})")
+    cams = tuple(int(c) for c in cams)
+    if len(set(cams)) != len(cams):
+        dup = sorted(c for c in set(cams) if cams.count(c) > 1)
+        raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one {unit} per camera and call")
+    return cams
+
+
+class LiveFrames:
+    """The front end of live scoring: per-camera rings of the last `span` resized uint8 frames on the device, and the clips that
+    are due gathered from them in one launch (include/advhip.h: "live frames").
+
+        lf = LiveFrames(n_cameras, frame_hw=(256, 340), frames_per_clip=16, frame_step=None, clip_stride=None, device="cuda:0")
+        due = lf.push(cams, frames, resize=256)   # one new decoded frame per listed camera -> the cameras whose clip is now due
+        clips = lf.windows(due)                   # (len(due) * frames_per_clip, FH, FW, 3) uint8: what forward_frames reads
+
+    span = frames_per_clip * frame_step; the frame pushed when a camera's count is k lies in slot k % span.  A clip is due after
+    the push that brings a camera's count to k iff k >= span and (k - span) % clip_stride == 0, and it is window (k - span) /
+    clip_stride of the camera's frames taken as an offline video (frames[w * s : w * s + span : d]) byte for byte, so features and
+    scores are the offline ones.  No LoopPad runs live: a camera below `span` frames has no clip.  `frame_step` and `clip_stride`
+    are ops.resolve_sampling's (None: 1 and the span).  The state is the ring (n_cameras, span, FH, FW, 3), the counts with a
+    mirror on the host, one clip buffer (n_cameras * frames_per_clip, FH, FW, 3) -- the ring's size at frame_step 1 -- and one
+    staging buffer (n_cameras, FH, FW, 3) the resize writes to.  Device id vectors are cached by their checked tuples: a push of
+    device frames at ring size + windows on a repeated camera set uploads nothing, synchronises nothing and dispatches no torch
+    arithmetic.  CUDA tensors only; no fallback."""
+
+    MAX_ROWS = 65535  # frame rows of one launch (the grid's second dimension)
+
+    def __init__(self, n_cameras: int, frame_hw=(256, 340), frames_per_clip: int = 16, frame_step: Optional[int] = None,
+                 clip_stride: Optional[int] = None, device="cuda:0"):
+        from . import ops
+
+        try:
+            fh, fw = frame_hw
+        except (TypeError, ValueError):
+            raise HipExtensionError(f"LiveFrames: frame_hw = {frame_hw!r} is not a pair (FH, FW)") from None
+        for name, v in (("n_cameras", n_cameras), ("frame_hw[0]", fh), ("frame_hw[1]", fw), ("frames_per_clip", frames_per_clip)):
+            if isinstance(v, bool) or torch.is_tensor(v) or int(v) != v or int(v) < 1:
+                raise HipExtensionError(f"LiveFrames: {name} = {v!r} is not an integer >= 1")
+        self.n_cameras, self.frame_hw, self.frames_per_clip = int(n_cameras), (int(fh), int(fw)), int(frames_per_clip)
+        self.clip_stride, _, self.frame_step = ops.resolve_sampling(self.frames_per_clip, clip_stride, None, frame_step)
+        self.span = self.frames_per_clip * self.frame_step
+        if self.n_cameras * self.frames_per_clip > self.MAX_ROWS:
+            raise HipExtensionError(f"LiveFrames: {self.n_cameras} cameras x {self.frames_per_clip} frames per clip is above the {self.MAX_ROWS} frame "
+                                    f"rows one gather launch takes")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise HipExtensionError(f"LiveFrames: device '{self.device}': the rings live on the GPU (there is no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        frame = self.frame_hw + (3,)
+        self.ring = torch.zeros((self.n_cameras, self.span) + frame, dtype=torch.uint8, device=self.device)
+        self._counts = torch.zeros((self.n_cameras,), dtype=torch.int64, device=self.device)
+        self._host = [0] * self.n_cameras
+        self._clips = torch.empty((self.n_cameras * self.frames_per_clip,) + frame, dtype=torch.uint8, device=self.device)
+        self._staging = torch.empty((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
+        self._ids = _Lru(lambda cams: torch.tensor(cams, dtype=torch.int32).to(self.device))  # keyed by checked tuples only
+
+    @property
+    def counts(self) -> torch.Tensor:
+        """Frames pushed so far per camera: int64 (n_cameras,) on the device."""
+        return self._counts
+
+    @property
+    def counts_host(self) -> Tuple[int, ...]:
+        """The same numbers on the host, kept by push / reset: nothing is read back."""
+        return tuple(self._host)
+
+    def _check_cams(self, cams, what: str) -> Tuple[int, ...]:
+        return _checked_cams(cams, what, self.n_cameras, self._ids.items, "frame")
+
+    def is_due(self, count: int) -> bool:
+        """The due rule: a clip is due at a camera's count k iff k >= span and (k - span) % clip_stride == 0."""
+        return count >= self.span and (count - self.span) % self.clip_stride == 0
+
+    def _source_hw(self, frames: torch.Tensor, pixel_format, surface) -> Optional[Tuple[int, int]]:
+        """(H, W) of the frames resize_u8 is about to read, or None where their form is not one it takes (it says so itself)."""
+        from . import resize as rz
+
+        pf = rz.resolve_pixel_format(pixel_format)
+        if pf is None:
+            return tuple(frames.shape[1:3]) if surface is None and frames.dim() == 4 else None
+        if surface is not None:
+            if frames.dim() != 2:
+                return None
+            sf = rz.resolve_surface(surface, pf, frames.shape[1])
+            return sf.height, sf.width
+        return rz.frame_hw(frames.shape) if frames.dim() == 3 else None
+
+    def push(self, cams: Sequence[int], frames: torch.Tensor, resize=None, resample="bilinear", pixel_format=None, surface=None) -> Tuple[int, ...]:
+        """One new decoded frame for each camera of `cams` (distinct host ints); `frames` uint8 with len(cams) leading rows, on the
+        host (copied non-blocking on the current stream) or on the device.  Without `resize`: (n, FH, FW, 3), already at ring
+        size.  With `resize` (resize_u8's `size`): whatever resize_u8 takes -- packed RGB (n, H, W, 3), 4:2:0 (n, 3H/2, W) with
+        `pixel_format`, (n, frame_bytes) with `surface` -- resized into the staging buffer; a result of another size than frame_hw
+        is refused before anything is launched.  All frames of one call share a geometry.  -> the listed cameras whose clip
+        became due with this push, in `cams` order, decided on the host mirror of the counts."""
+        from . import resize as rz
+
+        what = "LiveFrames.push"
+        cams = self._check_cams(cams, what)
+        n = len(cams)
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 2 or frames.shape[0] != n:
+            raise HipExtensionError(f"{what}: frames must be a torch.uint8 tensor with {n} leading rows, one frame per listed camera, got "
+                                    f"{getattr(frames, 'dtype', type(frames).__name__)} {tuple(getattr(frames, 'shape', ()))}")
+        if resize is None:
+            if pixel_format is not None or surface is not None:
+                raise HipExtensionError(f"{what}: pixel_format / surface describe frames to be converted: give resize= (the ring's size {self.frame_hw} "
+                                        f"for frames already that large)")
+            want = (n,) + self.frame_hw + (3,)
+            if tuple(frames.shape) != want:
+                raise HipExtensionError(f"{what}: frames must be {want} (frames at ring size; resize= takes decoded frames), got {tuple(frames.shape)}")
+        else:
+            hw = self._source_hw(frames, pixel_format, surface)
+            if hw is not None and rz.output_size(hw[0], hw[1], resize) != self.frame_hw:
+                raise HipExtensionError(f"{what}: resize={resize!r} of {hw[0]} x {hw[1]} frames gives {rz.output_size(hw[0], hw[1], resize)}, the rings "
+                                        f"hold {self.frame_hw} frames")
+        if not frames.is_cuda:
+            frames = frames.to(self.device, non_blocking=True)
+        if resize is not None:
+            frames = rz.resize_u8(frames, resize, resample, out=self._staging[:n], pixel_format=pixel_format, surface=surface)
+        mil_ops.frame_ring_push(frames, self._ids(cams), self.ring, self._counts)
+        for c in cams:
+            self._host[c] += 1
+        return tuple(c for c in cams if self.is_due(self._host[c]))
+
+    def windows(self, cams: Sequence[int]) -> torch.Tensor:
+        """The newest windows of the listed cameras, back to back in `cams` order: (len(cams) * frames_per_clip, FH, FW, 3) uint8,
+        every frame_step-th frame of each camera's last `span`, oldest first -- one launch into the owned clip buffer, of which
+        the result is a view (the next call overwrites it).  Every listed camera must have `span` frames."""
+        cams = self._check_cams(cams, "LiveFrames.windows")
+        short = [c for c in cams if self._host[c] < self.span]
+        if short:
+            raise HipExtensionError(f"LiveFrames.windows: cameras {short} have fewer than span = {self.span} frames: no clip yet (no LoopPad runs live)")
+        dst = self._clips[: len(cams) * self.frames_per_clip]
+        return mil_ops.frame_ring_windows(self.ring, self._counts, self._ids(cams), dst, self.frames_per_clip, self.frame_step)
+
+    def reset(self, cams: Sequence[int]) -> None:
+        """The listed cameras start over at count 0: their rings' old frames can no longer reach a window."""
+        cams = self._check_cams(cams, "LiveFrames.reset")
+        self._counts[self._ids(cams).long()] = 0
+        for c in cams:
+            self._host[c] = 0
 
 
 class LiveScorer:
@@ -131,24 +296,7 @@ class LiveScorer:
         return tuple(self._host)
 
     def _check_cams(self, cams, what: str) -> Tuple[int, ...]:
-        if type(cams) is tuple and all(type(c) is int for c in cams) and cams in self._ids.items:
-            return cams  # (a camera set seen before was checked then)
-        try:
-            cams = tuple(cams)
-        except TypeError:
-            raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
-        if not cams:
-            raise HipExtensionError(f"{what}: an empty list of cameras")
-        for c in cams:
-            if isinstance(c, bool) or torch.is_tensor(c) or int(c) != c:
-                raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
-            if not 0 <= int(c) < self.n_cameras:
-                raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {self.n_cameras})")
-        cams = tuple(int(c) for c in cams)
-        if len(set(cams)) != len(cams):
-            dup = sorted(c for c in set(cams) if cams.count(c) > 1)
-            raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one clip per camera and call")
-        return cams
+        return _checked_cams(cams, what, self.n_cameras, self._ids.items, "clip")
 
     def push(self, cams: Sequence[int], feats: torch.Tensor) -> None:
         """One new clip for each camera of `cams` (distinct host ints): feats (len(cams), ncrops, channels) fp32 on the device."""
@@ -230,3 +378,43 @@ class LiveScorer:
             raise HipExtensionError(f"LiveScorer.step_frames: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
         self.push(cams, feats.reshape(len(cams), self.ncrops, self.channels))
         return self.score(cams)
+
+    _PUSH_KW, _FORWARD_KW = ("resize", "resample", "pixel_format", "surface"), ("crop", "crops", "normalize")
+
+    def step_camera_frames(self, backbone, live_frames: LiveFrames, cams: Sequence[int], frames: torch.Tensor, **kw) -> Optional[LiveScores]:
+        """One new decoded frame per listed camera, through to the scores: `live_frames.push(cams, frames, ...)`; when no clip
+        became due, None, with nothing else launched; else `live_frames.windows(due)`, backbone.forward_frames on those
+        back-to-back clips (the gather has applied clip_stride and frame_step already), `push(due, feats)` and `score(due)`.
+        `kw`: push's resize / resample / pixel_format / surface and forward_frames' crop / crops / normalize, with len(crops) =
+        ncrops; frames_per_clip, frame_step and clip_stride are the LiveFrames' own and refused here.  The features and scores of
+        a camera are those of its frames as an offline video, window by window.  With `events=` every due window is one sample
+        of the camera's series: a sample is then clip_stride frames, not span frames, and EventSpec's lengths (smooth, merge_gap,
+        min_len) count such samples."""
+        from . import ops
+
+        what = "LiveScorer.step_camera_frames"
+        if not isinstance(live_frames, LiveFrames):
+            raise HipExtensionError(f"{what}: live_frames must be a LiveFrames, got {type(live_frames).__name__}")
+        own = [k for k in ("frames_per_clip", "frame_step", "clip_stride") if k in kw]
+        if own:
+            raise HipExtensionError(f"{what}: {', '.join(own)} belong to the LiveFrames (frames_per_clip {live_frames.frames_per_clip}, frame_step "
+                                    f"{live_frames.frame_step}, clip_stride {live_frames.clip_stride}): they are set where the rings are built")
+        unknown = [k for k in kw if k not in self._PUSH_KW + self._FORWARD_KW]
+        if unknown:
+            raise HipExtensionError(f"{what}: unknown arguments {unknown}: push takes {list(self._PUSH_KW)}, forward_frames {list(self._FORWARD_KW)}")
+        if live_frames.n_cameras != self.n_cameras or live_frames.device != self.device:
+            raise HipExtensionError(f"{what}: the LiveFrames holds {live_frames.n_cameras} cameras on {live_frames.device}, the LiveScorer "
+                                    f"{self.n_cameras} on {self.device}")
+        crops = ops.resolve_crops(kw.get("crops"))
+        if len(crops) != self.ncrops:
+            raise HipExtensionError(f"{what}: {len(crops)} crops, the rings hold {self.ncrops}")
+        due = live_frames.push(cams, frames, **{k: kw[k] for k in self._PUSH_KW if k in kw})
+        if not due:
+            return None
+        clips = live_frames.windows(due)
+        feats = backbone.forward_frames(clips, 0, len(due) * self.ncrops, frames_per_clip=live_frames.frames_per_clip,
+                                        **{k: kw[k] for k in self._FORWARD_KW if k in kw})
+        if feats.numel() != len(due) * self.ncrops * self.channels:
+            raise HipExtensionError(f"{what}: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
+        self.push(due, feats.reshape(len(due), self.ncrops, self.channels))
+        return self.score(due)

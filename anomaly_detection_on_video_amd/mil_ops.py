@@ -312,6 +312,55 @@ def crop_mean_last(scores: torch.Tensor, lens: torch.Tensor, cam_ids: torch.Tens
     return latest
 
 
+FRAME_RING_CHUNK = 1024  # elements of the access width (16, 4 or 1 bytes) one workgroup of the two launches below copies (csrc/live.hip: FRAME_CHUNK)
+
+
+def _frame_ring(ring, what: str):
+    """(ring, n_cam, R, frame_bytes) of a frame ring: uint8 (n_cam, R, ...) with any trailing dims (a frame is what lies behind R)."""
+    if not torch.is_tensor(ring) or ring.dim() < 3:
+        raise _lib.HipExtensionError(f"{what}: ring must be a torch.uint8 tensor (n_cam, R, frame_bytes) or (n_cam, R, FH, FW, 3) on the GPU, got "
+                                     f"{tuple(getattr(ring, 'shape', ())) or type(ring).__name__}")
+    ring = _live_arg(ring, torch.uint8, (None,) * ring.dim(), what, "ring")
+    n_cam, R = ring.shape[:2]
+    return ring, n_cam, R, ring.numel() // (n_cam * R)
+
+
+def frame_ring_push(frames: torch.Tensor, cam_ids: torch.Tensor, ring: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """One new frame for each of n distinct cameras into their frame rings (include/advhip.h: live frames): ring uint8 (n_cam, R,
+    frame_bytes) -- or (n_cam, R, FH, FW, 3), a frame is what lies behind R --, frames uint8 (n,) + the ring's frame shape, cam_ids
+    int32 (n,), counts int64 (n_cam,), all on the device.  Camera c = cam_ids[i] gets ring[c, counts[c] % R] = frames[i]; then
+    counts[c] += 1.  An id outside [0, n_cam) writes nothing; the same id twice is an error this wrapper cannot see.  A copy of
+    bits by 16-, 4- or 1-byte accesses, whichever the pointers and the frame size allow.  Two launches, no autograd."""
+    what = "frame_ring_push"
+    ring, n_cam, R, fb = _frame_ring(ring, what)
+    frames = _live_arg(frames, torch.uint8, (None,) + tuple(ring.shape[2:]), what, "frames", ring.device)
+    cam_ids = _live_arg(cam_ids, torch.int32, (frames.shape[0],), what, "cam_ids", ring.device)
+    counts = _live_arg(counts, torch.int64, (n_cam,), what, "counts", ring.device)
+    require_gpu(ring)  # (the current device)
+    check(_lib.load().advhip_frame_ring_push_u8(ptr(frames), ptr(cam_ids), ptr(ring), ptr(counts), frames.shape[0], n_cam, R, fb, stream()), what)
+    return ring
+
+
+def frame_ring_windows(ring: torch.Tensor, counts: torch.Tensor, cam_ids: torch.Tensor, dst: torch.Tensor, frames_per_clip: int,
+                       frame_step: int) -> torch.Tensor:
+    """The newest windows of the nb listed cameras as back-to-back clips, one launch: dst uint8 (nb * frames_per_clip,) + the ring's
+    frame shape, cam_ids int32 (nb,); rows [v * fpc, (v + 1) * fpc) are entries t = 0 .. fpc - 1 of camera c = cam_ids[v], entry t
+    from slot (counts[c] + t * frame_step) % R, oldest first (R = frames_per_clip * frame_step, anything else is refused).  The rows
+    of a camera below R frames, or of an id outside [0, n_cam), stay as they are.  A copy of bits.  No autograd."""
+    what = "frame_ring_windows"
+    ring, n_cam, R, fb = _frame_ring(ring, what)
+    for name, v in (("frames_per_clip", frames_per_clip), ("frame_step", frame_step)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise _lib.HipExtensionError(f"{what}: {name} {v!r} is not a positive integer")
+    counts = _live_arg(counts, torch.int64, (n_cam,), what, "counts", ring.device)
+    cam_ids = _live_arg(cam_ids, torch.int32, (None,), what, "cam_ids", ring.device)
+    dst = _live_arg(dst, torch.uint8, (cam_ids.shape[0] * frames_per_clip,) + tuple(ring.shape[2:]), what, "dst", ring.device)
+    require_gpu(ring)
+    check(_lib.load().advhip_frame_ring_windows_u8(ptr(ring), ptr(counts), ptr(cam_ids), ptr(dst), cam_ids.shape[0], n_cam, R, fb, frames_per_clip,
+                                                   frame_step, stream()), what)
+    return dst
+
+
 LIVE_EVENTS_STATE = ("ring", "samples", "cand_int", "cand_peak", "cand_sum", "alert", "open_start", "log_int", "log_f", "emitted")
 
 

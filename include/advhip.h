@@ -844,6 +844,35 @@ int advhip_ring_windows_f32(const float* ring, const int64_t* counts, const int3
 int advhip_crop_mean_last_f32(const float* scores, const int32_t* lens, const int32_t* cam_ids, float* latest, int32_t nb,
                               int32_t ncrops, int32_t Tmax, void* stream);
 
+/* --- live frames: per-camera rings of resized uint8 frames, due clips gathered on the device -------
+ * State owned by the caller, all on the device: ring uint8 (n_cam, R, frame_bytes) = every camera's last R frames (resized,
+ * packed RGB: frame_bytes = FH * FW * 3), counts int64 (n_cam,) = the frames pushed so far per camera.  R = frames_per_clip *
+ * frame_step is the span of a clip.
+ * THE SLOT RULE: the frame pushed when a camera's count is k lies in slot k % R.
+ * THE WINDOW RULE: a camera at count k >= R has a window of frames_per_clip entries, oldest first; entry t is frame number
+ * k - R + t * frame_step of the camera's series and lies in slot (k + t * frame_step) % R.
+ * THE DUE RULE (the host's, no kernel knows it): a clip is due after the push that brings a camera's count to k iff k >= R and
+ * (k - R) % clip_stride == 0, 1 <= clip_stride <= R.  It is window w = (k - R) / clip_stride of the camera's series taken as an
+ * offline video: frames[w * clip_stride : w * clip_stride + R : frame_step], byte for byte.  No LoopPad runs live: a camera
+ * below R frames has no clip.
+ *
+ * Both calls are copies of bits in advhip_gather_batch_f32's form (a frame cut into chunks, all of a lane's loads before its
+ * stores, 64-bit byte offsets).  The access width is chosen from both data pointers and frame_bytes: 16 bytes when all three
+ * are multiples of 16 (the working frame is: 256 * 340 * 3 = 261 120), 4 bytes when multiples of 4, else single bytes; never
+ * an unaligned wide access.  Null pointers, non-positive sizes and more than 65 535 frame rows in one launch are refused.
+ *
+ * One new frame for each of n DISTINCT cameras: frames uint8 (n, frame_bytes) contiguous, cam_ids int32 (n,) on the device.  For
+ * c = cam_ids[i]: ring[c, counts[c] % R] = frames[i]; a second launch of the same call then does counts[c] += 1.  An id outside
+ * [0, n_cam) writes nothing and advances nothing.  The same id twice in one call is the caller's error. */
+int advhip_frame_ring_push_u8(const uint8_t* frames, const int32_t* cam_ids, uint8_t* ring, int64_t* counts, int32_t n, int32_t n_cam,
+                              int32_t R, int64_t frame_bytes, void* stream);
+/* The windows of the nb listed cameras as back-to-back clips: dst uint8 (nb * frames_per_clip, frame_bytes); rows
+ * [v * frames_per_clip, (v + 1) * frames_per_clip) are the window of c = cam_ids[v] by the window rule.  The rows of a camera
+ * whose count is below R, or whose id is outside [0, n_cam), are left as they are.  R != frames_per_clip * frame_step is refused. */
+int advhip_frame_ring_windows_u8(const uint8_t* ring, const int64_t* counts, const int32_t* cam_ids, uint8_t* dst, int32_t nb,
+                                 int32_t n_cam, int32_t R, int64_t frame_bytes, int32_t frames_per_clip, int32_t frame_step,
+                                 void* stream);
+
 /* Clip pre-processing on the device: uint8 frames (N, T, C, H, W) -> fp32 (N, C, T, H, W) with
  * y = (x - mean) / std.  Replaces PILToTensor().float() + GroupNormalize(114.75, 57.375)
  * (src/dataset.py:175-183) and the permute of extract_features.py:83, so that only uint8 pixels
