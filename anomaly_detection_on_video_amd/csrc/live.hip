@@ -132,6 +132,30 @@ inline int frame_access_bytes(const void* a, const void* b, long long frame_byte
   return (bits & 15) == 0 ? 16 : (bits & 3) == 0 ? 4 : 1;
 }
 
+// One frame copy of `rows` frames between `a` and `b`: the access width, the chunks of a frame, the grid's bounds, then
+// launch(V{}, grid) with V = u32x4, unsigned or unsigned char -- the caller's lambda names its kernel<V> and passes its arguments.
+template <typename Launch>
+int launch_frame_copy(const void* a, const void* b, long long frame_bytes, long long rows, const char* who, Launch launch) {
+  const int width = frame_access_bytes(a, b, frame_bytes);
+  const long long chunks = (frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK;
+  ADVHIP_REQUIRE(rows <= 65535 && chunks * rows * 256 < (1ll << 32), "%s: %lld rows of %lld bytes are outside the launch grid", who, rows, frame_bytes);
+  const dim3 grid((unsigned)chunks, (unsigned)rows);
+  if (width == 16)
+    launch(u32x4{}, grid);
+  else if (width == 4)
+    launch(unsigned{}, grid);
+  else
+    launch((unsigned char)0, grid);
+  return check_launch(who);
+}
+
+// The counts of the n listed cameras plus one, behind the kernel that read them.
+inline int launch_ring_advance(const int32_t* cam_ids, int64_t* counts, int32_t n, int32_t n_cam, void* stream, const char* who) {
+  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (long long*)counts,
+                     (int)n, (int)n_cam);
+  return check_launch(who);
+}
+
 }  // namespace advhip
 
 using namespace advhip;
@@ -141,26 +165,12 @@ extern "C" int advhip_frame_ring_push_u8(const uint8_t* frames, const int32_t* c
   ADVHIP_REQUIRE(frames && cam_ids && ring && counts, "frame_ring_push: null pointer");
   ADVHIP_REQUIRE(n > 0 && n_cam > 0 && R > 0 && frame_bytes > 0, "frame_ring_push: bad shape (n=%d n_cam=%d R=%d frame_bytes=%lld)", n, n_cam, R,
                  (long long)frame_bytes);
-  const int width = frame_access_bytes(frames, ring, frame_bytes);
-  const long long chunks = (frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK;
-  ADVHIP_REQUIRE(n <= 65535 && chunks * n * 256 < (1ll << 32), "frame_ring_push: %d rows of %lld bytes are outside the launch grid", n,
-                 (long long)frame_bytes);
-  const dim3 grid((unsigned)chunks, (unsigned)n);
-  const auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, frames, (const int*)cam_ids, ring, (const long long*)counts, (int)n_cam, (int)R,
-                       (long long)frame_bytes);
-  };
-  if (width == 16)
-    launch(frame_ring_push_kernel<u32x4>);
-  else if (width == 4)
-    launch(frame_ring_push_kernel<unsigned>);
-  else
-    launch(frame_ring_push_kernel<unsigned char>);
-  const int rc = check_launch("frame_ring_push");
+  const int rc = launch_frame_copy(frames, ring, frame_bytes, n, "frame_ring_push", [&](auto v, dim3 grid) {
+    hipLaunchKernelGGL(frame_ring_push_kernel<decltype(v)>, grid, dim3(256), 0, (hipStream_t)stream, frames, (const int*)cam_ids, ring,
+                       (const long long*)counts, (int)n_cam, (int)R, (long long)frame_bytes);
+  });
   if (rc != ADVHIP_OK) return rc;
-  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (long long*)counts,
-                     (int)n, (int)n_cam);
-  return check_launch("frame_ring_push (counts)");
+  return launch_ring_advance(cam_ids, counts, n, n_cam, stream, "frame_ring_push (counts)");
 }
 
 extern "C" int advhip_frame_ring_windows_u8(const uint8_t* ring, const int64_t* counts, const int32_t* cam_ids, uint8_t* dst, int32_t nb,
@@ -172,23 +182,10 @@ extern "C" int advhip_frame_ring_windows_u8(const uint8_t* ring, const int64_t* 
                  (long long)frame_bytes, frames_per_clip, frame_step);
   ADVHIP_REQUIRE((long long)frames_per_clip * frame_step == R, "frame_ring_windows: R=%d is not frames_per_clip * frame_step = %d * %d", R,
                  frames_per_clip, frame_step);
-  const long long rows = (long long)nb * frames_per_clip;
-  const int width = frame_access_bytes(ring, dst, frame_bytes);
-  const long long chunks = (frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK;
-  ADVHIP_REQUIRE(rows <= 65535 && chunks * rows * 256 < (1ll << 32), "frame_ring_windows: %lld rows of %lld bytes are outside the launch grid", rows,
-                 (long long)frame_bytes);
-  const dim3 grid((unsigned)chunks, (unsigned)rows);
-  const auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, ring, (const long long*)counts, (const int*)cam_ids, dst, (int)n_cam, (int)R,
-                       (long long)frame_bytes, (int)frames_per_clip, (int)frame_step);
-  };
-  if (width == 16)
-    launch(frame_ring_windows_kernel<u32x4>);
-  else if (width == 4)
-    launch(frame_ring_windows_kernel<unsigned>);
-  else
-    launch(frame_ring_windows_kernel<unsigned char>);
-  return check_launch("frame_ring_windows");
+  return launch_frame_copy(ring, dst, frame_bytes, (long long)nb * frames_per_clip, "frame_ring_windows", [&](auto v, dim3 grid) {
+    hipLaunchKernelGGL(frame_ring_windows_kernel<decltype(v)>, grid, dim3(256), 0, (hipStream_t)stream, ring, (const long long*)counts,
+                       (const int*)cam_ids, dst, (int)n_cam, (int)R, (long long)frame_bytes, (int)frames_per_clip, (int)frame_step);
+  });
 }
 
 extern "C" int advhip_ring_push_f32(const float* feats, const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam,
@@ -204,9 +201,7 @@ extern "C" int advhip_ring_push_f32(const float* feats, const int32_t* cam_ids, 
                      (const long long*)counts, (int)n_cam, (int)ncrops, (int)W, (int)C, tab);
   const int rc = check_launch("ring_push");
   if (rc != ADVHIP_OK) return rc;
-  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (long long*)counts,
-                     (int)n, (int)n_cam);
-  return check_launch("ring_push (counts)");
+  return launch_ring_advance(cam_ids, counts, n, n_cam, stream, "ring_push (counts)");
 }
 
 extern "C" int advhip_ring_windows_f32(const float* ring, const int64_t* counts, const int32_t* cam_ids, float* dst, int32_t nb, int32_t n_cam,

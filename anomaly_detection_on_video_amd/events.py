@@ -16,14 +16,12 @@ The rule (this package's definition; include/advhip.h restates it for the kernel
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
 
 import numpy as np
 
 MAX_SMOOTH = 1023
-LIVE_CACHE_ENTRIES = 64  # camera sets a LiveEventTracker keeps on the device (least recently used out first)
 
 
 @dataclass(frozen=True)
@@ -289,14 +287,14 @@ class LiveEventTracker:
     count to `live_emission_count(e, spec)`.  `log`: the events kept per camera between two drains.
 
     `alert` (1 iff a candidate is open, strong and at least min_len long), `open_start` (its start, or -1), `emitted` and
-    `samples` are device tensors; `samples_host` is the host's mirror of the last.  Camera-id tensors are cached by tuple: a
-    repeated camera set uploads nothing.  CUDA only; no fallback."""
+    `samples` are device tensors; `samples_host` is the host's mirror of the last.  `cams` are checked and their id
+    tensors cached by `self.cameras`, a live.CameraSet: a repeated camera set uploads nothing.  `cameras`: the CameraSet of the same
+    cameras whose id cache to share (LiveScorer passes its own; the sample counts stay the tracker's).  CUDA only; no fallback."""
 
-    def __init__(self, spec, n_cameras: int, log: int = 64, device="cuda:0"):
-        import torch
-
+    def __init__(self, spec, n_cameras: int, log: int = 64, device="cuda:0", cameras=None):
         from . import mil_ops
         from ._lib import HipExtensionError
+        from .live import CameraSet, host_int
 
         try:
             self.spec = resolve_event_spec(spec)
@@ -305,18 +303,15 @@ class LiveEventTracker:
         if self.spec is None:
             raise HipExtensionError("LiveEventTracker: no event spec")
         for name, v in (("n_cameras", n_cameras), ("log", log)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < 1 << 31:
+            if (k := host_int(v, floats=False)) is None or not 1 <= k < 1 << 31:
                 raise HipExtensionError(f"LiveEventTracker: {name} = {v!r} is not an integer in [1, 2^31)")
         self.n_cameras, self.log = int(n_cameras), int(log)
-        self.device = torch.device(device)
+        self.cameras = CameraSet(self.n_cameras, device, "sample", share=cameras)
+        self.device = self.cameras.device
         if self.device.type != "cuda":
             raise HipExtensionError(f"LiveEventTracker: device '{self.device}': the state lives on the GPU (there is no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         self.state = mil_ops.live_events_state(self.n_cameras, self.spec.smooth, self.log, self.device)
-        self._host = [0] * self.n_cameras
         self._drained = np.zeros(self.n_cameras, dtype=np.int64)
-        self._ids: "OrderedDict[tuple, object]" = OrderedDict()
 
     alert = property(lambda self: self.state["alert"])
     open_start = property(lambda self: self.state["open_start"])
@@ -326,38 +321,7 @@ class LiveEventTracker:
     @property
     def samples_host(self) -> tuple:
         """Samples fed per camera since its last finish / reset, kept by update / finish / reset: nothing is read back."""
-        return tuple(self._host)
-
-    def _cams(self, cams, what: str):
-        """-> (the checked tuple, its int32 device tensor)"""
-        import torch
-
-        from ._lib import HipExtensionError
-
-        if type(cams) is tuple and cams in self._ids and all(type(c) is int for c in cams):
-            self._ids.move_to_end(cams)
-            return cams, self._ids[cams]  # (a camera set seen before was checked then)
-        if torch.is_tensor(cams) or isinstance(cams, np.ndarray):
-            raise HipExtensionError(f"{what}: cams must be a sequence of host integers, got a {type(cams).__name__} (the ids are checked on the host)")
-        try:
-            cams = tuple(cams)
-        except TypeError:
-            raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
-        if not cams:
-            raise HipExtensionError(f"{what}: an empty list of cameras")
-        for c in cams:
-            if isinstance(c, bool) or torch.is_tensor(c) or not isinstance(c, (int, float, np.integer, np.floating)) or int(c) != c:
-                raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
-            if not 0 <= int(c) < self.n_cameras:
-                raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {self.n_cameras})")
-        cams = tuple(int(c) for c in cams)
-        if len(set(cams)) != len(cams):
-            dup = sorted(c for c in set(cams) if cams.count(c) > 1)
-            raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one sample per camera and call")
-        ids = self._ids[cams] = torch.tensor(cams, dtype=torch.int32).to(self.device)
-        if len(self._ids) > LIVE_CACHE_ENTRIES:
-            self._ids.popitem(last=False)
-        return cams, ids
+        return tuple(self.cameras.host)
 
     def _launch(self, ids, scores, by_camera: bool, mode: int) -> None:
         from . import mil_ops
@@ -370,13 +334,12 @@ class LiveEventTracker:
         or with by_camera (n_cameras,) indexed by camera id (LiveScorer.latest as it is)."""
         from ._lib import LIVE_EVENTS_UPDATE, HipExtensionError
 
-        cams, ids = self._cams(cams, "LiveEventTracker.update")
-        full = [c for c in cams if self._host[c] >= MAX_LIVE_SAMPLES]
+        cams = self.cameras.check(cams, "LiveEventTracker.update")
+        full = [c for c in cams if self.cameras.host[c] >= MAX_LIVE_SAMPLES]
         if full:
             raise HipExtensionError(f"LiveEventTracker.update: cameras {full} have fed 2^31 - 1 samples (positions are int32): finish or reset them")
-        self._launch(ids, scores, bool(by_camera), LIVE_EVENTS_UPDATE)
-        for c in cams:
-            self._host[c] += 1
+        self._launch(self.cameras.ids(cams), scores, bool(by_camera), LIVE_EVENTS_UPDATE)
+        self.cameras.bump(cams)
 
     def finish(self, cams) -> None:
         """The listed cameras' series end here: their pending (smooth - 1) / 2 samples are finalised as at a video's end, an open
@@ -392,10 +355,9 @@ class LiveEventTracker:
         self._clear(cams, "LiveEventTracker.reset", LIVE_EVENTS_RESET)
 
     def _clear(self, cams, what: str, mode: int) -> None:
-        cams, ids = self._cams(cams, what)
-        self._launch(ids, None, False, mode)
-        for c in cams:
-            self._host[c] = 0
+        cams = self.cameras.check(cams, what)
+        self._launch(self.cameras.ids(cams), None, False, mode)
+        self.cameras.clear(cams)
 
     def drain(self) -> LiveDrain:
         """The events emitted since the previous drain: ONE read-back (of `emitted`), then one gather of their log rows on the

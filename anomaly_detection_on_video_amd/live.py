@@ -24,12 +24,16 @@ synchronises nothing and dispatches no torch arithmetic.
 
 `LiveFrames` is the front end: per-camera rings of the last `span` resized uint8 frames, one decoded frame per camera and push,
 and the clips that are due gathered in one launch into the buffer I3Res50.forward_frames reads -- each one window w of the
-camera's frames as an offline video, byte for byte."""
+camera's frames as an offline video, byte for byte.
+
+All three classes (and events.LiveEventTracker) keep their cameras in one `CameraSet`: the rule for `cams`, the cached id vectors,
+the host mirror of the counts."""
 from __future__ import annotations
 
 from collections import OrderedDict
 from typing import NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import mil_ops
@@ -60,26 +64,64 @@ class _Lru:
         return val
 
 
-def _checked_cams(cams, what: str, n_cameras: int, seen, unit: str) -> Tuple[int, ...]:
-    """`cams` as a tuple of distinct host ints in [0, n_cameras); `seen` holds the tuples checked before (the id cache's keys)."""
-    if type(cams) is tuple and all(type(c) is int for c in cams) and cams in seen:
-        return cams  # (a camera set seen before was checked then)
-    try:
-        cams = tuple(cams)
-    except TypeError:
-        raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
-    if not cams:
-        raise HipExtensionError(f"{what}: an empty list of cameras")
-    for c in cams:
-        if isinstance(c, bool) or torch.is_tensor(c) or int(c) != c:
-            raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
-        if not 0 <= int(c) < n_cameras:
-            raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {n_cameras})")
-    cams = tuple(int(c) for c in cams)
-    if len(set(cams)) != len(cams):
-        dup = sorted(c for c in set(cams) if cams.count(c) > 1)
-        raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one {unit} per camera and call")
-    return cams
+def host_int(v, floats: bool = True) -> Optional[int]:
+    """`v` as an int where it is an integer-valued host number -- never a bool, a tensor or a string; floats=False: of an integer
+    type -- else None.  The bounds and the message are the caller's."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer) + ((float, np.floating) if floats else ())):
+        return None
+    return int(v) if isinstance(v, (int, np.integer)) or float(v).is_integer() else None
+
+
+def _resolve_device(device) -> torch.device:
+    """A bare "cuda" means the current device.  Whether anything but a GPU will do is the caller's to say."""
+    device = torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+
+class CameraSet:
+    """The cameras of one live object: how many and on which device, the one rule for the `cams` of a call (`check`), the device
+    vectors of checked id tuples (`ids`, an LRU cache of CACHE_ENTRIES) and the host mirror of a per-camera count (`host`, moved by
+    `bump` and `clear` only).  `unit` names what a call brings each listed camera: a frame, a clip, a sample.  `share`: a
+    CameraSet of the same cameras whose id cache this one uses -- a tuple is then uploaded once for both; the counts stay apart."""
+
+    def __init__(self, n_cameras: int, device, unit: str, share: Optional["CameraSet"] = None):
+        self.n_cameras, self.device, self.unit = n_cameras, _resolve_device(device), unit
+        if share is not None and (share.n_cameras, share.device) != (self.n_cameras, self.device):
+            raise HipExtensionError(f"CameraSet: {share.n_cameras} cameras on {share.device} share no ids with {self.n_cameras} on {self.device}")
+        self.host = [0] * n_cameras
+        # (keyed by checked tuples only)
+        self.ids = share.ids if share is not None else _Lru(lambda cams: torch.tensor(cams, dtype=torch.int32).to(self.device))
+
+    def check(self, cams, what: str) -> Tuple[int, ...]:
+        """`cams` as a tuple of distinct host ints in [0, n_cameras), or a refusal that starts with `what`."""
+        if type(cams) is tuple and all(type(c) is int for c in cams) and cams in self.ids.items:
+            return cams  # (a camera set seen before was checked then)
+        if torch.is_tensor(cams) or isinstance(cams, np.ndarray):
+            raise HipExtensionError(f"{what}: cams must be a sequence of host integers, got a {type(cams).__name__} (the ids are checked on the host)")
+        try:
+            cams = tuple(cams)
+        except TypeError:
+            raise HipExtensionError(f"{what}: cams must be a sequence of camera ids, got {type(cams).__name__}") from None
+        if not cams:
+            raise HipExtensionError(f"{what}: an empty list of cameras")
+        for c in cams:
+            if host_int(c) is None:
+                raise HipExtensionError(f"{what}: camera id {c!r} is not a host integer")
+            if not 0 <= int(c) < self.n_cameras:
+                raise HipExtensionError(f"{what}: camera id {int(c)} is out of range [0, {self.n_cameras})")
+        cams = tuple(int(c) for c in cams)
+        if len(set(cams)) != len(cams):
+            dup = sorted(c for c in set(cams) if cams.count(c) > 1)
+            raise HipExtensionError(f"{what}: duplicate camera ids {dup}: one {self.unit} per camera and call")
+        return cams
+
+    def bump(self, cams) -> None:
+        for c in cams:
+            self.host[c] += 1
+
+    def clear(self, cams) -> None:
+        for c in cams:
+            self.host[c] = 0
 
 
 class LiveFrames:
@@ -111,7 +153,7 @@ class LiveFrames:
         except (TypeError, ValueError):
             raise HipExtensionError(f"LiveFrames: frame_hw = {frame_hw!r} is not a pair (FH, FW)") from None
         for name, v in (("n_cameras", n_cameras), ("frame_hw[0]", fh), ("frame_hw[1]", fw), ("frames_per_clip", frames_per_clip)):
-            if isinstance(v, bool) or torch.is_tensor(v) or int(v) != v or int(v) < 1:
+            if (k := host_int(v)) is None or k < 1:
                 raise HipExtensionError(f"LiveFrames: {name} = {v!r} is not an integer >= 1")
         self.n_cameras, self.frame_hw, self.frames_per_clip = int(n_cameras), (int(fh), int(fw)), int(frames_per_clip)
         self.clip_stride, _, self.frame_step = ops.resolve_sampling(self.frames_per_clip, clip_stride, None, frame_step)
@@ -119,18 +161,15 @@ class LiveFrames:
         if self.n_cameras * self.frames_per_clip > self.MAX_ROWS:
             raise HipExtensionError(f"LiveFrames: {self.n_cameras} cameras x {self.frames_per_clip} frames per clip is above the {self.MAX_ROWS} frame "
                                     f"rows one gather launch takes")
-        self.device = torch.device(device)
+        self.cameras = CameraSet(self.n_cameras, device, "frame")
+        self.device = self.cameras.device
         if self.device.type != "cuda":
             raise HipExtensionError(f"LiveFrames: device '{self.device}': the rings live on the GPU (there is no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         frame = self.frame_hw + (3,)
         self.ring = torch.zeros((self.n_cameras, self.span) + frame, dtype=torch.uint8, device=self.device)
         self._counts = torch.zeros((self.n_cameras,), dtype=torch.int64, device=self.device)
-        self._host = [0] * self.n_cameras
         self._clips = torch.empty((self.n_cameras * self.frames_per_clip,) + frame, dtype=torch.uint8, device=self.device)
         self._staging = torch.empty((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
-        self._ids = _Lru(lambda cams: torch.tensor(cams, dtype=torch.int32).to(self.device))  # keyed by checked tuples only
 
     @property
     def counts(self) -> torch.Tensor:
@@ -140,10 +179,7 @@ class LiveFrames:
     @property
     def counts_host(self) -> Tuple[int, ...]:
         """The same numbers on the host, kept by push / reset: nothing is read back."""
-        return tuple(self._host)
-
-    def _check_cams(self, cams, what: str) -> Tuple[int, ...]:
-        return _checked_cams(cams, what, self.n_cameras, self._ids.items, "frame")
+        return tuple(self.cameras.host)
 
     def is_due(self, count: int) -> bool:
         """The due rule: a clip is due at a camera's count k iff k >= span and (k - span) % clip_stride == 0."""
@@ -173,7 +209,7 @@ class LiveFrames:
         from . import resize as rz
 
         what = "LiveFrames.push"
-        cams = self._check_cams(cams, what)
+        cams = self.cameras.check(cams, what)
         n = len(cams)
         if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 2 or frames.shape[0] != n:
             raise HipExtensionError(f"{what}: frames must be a torch.uint8 tensor with {n} leading rows, one frame per listed camera, got "
@@ -194,28 +230,26 @@ class LiveFrames:
             frames = frames.to(self.device, non_blocking=True)
         if resize is not None:
             frames = rz.resize_u8(frames, resize, resample, out=self._staging[:n], pixel_format=pixel_format, surface=surface)
-        mil_ops.frame_ring_push(frames, self._ids(cams), self.ring, self._counts)
-        for c in cams:
-            self._host[c] += 1
-        return tuple(c for c in cams if self.is_due(self._host[c]))
+        mil_ops.frame_ring_push(frames, self.cameras.ids(cams), self.ring, self._counts)
+        self.cameras.bump(cams)
+        return tuple(c for c in cams if self.is_due(self.cameras.host[c]))
 
     def windows(self, cams: Sequence[int]) -> torch.Tensor:
         """The newest windows of the listed cameras, back to back in `cams` order: (len(cams) * frames_per_clip, FH, FW, 3) uint8,
         every frame_step-th frame of each camera's last `span`, oldest first -- one launch into the owned clip buffer, of which
         the result is a view (the next call overwrites it).  Every listed camera must have `span` frames."""
-        cams = self._check_cams(cams, "LiveFrames.windows")
-        short = [c for c in cams if self._host[c] < self.span]
+        cams = self.cameras.check(cams, "LiveFrames.windows")
+        short = [c for c in cams if self.cameras.host[c] < self.span]
         if short:
             raise HipExtensionError(f"LiveFrames.windows: cameras {short} have fewer than span = {self.span} frames: no clip yet (no LoopPad runs live)")
         dst = self._clips[: len(cams) * self.frames_per_clip]
-        return mil_ops.frame_ring_windows(self.ring, self._counts, self._ids(cams), dst, self.frames_per_clip, self.frame_step)
+        return mil_ops.frame_ring_windows(self.ring, self._counts, self.cameras.ids(cams), dst, self.frames_per_clip, self.frame_step)
 
     def reset(self, cams: Sequence[int]) -> None:
         """The listed cameras start over at count 0: their rings' old frames can no longer reach a window."""
-        cams = self._check_cams(cams, "LiveFrames.reset")
-        self._counts[self._ids(cams).long()] = 0
-        for c in cams:
-            self._host[c] = 0
+        cams = self.cameras.check(cams, "LiveFrames.reset")
+        self._counts[self.cameras.ids(cams).long()] = 0
+        self.cameras.clear(cams)
 
 
 class LiveScorer:
@@ -230,7 +264,7 @@ class LiveScorer:
     def __init__(self, scorer, n_cameras: int, window: int = 32, ncrops: int = 10, channels: int = 2048, device="cuda:0",
                  max_rows: int = DEFAULT_MAX_ROWS, events=None, event_log: int = 64):
         for name, v in (("n_cameras", n_cameras), ("window", window), ("ncrops", ncrops), ("channels", channels)):
-            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            if (k := host_int(v)) is None or k < 1:
                 raise HipExtensionError(f"LiveScorer: {name} = {v!r} is not an integer >= 1 (window < 1 holds no clip)")
         from .events import resolve_event_spec
 
@@ -238,7 +272,7 @@ class LiveScorer:
             spec = resolve_event_spec(events)
         except ValueError as e:
             raise HipExtensionError(f"LiveScorer: {e}") from None
-        if spec is not None and (isinstance(event_log, bool) or not isinstance(event_log, int) or event_log < 1):
+        if spec is not None and ((k := host_int(event_log, floats=False)) is None or k < 1):
             raise HipExtensionError(f"LiveScorer: event_log = {event_log!r} is not an integer >= 1")
         self.scorer = scorer
         self.n_cameras, self.window, self.ncrops, self.channels = int(n_cameras), int(window), int(ncrops), int(channels)
@@ -248,26 +282,23 @@ class LiveScorer:
         if rows > int(max_rows):
             raise HipExtensionError(f"LiveScorer: {self.n_cameras} cameras x {self.ncrops} crops x {self.window} clips = {rows} rows is above the "
                                     f"scorer's row limit of {int(max_rows)}")
-        self.device = torch.device(device)
+        self.cameras = CameraSet(self.n_cameras, device, "clip")
+        self.device = self.cameras.device
         if self.device.type != "cuda":
             raise HipExtensionError(f"LiveScorer: device '{self.device}': the rings live on the GPU (there is no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         shape = (self.n_cameras, self.ncrops, self.window, self.channels + 1)
         self.ring = torch.zeros(shape, dtype=torch.float32, device=self.device)
         self._counts = torch.zeros((self.n_cameras,), dtype=torch.int64, device=self.device)
-        self._host = [0] * self.n_cameras
         self.latest = torch.full((self.n_cameras,), float("nan"), dtype=torch.float32, device=self.device)
         # (never initialised: the rows behind a window hold what an earlier call left there, which the padded pass never reads as values)
         self._batch = torch.empty(shape, dtype=torch.float32, device=self.device).view(-1)
         self._iota = torch.arange(self.n_cameras, dtype=torch.int32).to(self.device)
-        self._ids = _Lru(lambda cams: torch.tensor(cams, dtype=torch.int32).to(self.device))  # keyed by checked tuples only
         self._lens = _Lru(self._make_lens)
         self.events = None
         if spec is not None:
             from .events import LiveEventTracker
 
-            self.events = LiveEventTracker(spec, self.n_cameras, log=event_log, device=self.device)
+            self.events = LiveEventTracker(spec, self.n_cameras, log=event_log, device=self.device, cameras=self.cameras)
 
     def _make_lens(self, key):
         from .models.mgfn.modeling_mgfn import PaddedLens
@@ -293,43 +324,39 @@ class LiveScorer:
     @property
     def counts_host(self) -> Tuple[int, ...]:
         """The same numbers on the host, kept by push / reset: nothing is read back."""
-        return tuple(self._host)
-
-    def _check_cams(self, cams, what: str) -> Tuple[int, ...]:
-        return _checked_cams(cams, what, self.n_cameras, self._ids.items, "clip")
+        return tuple(self.cameras.host)
 
     def push(self, cams: Sequence[int], feats: torch.Tensor) -> None:
         """One new clip for each camera of `cams` (distinct host ints): feats (len(cams), ncrops, channels) fp32 on the device."""
-        cams = self._check_cams(cams, "LiveScorer.push")
+        cams = self.cameras.check(cams, "LiveScorer.push")
         want = (len(cams), self.ncrops, self.channels)
         if not torch.is_tensor(feats) or tuple(feats.shape) != want:
             raise HipExtensionError(f"LiveScorer.push: feats must be {want} (cameras, crops, channels), got {tuple(getattr(feats, 'shape', ()))}")
-        mil_ops.ring_push(feats, self._ids(cams), self.ring, self._counts)
-        for c in cams:
-            self._host[c] += 1
+        mil_ops.ring_push(feats, self.cameras.ids(cams), self.ring, self._counts)
+        self.cameras.bump(cams)
 
     def score(self, cams: Optional[Sequence[int]] = None) -> LiveScores:
         """The windows of the listed cameras (None: every camera with at least one clip, ascending) scored in one padded pass."""
         if cams is None:
-            cams = tuple(c for c, k in enumerate(self._host) if k > 0)
+            cams = tuple(c for c, k in enumerate(self.cameras.host) if k > 0)
             if not cams:
                 raise HipExtensionError("LiveScorer.score: no camera has a clip yet")
         else:
-            cams = self._check_cams(cams, "LiveScorer.score")
-            empty = [c for c in cams if self._host[c] == 0]
+            cams = self.cameras.check(cams, "LiveScorer.score")
+            empty = [c for c in cams if self.cameras.host[c] == 0]
             if empty:
                 raise HipExtensionError(f"LiveScorer.score: cameras {empty} have no clip yet")
         feed = None
         if self.events is not None:  # which of the listed cameras have a new clip for the tracker: decided before anything is launched
-            fed = self.events._host
-            ahead = [c for c in cams if self._host[c] > fed[c] + 1]
+            fed = self.events.cameras.host
+            ahead = [c for c in cams if self.cameras.host[c] > fed[c] + 1]
             if ahead:
                 raise HipExtensionError(f"LiveScorer.score: cameras {ahead} are more than one clip ahead of their event series (pushed twice, scored "
                                         f"once): every clip's score is a sample; score after every push, or reset the cameras")
-            feed = tuple(c for c in cams if self._host[c] == fed[c] + 1)
-        lens = tuple(min(self._host[c], self.window) for c in cams)
+            feed = tuple(c for c in cams if self.cameras.host[c] == fed[c] + 1)
+        lens = tuple(min(self.cameras.host[c], self.window) for c in cams)
         nb, tmax = len(cams), max(lens)
-        ids, pl = self._ids(cams), self._lens((lens, tmax))
+        ids, pl = self.cameras.ids(cams), self._lens((lens, tmax))
         video = self._batch[: nb * self.ncrops * tmax * (self.channels + 1)].view(nb, self.ncrops, tmax, self.channels + 1)
         mil_ops.ring_windows(self.ring, self._counts, ids, video)
         rows, _ = self.scorer._score_padded_rows(video, pl)
@@ -347,14 +374,13 @@ class LiveScorer:
     def reset(self, cams: Sequence[int]) -> None:
         """The listed cameras start over: count 0, latest NaN (their rings' old clips can no longer be reached).  With `events`
         their event series start over too, an open event is dropped: call `self.events.finish(cams)` first to keep it."""
-        cams = self._check_cams(cams, "LiveScorer.reset")
+        cams = self.cameras.check(cams, "LiveScorer.reset")
         if self.events is not None:
             self.events.reset(cams)
-        idx = self._ids(cams).long()
+        idx = self.cameras.ids(cams).long()
         self._counts[idx] = 0
         self.latest[idx] = float("nan")
-        for c in cams:
-            self._host[c] = 0
+        self.cameras.clear(cams)
 
     def step_frames(self, backbone, frames_u8: torch.Tensor, cams: Sequence[int], **sampling) -> LiveScores:
         """One clip per camera straight from resized uint8 frames: `frames_u8` (len(cams) * span, FH, FW, 3) on the device holds
@@ -363,7 +389,7 @@ class LiveScorer:
         -> backbone.forward_frames, `push`, `score(cams)`."""
         from . import ops
 
-        cams = self._check_cams(cams, "LiveScorer.step_frames")
+        cams = self.cameras.check(cams, "LiveScorer.step_frames")
         fpc = sampling.get("frames_per_clip", 16)
         s, crops, d = ops.resolve_sampling(fpc, sampling.get("clip_stride"), sampling.get("crops"), sampling.get("frame_step"))
         if s != fpc * d:
@@ -373,9 +399,13 @@ class LiveScorer:
         if not torch.is_tensor(frames_u8) or frames_u8.dim() != 4 or frames_u8.shape[0] != len(cams) * fpc * d:
             raise HipExtensionError(f"LiveScorer.step_frames: frames_u8 must be ({len(cams) * fpc * d}, FH, FW, 3): {fpc * d} frames for each of "
                                     f"{len(cams)} cameras, got {tuple(getattr(frames_u8, 'shape', ()))}")
-        feats = backbone.forward_frames(frames_u8, 0, len(cams) * self.ncrops, **sampling)
+        return self._step_clips("LiveScorer.step_frames", backbone, frames_u8, cams, sampling)
+
+    def _step_clips(self, what: str, backbone, clips: torch.Tensor, cams: Tuple[int, ...], forward_kw: dict) -> LiveScores:
+        """The tail of both step methods: backbone.forward_frames on the back-to-back clips of `cams`, `push`, `score(cams)`."""
+        feats = backbone.forward_frames(clips, 0, len(cams) * self.ncrops, **forward_kw)
         if feats.numel() != len(cams) * self.ncrops * self.channels:
-            raise HipExtensionError(f"LiveScorer.step_frames: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
+            raise HipExtensionError(f"{what}: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
         self.push(cams, feats.reshape(len(cams), self.ncrops, self.channels))
         return self.score(cams)
 
@@ -411,10 +441,5 @@ class LiveScorer:
         due = live_frames.push(cams, frames, **{k: kw[k] for k in self._PUSH_KW if k in kw})
         if not due:
             return None
-        clips = live_frames.windows(due)
-        feats = backbone.forward_frames(clips, 0, len(due) * self.ncrops, frames_per_clip=live_frames.frames_per_clip,
-                                        **{k: kw[k] for k in self._FORWARD_KW if k in kw})
-        if feats.numel() != len(due) * self.ncrops * self.channels:
-            raise HipExtensionError(f"{what}: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
-        self.push(due, feats.reshape(len(due), self.ncrops, self.channels))
-        return self.score(due)
+        forward_kw = {"frames_per_clip": live_frames.frames_per_clip, **{k: kw[k] for k in self._FORWARD_KW if k in kw}}
+        return self._step_clips(what, backbone, live_frames.windows(due), due, forward_kw)

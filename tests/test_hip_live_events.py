@@ -291,13 +291,14 @@ def test_tracker_refusals():
     with pytest.raises(HipExtensionError, match=r"live_events_update: scores must be \(4,\), got \(2,\)"):
         t.update([0, 1], ok, by_camera=True)
     assert t.samples_host == (0,) * 4 and not t.samples.any() and not t.emitted.any()  # a refused call moves nothing
-    t._host[2] = (1 << 31) - 1
+    t.cameras.host[2] = (1 << 31) - 1
     with pytest.raises(HipExtensionError, match=r"LiveEventTracker.update: cameras \[2\] have fed 2\^31 - 1 samples"):
         t.update([0, 2], ok)
     assert t.samples_host[0] == 0
-    ids = t._cams((0, 1), "x")[1]
+    ids = t.cameras.ids(t.cameras.check((0, 1), "x"))
     t.update((0, 1), ok)
-    assert t._cams((0, 1), "x")[1] is ids and t._cams([0, 1], "x")[1] is not None  # the id tensor of a repeated camera set is reused
+    # the id tensor of a repeated camera set is reused
+    assert t.cameras.ids(t.cameras.check((0, 1), "x")) is ids and t.cameras.ids(t.cameras.check([0, 1], "x")) is ids
 
 
 def test_launch_wrapper_refusals():
