@@ -78,14 +78,6 @@ struct YuvCoef {
   int yoff, cy, crv, cgu, cgv, cbu;
 };
 
-// how a frame's chroma is addressed: Cb of sample (c, xc) at chroma[c * cw + xc * cs], Cr cr_off bytes behind it
-struct YuvLayout {
-  int cw, cs;
-  long long cr_off;
-  __device__ YuvLayout(int layout, int H, int W)
-      : cw(layout == 0 ? W : W / 2), cs(layout == 0 ? 2 : 1), cr_off(layout == 0 ? 1 : (long long)(H / 2) * (W / 2)) {}
-};
-
 // the three chroma terms of a sample, formed once for the pixels that share it (BITS: the sample depth, 8 or 10; the chroma
 // midpoint is 2^(BITS - 1) and the coefficients are 2^(8 + BITS) fixed point)
 template <int BITS>
@@ -142,99 +134,7 @@ struct alignas(4) Rgb4 {  // four packed RGB pixels
   uint32_t a, b, c;
 };
 
-// The conversion alone: dst row r = (f, y) <- source frame f (at byte f * fpitch); one wave per output row.  QUAD (W a multiple
-// of 4, both pointers 4-byte aligned): a lane converts four adjacent pixels = two chroma samples from one 4-byte Y load and one
-// 4-byte (NV12) or two 2-byte (I420) chroma loads, and stores their 12 bytes at once.  Otherwise a lane converts the pair that
-// shares one chroma sample and stores three 2-byte pieces (`even`: dst is 2-byte aligned; rows and pairs are, as W is even) or bytes.
-template <bool QUAD>
-__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int H,
-                                                              int W, int layout, YuvCoef k, int even, long long nrows) {
-  const int lane = threadIdx.x & 63;
-  const YuvLayout L(layout, H, W);
-  for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
-    const long long f = r / H;
-    const int y = (int)(r - f * H);
-    const uint8_t* yrow = src + f * fpitch + (long long)y * W;
-    const uint8_t* cb = src + f * fpitch + (long long)H * W + (long long)(y >> 1) * L.cw;
-    const uint8_t* cr = cb + L.cr_off;
-    uint8_t* out = dst + r * W * 3;
-    if constexpr (QUAD) {
-      for (int q = lane; q < W / 4; q += 64) {
-        const uint32_t yy = load_as<uint32_t>(yrow + 4 * q);
-        uint32_t cc;  // Cb0 | Cr0 << 8 | Cb1 << 16 | Cr1 << 24
-        if (layout == 0) {
-          cc = load_as<uint32_t>(cb + 4 * q);
-        } else {
-          const uint32_t u = load_as<uint16_t>(cb + 2 * q), v = load_as<uint16_t>(cr + 2 * q);
-          cc = (u & 255) | (v & 255) << 8 | (u >> 8) << 16 | (v >> 8) << 24;
-        }
-        const ChromaTerms<8> c0(cc & 255, (cc >> 8) & 255, k), c1((cc >> 16) & 255, cc >> 24, k);
-        const uint32_t p0 = yuv_rgb_packed(yy & 255, c0, k), p1 = yuv_rgb_packed((yy >> 8) & 255, c0, k);
-        const uint32_t p2 = yuv_rgb_packed((yy >> 16) & 255, c1, k), p3 = yuv_rgb_packed(yy >> 24, c1, k);
-        store_as(out + 12 * q, Rgb4{p0 | p1 << 24, p1 >> 8 | p2 << 16, p2 >> 16 | p3 << 8});
-      }
-    } else {
-      for (int p = lane; p < W / 2; p += 64) {
-        const ChromaTerms<8> c(cb[p * L.cs], cr[p * L.cs], k);
-        const uint32_t p0 = yuv_rgb_packed(yrow[2 * p], c, k), p1 = yuv_rgb_packed(yrow[2 * p + 1], c, k);
-        uint8_t* o = out + 6 * p;
-        if (even) {
-          store_as(o, (uint16_t)p0);
-          store_as(o + 2, (uint16_t)(p0 >> 16 | p1 << 8));
-          store_as(o + 4, (uint16_t)(p1 >> 8));
-        } else {
-          o[0] = (uint8_t)p0, o[1] = (uint8_t)(p0 >> 8), o[2] = (uint8_t)(p0 >> 16);
-          o[3] = (uint8_t)p1, o[4] = (uint8_t)(p1 >> 8), o[5] = (uint8_t)(p1 >> 16);
-        }
-      }
-    }
-  }
-}
-
-// resize_h_u8_kernel on 4:2:0 frames: every tap's pixel is converted to its three bytes first and accumulated as there, so the
-// output is byte for byte that kernel's on the converted frame.  The taps [x0, x0 + n) are walked chroma sample by chroma sample:
-// one chroma read and one set of products for the (up to) two taps that share it.
-__global__ __launch_bounds__(256) void resize_h_yuv420_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int H,
-                                                                int W, int OW, int row0, int rows, const int* __restrict__ xb,
-                                                                const int* __restrict__ xk, int ksize, int layout, YuvCoef k, long long nrows) {
-  const int lane = threadIdx.x & 63;
-  const YuvLayout L(layout, H, W);
-  for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
-    const long long f = r / rows;
-    const int y = row0 + (int)(r - f * rows);
-    const uint8_t* yrow = src + f * fpitch + (long long)y * W;
-    const uint8_t* cb = src + f * fpitch + (long long)H * W + (long long)(y >> 1) * L.cw;
-    const uint8_t* cr = cb + L.cr_off;
-    uint8_t* out = dst + r * OW * 3;
-    for (int x = lane; x < OW; x += 64) {
-      int x0 = xb[2 * x];
-      int n = min(xb[2 * x + 1], ksize);
-      if (x0 < 0 || x0 + n > W) x0 = 0, n = 0;  // (never for tables from resize.py: a guard against a foreign table)
-      const int xe = x0 + n;
-      const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
-      int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
-      for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
-        const ChromaTerms<8> c(cb[xc * L.cs], cr[xc * L.cs], k);
-#pragma unroll
-        for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
-          if (xs >= x0 && xs < xe) {
-            int pr, pg, pb;
-            yuv_rgb(yrow[xs], c, k, pr, pg, pb);
-            const int wk = w[xs];
-            s0 += pr * wk;
-            s1 += pg * wk;
-            s2 += pb * wk;
-          }
-        }
-      }
-      out[3 * x] = clip8(s0);
-      out[3 * x + 1] = clip8(s1);
-      out[3 * x + 2] = clip8(s2);
-    }
-  }
-}
-
-// --- decoder surfaces (include/advhip.h): the same two kernels on frames described by byte geometry and sample depth.  A sample
+// --- decoder surfaces (include/advhip.h): 4:2:0 frames described by byte geometry and sample depth.  A sample
 // is a byte (BITS 8) or a little-endian 16-bit word whose value is (word >> shift) & 1023 (BITS 10); every offset, pitch and
 // step is in bytes from the frame's first byte.  NV12 / NV21 / I420 / YV12 / P010 / yuv420p10le are nothing but these numbers.
 struct YuvSurface {
@@ -276,75 +176,148 @@ __device__ __forceinline__ void yuv_sample4(const uint8_t* p, int shift, int (&v
   }
 }
 
-// yuv420_to_rgb_u8_kernel on a surface.  QUAD is chosen on the host (launch_yuv420_to_rgb) from the alignment of everything that
-// enters an address: a lane converts four pixels from one load of four Y samples and one load of two (Cb, Cr) pairs (interleaved
-// chroma, in either order) or two loads of two samples (planar chroma).  Otherwise the pair path, as there.
-template <int BITS, bool QUAD>
-__global__ __launch_bounds__(256) void yuv420_surface_to_rgb_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
-                                                                      int H, int W, YuvSurface S, YuvCoef k, int even, long long nrows) {
-  constexpr int SB = BITS == 8 ? 1 : 2;  // bytes per sample
+// --- where a kernel reads its 4:2:0 samples: one of two sources, built in the kernel from its arguments (Arg, and the frame's size)
+// and used by value.  Both answer the same questions -- the rows of source row y, one luma sample, one chroma pair, and the four
+// luma samples and two chroma pairs of four adjacent pixels from whole loads -- so each kernel below is written once; the compact
+// frames keep their own instantiation with its compile-time addressing.  `Size` is what the horizontal pass
+// carries of the frame's size: each source names what it reads, so each instantiation keeps the argument block it had.
+struct YuvRow {
+  const uint8_t *y, *cb, *cr;
+};
+
+// the compact 8-bit frame (3H/2, W): int pitches from H, W and the layout, byte loads, no shift.  Cb of sample (c, xc) is at
+// chroma[c * cw + xc * cs], Cr cr_off bytes behind it.
+struct CompactSource {
+  using Arg = int;  // the layout
+  static constexpr int BITS = 8;
+  struct Size {
+    int H, W;  // (the chroma rows start behind H * W bytes of luma)
+  };
+  int layout, H, W, cw, cs;
+  long long cr_off;
+  __device__ CompactSource(int layout, Size s) : CompactSource(layout, s.H, s.W) {}
+  __device__ CompactSource(int layout, int H, int W)
+      : layout(layout), H(H), W(W), cw(layout == 0 ? W : W / 2), cs(layout == 0 ? 2 : 1), cr_off(layout == 0 ? 1 : (long long)(H / 2) * (W / 2)) {}
+  __device__ __forceinline__ YuvRow row(const uint8_t* frame, int y) const {
+    const uint8_t* yrow = frame + (long long)y * W;
+    const uint8_t* cb = frame + (long long)H * W + (long long)(y >> 1) * cw;
+    return {yrow, cb, cb + cr_off};
+  }
+  __device__ __forceinline__ int luma(const YuvRow& r, int x) const { return r.y[x]; }
+  __device__ __forceinline__ void chroma_pair(const YuvRow& r, int xc, int& cb, int& cr) const { cb = r.cb[xc * cs], cr = r.cr[xc * cs]; }
+  // pixels 4 q .. 4 q + 3: yy from one 4-byte load, c = Cb0, Cr0, Cb1, Cr1 from one 4-byte (NV12) or two 2-byte (I420) loads
+  __device__ __forceinline__ void quad(const YuvRow& r, int q, int (&yy)[4], int (&c)[4]) const {
+    const uint32_t yw = load_as<uint32_t>(r.y + 4 * q);
+    uint32_t cc;  // Cb0 | Cr0 << 8 | Cb1 << 16 | Cr1 << 24
+    if (layout == 0) {
+      cc = load_as<uint32_t>(r.cb + 4 * q);
+    } else {
+      const uint32_t u = load_as<uint16_t>(r.cb + 2 * q), v = load_as<uint16_t>(r.cr + 2 * q);
+      cc = (u & 255) | (v & 255) << 8 | (u >> 8) << 16 | (v >> 8) << 24;
+    }
+    yy[0] = yw & 255, yy[1] = (yw >> 8) & 255, yy[2] = (yw >> 16) & 255, yy[3] = yw >> 24;
+    c[0] = cc & 255, c[1] = (cc >> 8) & 255, c[2] = (cc >> 16) & 255, c[3] = cc >> 24;
+  }
+};
+
+// a decoder surface: 64-bit byte geometry by value, samples of BITS bits
+template <int BITS_>
+struct SurfaceSource {
+  using Arg = YuvSurface;
+  static constexpr int BITS = BITS_, SB = BITS == 8 ? 1 : 2;  // SB: bytes per sample
+  struct Size {
+    int W;
+  };
+  YuvSurface S;
+  __device__ SurfaceSource(const YuvSurface& S, Size) : S(S) {}
+  __device__ SurfaceSource(const YuvSurface& S, int, int) : S(S) {}
+  __device__ __forceinline__ YuvRow row(const uint8_t* frame, int y) const {
+    return {frame + S.y_off + y * S.y_pitch, frame + S.cb_off + (y >> 1) * S.c_pitch, frame + S.cr_off + (y >> 1) * S.c_pitch};
+  }
+  // (the column widened by the caller: the byte offset is formed in 64 bits, as every other offset of a surface)
+  __device__ __forceinline__ int luma(const YuvRow& r, long long x) const { return yuv_sample<BITS>(r.y + x * SB, S.shift); }
+  __device__ __forceinline__ void chroma_pair(const YuvRow& r, int xc, int& cb, int& cr) const {
+    cb = yuv_sample<BITS>(r.cb + (long long)xc * S.c_step, S.shift), cr = yuv_sample<BITS>(r.cr + (long long)xc * S.c_step, S.shift);
+  }
+  // pixels 4 q .. 4 q + 3: yy from one load of four samples, c = Cb0, Cr0, Cb1, Cr1 from one load of two pairs (interleaved chroma,
+  // in either order) or two loads of two samples (planar)
+  __device__ __forceinline__ void quad(const YuvRow& r, int q, int (&yy)[4], int (&c)[4]) const {
+    yuv_sample4<BITS>(r.y + 4 * SB * q, S.shift, yy);
+    if (S.c_step == 2 * SB) {  // interleaved pairs: the two offsets are one sample apart
+      yuv_sample4<BITS>((S.cb_off < S.cr_off ? r.cb : r.cr) + 4 * SB * q, S.shift, c);
+      if (S.cr_off < S.cb_off) {
+        const int c0 = c[0], c2 = c[2];
+        c[0] = c[1], c[1] = c0, c[2] = c[3], c[3] = c2;
+      }
+    } else {
+      yuv_sample2<BITS>(r.cb + 2 * SB * q, S.shift, c[0], c[2]);
+      yuv_sample2<BITS>(r.cr + 2 * SB * q, S.shift, c[1], c[3]);
+    }
+  }
+};
+
+// two packed pixels (R | G << 8 | B << 16 each) -> their six bytes at o, as three 2-byte pieces (`even`: o is 2-byte aligned) or bytes
+__device__ __forceinline__ void store_rgb_pair(uint8_t* o, uint32_t p0, uint32_t p1, int even) {
+  if (even) {
+    store_as(o, (uint16_t)p0);
+    store_as(o + 2, (uint16_t)(p0 >> 16 | p1 << 8));
+    store_as(o + 4, (uint16_t)(p1 >> 8));
+  } else {
+    o[0] = (uint8_t)p0, o[1] = (uint8_t)(p0 >> 8), o[2] = (uint8_t)(p0 >> 16);
+    o[3] = (uint8_t)p1, o[4] = (uint8_t)(p1 >> 8), o[5] = (uint8_t)(p1 >> 16);
+  }
+}
+
+// The conversion alone: dst row r = (f, y) <- source frame f (at byte f * fpitch); one wave per output row.  QUAD is chosen on the
+// host (launch_to_rgb) from the alignment of everything that enters an address: a lane converts four adjacent pixels = two chroma
+// samples from one load of four Y samples and the source's load of two (Cb, Cr) pairs, and stores their 12 bytes at once.  Otherwise
+// a lane converts the pair that shares one chroma sample and stores six bytes (store_rgb_pair; rows and pairs are 2-byte aligned
+// where dst is, as W is even).
+template <class Src, bool QUAD>
+__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int H,
+                                                              int W, typename Src::Arg arg, YuvCoef k, int even, long long nrows) {
+  using Terms = ChromaTerms<Src::BITS>;
   const int lane = threadIdx.x & 63;
+  const Src S(arg, H, W);
   for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
     const long long f = r / H;
     const int y = (int)(r - f * H);
-    const uint8_t* frame = src + f * fpitch;
-    const uint8_t* yrow = frame + S.y_off + y * S.y_pitch;
-    const uint8_t* cb = frame + S.cb_off + (y >> 1) * S.c_pitch;
-    const uint8_t* cr = frame + S.cr_off + (y >> 1) * S.c_pitch;
+    const YuvRow in = S.row(src + f * fpitch, y);
     uint8_t* out = dst + r * W * 3;
     if constexpr (QUAD) {
       for (int q = lane; q < W / 4; q += 64) {
-        int yy[4], c[4];  // c: Cb0, Cr0, Cb1, Cr1
-        yuv_sample4<BITS>(yrow + 4 * SB * q, S.shift, yy);
-        if (S.c_step == 2 * SB) {  // interleaved pairs: the two offsets are one sample apart
-          yuv_sample4<BITS>((S.cb_off < S.cr_off ? cb : cr) + 4 * SB * q, S.shift, c);
-          if (S.cr_off < S.cb_off) {
-            const int c0 = c[0], c2 = c[2];
-            c[0] = c[1], c[1] = c0, c[2] = c[3], c[3] = c2;
-          }
-        } else {
-          yuv_sample2<BITS>(cb + 2 * SB * q, S.shift, c[0], c[2]);
-          yuv_sample2<BITS>(cr + 2 * SB * q, S.shift, c[1], c[3]);
-        }
-        const ChromaTerms<BITS> c0(c[0], c[1], k), c1(c[2], c[3], k);
+        int yy[4], c[4];
+        S.quad(in, q, yy, c);
+        const Terms c0(c[0], c[1], k), c1(c[2], c[3], k);
         const uint32_t p0 = yuv_rgb_packed(yy[0], c0, k), p1 = yuv_rgb_packed(yy[1], c0, k);
         const uint32_t p2 = yuv_rgb_packed(yy[2], c1, k), p3 = yuv_rgb_packed(yy[3], c1, k);
         store_as(out + 12 * q, Rgb4{p0 | p1 << 24, p1 >> 8 | p2 << 16, p2 >> 16 | p3 << 8});
       }
     } else {
       for (int p = lane; p < W / 2; p += 64) {
-        const ChromaTerms<BITS> c(yuv_sample<BITS>(cb + (long long)p * S.c_step, S.shift), yuv_sample<BITS>(cr + (long long)p * S.c_step, S.shift), k);
-        const uint32_t p0 = yuv_rgb_packed(yuv_sample<BITS>(yrow + 2 * SB * p, S.shift), c, k);
-        const uint32_t p1 = yuv_rgb_packed(yuv_sample<BITS>(yrow + 2 * SB * p + SB, S.shift), c, k);
-        uint8_t* o = out + 6 * p;
-        if (even) {
-          store_as(o, (uint16_t)p0);
-          store_as(o + 2, (uint16_t)(p0 >> 16 | p1 << 8));
-          store_as(o + 4, (uint16_t)(p1 >> 8));
-        } else {
-          o[0] = (uint8_t)p0, o[1] = (uint8_t)(p0 >> 8), o[2] = (uint8_t)(p0 >> 16);
-          o[3] = (uint8_t)p1, o[4] = (uint8_t)(p1 >> 8), o[5] = (uint8_t)(p1 >> 16);
-        }
+        int cb, cr;
+        S.chroma_pair(in, p, cb, cr);
+        const Terms c(cb, cr, k);
+        store_rgb_pair(out + 6 * p, yuv_rgb_packed(S.luma(in, 2 * p), c, k), yuv_rgb_packed(S.luma(in, 2 * p + 1), c, k), even);
       }
     }
   }
 }
 
-// resize_h_yuv420_u8_kernel on a surface: the same walk, chroma sample by chroma sample, and the same 2^21 rounding
-template <int BITS>
-__global__ __launch_bounds__(256) void resize_h_yuv420_surface_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
-                                                                        int W, int OW, int row0, int rows, const int* __restrict__ xb,
-                                                                        const int* __restrict__ xk, int ksize, YuvSurface S, YuvCoef k,
-                                                                        long long nrows) {
-  constexpr int SB = BITS == 8 ? 1 : 2;
-  const int lane = threadIdx.x & 63;
+// resize_h_u8_kernel on 4:2:0 frames: every tap's pixel is converted to its three bytes first and accumulated as there, so the
+// output is byte for byte that kernel's on the converted frame.  The taps [x0, x0 + n) are walked chroma sample by chroma sample:
+// one chroma read and one set of products for the (up to) two taps that share it.
+template <class Src>
+__global__ __launch_bounds__(256) void resize_h_yuv420_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
+                                                                typename Src::Size size, int OW, int row0, int rows, const int* __restrict__ xb,
+                                                                const int* __restrict__ xk, int ksize, typename Src::Arg arg, YuvCoef k,
+                                                                long long nrows) {
+  const int lane = threadIdx.x & 63, W = size.W;
+  const Src S(arg, size);
   for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < nrows; r += (long long)gridDim.x * 4) {
     const long long f = r / rows;
     const int y = row0 + (int)(r - f * rows);
-    const uint8_t* frame = src + f * fpitch;
-    const uint8_t* yrow = frame + S.y_off + y * S.y_pitch;
-    const uint8_t* cb = frame + S.cb_off + (y >> 1) * S.c_pitch;
-    const uint8_t* cr = frame + S.cr_off + (y >> 1) * S.c_pitch;
+    const YuvRow in = S.row(src + f * fpitch, y);
     uint8_t* out = dst + r * OW * 3;
     for (int x = lane; x < OW; x += 64) {
       int x0 = xb[2 * x];
@@ -354,12 +327,14 @@ __global__ __launch_bounds__(256) void resize_h_yuv420_surface_u8_kernel(const u
       const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
       int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
       for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
-        const ChromaTerms<BITS> c(yuv_sample<BITS>(cb + (long long)xc * S.c_step, S.shift), yuv_sample<BITS>(cr + (long long)xc * S.c_step, S.shift), k);
+        int cb, cr;
+        S.chroma_pair(in, xc, cb, cr);
+        const ChromaTerms<Src::BITS> c(cb, cr, k);
 #pragma unroll
         for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
           if (xs >= x0 && xs < xe) {
             int pr, pg, pb;
-            yuv_rgb(yuv_sample<BITS>(yrow + (long long)xs * SB, S.shift), c, k, pr, pg, pb);
+            yuv_rgb(S.luma(in, xs), c, k, pr, pg, pb);
             const int wk = w[xs];
             s0 += pr * wk;
             s1 += pg * wk;
@@ -383,6 +358,70 @@ static bool mul_ok(long long a, long long b, long long c, long long d, long long
   return !__builtin_mul_overflow(a, b, &t) && !__builtin_mul_overflow(t, c, &t) && !__builtin_mul_overflow(t, d, out);
 }
 
+// every kernel here: a wave per row, four rows per block
+static int row_grid(long long nrows) { return (int)std::min<long long>((nrows + 3) / 4, 256 * 256); }
+
+// source frames 0, frame_step, 2 frame_step, ... -> a compact output (F_src < 1 passes through: the caller refuses it)
+static int64_t sampled_frames(int64_t F_src, int32_t frame_step) { return F_src < 1 ? F_src : (F_src - 1) / frame_step + 1; }
+
+// bytes from one sampled 4:2:0 source frame to the next -> *pitch, false where the product overflows (never with F > 1 frames whose
+// bytes were counted: it lies inside them).  A single frame has no next one: its pitch is 0.
+static bool source_pitch(long long frame_bytes, int32_t frame_step, int64_t F, long long* pitch) {
+  const bool ok = mul_ok(frame_bytes, frame_step, 1, 1, pitch);
+  if (F == 1) *pitch = 0;
+  return ok;
+}
+
+// the eleven resize arguments of the resize entry points
+struct ResizeArgs {
+  int32_t C, OH, OW;
+  const int32_t *xbounds, *xcoef;
+  int32_t xksize;
+  const int32_t *ybounds, *ycoef;
+  int32_t yksize, row0, rows;
+};
+
+// Which passes the resize of F frames H x W -> OH x OW runs, with what they need checked: tables and a ksize per pass, the
+// horizontal pass's rows inside the frame (all of them where no vertical pass follows) and the workspace between the passes.
+// `converted` (4:2:0 frames): a vertical pass alone reads the converted F x H x W x C frames from the workspace, not the source.
+struct PassPlan {
+  bool horiz, vert;
+  long long ws_bytes;  // of the horizontal pass's rows
+};
+
+static int plan_passes(const char* who, int64_t F, int32_t H, int32_t W, const ResizeArgs& R, const uint8_t* ws, bool converted,
+                       PassPlan* P) {
+  *P = {R.OW != W, R.OH != H, 0};
+  ADVHIP_REQUIRE((long long)W * R.C <= INT32_MAX && (long long)R.OW * R.C <= INT32_MAX, "%s: rows of %d / %d pixels are too long", who, W, R.OW);
+  if (P->horiz) {
+    ADVHIP_REQUIRE(R.xbounds && R.xcoef, "%s: null horizontal tables", who);
+    ADVHIP_REQUIRE(R.xksize >= 1, "%s: horizontal ksize %d < 1", who, R.xksize);
+    ADVHIP_REQUIRE(R.row0 >= 0 && R.rows >= 1 && (long long)R.row0 + R.rows <= H, "%s: rows [%d, %lld) of the horizontal pass outside the %d-row frames",
+                   who, R.row0, (long long)R.row0 + R.rows, H);
+    ADVHIP_REQUIRE(P->vert || (R.row0 == 0 && R.rows == H), "%s: without a vertical pass the horizontal pass must compute all %d rows", who, H);
+    ADVHIP_REQUIRE(mul_ok(F, R.rows, R.OW, R.C, &P->ws_bytes), "%s: workspace size overflows int64", who);
+    ADVHIP_REQUIRE(ws || !P->vert, "%s: null workspace for the horizontal pass (%lld bytes)", who, P->ws_bytes);
+  } else if (P->vert && converted) {  // (the caller counted these bytes: no overflow)
+    ADVHIP_REQUIRE(ws, "%s: null workspace for the converted frames of a vertical-only resize (%lld bytes)", who, (long long)F * H * W * R.C);
+  }
+  if (P->vert) {
+    ADVHIP_REQUIRE(R.ybounds && R.ycoef, "%s: null vertical tables", who);
+    ADVHIP_REQUIRE(R.yksize >= 1, "%s: vertical ksize %d < 1", who, R.yksize);
+  }
+  return ADVHIP_OK;
+}
+
+// the vertical pass of a plan: from the horizontal pass's rows in the workspace, or (no horizontal pass) from whole H-row RGB
+// frames at `frames`, `pitch` bytes apart
+static int launch_vertical(const char* what, const PassPlan& P, const ResizeArgs& R, const uint8_t* frames, long long pitch, const uint8_t* ws,
+                           uint8_t* dst, int64_t F, int32_t H, hipStream_t s) {
+  const long long nrows = F * R.OH;
+  hipLaunchKernelGGL(resize_v_u8_kernel, dim3(row_grid(nrows)), dim3(256), 0, s, P.horiz ? ws : frames, dst,
+                     P.horiz ? (long long)R.rows * R.OW * R.C : pitch, P.horiz ? R.rows : H, R.OH, R.OW * R.C, P.horiz ? R.row0 : 0, R.ybounds, R.ycoef,
+                     R.yksize, nrows);
+  return check_launch(what);
+}
+
 extern "C" int advhip_resize_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F, int32_t H, int32_t W, int32_t C, int32_t OH,
                                 int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds,
                                 const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, void* stream) {
@@ -393,33 +432,21 @@ extern "C" int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_
                                         int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                                         const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows,
                                         void* stream) {
+  const ResizeArgs R{C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, row0, rows};
   ADVHIP_REQUIRE(src && dst, "resize_u8: null frames or output");
   ADVHIP_REQUIRE(frame_step >= 1, "resize_u8: frame step %d", frame_step);
-  // source frames 0, frame_step, 2 frame_step, ... -> a compact output (F_src < 1 is refused below)
-  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
+  const int64_t F = sampled_frames(F_src, frame_step);
   ADVHIP_REQUIRE(F >= 1 && H >= 1 && W >= 1 && OH >= 1 && OW >= 1, "resize_u8: sizes must be >= 1 (F=%lld, %d x %d -> %d x %d)",
                  (long long)F, H, W, OH, OW);
   ADVHIP_REQUIRE(C == 3, "resize_u8: frames must have 3 channels (RGB), got C=%d", C);
-  const bool horiz = OW != W, vert = OH != H;
-  long long in_bytes, out_bytes, ws_bytes = 0;
+  long long in_bytes, out_bytes;
   ADVHIP_REQUIRE(mul_ok(F_src, H, W, C, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes), "resize_u8: frame sizes overflow int64");
-  const long long frame_bytes = (long long)H * W * C, src_pitch = F > 1 ? frame_bytes * frame_step : frame_bytes;  // (F > 1: inside in_bytes)
-  ADVHIP_REQUIRE((long long)W * C <= INT32_MAX && (long long)OW * C <= INT32_MAX, "resize_u8: rows of %d / %d pixels are too long", W, OW);
-  if (horiz) {
-    ADVHIP_REQUIRE(xbounds && xcoef, "resize_u8: null horizontal tables");
-    ADVHIP_REQUIRE(xksize >= 1, "resize_u8: horizontal ksize %d < 1", xksize);
-    ADVHIP_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= H, "resize_u8: rows [%d, %lld) of the horizontal pass outside the %d-row frames",
-                   row0, (long long)row0 + rows, H);
-    ADVHIP_REQUIRE(vert || (row0 == 0 && rows == H), "resize_u8: without a vertical pass the horizontal pass must compute all %d rows", H);
-    ADVHIP_REQUIRE(mul_ok(F, rows, OW, C, &ws_bytes), "resize_u8: workspace size overflows int64");
-    ADVHIP_REQUIRE(ws || !vert, "resize_u8: null workspace for the horizontal pass (%lld bytes)", ws_bytes);
-  }
-  if (vert) {
-    ADVHIP_REQUIRE(ybounds && ycoef, "resize_u8: null vertical tables");
-    ADVHIP_REQUIRE(yksize >= 1, "resize_u8: vertical ksize %d < 1", yksize);
-  }
+  // (F > 1: the product is inside in_bytes; a single frame keeps a pitch that the strided copy below accepts)
+  const long long frame_bytes = (long long)H * W * C, src_pitch = F > 1 ? frame_bytes * frame_step : frame_bytes;
+  PassPlan P;
+  if (const int rc = plan_passes("resize_u8", F, H, W, R, ws, false, &P); rc != ADVHIP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (!horiz && !vert) {  // Pillow returns a copy
+  if (!P.horiz && !P.vert) {  // Pillow returns a copy
     hipError_t e = hipSuccess;
     if (frame_step > 1) e = hipMemcpy2DAsync(dst, (size_t)frame_bytes, src, (size_t)src_pitch, (size_t)frame_bytes, (size_t)F, hipMemcpyDeviceToDevice, s);
     else if (src != dst) e = hipMemcpyAsync(dst, src, (size_t)in_bytes, hipMemcpyDeviceToDevice, s);
@@ -429,23 +456,14 @@ extern "C" int advhip_resize_u8_sampled(const uint8_t* src, uint8_t* dst, uint8_
     }
     return ADVHIP_OK;
   }
-  if (horiz) {
+  if (P.horiz) {
     const long long nrows = F * rows;
-    const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid), dim3(256), 0, s, src, vert ? ws : dst, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
-                       nrows);
+    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(row_grid(nrows)), dim3(256), 0, s, src, P.vert ? ws : dst, src_pitch, W, OW, row0, rows, xbounds, xcoef,
+                       xksize, nrows);
     const int rc = check_launch("resize_u8 horizontal pass");
     if (rc != ADVHIP_OK) return rc;
   }
-  if (vert) {
-    const long long nrows = F * OH;
-    const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid), dim3(256), 0, s, horiz ? (const uint8_t*)ws : src, dst,
-                       horiz ? (long long)rows * OW * C : src_pitch, horiz ? rows : H, OH, OW * C,
-                       horiz ? row0 : 0, ybounds, ycoef, yksize, nrows);
-    return check_launch("resize_u8 vertical pass");
-  }
-  return ADVHIP_OK;
+  return P.vert ? launch_vertical("resize_u8 vertical pass", P, R, src, src_pitch, ws, dst, F, H, s) : ADVHIP_OK;
 }
 
 // where the 4:2:0 samples of a frame are: a surface by its numbers, with the frame pitch the caller gave
@@ -506,61 +524,51 @@ static int check_surface(const char* who, const uint8_t* src, int32_t H, int32_t
   return check_yuv_coef(who, k, Y.bits);
 }
 
-// (every argument checked by the caller) frames 0, frame_step, ... of src -> compact RGB frames in dst
-static int launch_yuv420_to_rgb(const uint8_t* src, uint8_t* dst, long long F, long long src_pitch, int H, int W, int layout, const YuvCoef& k,
-                                hipStream_t s) {
+// one source's conversion kernel, with or without the four-pixel path
+template <class Src>
+static void launch_to_rgb_from(bool quad, const typename Src::Arg& arg, const uint8_t* src, uint8_t* dst, long long F, long long src_pitch, int H, int W,
+                               const YuvCoef& k, hipStream_t s) {
   const long long nrows = F * H;
-  const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-  const bool quad = W % 4 == 0 && (uintptr_t)src % 4 == 0 && (uintptr_t)dst % 4 == 0;  // (a frame is 3 H / 2 * W bytes: a multiple of 4 then)
-  if (quad) hipLaunchKernelGGL(yuv420_to_rgb_u8_kernel<true>, dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, layout, k, 1, nrows);
+  if (quad) hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<Src, true>), dim3(row_grid(nrows)), dim3(256), 0, s, src, dst, src_pitch, H, W, arg, k, 1, nrows);
   else
-    hipLaunchKernelGGL(yuv420_to_rgb_u8_kernel<false>, dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, layout, k,
-                       (int)((uintptr_t)dst % 2 == 0), nrows);
-  return check_launch("yuv420_to_rgb_u8");
-}
-
-template <int BITS>
-static void launch_surface_to_rgb_bits(bool quad, int grid, hipStream_t s, const uint8_t* src, uint8_t* dst, long long src_pitch, int H, int W,
-                                       const YuvSurface& S, const YuvCoef& k, long long nrows) {
-  if (quad) hipLaunchKernelGGL((yuv420_surface_to_rgb_u8_kernel<BITS, true>), dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, S, k, 1, nrows);
-  else
-    hipLaunchKernelGGL((yuv420_surface_to_rgb_u8_kernel<BITS, false>), dim3(grid), dim3(256), 0, s, src, dst, src_pitch, H, W, S, k,
+    hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<Src, false>), dim3(row_grid(nrows)), dim3(256), 0, s, src, dst, src_pitch, H, W, arg, k,
                        (int)((uintptr_t)dst % 2 == 0), nrows);
 }
 
-// the same for a surface.  The four-pixel path needs every load and the 12-byte store aligned: Y and interleaved chroma are read
-// 4 sb bytes at a time, planar chroma 2 sb bytes, so everything that enters those addresses must be a multiple of that -- the
-// pointer, the frame pitch (where a second frame is read), the offsets and the pitches.
-static int launch_surface_to_rgb(const uint8_t* src, uint8_t* dst, long long F, long long src_pitch, int H, int W, const Yuv420Source& Y,
-                                 const YuvCoef& k, hipStream_t s) {
+// (every argument checked by the caller) frames 0, frame_step, ... of src -> compact RGB frames in dst; `compact` frames run their
+// own instantiation, a surface the surface ones.  The four-pixel path needs every load and the 12-byte store aligned.  Compact
+// frames: W a multiple of 4 and both pointers 4-byte aligned (a frame is 3 H / 2 * W bytes: a multiple of 4 then).  A surface: Y and
+// interleaved chroma are read 4 sb bytes at a time, planar chroma 2 sb bytes, so everything that enters those addresses must be a
+// multiple of that -- the pointer, the frame pitch (where a second frame is read), the offsets and the pitches.
+static int launch_to_rgb(bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, long long F, long long src_pitch, int H,
+                         int W, const YuvCoef& k, hipStream_t s) {
   const YuvSurface& S = Y.S;
-  const long long nrows = F * H;
-  const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
   const int sb = Y.bits == 8 ? 1 : 2;
   const long long ya = 4 * sb, ca = S.c_step == 2 * sb ? 4 * sb : 2 * sb;
-  const bool quad = W % 4 == 0 && (uintptr_t)dst % 4 == 0 && ((uintptr_t)src | src_pitch | S.y_off | S.y_pitch) % ya == 0 &&
-                    ((uintptr_t)src | src_pitch | std::min(S.cb_off, S.cr_off) | S.c_pitch) % ca == 0 &&
-                    (S.c_step == 2 * sb || (S.cb_off | S.cr_off) % ca == 0);
-  if (Y.bits == 8) launch_surface_to_rgb_bits<8>(quad, grid, s, src, dst, src_pitch, H, W, S, k, nrows);
-  else launch_surface_to_rgb_bits<10>(quad, grid, s, src, dst, src_pitch, H, W, S, k, nrows);
-  return check_launch("yuv420_surface_to_rgb_u8");
+  const bool quad = W % 4 == 0 && (uintptr_t)dst % 4 == 0 &&
+                    (compact ? (uintptr_t)src % 4 == 0
+                             : ((uintptr_t)src | src_pitch | S.y_off | S.y_pitch) % ya == 0 &&
+                                   ((uintptr_t)src | src_pitch | std::min(S.cb_off, S.cr_off) | S.c_pitch) % ca == 0 &&
+                                   (S.c_step == 2 * sb || (S.cb_off | S.cr_off) % ca == 0));
+  if (compact) launch_to_rgb_from<CompactSource>(quad, layout, src, dst, F, src_pitch, H, W, k, s);
+  else if (Y.bits == 8) launch_to_rgb_from<SurfaceSource<8>>(quad, S, src, dst, F, src_pitch, H, W, k, s);
+  else launch_to_rgb_from<SurfaceSource<10>>(quad, S, src, dst, F, src_pitch, H, W, k, s);
+  return check_launch(compact ? "yuv420_to_rgb_u8" : "yuv420_surface_to_rgb_u8");
 }
 
-// both conversion entry points: `compact` frames run their own kernels, a surface the surface kernels
+// both conversion entry points
 static int yuv420_to_rgb(const char* who, bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, int64_t F_src,
                          int32_t frame_step, int32_t H, int32_t W, const YuvCoef& k, void* stream) {
   ADVHIP_REQUIRE(src && dst, "%s: null frames or output", who);
   ADVHIP_REQUIRE(frame_step >= 1, "%s: frame step %d", who, frame_step);
-  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
+  const int64_t F = sampled_frames(F_src, frame_step);
   ADVHIP_REQUIRE(F >= 1, "%s: %lld frames", who, (long long)F_src);
   if (const int rc = compact ? check_yuv420(who, H, W, layout, k) : check_surface(who, src, H, W, Y, k); rc != ADVHIP_OK) return rc;
   long long in_bytes, out_bytes, pitch;
-  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, H, W, 3, &out_bytes) && mul_ok(Y.frame_pitch, frame_step, 1, 1, &pitch),
+  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, H, W, 3, &out_bytes) && source_pitch(Y.frame_pitch, frame_step, F, &pitch),
                  "%s: frame sizes overflow int64", who);
   ADVHIP_REQUIRE((long long)W * 3 <= INT32_MAX, "%s: rows of %d pixels are too long", who, W);
-  if (F == 1) pitch = 0;  // (F > 1: inside in_bytes)
-  if (compact) return launch_yuv420_to_rgb(src, dst, F, pitch, H, W, layout, k, (hipStream_t)stream);
-  return launch_surface_to_rgb(src, dst, F, pitch, H, W, Y, k, (hipStream_t)stream);
+  return launch_to_rgb(compact, layout, Y, src, dst, F, pitch, H, W, k, (hipStream_t)stream);
 }
 
 extern "C" int advhip_yuv420_to_rgb_u8(const uint8_t* src, uint8_t* dst, int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t layout,
@@ -577,76 +585,48 @@ extern "C" int advhip_yuv420_surface_to_rgb_u8(const uint8_t* src, uint8_t* dst,
   return yuv420_to_rgb("yuv420_surface_to_rgb_u8", false, -1, Y, src, dst, F_src, frame_step, H, W, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
 }
 
-// both fused-resize entry points, as above
+// both fused-resize entry points
 static int resize_yuv420(const char* who, bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, uint8_t* ws,
-                         int64_t F_src, int32_t frame_step, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds,
-                         const int32_t* xcoef, int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0,
-                         int32_t rows, const YuvCoef& k, void* stream) {
+                         int64_t F_src, int32_t frame_step, int32_t H, int32_t W, const ResizeArgs& R, const YuvCoef& k, void* stream) {
   ADVHIP_REQUIRE(src && dst, "%s: null frames or output", who);
   ADVHIP_REQUIRE(frame_step >= 1, "%s: frame step %d", who, frame_step);
-  const int64_t F = F_src < 1 ? F_src : (F_src - 1) / frame_step + 1;
-  ADVHIP_REQUIRE(F >= 1 && OH >= 1 && OW >= 1, "%s: sizes must be >= 1 (F=%lld, -> %d x %d)", who, (long long)F, OH, OW);
-  ADVHIP_REQUIRE(C == 3, "%s: the output has 3 channels (RGB), got C=%d", who, C);
+  const int64_t F = sampled_frames(F_src, frame_step);
+  ADVHIP_REQUIRE(F >= 1 && R.OH >= 1 && R.OW >= 1, "%s: sizes must be >= 1 (F=%lld, -> %d x %d)", who, (long long)F, R.OH, R.OW);
+  ADVHIP_REQUIRE(R.C == 3, "%s: the output has 3 channels (RGB), got C=%d", who, R.C);
   if (const int rc = compact ? check_yuv420(who, H, W, layout, k) : check_surface(who, src, H, W, Y, k); rc != ADVHIP_OK) return rc;
-  const bool horiz = OW != W, vert = OH != H;
-  long long in_bytes, out_bytes, rgb_bytes, src_pitch, ws_bytes = 0;
-  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, OH, OW, C, &out_bytes) && mul_ok(F, H, W, C, &rgb_bytes) &&
-                     mul_ok(Y.frame_pitch, frame_step, 1, 1, &src_pitch),
+  long long in_bytes, out_bytes, rgb_bytes, src_pitch;
+  ADVHIP_REQUIRE(mul_ok(F_src, Y.frame_pitch, 1, 1, &in_bytes) && mul_ok(F, R.OH, R.OW, R.C, &out_bytes) && mul_ok(F, H, W, R.C, &rgb_bytes) &&
+                     source_pitch(Y.frame_pitch, frame_step, F, &src_pitch),
                  "%s: frame sizes overflow int64", who);
-  if (F == 1) src_pitch = 0;  // (F > 1: inside in_bytes)
-  ADVHIP_REQUIRE((long long)W * C <= INT32_MAX && (long long)OW * C <= INT32_MAX, "%s: rows of %d / %d pixels are too long", who, W, OW);
-  if (horiz) {
-    ADVHIP_REQUIRE(xbounds && xcoef, "%s: null horizontal tables", who);
-    ADVHIP_REQUIRE(xksize >= 1, "%s: horizontal ksize %d < 1", who, xksize);
-    ADVHIP_REQUIRE(row0 >= 0 && rows >= 1 && (long long)row0 + rows <= H, "%s: rows [%d, %lld) of the horizontal pass outside the %d-row frames", who,
-                   row0, (long long)row0 + rows, H);
-    ADVHIP_REQUIRE(vert || (row0 == 0 && rows == H), "%s: without a vertical pass the horizontal pass must compute all %d rows", who, H);
-    ADVHIP_REQUIRE(mul_ok(F, rows, OW, C, &ws_bytes), "%s: workspace size overflows int64", who);
-    ADVHIP_REQUIRE(ws || !vert, "%s: null workspace for the horizontal pass (%lld bytes)", who, ws_bytes);
-  } else if (vert) {
-    ADVHIP_REQUIRE(ws, "%s: null workspace for the converted frames of a vertical-only resize (%lld bytes)", who, rgb_bytes);
-  }
-  if (vert) {
-    ADVHIP_REQUIRE(ybounds && ycoef, "%s: null vertical tables", who);
-    ADVHIP_REQUIRE(yksize >= 1, "%s: vertical ksize %d < 1", who, yksize);
-  }
+  PassPlan P;
+  if (const int rc = plan_passes(who, F, H, W, R, ws, true, &P); rc != ADVHIP_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (horiz) {
-    const long long nrows = F * rows;
-    const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    uint8_t* to = vert ? ws : dst;
-    if (compact)
-      hipLaunchKernelGGL(resize_h_yuv420_u8_kernel, dim3(grid), dim3(256), 0, s, src, to, src_pitch, H, W, OW, row0, rows, xbounds, xcoef, xksize, layout,
-                         k, nrows);
-    else if (Y.bits == 8)
-      hipLaunchKernelGGL(resize_h_yuv420_surface_u8_kernel<8>, dim3(grid), dim3(256), 0, s, src, to, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
-                         Y.S, k, nrows);
-    else
-      hipLaunchKernelGGL(resize_h_yuv420_surface_u8_kernel<10>, dim3(grid), dim3(256), 0, s, src, to, src_pitch, W, OW, row0, rows, xbounds, xcoef, xksize,
-                         Y.S, k, nrows);
+  uint8_t* to = P.vert ? ws : dst;
+  if (P.horiz) {
+    const long long nrows = F * R.rows;
+    auto launch = [&](auto kernel, const auto& size, const auto& arg) {
+      hipLaunchKernelGGL(kernel, dim3(row_grid(nrows)), dim3(256), 0, s, src, to, src_pitch, size, R.OW, R.row0, R.rows, R.xbounds, R.xcoef, R.xksize, arg, k,
+                         nrows);
+    };
+    if (compact) launch(resize_h_yuv420_u8_kernel<CompactSource>, CompactSource::Size{H, W}, layout);
+    else if (Y.bits == 8) launch(resize_h_yuv420_u8_kernel<SurfaceSource<8>>, SurfaceSource<8>::Size{W}, Y.S);
+    else launch(resize_h_yuv420_u8_kernel<SurfaceSource<10>>, SurfaceSource<10>::Size{W}, Y.S);
     const int rc = check_launch("resize_yuv420_u8 horizontal pass");
     if (rc != ADVHIP_OK) return rc;
   } else {  // rare: the conversion launch, into dst (the identity) or into the workspace the vertical pass then reads
-    const int rc = compact ? launch_yuv420_to_rgb(src, vert ? ws : dst, F, src_pitch, H, W, layout, k, s)
-                           : launch_surface_to_rgb(src, vert ? ws : dst, F, src_pitch, H, W, Y, k, s);
+    const int rc = launch_to_rgb(compact, layout, Y, src, to, F, src_pitch, H, W, k, s);
     if (rc != ADVHIP_OK) return rc;
   }
-  if (vert) {  // the RGB resize's own vertical pass
-    const long long nrows = F * OH;
-    const int grid = (int)std::min<long long>((nrows + 3) / 4, 256 * 256);
-    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid), dim3(256), 0, s, (const uint8_t*)ws, dst, horiz ? (long long)rows * OW * C : (long long)H * W * C,
-                       horiz ? rows : H, OH, OW * C, horiz ? row0 : 0, ybounds, ycoef, yksize, nrows);
-    return check_launch("resize_yuv420_u8 vertical pass");
-  }
-  return ADVHIP_OK;
+  // the RGB resize's own vertical pass
+  return P.vert ? launch_vertical("resize_yuv420_u8 vertical pass", P, R, ws, (long long)H * W * R.C, ws, dst, F, H, s) : ADVHIP_OK;
 }
 
 extern "C" int advhip_resize_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int32_t H, int32_t W,
                                        int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
                                        const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, int32_t row0, int32_t rows, int32_t layout,
                                        int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
-  return resize_yuv420("resize_yuv420_u8", true, layout, compact_source(H, W, layout), src, dst, ws, F_src, frame_step, H, W, C, OH, OW, xbounds, xcoef,
-                       xksize, ybounds, ycoef, yksize, row0, rows, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+  return resize_yuv420("resize_yuv420_u8", true, layout, compact_source(H, W, layout), src, dst, ws, F_src, frame_step, H, W,
+                       {C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, row0, rows}, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
 }
 
 extern "C" int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int32_t frame_step, int64_t frame_pitch,
@@ -656,6 +636,6 @@ extern "C" int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst,
                                                int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
                                                int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
   const Yuv420Source Y{bits, frame_pitch, {y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, shift}};
-  return resize_yuv420("resize_yuv420_surface_u8", false, -1, Y, src, dst, ws, F_src, frame_step, H, W, C, OH, OW, xbounds, xcoef, xksize, ybounds,
-                       ycoef, yksize, row0, rows, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+  return resize_yuv420("resize_yuv420_surface_u8", false, -1, Y, src, dst, ws, F_src, frame_step, H, W,
+                       {C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, row0, rows}, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
 }

@@ -350,15 +350,6 @@ def tables(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, st
     return t
 
 
-def _yuv_frames(who: str, frames: torch.Tensor, pf: PixelFormat) -> Tuple[int, int, int]:
-    """(F, H, W) of uint8 (F, 3H/2, W) 4:2:0 frames on the GPU."""
-    require_gpu(frames)
-    if frames.dtype != torch.uint8 or frames.dim() != 3:
-        raise HipExtensionError(f"{who} wants uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
-    h, w = frame_hw(frames.shape)
-    return frames.shape[0], h, w
-
-
 def _check_out(who: str, frames: torch.Tensor, out: torch.Tensor, shape: tuple) -> None:
     require_gpu(frames, out)
     if out.dtype != torch.uint8 or tuple(out.shape) != shape:
@@ -375,17 +366,36 @@ def _frame_step(who: str, frame_step) -> int:
     return d
 
 
-def _surface_frames(who: str, frames: torch.Tensor, pf: PixelFormat, surface) -> Tuple[int, Surface]:
-    """(F, the resolved Surface) of uint8 (F, frame_bytes) frames on the GPU."""
+class _Source(NamedTuple):
+    """What `frames` are: their sizes, the entry points of that kind of frame (`convert` is None for packed RGB, which has
+    nothing to convert) and the arguments those take before (H, W) and behind the resize arguments."""
+    F_src: int
+    H: int
+    W: int
+    convert: Optional[str]
+    resize: str
+    before: tuple
+    after: tuple
+
+
+def _source(who: str, frames: torch.Tensor, pf: Optional[PixelFormat], surface) -> _Source:
+    """Packed RGB (F, H, W, 3) (`pf` None), compact 4:2:0 frames (F, 3H/2, W) or surfaces (F, frame_bytes): uint8, on the GPU."""
     require_gpu(frames)
+    if pf is None:
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise HipExtensionError(f"{who} wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
+        return _Source(*frames.shape[:3], None, "advhip_resize_u8_sampled", (), ())
+    if surface is None:
+        if frames.dtype != torch.uint8 or frames.dim() != 3:
+            raise HipExtensionError(f"{who} wants uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
+        h, w = frame_hw(frames.shape)
+        return _Source(frames.shape[0], h, w, "advhip_yuv420_to_rgb_u8", "advhip_resize_yuv420_u8", (), (LAYOUTS[pf.layout],) + yuv_coefficients(pf))
     if frames.dtype != torch.uint8 or frames.dim() != 2:
         raise HipExtensionError(f"{who} with surface= wants uint8 (F, frame_bytes) frames, got {frames.dtype} {tuple(frames.shape)}")
-    return frames.shape[0], resolve_surface(surface, pf, frames.shape[1])
-
-
-def _surface_args(sf: Surface, pf: PixelFormat) -> tuple:
-    """The tail of both surface entry points: bits, shift, the geometry, the coefficients."""
-    return (sf.bits, sf.shift, sf.y_offset, sf.y_pitch, sf.cb_offset, sf.cr_offset, sf.chroma_pitch, sf.chroma_step) + yuv_coefficients(pf, sf.bits)
+    sf = resolve_surface(surface, pf, frames.shape[1])
+    geometry = (sf.bits, sf.shift, sf.y_offset, sf.y_pitch, sf.cb_offset, sf.cr_offset, sf.chroma_pitch, sf.chroma_step)
+    return _Source(frames.shape[0], sf.height, sf.width, "advhip_yuv420_surface_to_rgb_u8", "advhip_resize_yuv420_surface_u8", (frames.shape[1],),
+                   geometry + yuv_coefficients(pf, sf.bits))
 
 
 def yuv420_to_rgb_u8(frames: torch.Tensor, pixel_format, out: Optional[torch.Tensor] = None,
@@ -400,22 +410,14 @@ def yuv420_to_rgb_u8(frames: torch.Tensor, pixel_format, out: Optional[torch.Ten
     if pf is None:
         raise ValueError("yuv420_to_rgb_u8: pixel_format None is packed RGB, there is nothing to convert")
     d = _frame_step("yuv420_to_rgb_u8", frame_step)
-    if surface is None:
-        F_src, H, W = _yuv_frames("yuv420_to_rgb_u8", frames, pf)
-    else:
-        F_src, sf = _surface_frames("yuv420_to_rgb_u8", frames, pf, surface)
-        H, W = sf.height, sf.width
-    F = -(-F_src // d)
+    src = _source("yuv420_to_rgb_u8", frames, pf, surface)
+    shape = (-(-src.F_src // d), src.H, src.W, 3)
     if out is None:
-        out = torch.empty((F, H, W, 3), device=frames.device, dtype=torch.uint8)
+        out = torch.empty(shape, device=frames.device, dtype=torch.uint8)
     else:
-        _check_out("yuv420_to_rgb_u8", frames, out, (F, H, W, 3))
-    if surface is None:
-        check(_lib.load().advhip_yuv420_to_rgb_u8(ptr(frames), ptr(out), F_src, d, H, W, LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
-              "yuv420_to_rgb_u8")
-    else:
-        check(_lib.load().advhip_yuv420_surface_to_rgb_u8(ptr(frames), ptr(out), F_src, d, frames.shape[1], H, W, *_surface_args(sf, pf),
-                                                          stream(frames)), "yuv420_to_rgb_u8")
+        _check_out("yuv420_to_rgb_u8", frames, out, shape)
+    check(getattr(_lib.load(), src.convert)(ptr(frames), ptr(out), src.F_src, d, *src.before, src.H, src.W, *src.after, stream(frames)),
+          "yuv420_to_rgb_u8")
     return out
 
 
@@ -436,19 +438,14 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     in yuv420_to_rgb_u8, and the result is again resize_u8(yuv420_to_rgb_u8(frames, pixel_format, surface=surface), ...)."""
     d = _frame_step("resize_u8", frame_step)
     pf = resolve_pixel_format(pixel_format)
-    if pf is not None:
-        return _resize_yuv420_u8(frames, size, resample, out, d, pf, surface)
-    if surface is not None:
+    if pf is None and surface is not None:
         raise ValueError("resize_u8: surface= describes 4:2:0 frames and needs a pixel_format")
-    require_gpu(frames)
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-        raise HipExtensionError(f"resize_u8 wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
-    F_src, H, W, _ = frames.shape
-    F = -(-F_src // d)
+    src = _source("resize_u8", frames, pf, surface)
+    F, H, W, yuv = -(-src.F_src // d), src.H, src.W, pf is not None
     name = filter_name(resample)
     oh, ow = output_size(H, W, size)
     if out is None:
-        if (oh, ow) == (H, W):
+        if not yuv and (oh, ow) == (H, W):  # (4:2:0 frames always come back converted)
             return frames if d == 1 else frames[::d]
         out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
     else:
@@ -456,48 +453,9 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     t = tables(H, W, oh, ow, name, frames.device)
     p, b, (o_xb, o_xk, o_yb, o_yk) = t.plan, t.buf, t.offsets
     ws = None
-    if p.horizontal and p.vertical:
-        ws = torch.empty((F * p.rows * ow * 3,), device=frames.device, dtype=torch.uint8)
-    if d == 1:
-        check(_lib.load().advhip_resize_u8(ptr(frames), ptr(out), ptr(ws), F, H, W, 3, oh, ow,
-                                           ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
-                                           ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
-              "resize_u8")
-    else:
-        check(_lib.load().advhip_resize_u8_sampled(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, 3, oh, ow,
-                                                   ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1],
-                                                   ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows, stream(frames)),
-              "resize_u8")
-    return out
-
-
-def _resize_yuv420_u8(frames: torch.Tensor, size, resample, out: Optional[torch.Tensor], d: int, pf: PixelFormat,
-                      surface: Optional[Surface] = None) -> torch.Tensor:
-    """resize_u8 of 4:2:0 frames (advhip_resize_yuv420_u8; of surfaces, advhip_resize_yuv420_surface_u8)."""
-    if surface is None:
-        F_src, H, W = _yuv_frames("resize_u8", frames, pf)
-    else:
-        F_src, sf = _surface_frames("resize_u8", frames, pf, surface)
-        H, W = sf.height, sf.width
-    F = -(-F_src // d)
-    name = filter_name(resample)
-    oh, ow = output_size(H, W, size)
-    if out is None:
-        out = torch.empty((F, oh, ow, 3), device=frames.device, dtype=torch.uint8)
-    else:
-        _check_out("resize_u8", frames, out, (F, oh, ow, 3))
-    t = tables(H, W, oh, ow, name, frames.device)
-    p, b, (o_xb, o_xk, o_yb, o_yk) = t.plan, t.buf, t.offsets
-    ws = None
-    if p.vertical:  # the horizontal pass's rows, or (a vertical-only resize) the converted frames
+    if p.vertical and (p.horizontal or yuv):  # the horizontal pass's rows, or (a vertical-only resize of 4:2:0) the converted frames
         ws = torch.empty((F * p.rows * ow * 3 if p.horizontal else F * H * W * 3,), device=frames.device, dtype=torch.uint8)
     resize_args = (3, oh, ow, ptr(b[o_xb:]), ptr(b[o_xk:]), p.xcoef.shape[1], ptr(b[o_yb:]), ptr(b[o_yk:]), p.ycoef.shape[1], p.row0, p.rows)
-    if surface is None:
-        check(_lib.load().advhip_resize_yuv420_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, H, W, *resize_args,
-                                                  LAYOUTS[pf.layout], *yuv_coefficients(pf), stream(frames)),
-              "resize_u8")
-    else:
-        check(_lib.load().advhip_resize_yuv420_surface_u8(ptr(frames), ptr(out), ptr(ws), F_src, d, frames.shape[1], H, W, *resize_args,
-                                                          *_surface_args(sf, pf), stream(frames)),
-              "resize_u8")
+    check(getattr(_lib.load(), src.resize)(ptr(frames), ptr(out), ptr(ws), src.F_src, d, *src.before, H, W, *resize_args, *src.after, stream(frames)),
+          "resize_u8")
     return out
