@@ -102,8 +102,14 @@ ALGO_SMALL = _lib.ALGO_DMA2_BASE + _lib.ALGO_IGEMM_64x64  # few output tiles: 64
 ALGO_WIDE = _lib.ALGO_DMA2_BASE + _lib.ALGO_IGEMM_128x128
 
 
-def _desc(cin: int, cout: int, k: int, b: int, t: int, act: int) -> ConvDesc:
+def _desc(cin: int, cout: int, k: int, b: int, t: int, act: int, algo: Optional[int] = None, splits: Optional[int] = None) -> ConvDesc:
     # (1, C, 1, b, t) tensor, kernel (1, 1, k), padding (0, 0, k // 2): for k = 1 the caller folds (b, t) into one row
+    # `algo` / `splits`: pinned by the caller (tests of one tile at a size the rule below would never give it); a pinned tile runs
+    # unsplit unless the split count is pinned too, as in ops.conv3d_bn_act
+    if algo is not None or splits is not None:
+        d = _desc(cin, cout, k, b, t, act)
+        d.algo, d.splits = (d.algo if algo is None else algo), (splits if splits is not None else 1)
+        return d
     n = b * t
     tiles128 = -(-n // 128) * (cout // 64)
     algo, splits = ALGO, 1
@@ -287,9 +293,11 @@ def pack_dx(w: torch.Tensor) -> torch.Tensor:
 
 def conv_cn(x: torch.Tensor, w_packed: torch.Tensor, cout: int, k: int = 1, shift: Optional[torch.Tensor] = None,
             residual: Optional[torch.Tensor] = None, act: int = ACT_NONE, want_preact: bool = False,
-            dact_z: Optional[torch.Tensor] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+            dact_z: Optional[torch.Tensor] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, *,
+            algo: Optional[int] = None, splits: Optional[int] = None):
     """act(conv1d_k(x) + shift) or conv1d_k(x) + shift + residual for x (Cin, B, T) contiguous -> (Cout, B, T) [, pre-activation].
-    One launch, on torch's current stream of x's device (which must be the current device)."""
+    One launch, on torch's current stream of x's device (which must be the current device).  `algo` / `splits` pin the tile and the
+    K slices that `_desc` otherwise derives from the position count."""
     cin, b, t = x.shape
     _lib.require_gpu(x, w_packed, shift, residual, dact_z, *(ln or ()), contiguous=False)
     if not x.is_contiguous():
@@ -298,7 +306,9 @@ def conv_cn(x: torch.Tensor, w_packed: torch.Tensor, cout: int, k: int = 1, shif
         raise ValueError("conv_cn: ACT_MUL multiplies by the tensor passed as dact_z")
     if act != ACT_NONE and residual is not None:  # (the conv epilogue adds the residual BEFORE the activation, advhip_bgemm_f32 after)
         raise ValueError("conv_cn: an activation together with a residual is not offered (the two GEMM entry points order them differently)")
-    d = _desc(cin, cout, k, 1 if k == 1 else b, b * t if k == 1 else t, act)
+    shape = (cin, cout, k, 1 if k == 1 else b, b * t if k == 1 else t, act)
+    # (unpinned: the six arguments `_desc` always got -- the launch recorders that wrap it keep their signature)
+    d = _desc(*shape) if algo is None and splits is None else _desc(*shape, algo, splits)
     dev = x.device
     y = torch.empty((cout, b, t), device=dev, dtype=torch.float32)
     z = torch.empty_like(y) if want_preact else None
