@@ -270,6 +270,10 @@ SIGNATURES = {
     # frames_per_clip, frame_step, stream)
     "advhip_frame_ring_push_u8": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
     "advhip_frame_ring_windows_u8": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _P]),
+    # motion gate: (frames, cam_ids, anchor, state, scratch, n, n_cam, frame_bytes, pixel_delta, limit, stream) / (cam_ids, ring, counts, n,
+    # n_cam, ncrops, W, C1, stream)
+    "advhip_frame_gate_update_u8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
+    "advhip_ring_repeat_f32": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     # live events: (scores, cam_ids, ring, samples, cand_int, cand_peak, cand_sum, alert, open_start, log_int, log_f, emitted, nb, n_cam, K,
     # smooth, low, high, merge_gap, min_len, by_camera, mode, stream)
     "advhip_live_events_update_f32": (C.c_int, [_P] * 12 + [_I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _I, _P]),

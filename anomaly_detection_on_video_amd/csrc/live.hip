@@ -156,9 +156,187 @@ inline int launch_ring_advance(const int32_t* cam_ids, int64_t* counts, int32_t 
   return check_launch(who);
 }
 
+// ---- live frames: motion gate (include/advhip.h: "live frames: motion gate").  Integers only, no atomics: every workgroup
+// stores the count of its chunk, one workgroup per pushed row adds the counts up and applies the rule, a predicated frame copy
+// moves the anchor.  The three launches cut a frame into the same chunks (launch_frame_copy's, from the same three operands);
+// partial p of pushed row i lies in scratch[i * chunks + p], and the row's verdict replaces partial 0 once all are summed.
+constexpr int GATE_STILL_MAX = 1 << 30;
+
+// the sum of v over the 256 lanes of a workgroup, in every lane: xor-moves within the wave, the four waves' sums through LDS
+__device__ __forceinline__ int gate_block_sum(int v, int* wave_sums) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
+}
+
+// bytes of one element of V with |a - b| > tau, compared as integers
+__device__ __forceinline__ int gate_changed_bytes(unsigned a, unsigned b, int tau) {
+  int n = 0;
+#pragma unroll
+  for (int k = 0; k < 32; k += 8) {
+    const int d = (int)((a >> k) & 255u) - (int)((b >> k) & 255u);
+    n += (d < 0 ? -d : d) > tau;
+  }
+  return n;
+}
+__device__ __forceinline__ int gate_changed_bytes(u32x4 a, u32x4 b, int tau) {
+  return gate_changed_bytes(a.x, b.x, tau) + gate_changed_bytes(a.y, b.y, tau) + gate_changed_bytes(a.z, b.z, tau) +
+         gate_changed_bytes(a.w, b.w, tau);
+}
+__device__ __forceinline__ int gate_changed_bytes(unsigned char a, unsigned char b, int tau) {
+  const int d = (int)a - (int)b;
+  return (d < 0 ? -d : d) > tau;
+}
+
+// (a) workgroup (chunk, row i): the changed bytes of its chunk of frame i against the anchor of c = cam_ids[i]
+template <typename V>
+__global__ __launch_bounds__(256) void frame_gate_count_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ cam_ids,
+                                                               const unsigned char* __restrict__ anchor, int* __restrict__ scratch, int n_cam,
+                                                               long long frame_bytes, int tau) {
+  __shared__ int wave_sums[4];
+  const long long i = blockIdx.y;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;  // (the whole workgroup: nothing waits at the barrier)
+  const long long nv = frame_bytes / (long long)sizeof(V);
+  const V* __restrict__ f = reinterpret_cast<const V*>(frames + i * frame_bytes);
+  const V* __restrict__ a = reinterpret_cast<const V*>(anchor + (long long)c * frame_bytes);
+  const long long e0 = (long long)blockIdx.x * FRAME_CHUNK + threadIdx.x;
+  V vf[FRAME_UNROLL] = {}, va[FRAME_UNROLL] = {};  // (behind the frame's end both stay zero: no byte differs)
+#pragma unroll
+  for (int u = 0; u < FRAME_UNROLL; ++u) {
+    const long long e = e0 + u * 256;
+    if (e < nv) {
+      vf[u] = f[e];
+      va[u] = a[e];
+    }
+  }
+  int n = 0;
+#pragma unroll
+  for (int u = 0; u < FRAME_UNROLL; ++u) n += gate_changed_bytes(vf[u], va[u], tau);
+  n = gate_block_sum(n, wave_sums);
+  if (threadIdx.x == 0) scratch[i * gridDim.x + blockIdx.x] = n;
+}
+
+// (b) workgroup i: n = the sum of row i's partials, steps 2 and 3 of the rule on the camera's state row {still, epoch, changed,
+// peak}, and the verdict (1: the frame moves, the anchor is to be replaced) where partial 0 was
+__global__ __launch_bounds__(256) void frame_gate_decide_kernel(const int* __restrict__ cam_ids, int* __restrict__ state, int* __restrict__ scratch,
+                                                                int n_cam, int chunks, int limit) {
+  __shared__ int wave_sums[4];
+  const long long i = blockIdx.x;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;
+  int* __restrict__ part = scratch + i * chunks;
+  int n = 0;
+  for (int p = threadIdx.x; p < chunks; p += 256) n += part[p];
+  n = gate_block_sum(n, wave_sums);  // (its barrier stands between every read of the partials and the store of the verdict)
+  if (threadIdx.x != 0) return;
+  int* __restrict__ st = state + (long long)c * 4;
+  const int still = st[0];
+  const bool moves = still < 0 || n > limit;
+  if (moves) {
+    st[0] = 0;
+    st[1] = (int)((unsigned)st[1] + 1u);
+    st[2] = still < 0 ? -1 : n;
+    st[3] = 0;
+  } else {
+    st[0] = min(still + 1, GATE_STILL_MAX);
+    st[2] = n;
+    st[3] = max(st[3], n);
+  }
+  part[0] = moves;
+}
+
+// (c) frame_ring_push_kernel's copy, frame i -> the anchor of its camera, where the row's verdict says so
+template <typename V>
+__global__ __launch_bounds__(256) void frame_gate_anchor_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ cam_ids,
+                                                                unsigned char* __restrict__ anchor, const int* __restrict__ scratch, int n_cam,
+                                                                long long frame_bytes) {
+  const long long i = blockIdx.y;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;
+  if (!scratch[i * gridDim.x]) return;
+  frame_copy_chunk<V>(frames + i * frame_bytes, anchor + (long long)c * frame_bytes, frame_bytes);
+}
+
+// One wavefront per row (i, k): the newest clip of camera c = cam_ids[i], crop k, again -- its C1 dwords from slot (count - 1) % W
+// to slot count % W, every lane's loads of a round before its stores.  The count is only read here.
+__global__ __launch_bounds__(64) void ring_repeat_kernel(const int* __restrict__ cam_ids, float* __restrict__ ring, const long long* __restrict__ counts,
+                                                         int n_cam, int ncrops, int W, int C1) {
+  const int i = blockIdx.x / ncrops, k = blockIdx.x % ncrops;
+  const int c = cam_ids[i];
+  if (c < 0 || c >= n_cam) return;
+  const long long count = counts[c];
+  if (count < 1) return;  // no clip to repeat
+  const long long from = (count - 1) % W, to = count % W;
+  if (from == to) return;  // W == 1: the clip lies where it belongs
+  unsigned* __restrict__ row = (unsigned*)ring + ((long long)c * ncrops + k) * W * C1;
+  const unsigned* __restrict__ s = row + from * C1;
+  unsigned* __restrict__ d = row + to * C1;
+  int j = threadIdx.x;
+  for (; j + 64 * (RW_UNROLL - 1) < C1; j += 64 * RW_UNROLL) {
+    unsigned r[RW_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RW_UNROLL; ++u) r[u] = s[j + 64 * u];
+#pragma unroll
+    for (int u = 0; u < RW_UNROLL; ++u) d[j + 64 * u] = r[u];
+  }
+  for (; j < C1; j += 64) d[j] = s[j];
+}
+
+// ring_advance_kernel for cameras that hold a clip: a camera at count 0 has nothing to repeat and stays there
+__global__ __launch_bounds__(256) void ring_repeat_advance_kernel(const int* __restrict__ cam_ids, long long* __restrict__ counts, int n, int n_cam) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = cam_ids[i];
+  if (c >= 0 && c < n_cam && counts[c] > 0) counts[c] += 1;  // ids are distinct: one thread per count
+}
+
 }  // namespace advhip
 
 using namespace advhip;
+
+extern "C" int advhip_frame_gate_update_u8(const uint8_t* frames, const int32_t* cam_ids, uint8_t* anchor, int32_t* state, int32_t* scratch,
+                                           int32_t n, int32_t n_cam, int64_t frame_bytes, int32_t pixel_delta, int32_t limit, void* stream) {
+  ADVHIP_REQUIRE(frames && cam_ids && anchor && state && scratch, "frame_gate_update: null pointer");
+  ADVHIP_REQUIRE(n > 0 && n_cam > 0 && frame_bytes > 0 && frame_bytes < (1ll << 31), "frame_gate_update: bad shape (n=%d n_cam=%d frame_bytes=%lld)", n,
+                 n_cam, (long long)frame_bytes);
+  ADVHIP_REQUIRE(n <= n_cam, "frame_gate_update: %d frames for %d cameras: one frame per camera and call (the scratch holds n_cam rows)", n, n_cam);
+  ADVHIP_REQUIRE(pixel_delta >= 0 && pixel_delta <= 255, "frame_gate_update: pixel_delta %d outside [0, 255]", pixel_delta);
+  ADVHIP_REQUIRE(limit >= 0 && limit <= frame_bytes, "frame_gate_update: limit %d outside [0, frame_bytes = %lld]", limit, (long long)frame_bytes);
+  const char* who = "frame_gate_update";
+  const int width = frame_access_bytes(frames, anchor, frame_bytes);
+  const int chunks = (int)((frame_bytes / width + FRAME_CHUNK - 1) / FRAME_CHUNK);  // launch_frame_copy's, below
+  int rc = launch_frame_copy(frames, anchor, frame_bytes, n, who, [&](auto v, dim3 grid) {
+    hipLaunchKernelGGL(frame_gate_count_kernel<decltype(v)>, grid, dim3(256), 0, (hipStream_t)stream, frames, (const int*)cam_ids,
+                       (const unsigned char*)anchor, (int*)scratch, (int)n_cam, (long long)frame_bytes, (int)pixel_delta);
+  });
+  if (rc != ADVHIP_OK) return rc;
+  hipLaunchKernelGGL(frame_gate_decide_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids, (int*)state, (int*)scratch,
+                     (int)n_cam, chunks, (int)limit);
+  rc = check_launch("frame_gate_update (state)");
+  if (rc != ADVHIP_OK) return rc;
+  return launch_frame_copy(frames, anchor, frame_bytes, n, "frame_gate_update (anchor)", [&](auto v, dim3 grid) {
+    hipLaunchKernelGGL(frame_gate_anchor_kernel<decltype(v)>, grid, dim3(256), 0, (hipStream_t)stream, frames, (const int*)cam_ids, anchor,
+                       (const int*)scratch, (int)n_cam, (long long)frame_bytes);
+  });
+}
+
+extern "C" int advhip_ring_repeat_f32(const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam, int32_t ncrops, int32_t W,
+                                      int32_t C1, void* stream) {
+  ADVHIP_REQUIRE(cam_ids && ring && counts, "ring_repeat: null pointer");
+  ADVHIP_REQUIRE(n > 0 && n_cam > 0 && ncrops > 0 && W > 0 && C1 > 0, "ring_repeat: bad shape");
+  const long long rows = (long long)n * ncrops;
+  ADVHIP_REQUIRE(rows < (1ll << 31), "ring_repeat: %lld rows is outside the launch grid", rows);
+  hipLaunchKernelGGL(ring_repeat_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, (const int*)cam_ids, ring, (const long long*)counts,
+                     (int)n_cam, (int)ncrops, (int)W, (int)C1);
+  const int rc = check_launch("ring_repeat");
+  if (rc != ADVHIP_OK) return rc;
+  hipLaunchKernelGGL(ring_repeat_advance_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const int*)cam_ids,
+                     (long long*)counts, (int)n, (int)n_cam);
+  return check_launch("ring_repeat (counts)");
+}
 
 extern "C" int advhip_frame_ring_push_u8(const uint8_t* frames, const int32_t* cam_ids, uint8_t* ring, int64_t* counts, int32_t n, int32_t n_cam,
                                          int32_t R, int64_t frame_bytes, void* stream) {

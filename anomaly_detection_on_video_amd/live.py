@@ -26,12 +26,30 @@ synchronises nothing and dispatches no torch arithmetic.
 and the clips that are due gathered in one launch into the buffer I3Res50.forward_frames reads -- each one window w of the
 camera's frames as an offline video, byte for byte.
 
+    lf = LiveFrames(n_cameras, ..., motion=MotionGate(pixel_delta=6, max_changed=0.002))   # (numbers for illustration only)
+
+`motion=` adds a per-camera motion gate on the device (include/advhip.h: "live frames: motion gate"); the default, None,
+allocates and launches nothing.  THE RULE: every camera has an anchor frame and a row {still, epoch, changed, peak}, at first
+{-1, 0, -1, 0}.  For a pushed frame f (at ring size), n = the byte positions with |f[i] - anchor[i]| > pixel_delta, compared as
+integers (both signs count, |d| == pixel_delta is not changed).  Without an anchor (still == -1) or with n > limit the frame
+MOVES: anchor := f, still := 0, epoch += 1, peak := 0, changed := n (-1 without an anchor).  Otherwise it is STILL: still :=
+min(still + 1, 2^30), changed := n, peak := max(peak, n), the anchor stays.  A due window is QUIET iff still + 1 >= span: all its
+frames lie within the tolerance of one anchor frame.  `gate_decision`, on the host, from the one read-back of {still, epoch}: a
+quiet window is HELD iff ref_epoch[c] == epoch and (max_hold is None or holds[c] < max_hold), and then holds[c] += 1; an
+extracted quiet window does ref_epoch[c] := epoch, holds[c] := 0; an extracted window that is not quiet does ref_epoch[c] :=
+None, holds[c] := 0.  So the first quiet window after any motion is always extracted (the reference of the still scene), only
+later quiet windows under the same anchor repeat it (`LiveScorer.hold`: the camera's newest clip row again, bit for bit), a
+clip that contains motion is never repeated, and slow drift, measured against the fixed anchor, eventually moves.  `reset` does
+still := -1, epoch += 1 and clears ref_epoch[c] and holds[c].
+
 All three classes (and events.LiveEventTracker) keep their cameras in one `CameraSet`: the rule for `cams`, the cached id vectors,
 the host mirror of the counts."""
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
-from typing import NamedTuple, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -124,6 +142,90 @@ class CameraSet:
             self.host[c] = 0
 
 
+@dataclass(frozen=True)
+class MotionGate:
+    """The motion gate's numbers (the module docstring has the rule).  `pixel_delta`: how far a byte may lie from the anchor's and
+    still count as unchanged, an int in [0, 255].  `max_changed`: how many changed bytes a still frame may have -- an int >= 0
+    (bytes) or a float in [0, 1] (a share of frame_bytes; `limit` floors it once).  `max_hold`: None, or how many windows in a
+    row may repeat one reference before the next quiet window is extracted again, an int >= 1.  pixel_delta and max_changed have
+    NO defaults: what suits a real camera (sensor noise, compression, auto-exposure) has not been measured by anybody."""
+    pixel_delta: int
+    max_changed: Union[int, float]
+    max_hold: Optional[int] = None
+
+    def __post_init__(self):
+        tau, mc, mh = self.pixel_delta, self.max_changed, self.max_hold
+        if host_int(tau, floats=False) is None:
+            raise ValueError(f"motion: pixel_delta={tau!r} is not an integer")
+        if not 0 <= int(tau) <= 255:
+            raise ValueError(f"motion: pixel_delta={int(tau)} outside [0, 255]")
+        if isinstance(mc, bool) or not isinstance(mc, (int, float, np.integer, np.floating)):
+            raise ValueError(f"motion: max_changed={mc!r} is neither an integer (bytes) nor a float (a share of the frame)")
+        if isinstance(mc, (float, np.floating)):
+            if not math.isfinite(float(mc)):
+                raise ValueError(f"motion: max_changed={mc!r} is not finite")
+            if float(mc) < 0:
+                raise ValueError(f"motion: max_changed={mc!r} is negative")
+            if float(mc) > 1:
+                raise ValueError(f"motion: max_changed={mc!r} is a share above 1 (an integer counts bytes)")
+            mc = float(mc)
+        else:
+            if int(mc) < 0:
+                raise ValueError(f"motion: max_changed={int(mc)} is negative")
+            mc = int(mc)
+        if mh is not None:
+            if host_int(mh, floats=False) is None:
+                raise ValueError(f"motion: max_hold={mh!r} is neither None nor an integer")
+            if int(mh) < 1:
+                raise ValueError(f"motion: max_hold={int(mh)} is below 1")
+            mh = int(mh)
+        for name, v in (("pixel_delta", int(tau)), ("max_changed", mc), ("max_hold", mh)):
+            object.__setattr__(self, name, v)
+
+    def limit(self, frame_bytes: int) -> int:
+        """The changed bytes a still frame may have: max_changed itself (at most frame_bytes), or floor(share * frame_bytes)."""
+        if isinstance(self.max_changed, float):
+            return min(int(math.floor(self.max_changed * frame_bytes)), frame_bytes)
+        return min(self.max_changed, frame_bytes)
+
+
+_GATE_FIELDS = ("pixel_delta", "max_changed", "max_hold")
+
+
+def resolve_motion_gate(spec) -> Optional[MotionGate]:
+    """None -> None (the gate is off); a MotionGate, a mapping with the keys pixel_delta, max_changed[, max_hold] or a tuple in
+    that order -> a checked MotionGate.  Refuses with a ValueError that names the field."""
+    if spec is None:
+        return None
+    if isinstance(spec, MotionGate):
+        return spec
+    if hasattr(spec, "keys"):
+        kw = {k: spec[k] for k in spec.keys()}
+        unknown = sorted(set(kw) - set(_GATE_FIELDS))
+        if unknown:
+            raise ValueError(f"motion: unknown key(s) {unknown}; the keys are {list(_GATE_FIELDS)}")
+    elif isinstance(spec, (tuple, list)):
+        if not 2 <= len(spec) <= 3:
+            raise ValueError(f"motion: a tuple holds (pixel_delta, max_changed[, max_hold]), got {len(spec)} values")
+        kw = dict(zip(_GATE_FIELDS, spec))
+    else:
+        raise ValueError(f"motion: expected a mapping, a tuple or a MotionGate, got {type(spec).__name__}")
+    for name in _GATE_FIELDS[:2]:
+        if name not in kw:
+            raise ValueError(f"motion: {name} is missing (it has no default: nobody has measured what suits a real camera)")
+    return MotionGate(kw["pixel_delta"], kw["max_changed"], kw.get("max_hold"))
+
+
+def gate_decision(still: int, epoch: int, span: int, ref_epoch: Optional[int], holds: int, max_hold: Optional[int]):
+    """The motion gate's decision for one due window (the module docstring has the rule): the camera's {still, epoch} as read
+    back, the window's span, and the host's ref_epoch (None: no reference) and holds for it -> (held, ref_epoch, holds) with the
+    bookkeeping as it stands after the decision.  held: the window repeats the previous clip; else it is extracted."""
+    quiet = still + 1 >= span
+    if quiet and ref_epoch is not None and ref_epoch == epoch and (max_hold is None or holds < max_hold):
+        return True, ref_epoch, holds + 1
+    return False, (epoch if quiet else None), 0
+
+
 class LiveFrames:
     """The front end of live scoring: per-camera rings of the last `span` resized uint8 frames on the device, and the clips that
     are due gathered from them in one launch (include/advhip.h: "live frames").
@@ -140,12 +242,24 @@ class LiveFrames:
     mirror on the host, one clip buffer (n_cameras * frames_per_clip, FH, FW, 3) -- the ring's size at frame_step 1 -- and one
     staging buffer (n_cameras, FH, FW, 3) the resize writes to.  Device id vectors are cached by their checked tuples: a push of
     device frames at ring size + windows on a repeated camera set uploads nothing, synchronises nothing and dispatches no torch
-    arithmetic.  CUDA tensors only; no fallback."""
+    arithmetic.  CUDA tensors only; no fallback.
+
+        lf = LiveFrames(n_cameras, ..., motion=MotionGate(pixel_delta, max_changed, max_hold=None))
+        due = lf.push(cams, frames)               # the gate's update runs on the frames on their way into the ring; every due camera
+        extract, held = lf.decide(due)            # the one read-back: whose window goes through the backbone, whose repeats
+
+    `motion` (resolve_motion_gate; None, the default: nothing is allocated or launched, `push` is launch for launch what it is
+    without the argument) adds the motion gate of the module docstring: `anchor` (n_cameras, FH, FW, 3) uint8, `gate_state`
+    (n_cameras, 4) int32 = {still, epoch, changed, peak}, a scratch for the counts and a pinned host buffer.  `push` then runs
+    mil_ops.frame_gate_update in front of the ring push, and a step on which nothing is due still uploads nothing, synchronises
+    nothing and dispatches no torch arithmetic; `decide`, called on due steps only, copies gate_state to the host and
+    synchronises the stream once.  `last_decision` = (extract, held) of the last decide, `extracted_total` and `held_total`
+    count windows; all three are host values."""
 
     MAX_ROWS = 65535  # frame rows of one launch (the grid's second dimension)
 
     def __init__(self, n_cameras: int, frame_hw=(256, 340), frames_per_clip: int = 16, frame_step: Optional[int] = None,
-                 clip_stride: Optional[int] = None, device="cuda:0"):
+                 clip_stride: Optional[int] = None, device="cuda:0", motion=None):
         from . import ops
 
         try:
@@ -161,6 +275,13 @@ class LiveFrames:
         if self.n_cameras * self.frames_per_clip > self.MAX_ROWS:
             raise HipExtensionError(f"LiveFrames: {self.n_cameras} cameras x {self.frames_per_clip} frames per clip is above the {self.MAX_ROWS} frame "
                                     f"rows one gather launch takes")
+        try:
+            self.motion = resolve_motion_gate(motion)
+        except ValueError as e:
+            raise HipExtensionError(f"LiveFrames: {e}") from None
+        fb = self.frame_hw[0] * self.frame_hw[1] * 3
+        if self.motion is not None and fb >= 1 << 31:
+            raise HipExtensionError(f"LiveFrames: frames of {fb} bytes: the motion gate counts changed bytes in int32 (frame_bytes < 2^31)")
         self.cameras = CameraSet(self.n_cameras, device, "frame")
         self.device = self.cameras.device
         if self.device.type != "cuda":
@@ -170,6 +291,16 @@ class LiveFrames:
         self._counts = torch.zeros((self.n_cameras,), dtype=torch.int64, device=self.device)
         self._clips = torch.empty((self.n_cameras * self.frames_per_clip,) + frame, dtype=torch.uint8, device=self.device)
         self._staging = torch.empty((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
+        self.last_decision, self.extracted_total, self.held_total = None, 0, 0
+        if self.motion is not None:
+            self.gate_limit = self.motion.limit(fb)
+            self.anchor = torch.zeros((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
+            self.gate_state = torch.tensor([mil_ops.GATE_STATE_INIT] * self.n_cameras, dtype=torch.int32).to(self.device)
+            self._gate_scratch = torch.zeros((mil_ops.frame_gate_scratch(self.n_cameras, fb),), dtype=torch.int32, device=self.device)
+            self._gate_host = torch.empty((self.n_cameras, 4), dtype=torch.int32, pin_memory=True)
+            self._gate_rows = self._gate_host.numpy()  # (the same memory: what `decide` reads behind its synchronisation)
+            self._ref_epoch, self._holds = [None] * self.n_cameras, [0] * self.n_cameras
+            self._decided_at = [0] * self.n_cameras  # the count at which a camera's window was last decided
 
     @property
     def counts(self) -> torch.Tensor:
@@ -230,9 +361,41 @@ class LiveFrames:
             frames = frames.to(self.device, non_blocking=True)
         if resize is not None:
             frames = rz.resize_u8(frames, resize, resample, out=self._staging[:n], pixel_format=pixel_format, surface=surface)
+        if self.motion is not None:  # on the frames as they enter the ring (its checks of `frames` are the ring push's: refused here, nothing has moved)
+            mil_ops.frame_gate_update(frames, self.cameras.ids(cams), self.anchor, self.gate_state, self._gate_scratch, self.motion.pixel_delta,
+                                      self.gate_limit)
         mil_ops.frame_ring_push(frames, self.cameras.ids(cams), self.ring, self._counts)
         self.cameras.bump(cams)
         return tuple(c for c in cams if self.is_due(self.cameras.host[c]))
+
+    def decide(self, due: Sequence[int]) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+        """The motion gate's decision for the cameras whose clip the last push made due -> (extract, held), both in `due` order:
+        the windows of `extract` go through the backbone, the cameras of `held` repeat their previous clip (LiveScorer.hold).
+        One copy of gate_state into the pinned host buffer and one synchronisation of the current stream, then `gate_decision`
+        per camera; the bookkeeping (ref_epoch, holds, the totals, last_decision) is committed here, so a window is decided once."""
+        what = "LiveFrames.decide"
+        if self.motion is None:
+            raise HipExtensionError(f"{what}: this LiveFrames has no motion gate (motion=None): every due window is extracted")
+        due = self.cameras.check(due, what)
+        host = self.cameras.host
+        early = [c for c in due if not self.is_due(host[c])]
+        if early:
+            raise HipExtensionError(f"{what}: cameras {early} have no clip due at their counts {[host[c] for c in early]} (decide takes what push returned)")
+        again = [c for c in due if self._decided_at[c] == host[c]]
+        if again:
+            raise HipExtensionError(f"{what}: the windows of cameras {again} are decided already: one decision per due window")
+        self._gate_host.copy_(self.gate_state, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        extract, held = [], []
+        for c in due:
+            still, epoch = int(self._gate_rows[c, 0]), int(self._gate_rows[c, 1])
+            is_held, self._ref_epoch[c], self._holds[c] = gate_decision(still, epoch, self.span, self._ref_epoch[c], self._holds[c], self.motion.max_hold)
+            (held if is_held else extract).append(c)
+            self._decided_at[c] = host[c]
+        self.last_decision = (tuple(extract), tuple(held))
+        self.extracted_total += len(extract)
+        self.held_total += len(held)
+        return self.last_decision
 
     def windows(self, cams: Sequence[int]) -> torch.Tensor:
         """The newest windows of the listed cameras, back to back in `cams` order: (len(cams) * frames_per_clip, FH, FW, 3) uint8,
@@ -246,10 +409,17 @@ class LiveFrames:
         return mil_ops.frame_ring_windows(self.ring, self._counts, self.cameras.ids(cams), dst, self.frames_per_clip, self.frame_step)
 
     def reset(self, cams: Sequence[int]) -> None:
-        """The listed cameras start over at count 0: their rings' old frames can no longer reach a window."""
+        """The listed cameras start over at count 0: their rings' old frames can no longer reach a window.  With a motion gate
+        they lose their anchor too (still := -1, epoch += 1) and the host forgets their reference and their holds."""
         cams = self.cameras.check(cams, "LiveFrames.reset")
-        self._counts[self.cameras.ids(cams).long()] = 0
+        idx = self.cameras.ids(cams).long()
+        self._counts[idx] = 0
         self.cameras.clear(cams)
+        if self.motion is not None:
+            self.gate_state[idx, 0] = -1
+            self.gate_state[idx, 1] += 1
+            for c in cams:
+                self._ref_epoch[c], self._holds[c], self._decided_at[c] = None, 0, 0
 
 
 class LiveScorer:
@@ -335,6 +505,18 @@ class LiveScorer:
         mil_ops.ring_push(feats, self.cameras.ids(cams), self.ring, self._counts)
         self.cameras.bump(cams)
 
+    def hold(self, cams: Sequence[int]) -> None:
+        """The newest clip of each listed camera again (mil_ops.ring_repeat): every crop's row, magnitude channel included, bit
+        for bit from slot (k - 1) % window to slot k % window at the camera's count k, and the count goes up by one -- what the
+        motion gate does for a still camera instead of the backbone.  The repeated clip is a clip like any other: it is scored,
+        and with `events=` it is a sample of the camera's series.  A camera without a clip is refused."""
+        cams = self.cameras.check(cams, "LiveScorer.hold")
+        empty = [c for c in cams if self.cameras.host[c] == 0]
+        if empty:
+            raise HipExtensionError(f"LiveScorer.hold: cameras {empty} have no clip to repeat (their count is 0)")
+        mil_ops.ring_repeat(self.cameras.ids(cams), self.ring, self._counts)
+        self.cameras.bump(cams)
+
     def score(self, cams: Optional[Sequence[int]] = None) -> LiveScores:
         """The windows of the listed cameras (None: every camera with at least one clip, ascending) scored in one padded pass."""
         if cams is None:
@@ -403,11 +585,15 @@ class LiveScorer:
 
     def _step_clips(self, what: str, backbone, clips: torch.Tensor, cams: Tuple[int, ...], forward_kw: dict) -> LiveScores:
         """The tail of both step methods: backbone.forward_frames on the back-to-back clips of `cams`, `push`, `score(cams)`."""
+        self._extract_clips(what, backbone, clips, cams, forward_kw)
+        return self.score(cams)
+
+    def _extract_clips(self, what: str, backbone, clips: torch.Tensor, cams: Tuple[int, ...], forward_kw: dict) -> None:
+        """backbone.forward_frames on the back-to-back clips of `cams`, then `push`."""
         feats = backbone.forward_frames(clips, 0, len(cams) * self.ncrops, **forward_kw)
         if feats.numel() != len(cams) * self.ncrops * self.channels:
             raise HipExtensionError(f"{what}: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
         self.push(cams, feats.reshape(len(cams), self.ncrops, self.channels))
-        return self.score(cams)
 
     _PUSH_KW, _FORWARD_KW = ("resize", "resample", "pixel_format", "surface"), ("crop", "crops", "normalize")
 
@@ -419,7 +605,10 @@ class LiveScorer:
         ncrops; frames_per_clip, frame_step and clip_stride are the LiveFrames' own and refused here.  The features and scores of
         a camera are those of its frames as an offline video, window by window.  With `events=` every due window is one sample
         of the camera's series: a sample is then clip_stride frames, not span frames, and EventSpec's lengths (smooth, merge_gap,
-        min_len) count such samples."""
+        min_len) count such samples.  A LiveFrames with a motion gate: push, `live_frames.decide(due)` -> (extract, held), then
+        windows / forward_frames / push for `extract` only (skipped when it is empty), `hold(held)`, and `score(due)` in one
+        padded pass; a held clip is a sample like any other.  A camera that starts over is reset in both objects: the gate's
+        reference is a clip in this object's ring, and `hold` refuses a camera whose ring is empty."""
         from . import ops
 
         what = "LiveScorer.step_camera_frames"
@@ -442,4 +631,12 @@ class LiveScorer:
         if not due:
             return None
         forward_kw = {"frames_per_clip": live_frames.frames_per_clip, **{k: kw[k] for k in self._FORWARD_KW if k in kw}}
-        return self._step_clips(what, backbone, live_frames.windows(due), due, forward_kw)
+        if live_frames.motion is None:
+            return self._step_clips(what, backbone, live_frames.windows(due), due, forward_kw)
+        # the motion gate: the backbone sees the windows that moved (and every still scene's first), a still camera repeats its clip
+        extract, held = live_frames.decide(due)
+        if extract:
+            self._extract_clips(what, backbone, live_frames.windows(extract), extract, forward_kw)
+        if held:
+            self.hold(held)
+        return self.score(due)

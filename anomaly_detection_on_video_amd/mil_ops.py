@@ -361,6 +361,67 @@ def frame_ring_windows(ring: torch.Tensor, counts: torch.Tensor, cam_ids: torch.
     return dst
 
 
+GATE_STATE_INIT = (-1, 0, -1, 0)  # a camera's state row {still, epoch, changed, peak} before its first frame (include/advhip.h: motion gate)
+
+
+def frame_gate_scratch(n_cam: int, frame_bytes: int) -> int:
+    """int32 entries of `frame_gate_update`'s scratch: one per camera and chunk of a frame at single-byte accesses."""
+    return int(n_cam) * ((int(frame_bytes) + FRAME_RING_CHUNK - 1) // FRAME_RING_CHUNK)
+
+
+def frame_gate_update(frames: torch.Tensor, cam_ids: torch.Tensor, anchor: torch.Tensor, state: torch.Tensor, scratch: torch.Tensor,
+                      pixel_delta: int, limit: int) -> torch.Tensor:
+    """The motion gate's update for one new frame of each of n distinct cameras (include/advhip.h: live frames: motion gate):
+    anchor uint8 (n_cam, frame_bytes) -- or (n_cam, FH, FW, 3), a frame is what lies behind n_cam --, frames uint8 (n,) + the
+    anchor's frame shape with n <= n_cam, cam_ids int32 (n,), state int32 (n_cam, 4) = {still, epoch, changed, peak} per camera,
+    scratch int32 with at least `frame_gate_scratch(n_cam, frame_bytes)` entries, all on the device.  For c = cam_ids[i]: n =
+    the bytes of frames[i] more than pixel_delta (0 .. 255) away from anchor[c]; without an anchor (still == -1) or with n >
+    limit (0 .. frame_bytes) the frame moves -- anchor[c] = frames[i], still = 0, epoch += 1 --, else still += 1.  An id outside
+    [0, n_cam) writes nothing; the same id twice is an error this wrapper cannot see.  Integers only, 16-, 4- or 1-byte accesses
+    as `frame_ring_push`.  Three launches, nothing is read back, no autograd.  -> state."""
+    what = "frame_gate_update"
+    if not torch.is_tensor(anchor) or anchor.dim() < 2:
+        raise _lib.HipExtensionError(f"{what}: anchor must be a torch.uint8 tensor (n_cam, frame_bytes) or (n_cam, FH, FW, 3) on the GPU, got "
+                                     f"{tuple(getattr(anchor, 'shape', ())) or type(anchor).__name__}")
+    anchor = _live_arg(anchor, torch.uint8, (None,) * anchor.dim(), what, "anchor")
+    n_cam = anchor.shape[0]
+    fb = anchor.numel() // n_cam
+    frames = _live_arg(frames, torch.uint8, (None,) + tuple(anchor.shape[1:]), what, "frames", anchor.device)
+    n = frames.shape[0]
+    if n > n_cam:
+        raise _lib.HipExtensionError(f"{what}: {n} frames for {n_cam} cameras: one frame per camera and call")
+    cam_ids = _live_arg(cam_ids, torch.int32, (n,), what, "cam_ids", anchor.device)
+    state = _live_arg(state, torch.int32, (n_cam, 4), what, "state", anchor.device)
+    scratch = _live_arg(scratch, torch.int32, (None,), what, "scratch", anchor.device)
+    if scratch.shape[0] < frame_gate_scratch(n_cam, fb):
+        raise _lib.HipExtensionError(f"{what}: scratch holds {scratch.shape[0]} entries, {n_cam} cameras x {fb} bytes need "
+                                     f"{frame_gate_scratch(n_cam, fb)} (frame_gate_scratch)")
+    for name, v, hi in (("pixel_delta", pixel_delta, 255), ("limit", limit, fb)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= hi:
+            raise _lib.HipExtensionError(f"{what}: {name} {v!r} is not an integer in [0, {hi}]")
+    if fb >= 1 << 31:
+        raise _lib.HipExtensionError(f"{what}: frames of {fb} bytes: the counts are int32 (frame_bytes < 2^31)")
+    require_gpu(anchor)  # (the current device)
+    check(_lib.load().advhip_frame_gate_update_u8(ptr(frames), ptr(cam_ids), ptr(anchor), ptr(state), ptr(scratch), n, n_cam, fb, pixel_delta, limit,
+                                                  stream()), what)
+    return state
+
+
+def ring_repeat(cam_ids: torch.Tensor, ring: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """The newest clip of each of n distinct cameras again (include/advhip.h: motion gate, holding): cam_ids int32 (n,), ring
+    (n_cam, ncrops, W, C + 1) fp32, counts int64 (n_cam,).  Camera c = cam_ids[i] with counts[c] >= 1 gets ring[c, :, counts[c] %
+    W] = ring[c, :, (counts[c] - 1) % W] bit for bit, magnitude channel included (at W == 1 nothing is copied); then counts[c] +=
+    1.  A camera at count 0 or an id outside [0, n_cam) writes nothing and advances nothing.  Two launches, no autograd."""
+    what = "ring_repeat"
+    ring = _live_arg(ring, torch.float32, (None, None, None, None), what, "ring")
+    n_cam, ncrops, W, C1 = ring.shape
+    cam_ids = _live_arg(cam_ids, torch.int32, (None,), what, "cam_ids", ring.device)
+    counts = _live_arg(counts, torch.int64, (n_cam,), what, "counts", ring.device)
+    require_gpu(ring)  # (the current device)
+    check(_lib.load().advhip_ring_repeat_f32(ptr(cam_ids), ptr(ring), ptr(counts), cam_ids.shape[0], n_cam, ncrops, W, C1, stream()), what)
+    return ring
+
+
 LIVE_EVENTS_STATE = ("ring", "samples", "cand_int", "cand_peak", "cand_sum", "alert", "open_start", "log_int", "log_f", "emitted")
 
 

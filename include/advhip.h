@@ -873,6 +873,38 @@ int advhip_frame_ring_windows_u8(const uint8_t* ring, const int64_t* counts, con
                                  int32_t n_cam, int32_t R, int64_t frame_bytes, int32_t frames_per_clip, int32_t frame_step,
                                  void* stream);
 
+/* --- live frames: motion gate -- a still camera's due window repeats its previous clip --------------
+ * THE RULE.  Two numbers: pixel_delta (tau, 0 .. 255) and limit (changed bytes a still frame may have, 0 .. frame_bytes).
+ * State owned by the caller, per camera, on the device: an anchor frame uint8 (frame_bytes) and one row int32[4] =
+ * {still, epoch, changed, peak}, which starts as {-1, 0, -1, 0}.  For every pushed frame f of camera c (at ring size):
+ *   1. n = the number of byte positions i with |f[i] - anchor[i]| > tau, compared as integers: both signs count, |d| == tau
+ *      is not changed.
+ *   2. still == -1 (no anchor yet) or n > limit: the frame MOVES.  anchor := f, still := 0, epoch += 1 (it wraps at 2^32),
+ *      peak := 0, changed := n, or -1 where there was no anchor.
+ *   3. otherwise the frame is STILL: still := min(still + 1, 2^30), changed := n, peak := max(peak, n); the anchor stays.
+ * A due window of span R is QUIET iff still + 1 >= R: all R frames under it lie within the tolerance of one anchor frame.
+ * The decision (the host's, from a read-back of {still, epoch}; no kernel knows it), with ref_epoch[c] (or none) and holds[c]:
+ * a quiet window is HELD iff ref_epoch[c] == epoch and (max_hold is none or holds[c] < max_hold), then holds[c] += 1; an
+ * extracted quiet window does ref_epoch[c] := epoch, holds[c] := 0; an extracted window that is not quiet does ref_epoch[c] :=
+ * none, holds[c] := 0.  So the first quiet window after any motion is always extracted -- it is the reference of the still
+ * scene --, only later quiet windows under the same anchor repeat it, a clip that contains motion is never repeated, and slow
+ * drift, measured against the fixed anchor, eventually moves.  A reset does still := -1, epoch += 1.
+ *
+ * One update for each of n DISTINCT cameras, n <= n_cam: frames uint8 (n, frame_bytes), cam_ids int32 (n,), anchor uint8
+ * (n_cam, frame_bytes), state int32 (n_cam, 4), scratch int32 of at least n_cam * ceil(frame_bytes / 1024) entries (the chunks
+ * of a frame at single-byte accesses; its contents mean nothing between calls).  Three launches, integers only, no atomics:
+ * every workgroup stores the count of its chunk, one workgroup per frame adds them and applies steps 2 and 3, a predicated
+ * copy in advhip_frame_ring_push_u8's form moves the anchor.  The access width is chosen as there, from frames, anchor and
+ * frame_bytes.  An id outside [0, n_cam) writes nothing.  frame_bytes < 2^31; the rings and counts are not touched. */
+int advhip_frame_gate_update_u8(const uint8_t* frames, const int32_t* cam_ids, uint8_t* anchor, int32_t* state, int32_t* scratch,
+                                int32_t n, int32_t n_cam, int64_t frame_bytes, int32_t pixel_delta, int32_t limit, void* stream);
+/* Holding: the newest clip of each of n DISTINCT cameras again.  For c = cam_ids[i] with counts[c] >= 1, every crop's row of C1
+ * floats, magnitude channel included, is copied bit for bit from slot (counts[c] - 1) % W to slot counts[c] % W of ring (n_cam,
+ * ncrops, W, C1) (one wavefront per row; at W == 1 the two are one slot and nothing is copied); a second launch then does
+ * counts[c] += 1.  A camera at count 0 or an id outside [0, n_cam) writes nothing and advances nothing. */
+int advhip_ring_repeat_f32(const int32_t* cam_ids, float* ring, int64_t* counts, int32_t n, int32_t n_cam, int32_t ncrops, int32_t W,
+                           int32_t C1, void* stream);
+
 /* Clip pre-processing on the device: uint8 frames (N, T, C, H, W) -> fp32 (N, C, T, H, W) with
  * y = (x - mean) / std.  Replaces PILToTensor().float() + GroupNormalize(114.75, 57.375)
  * (src/dataset.py:175-183) and the permute of extract_features.py:83, so that only uint8 pixels
