@@ -1137,6 +1137,7 @@ struct DmaCfg {
 using lds_ptr_t = __attribute__((address_space(3))) void*;
 using i32x8 = __attribute__((ext_vector_type(8))) int;
 using i32x16 = __attribute__((ext_vector_type(16))) int;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 // N consecutive {byte offset, coordinate bits} table entries through the scalar cache.  Inline asm
 // (load + wait in one statement) because hipcc will not use SMEM for a table it cannot prove
@@ -1183,6 +1184,58 @@ __device__ __forceinline__ void lds_read(Frag<NF>& f, unsigned addr) {
 template <int CNT, int NA, int NB>
 __device__ __forceinline__ void lds_wait(Frag<NA>& a, Frag<NB>& b) {
   asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a.v), "+v"(b.v) : "n"(CNT));
+}
+
+// Bytes per lane of the wide `buffer_load ... lds`.  The 16-byte form exists on gfx950 only: hipcc's HOST pass (which merely
+// parses a kernel body) silently drops the kernel's launch stub when it meets it in a template-dependent statement, so the host
+// pass sees the 4-byte form.
+#if defined(__HIP_DEVICE_COMPILE__)
+constexpr int DMA16_BYTES = 16;
+#else
+constexpr int DMA16_BYTES = 4;
+#endif
+
+// The wait at the top of a k-tile of an NS-deep LDS-DMA ring: tile kt has landed once only the loads of the `younger` tiles
+// issued after it (<= NS - 2 of them in flight, PER_TILE instructions per wave each) are outstanding.  vmcnt takes an immediate,
+// hence one s_waitcnt per count Y = min(younger, NS - 2); a 2-deep ring has the one `s_waitcnt vmcnt(0)`.
+// Call it as ring_wait<NS, PER_TILE>(younger): Y is the chain's own index and is never given by a caller.
+template <int NS, int PER_TILE, int Y = NS - 2>
+__device__ __forceinline__ void ring_wait(int younger) {
+  if constexpr (Y == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    if (younger >= Y) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Y * PER_TILE) : "memory");
+    else ring_wait<NS, PER_TILE, Y - 1>(younger);
+  }
+}
+
+// One ring stage of the plain fp32 MFMA loop: KS k-steps of FM x FN MFMAs on the [k][BM] / [k][BN] tiles whose k-step-0 fragments
+// this lane reads at LDS byte addresses aa / ba.  k-step ks sits ks * 4 rows further down both tiles -> immediate offsets.  The
+// two fragment reads of step ks + 1 are issued ahead of step ks's MFMAs and may stay in flight across its wait.
+template <int BM, int BN, int FM, int FN, int KS>
+__device__ __forceinline__ void mfma_stage(f32x4 (&acc)[FM][FN], const unsigned aa, const unsigned ba) {
+  Frag<FM> fa[2];
+  Frag<FN> fb[2];
+  lds_read<FM, 0>(fa[0], aa);
+  lds_read<FN, 0>(fb[0], ba);
+  auto body = [&](auto ks_c) {
+    constexpr int ks = decltype(ks_c)::value;
+    if constexpr (ks + 1 < KS) {
+      lds_read<FM, (ks + 1) * 4 * BM * 4>(fa[(ks + 1) & 1], aa);
+      lds_read<FN, (ks + 1) * 4 * BN * 4>(fb[(ks + 1) & 1], ba);
+      lds_wait<2>(fa[ks & 1], fb[ks & 1]);  // the two reads of step ks+1 may stay in flight
+    } else {
+      lds_wait<0>(fa[ks & 1], fb[ks & 1]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[ks & 1].v[i], fb[ks & 1].v[j], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  [&]<int... I>(std::integer_sequence<int, I...>) { (body(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, KS>{});
 }
 
 // Waves per SIMD the register allocator must leave room for = the residency LDS allows.  The
@@ -1476,11 +1529,6 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
   constexpr bool CAN16 = !CHECK && NS == 2 && epi_rows(EPI);
   constexpr int RPI16 = 256 / BM, LA16 = BK * BM / 1024;
   static_assert(LA16 >= 1, "tile too small for 16-byte A pieces");
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int A16_BYTES = 16;  // (the host pass only parses this body; see gemm_kk_dma_kernel)
-#else
-  constexpr int A16_BYTES = 4;
-#endif
   const bool a16 = A16ONLY || (CAN16 && a.a16 != 0);
   unsigned vbase16 = OOB;
   if constexpr (CAN16) {
@@ -1519,7 +1567,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
           eb = (ent[1] & rm[0]) | (ent[3] & rm[1]) | (ent[5] & rm[2]) | (ent[7] & rm[3]);
         }
         const unsigned voff = ((vmask_s & (unsigned)eb) == (unsigned)eb) ? vbase_s + (unsigned)eo : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(As + g * S_RPI * BM), A16_BYTES, voff, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(As + g * S_RPI * BM), DMA16_BYTES, voff, 0, 0, 0);
       }
       done16 = true;
     }
@@ -1528,7 +1576,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
 #pragma unroll
         for (int q = 0; q < LA16; ++q) {
           const int g = wave * LA16 + q;  // piece g = k-rows [g * RPI16, (g + 1) * RPI16) of the tile
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(As + g * RPI16 * BM), A16_BYTES, vbase16, (k0 + g * RPI16) * a.THW * 4, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(As + g * RPI16 * BM), DMA16_BYTES, vbase16, (k0 + g * RPI16) * a.THW * 4, 0, 0);
         }
         done16 = true;
       }
@@ -1580,46 +1628,39 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto mfma_step = [&](const Frag<FM>& fa, const Frag<FN>& fb) {
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa.v[i], fb.v[j], acc[i][j], 0, 0, 0);
-  };
-
-  // k-step ks of a stage sits ks*4 rows further down both tiles -> immediate offsets.
   // `pre`: also issue tile pre_k0 into ring stage `pstage` (a wave-uniform branch around the loads only: one copy of
   // the MFMA body, so the accumulators keep their registers across iterations).
   auto compute = [&](bool pre, int stage, int pre_k0, int pstage) {
     const unsigned aa = a_addr0 + (unsigned)(stage * D::STAGE) * 4u;
     const unsigned ba = b_addr0 + (unsigned)(stage * D::STAGE) * 4u;
-    Frag<FM> fa[2];
-    Frag<FN> fb[2];
     // the whole next tile's loads go out right after the barrier (micro-benchmark tools/dma_ceiling.hip modes 9/10 and
     // an A/B on the stack: one slice per k-step between the MFMA groups is 0.3-0.9 % slower)
     if (pre) issue_part(pre_k0, pstage, 0, 1);
     __builtin_amdgcn_sched_barrier(0);
-    lds_read<FM, 0>(fa[0], aa);
-    lds_read<FN, 0>(fb[0], ba);
-    // uint8 input: the A operands are pixel bytes (zero-extended by the LDS-DMA), one v_cvt_f32_ubyte0 each.  The operand is
-    // the pixel itself; -mean * (sum of the weights of the taps inside the clip) comes from the border-class table in the
-    // epilogue (taps outside read 0 and contribute nothing, as padding should).  Most of the time one wave per SIMD is in
-    // its MFMA phase (the others wait for their tiles), so a cvt -> MFMA dependency is exposed: the operands of step ks+1
-    // are converted beside the second half of step ks's MFMAs, and only step 0's conversion stands in front of its MFMAs.
-    auto cvt_u8 = [&](Frag<FM>& f) {
-      decltype(f.v) cv;  // (built in a fresh vector: hipcc 7.2 miscompiles the in-place per-element form `v[i] = f(v[i])`)
+    if constexpr (!U8) {
+      mfma_stage<BM, BN, FM, FN, KS>(acc, aa, ba);
+    } else {
+      Frag<FM> fa[2];
+      Frag<FN> fb[2];
+      lds_read<FM, 0>(fa[0], aa);
+      lds_read<FN, 0>(fb[0], ba);
+      // uint8 input: the A operands are pixel bytes (zero-extended by the LDS-DMA), one v_cvt_f32_ubyte0 each.  The operand is
+      // the pixel itself; -mean * (sum of the weights of the taps inside the clip) comes from the border-class table in the
+      // epilogue (taps outside read 0 and contribute nothing, as padding should).  Most of the time one wave per SIMD is in
+      // its MFMA phase (the others wait for their tiles), so a cvt -> MFMA dependency is exposed: the operands of step ks+1
+      // are converted beside the second half of step ks's MFMAs, and only step 0's conversion stands in front of its MFMAs.
+      auto cvt_u8 = [&](Frag<FM>& f) {
+        decltype(f.v) cv;  // (built in a fresh vector: hipcc 7.2 miscompiles the in-place per-element form `v[i] = f(v[i])`)
 #pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const float e = f.v[i];
-        cv[i] = u8_to_f32(e);
-      }
-      f.v = cv;
-    };
-    auto body = [&](auto ks_c) {
-      constexpr int ks = decltype(ks_c)::value;
-      if constexpr (U8) {
-        static_assert(!U8 || FM % 2 == 0, "uint8 input: two halves of the fragment rows");
+        for (int i = 0; i < FM; ++i) {
+          const float e = f.v[i];
+          cv[i] = u8_to_f32(e);
+        }
+        f.v = cv;
+      };
+      auto body = [&](auto ks_c) {
+        constexpr int ks = decltype(ks_c)::value;
+        static_assert(FM % 2 == 0, "uint8 input: two halves of the fragment rows");
         if constexpr (ks == 0) {
           lds_wait<0>(fa[0], fb[0]);
           cvt_u8(fa[0]);
@@ -1652,20 +1693,9 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
           }
         }
         __builtin_amdgcn_sched_barrier(0);
-        return;
-      }
-      if constexpr (ks + 1 < KS) {
-        lds_read<FM, (ks + 1) * 4 * BM * 4>(fa[(ks + 1) & 1], aa);
-        lds_read<FN, (ks + 1) * 4 * BN * 4>(fb[(ks + 1) & 1], ba);
-        lds_wait<2>(fa[ks & 1], fb[ks & 1]);  // the two reads of step ks+1 may stay in flight
-      } else {
-        lds_wait<0>(fa[ks & 1], fb[ks & 1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_step(fa[ks & 1], fb[ks & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    [&]<int... I>(std::integer_sequence<int, I...>) { (body(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, KS>{});
+      };
+      [&]<int... I>(std::integer_sequence<int, I...>) { (body(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, KS>{});
+    }
   };
 
   if constexpr (EPI == EPI_POOL233F) {
@@ -1703,12 +1733,7 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     if (kt0 + i < kt1) issue_tile((kt0 + i) * BK, i);
   int stage = 0;
   for (int kt = kt0; kt < kt1; ++kt) {
-    // tile kt has landed once only the loads of the younger tiles in flight (<= NS-2) are outstanding
-    const int younger = kt1 - 1 - kt;
-    if (NS == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the only tile in flight is tile kt
-    else if (NS == 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (LA + LB)) : "memory");
-    else if (younger >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LA + LB) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ring_wait<NS, LA + LB>(kt1 - 1 - kt);
     asm volatile("s_barrier" ::: "memory");  // all waves' parts of tile kt are in LDS; stage (kt-1)%NS is free
     const bool pre = kt + NS - 1 < kt1;
     if (pre) load_entries((kt + NS - 1) * BK);
@@ -1720,7 +1745,6 @@ __device__ __forceinline__ void conv3d_igemm_dma_tile(const ConvArgs& a, float* 
     // ---- in-kernel split-K reduction (cdna_hip_programming.md section 5, "In-launch split-K reduction", write-through form)
     // publish: thread tid owns float4 (i*FN+j) of its accumulators at [(i*FN+j)*256 + tid] of the (tile, slice) block:
     // whole 16-byte sc1 (write-through) stores, 4 KiB contiguous per store instruction of the workgroup
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     const auto rp = __builtin_amdgcn_make_buffer_rsrc(a.part, 0, a.part_bytes, 0x00020000);
     constexpr unsigned TILE_BYTES = BM * BN * 4;
     const unsigned my = (unsigned)(L * a.splits + split) * TILE_BYTES + (unsigned)tid * 16u;
@@ -1837,11 +1861,6 @@ void conv1x1_persist_kernel(const ConvArgs a, const int n_xcd) {
   constexpr int SLOTS = BM / 4;                            // float4 slots per staged channel row
   constexpr int EPT = BM * BN / 4 / 256;                   // float4 per epilogue thread and tile (8 or 4)
   constexpr int ROWS_PER_PASS = 256 / SLOTS;               // channel rows the 256 epilogue threads cover per pass
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int A16_BYTES = 16;  // (the host pass only parses this body; see gemm_kk_dma_kernel)
-#else
-  constexpr int A16_BYTES = 4;
-#endif
   __shared__ __attribute__((aligned(16))) float smem[RING + BM * BN];
   // staging: [BN channel rows][BM positions], the float4 slots of row n rotated by n (bank spread): never a ring stage
 
@@ -1875,31 +1894,11 @@ void conv1x1_persist_kernel(const ConvArgs a, const int n_xcd) {
 #pragma unroll
       for (int jn = 0; jn < FN; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // (keep the lambda: with mfma_stage called straight from the loop below hipcc assigns other scalar registers in the loader waves)
     auto compute = [&](int stage) {
       const unsigned aa = a_addr0 + (unsigned)(stage * D::STAGE) * 4u;
       const unsigned ba = b_addr0 + (unsigned)(stage * D::STAGE) * 4u;
-      Frag<FM> fa[2];
-      Frag<FN> fb[2];
-      lds_read<FM, 0>(fa[0], aa);
-      lds_read<FN, 0>(fb[0], ba);
-      auto body = [&](auto ks_c) {
-        constexpr int ks = decltype(ks_c)::value;
-        if constexpr (ks + 1 < KS) {
-          lds_read<FM, (ks + 1) * 4 * BM * 4>(fa[(ks + 1) & 1], aa);
-          lds_read<FN, (ks + 1) * 4 * BN * 4>(fb[(ks + 1) & 1], ba);
-          lds_wait<2>(fa[ks & 1], fb[ks & 1]);
-        } else {
-          lds_wait<0>(fa[ks & 1], fb[ks & 1]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int jn = 0; jn < FN; ++jn)
-            acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[ks & 1].v[i], fb[ks & 1].v[jn], acc[i][jn], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      [&]<int... I>(std::integer_sequence<int, I...>) { (body(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, KS>{});
+      mfma_stage<BM, BN, FM, FN, KS>(acc, aa, ba);
     };
 
     // scale / shift of this lane's FN channels of the current tile (these waves' only global loads: nothing else counts on their vmcnt)
@@ -1967,7 +1966,6 @@ void conv1x1_persist_kernel(const ConvArgs a, const int n_xcd) {
   // every wave runs the same code on one register set and up to four k-tiles are in flight per workgroup: the loads of k-tile
   // q + 4 go out in the interval in which k-tile q was written to LDS, and are written three intervals later.  Every
   // vector-memory operation of these waves is visible to hipcc, which counts its waits itself (no LDS-DMA left in the kernel).
-  using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
   constexpr int NA = BK * BM / 256, NB = BK * BN / 256;  // 16-byte loads per lane for a whole k-tile of A / B (8 or 4, and 4)
   const int lw = wave - 4;
   const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
@@ -2183,11 +2181,6 @@ void stem_u8_tap_kernel(const ConvArgs a) {
   const int2* __restrict__ tab = a.ktab_u8 + (size_t)(flip ? ntaps_pad : 0);
   const unsigned wvoff = (unsigned)((lane / 16) * BN + (lane % 16) * 4) * 4u;  // B piece: 4 k'-rows x 64 channels = 1 KiB
   const int a_wave_col = (wave & 1) * 64;
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int DMA_BYTES = 16;  // (the host pass only parses this body; see gemm_kk_dma_kernel)
-#else
-  constexpr int DMA_BYTES = 4;
-#endif
   int ent[2 * LA];
   auto issue_tile = [&](int t0, int stage) {  // taps [t0, t0 + BKT) and their 3 * BKT weight rows
     float* As = smem + stage * STAGE;
@@ -2201,7 +2194,7 @@ void stem_u8_tap_kernel(const ConvArgs a) {
     for (int g = 0; g < (NPB + 3) / 4; ++g) {
       const int piece = wave + 4 * g;
       if (piece < NPB)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(Bs + piece * 4 * BN), DMA_BYTES, wvoff, (3 * t0 + 4 * piece) * BN * 4, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(Bs + piece * 4 * BN), DMA16_BYTES, wvoff, (3 * t0 + 4 * piece) * BN * 4, 0, 0);
     }
   };
 
@@ -2307,13 +2300,6 @@ __device__ __forceinline__ void gemm_kk_body(const GemmKKArgs& g, const int bloc
   constexpr int STAGE = (BM + BN) * BK;  // floats
   constexpr int LA = BM * 4 / 256, LB = BN * 4 / 256;  // 16-byte LDS-DMA instructions per wave per k-tile
   static_assert(LA >= 1 && LB >= 1, "tile too small");
-  // the 16-byte LDS-DMA form exists on gfx950 only: hipcc's HOST pass (which merely parses this body) silently drops the
-  // kernel's launch stub when it meets it in a template-dependent statement, so the host pass sees the 4-byte form
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int DMA_BYTES = 16;
-#else
-  constexpr int DMA_BYTES = 4;
-#endif
   __shared__ __attribute__((aligned(16))) float smem[NS * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2342,10 +2328,10 @@ __device__ __forceinline__ void gemm_kk_body(const GemmKKArgs& g, const int bloc
     float* Bs = As + BM * BK;
 #pragma unroll
     for (int j = 0; j < LA; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(As + (wave * LA + j) * 16 * BK), DMA_BYTES, avoff[j], kt * BK * 4, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr_t)(As + (wave * LA + j) * 16 * BK), DMA16_BYTES, avoff[j], kt * BK * 4, 0, 0);
 #pragma unroll
     for (int j = 0; j < LB; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(Bs + (wave * LB + j) * 16 * BK), DMA_BYTES, bvoff[j], kt * BK * 4, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_ptr_t)(Bs + (wave * LB + j) * 16 * BK), DMA16_BYTES, bvoff[j], kt * BK * 4, 0, 0);
   };
 
   const int wm = wave >> 1, wn = wave & 1;
@@ -2375,15 +2361,7 @@ __device__ __forceinline__ void gemm_kk_body(const GemmKKArgs& g, const int bloc
     if (kt0 + i < kt1) issue(kt0 + i, i);
   int stage = 0;
   for (int kt = kt0; kt < kt1; ++kt) {
-    // tile kt has landed once only the loads of the younger tiles in flight (<= NS - 2) are outstanding
-    if constexpr (NS == 2) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      const int younger = kt1 - 1 - kt < NS - 2 ? kt1 - 1 - kt : NS - 2;
-      [&]<int... Y>(std::integer_sequence<int, Y...>) {
-        ((younger == Y ? (void)({ asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Y * (LA + LB)) : "memory"); }) : (void)0), ...);
-      }(std::make_integer_sequence<int, NS - 1>{});
-    }
+    ring_wait<NS, LA + LB>(kt1 - 1 - kt);
     asm volatile("s_barrier" ::: "memory");  // tile kt is in LDS for every wave; the stage read in the previous iteration is free
     if (kt + NS - 1 < kt1) issue(kt + NS - 1, stage == 0 ? NS - 1 : stage - 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -2420,7 +2398,6 @@ __device__ __forceinline__ void gemm_kk_body(const GemmKKArgs& g, const int bloc
   int out_split = split;
   if (g.part != nullptr && g.splits > 1) {
     // ---- in-kernel reduction of the K slices (the conv kernel's write-through form: cdna_hip_programming.md section 5)
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
     const auto rp = __builtin_amdgcn_make_buffer_rsrc(g.part, 0, g.part_bytes, 0x00020000);
     constexpr unsigned TILE_BYTES = BM * BN * 4;
     const unsigned my = (unsigned)(L * g.splits + split) * TILE_BYTES + (unsigned)tid * 16u;
