@@ -282,6 +282,9 @@ SIGNATURES = {
     "advhip_chan_layernorm_form": (_I, [_I, _L, _I]),
     "advhip_head_ln_fc_form": (_I, [_I, _L, _I]),
     "advhip_dwconv_t_form": (_I, [_I, _I]),
+    # which pooling kernel a launch takes: (W, kt, kh, kw, st, sh, sw, y_padded) / (n) -> form id
+    "advhip_maxpool3d_form": (_I, [_I] * 8),
+    "advhip_global_avgpool_form": (_I, [_I]),
 }
 
 # advhip_live_events_update_f32: the modes and the width of cand_int (ADVHIP_LIVE_EVENTS_* of include/advhip.h)
@@ -289,6 +292,9 @@ LIVE_EVENTS_UPDATE, LIVE_EVENTS_FINISH, LIVE_EVENTS_RESET, LIVE_EVENTS_CAND_INTS
 
 # advhip_bn_rows_form's answers (ADVHIP_BN_ROWS_* of include/advhip.h)
 BN_ROWS_GENERIC, BN_ROWS_REG256X4, BN_ROWS_REG256X12, BN_ROWS_REG1024X4 = 0, 1, 2, 3
+
+# advhip_maxpool3d_form's answers (ADVHIP_MAXPOOL_* of include/advhip.h)
+MAXPOOL_GENERIC, MAXPOOL_ROW233, MAXPOOL_TEMPORAL = 0, 1, 2
 
 _lib: Optional[C.CDLL] = None
 

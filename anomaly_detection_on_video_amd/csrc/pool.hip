@@ -1,12 +1,16 @@
 // Pooling kernels of the I3D backbone (HBM-bound, NCDHW fp32).
 //   maxpool3d      : nn.MaxPool3d, padding 0, floor mode   (/root/reference/src/i3d.py:212-217, 306, 309)
 //   global_avgpool : nn.AdaptiveAvgPool3d((1,1,1))         (/root/reference/src/i3d.py:244, 314)
+// Tests at the kernels' edges: tests/test_hip_pool_edges.py; which kernel a shape reaches: tests/test_pool_host.py.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
 
 namespace advhip {
+
+// Rows of up to AVG_BUTTERFLY_MAX positions take global_avgpool_kernel's two-chunk butterfly (advhip_global_avgpool_form).
+constexpr int AVG_BUTTERFLY_MAX = 128;
 
 // One thread per output element, consecutive threads along W (coalesced stores; the window
 // reads of neighbouring threads overlap and are served by L1/L2).
@@ -111,7 +115,7 @@ __global__ void global_avgpool_kernel(const float* __restrict__ x, float* __rest
   const long long row = blockIdx.x * (long long)(blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* p = x + row * n;
-  if (n <= 128) {
+  if (n <= AVG_BUTTERFLY_MAX) {
     float s0 = lane < n ? p[lane] : 0.f, s1 = 64 + lane < n ? p[64 + lane] : 0.f;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -128,9 +132,28 @@ __global__ void global_avgpool_kernel(const float* __restrict__ x, float* __rest
   if (lane == 0) y[row] = s / (float)n;
 }
 
+// Which kernel a maxpool3d_strided launch takes (advhip_maxpool3d_form): the wave-per-row kernel for the stem pool on even rows of
+// <= 128 floats (Wo < 64: one lane per output column), the temporal kernel for dense (kt,1,1) pools, else one thread per output.
+static int maxpool_form(int W, int kt, int kh, int kw, int st, int sh, int sw, bool y_padded) {
+  const int Wo = (W - kw) / sw + 1;
+  if (kt == 2 && kh == 3 && kw == 3 && st == 2 && sh == 2 && sw == 2 && W % 2 == 0 && W <= 128 && Wo < 64) return ADVHIP_MAXPOOL_ROW233;
+  if (kh == 1 && kw == 1 && sh == 1 && sw == 1 && !y_padded) return ADVHIP_MAXPOOL_TEMPORAL;
+  return ADVHIP_MAXPOOL_GENERIC;
+}
+
+// Which branch of global_avgpool_kernel a row length takes (advhip_global_avgpool_form)
+static int avgpool_form(int n) { return n <= AVG_BUTTERFLY_MAX ? 1 : 0; }
+
 }  // namespace advhip
 
 using namespace advhip;
+
+extern "C" int32_t advhip_maxpool3d_form(int32_t W, int32_t kt, int32_t kh, int32_t kw, int32_t st, int32_t sh, int32_t sw,
+                                         int32_t y_padded) {
+  return kw > 0 && sw > 0 ? maxpool_form(W, kt, kh, kw, st, sh, sw, y_padded != 0) : ADVHIP_MAXPOOL_GENERIC;
+}
+
+extern "C" int32_t advhip_global_avgpool_form(int32_t n) { return avgpool_form(n); }
 
 extern "C" int advhip_maxpool3d_f32(const float* x, float* y, int32_t B, int32_t C, int32_t T, int32_t H, int32_t W,
                                     int32_t kt, int32_t kh, int32_t kw, int32_t st, int32_t sh, int32_t sw,
@@ -166,7 +189,8 @@ extern "C" int advhip_maxpool3d_strided_f32(const float* x, float* y, int64_t y_
   ADVHIP_REQUIRE(y_batch_stride == 0 || y_batch_stride >= per_sample, "maxpool3d: y batch stride %lld < one sample (%lld)",
                  (long long)y_batch_stride, per_sample);
   const long long ypad = y_batch_stride > 0 ? y_batch_stride - per_sample : 0;
-  if (kt == 2 && kh == 3 && kw == 3 && st == 2 && sh == 2 && sw == 2 && W % 2 == 0 && W <= 128 && Wo < 64) {
+  const int form = maxpool_form(W, kt, kh, kw, st, sh, sw, ypad != 0);
+  if (form == ADVHIP_MAXPOOL_ROW233) {
     const long long rows = (long long)B * C * To * Ho;
     const long long blocks = (rows + 3) / 4;
     ADVHIP_REQUIRE(blocks < (1ll << 31), "maxpool3d: too many rows");
@@ -174,7 +198,7 @@ extern "C" int advhip_maxpool3d_strided_f32(const float* x, float* y, int64_t y_
                        Ho, Wo, rows, (long long)C * To * Ho, ypad);
     return check_launch("maxpool3d_233");
   }
-  if (kh == 1 && kw == 1 && sh == 1 && sw == 1 && ypad == 0) {
+  if (form == ADVHIP_MAXPOOL_TEMPORAL) {
     const int grid = (int)std::min<long long>((total + 1023) / 1024, 256 * 16);
     hipLaunchKernelGGL(maxpool3d_t_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, T, H * W, To, kt, st, total);
     return check_launch("maxpool3d_t");

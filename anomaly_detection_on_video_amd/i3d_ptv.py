@@ -106,20 +106,32 @@ class I3D8x8R50(nn.Module):
                              pk(rb.branch1_conv, rb.branch1_norm, p + ".branch1") if hasattr(rb, "branch1_conv") else None))
         self._plan, self._stamp = plan, stamp
 
-    def _head_weights(self, thw: Tuple[int, int, int], dev) -> torch.Tensor:
+    @staticmethod
+    def _head_weights_f64(thw: Tuple[int, int, int]) -> torch.Tensor:
         """AdaptiveAvgPool3d(1)(AvgPool3d(k, stride 1)(x)) as one weighted sum: weight of position i along an axis of
-        length n = (number of windows that cover i) / (n - k + 1) / k."""
+        length n = (number of windows that cover i) / (n - k + 1) / k.  -> (T, H, W) fp64 (tests/test_pool_host.py restates it
+        against torch's AvgPool3d)."""
+        ws = []
+        for n, k in zip(thw, HEAD_POOL):
+            if n < k:
+                raise ValueError(f"feature map {thw} smaller than the head's AvgPool3d{HEAD_POOL}")
+            nw = n - k + 1
+            ws.append(torch.tensor([(min(i, nw - 1) - max(i - k + 1, 0) + 1) / (nw * k) for i in range(n)], dtype=torch.float64))
+        return ws[0][:, None, None] * ws[1][None, :, None] * ws[2][None, None, :]
+
+    def _head_weights(self, thw: Tuple[int, int, int], dev) -> torch.Tensor:
+        """the weights of _head_weights_f64 rounded to fp32, as the (T H W, 1) operand of the head's GEMM on `dev`"""
         key = (thw, dev)
         if key not in self._head_w:
-            ws = []
-            for n, k in zip(thw, HEAD_POOL):
-                if n < k:
-                    raise ValueError(f"feature map {thw} smaller than the head's AvgPool3d{HEAD_POOL}")
-                nw = n - k + 1
-                ws.append(torch.tensor([(min(i, nw - 1) - max(i - k + 1, 0) + 1) / (nw * k) for i in range(n)], dtype=torch.float64))
-            w = (ws[0][:, None, None] * ws[1][None, :, None] * ws[2][None, None, :]).reshape(-1, 1).float()
-            self._head_w[key] = w.to(dev)
+            self._head_w[key] = self._head_weights_f64(thw).reshape(-1, 1).float().to(dev)
         return self._head_w[key]
+
+    def head(self, x: torch.Tensor) -> torch.Tensor:
+        """(B, C, T, H, W) -> (B, C, 1, 1, 1): the head's two average pools as one GEMM with _head_weights
+        (tests/test_hip_pool_edges.py)"""
+        B, Cc = x.shape[:2]
+        w = self._head_weights(tuple(x.shape[2:]), x.device)
+        return ops.bgemm(x.view(1, B * Cc, -1), w.view(1, -1, 1)).view(B, Cc, 1, 1, 1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.training:
@@ -141,6 +153,4 @@ class I3D8x8R50(nn.Module):
                     h = ops.conv3d_bn_act(h, cb, relu=True)
                     res = ops.conv3d_bn_act(x, sc, relu=False) if sc is not None else x
                     x = ops.conv3d_bn_act(h, cc, relu=True, residual=res)
-            B, Cc = x.shape[:2]
-            w = self._head_weights(tuple(x.shape[2:]), x.device)
-            return ops.bgemm(x.view(1, B * Cc, -1), w.view(1, -1, 1)).view(B, Cc, 1, 1, 1)
+            return self.head(x)

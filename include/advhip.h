@@ -1202,6 +1202,17 @@ int32_t advhip_head_ln_fc_form(int32_t C, int64_t N, int32_t aligned16);
 /* 0 = one element per thread, 1 = four consecutive t per thread (T % 4 == 0); the same rule forward and backward, K = 3 and 5 */
 int32_t advhip_dwconv_t_form(int32_t T, int32_t aligned16);
 
+/* The pooling launchers' rules, in the same way.  advhip_maxpool3d_strided_f32 (and advhip_maxpool3d_f32, which is it with a dense
+ * y) picks its kernel from the row length W, the window and the stride, and from `y_padded` (0 / 1): whether y_batch_stride leaves
+ * elements between consecutive samples of y (a stride of 0 or of exactly one sample is dense).  advhip_maxpool3d_padded_f32 has
+ * one kernel, the generic one, and no query. */
+#define ADVHIP_MAXPOOL_GENERIC 0  /* one thread per output element, any window, stride and padding */
+#define ADVHIP_MAXPOOL_ROW233 1   /* k(2,3,3) s(2,2,2) on even rows of <= 128 floats (fewer than 64 outputs): one wavefront per output row */
+#define ADVHIP_MAXPOOL_TEMPORAL 2 /* k(kt,1,1) s(st,1,1) into a dense y: four outputs per thread */
+int32_t advhip_maxpool3d_form(int32_t W, int32_t kt, int32_t kh, int32_t kw, int32_t st, int32_t sh, int32_t sw, int32_t y_padded);
+/* advhip_global_avgpool_f32: 1 = rows of n <= 128 positions, added as two 64-lane butterflies; 0 = longer rows, lanes stride the row */
+int32_t advhip_global_avgpool_form(int32_t n);
+
 #ifdef __cplusplus
 }
 #endif
