@@ -244,6 +244,11 @@ SIGNATURES = {
     "advhip_yuv420_surface_to_rgb_u8": (C.c_int, [_P, _P, _L, _I, _L, _I, _I] + [_I, _I, _L, _L, _L, _L, _L, _I] + [_I] * 6 + [_P]),
     "advhip_resize_yuv420_surface_u8": (C.c_int, [_P, _P, _P, _L, _I, _L, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I, _I]
                                         + [_I, _I, _L, _L, _L, _L, _L, _I] + [_I] * 6 + [_P]),
+    # (src, dst, ws, F_src, N, src_of, frame_step, table_of, n_tables, [frame_pitch,] H, W, C, OH, OW, the stacked tables, rowspan, ws_rows, ...)
+    "advhip_resize_roi_u8": (C.c_int, [_P, _P, _P, _L, _L, _P, _I, _P, _I] + [_I] * 5 + [_P, _P, _I, _P, _P, _I, _P, _I] + [_P]),
+    "advhip_resize_roi_yuv420_u8": (C.c_int, [_P, _P, _P, _L, _L, _P, _I, _P, _I] + [_I] * 5 + [_P, _P, _I, _P, _P, _I, _P, _I] + [_I] * 7 + [_P]),
+    "advhip_resize_roi_surface_u8": (C.c_int, [_P, _P, _P, _L, _L, _P, _I, _P, _I, _L] + [_I] * 5 + [_P, _P, _I, _P, _P, _I, _P, _I]
+                                     + [_I, _I, _L, _L, _L, _L, _L, _I] + [_I] * 6 + [_P]),
     "advhip_roc_counts_ws_bytes": (_L, [_L]),
     # (scores, pos, neg, M, thresholds, tps, fps, meta, workspace, workspace_bytes, stream)
     "advhip_roc_counts": (C.c_int, [_P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P]),

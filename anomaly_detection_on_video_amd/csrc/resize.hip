@@ -16,9 +16,46 @@ __device__ __forceinline__ uint8_t clip8(int s) {
   return (uint8_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
 }
 
-// Horizontal pass: dst row r = (f, y) of `rows` rows per frame <- src row (f, row0 + y); one wave per output row, a lane per
-// output pixel (three channels).  Bounds and coefficients of a pixel are read once for its three channels.  Output frame f reads
-// the source frame at byte f * fpitch: H * W * 3 for every frame, frame_step times that for every frame_step-th one.
+// The pass bodies: what one wave does with the row it was given.  The kernels differ in how a row finds its source frame and its
+// tables only -- one table set and a frame pitch (the three kernels below), or a lookup per output frame (the roi kernels) -- so
+// each body is written once and inlined into both.
+
+// One row of the horizontal pass: out pixel x < OW <- the taps of source row `in` (W pixels) that xb / xk name; a lane per output
+// pixel (three channels).  Bounds and coefficients of a pixel are read once for its three channels.
+__device__ __forceinline__ void resize_h_row(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int W, int OW, const int* __restrict__ xb,
+                                             const int* __restrict__ xk, int ksize, int lane) {
+  for (int x = lane; x < OW; x += 64) {
+    const int x0 = xb[2 * x];
+    int n = min(xb[2 * x + 1], ksize);
+    if (x0 < 0 || x0 + n > W) n = 0;  // (never for tables from resize.py: a guard against a foreign table)
+    const int* k = xk + (long long)x * ksize;
+    const uint8_t* p = in + x0 * 3;
+    int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
+    for (int j = 0; j < n; ++j) {
+      const int w = k[j];
+      s0 += (int)p[3 * j] * w;
+      s1 += (int)p[3 * j + 1] * w;
+      s2 += (int)p[3 * j + 2] * w;
+    }
+    out[3 * x] = clip8(s0);
+    out[3 * x + 1] = clip8(s1);
+    out[3 * x + 2] = clip8(s2);
+  }
+}
+
+// One row of the vertical pass: out byte q < rowbytes <- n rows of rowbytes bytes from `in` on, with the row's coefficients k (the
+// same for every lane); a lane per output byte.
+__device__ __forceinline__ void resize_v_row(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int rowbytes, const int* __restrict__ k, int n,
+                                             int lane) {
+  for (int q = lane; q < rowbytes; q += 64) {
+    int s = 1 << (RESIZE_BITS - 1);
+    for (int j = 0; j < n; ++j) s += (int)in[(long long)j * rowbytes + q] * k[j];
+    out[q] = clip8(s);
+  }
+}
+
+// Horizontal pass: dst row r = (f, y) of `rows` rows per frame <- src row (f, row0 + y); one wave per output row.  Output frame f
+// reads the source frame at byte f * fpitch: H * W * 3 for every frame, frame_step times that for every frame_step-th one.
 __global__ __launch_bounds__(256) void resize_h_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int W,
                                                          int OW, int row0, int rows, const int* __restrict__ xb,
                                                          const int* __restrict__ xk, int ksize, long long nrows) {
@@ -28,28 +65,12 @@ __global__ __launch_bounds__(256) void resize_h_u8_kernel(const uint8_t* __restr
     const int y = (int)(r - f * rows);
     const uint8_t* in = src + f * fpitch + (row0 + y) * (long long)W * 3;
     uint8_t* out = dst + r * OW * 3;
-    for (int x = lane; x < OW; x += 64) {
-      const int x0 = xb[2 * x];
-      int n = min(xb[2 * x + 1], ksize);
-      if (x0 < 0 || x0 + n > W) n = 0;  // (never for tables from resize.py: a guard against a foreign table)
-      const int* k = xk + (long long)x * ksize;
-      const uint8_t* p = in + x0 * 3;
-      int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
-      for (int j = 0; j < n; ++j) {
-        const int w = k[j];
-        s0 += (int)p[3 * j] * w;
-        s1 += (int)p[3 * j + 1] * w;
-        s2 += (int)p[3 * j + 2] * w;
-      }
-      out[3 * x] = clip8(s0);
-      out[3 * x + 1] = clip8(s1);
-      out[3 * x + 2] = clip8(s2);
-    }
+    resize_h_row(in, out, W, OW, xb, xk, ksize, lane);
   }
 }
 
-// Vertical pass: dst row (f, oy) <- rows [yb[oy].first - ybase, + count) of the IH-row source frame f; one wave per output row,
-// a lane per output byte (the row's coefficients are the same for every lane).  Source frame f starts at byte f * fpitch.
+// Vertical pass: dst row (f, oy) <- rows [yb[oy].first - ybase, + count) of the IH-row source frame f; one wave per output row.
+// Source frame f starts at byte f * fpitch.
 __global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch, int IH, int OH,
                                                          int rowbytes, int ybase, const int* __restrict__ yb,
                                                          const int* __restrict__ yk, int ksize, long long nrows) {
@@ -63,11 +84,76 @@ __global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restr
     const int* k = yk + (long long)oy * ksize;
     const uint8_t* in = src + f * fpitch + y0 * (long long)rowbytes;
     uint8_t* out = dst + r * rowbytes;
-    for (int q = lane; q < rowbytes; q += 64) {
-      int s = 1 << (RESIZE_BITS - 1);
-      for (int j = 0; j < n; ++j) s += (int)in[(long long)j * rowbytes + q] * k[j];
-      out[q] = clip8(s);
-    }
+    resize_v_row(in, out, rowbytes, k, n, lane);
+  }
+}
+
+// --- regions of interest: a table set per output frame (include/advhip.h).  The tables of set t start t * OW (or OH) entries into
+// the stacked arrays; rowspan[t] = (row0, rows) are the source rows its vertical table reads.  Where a row's frame is, which set it
+// uses and whether it is computed at all is decided once per row and is the same for the whole wave.
+struct RoiArgs {
+  const int *src_of, *table_of, *rowspan;  // device; the first two may be null
+  long long F_src, N;
+  int frame_step, n_tables, H, ws_rows;
+};
+
+struct RoiFrame {
+  long long src;  // the source frame
+  int table, row0, rows;
+  bool ok;  // both indices in range: the frame is computed
+};
+
+__device__ __forceinline__ RoiFrame roi_frame(const RoiArgs& A, long long i) {
+  RoiFrame f;
+  f.src = A.src_of ? (long long)A.src_of[i] : i * A.frame_step;
+  f.table = A.table_of ? A.table_of[i] : 0;
+  f.ok = f.src >= 0 && f.src < A.F_src && f.table >= 0 && f.table < A.n_tables;
+  f.row0 = f.rows = 0;
+  if (f.ok) {
+    f.row0 = A.rowspan[2 * f.table], f.rows = A.rowspan[2 * f.table + 1];
+    // (never for tables from resize.py: rowspan is device memory the host cannot check, so a span outside the frame or the
+    // workspace counts no rows here and no taps in the vertical pass)
+    if (f.row0 < 0 || f.rows < 0 || f.rows > A.ws_rows || f.row0 > A.H - f.rows) f.rows = 0;
+  }
+  return f;
+}
+
+// the row of this wave, the same number in every lane and known to be so
+__device__ __forceinline__ long long wave_row() { return (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// Horizontal pass with a table set per frame: ws row (i, y), y < rows of frame i's set <- row row0 + y of its source frame.  The
+// workspace is (N, ws_rows, OW, 3); a frame's slab is written from its first row on.
+__global__ __launch_bounds__(256) void resize_h_roi_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ ws, RoiArgs A, int W, int OW,
+                                                             const int* __restrict__ xb, const int* __restrict__ xk, int ksize) {
+  const int lane = threadIdx.x & 63;
+  const long long nrows = A.N * A.ws_rows;
+  for (long long r = wave_row(); r < nrows; r += (long long)gridDim.x * 4) {
+    const long long i = r / A.ws_rows;
+    const int y = (int)(r - i * A.ws_rows);
+    const RoiFrame f = roi_frame(A, i);
+    if (!f.ok || y >= f.rows) continue;
+    const uint8_t* in = src + (f.src * A.H + f.row0 + y) * (long long)W * 3;
+    resize_h_row(in, ws + r * OW * 3, W, OW, xb + (long long)f.table * OW * 2, xk + (long long)f.table * OW * ksize, ksize, lane);
+  }
+}
+
+// Vertical pass with a table set per frame: dst row (i, oy) <- rows [yb[oy].first - row0, + count) of the `rows` rows of frame i's
+// slab of the workspace.
+__global__ __launch_bounds__(256) void resize_v_roi_u8_kernel(const uint8_t* __restrict__ ws, uint8_t* __restrict__ dst, RoiArgs A, int OH, int rowbytes,
+                                                             const int* __restrict__ yb, const int* __restrict__ yk, int ksize) {
+  const int lane = threadIdx.x & 63;
+  const long long nrows = A.N * OH;
+  for (long long r = wave_row(); r < nrows; r += (long long)gridDim.x * 4) {
+    const long long i = r / OH;
+    const int oy = (int)(r - i * OH);
+    const RoiFrame f = roi_frame(A, i);
+    if (!f.ok) continue;
+    const int* b = yb + ((long long)f.table * OH + oy) * 2;
+    const int y0 = b[0] - f.row0;
+    int n = min(b[1], ksize);
+    if (y0 < 0 || y0 + n > f.rows) n = 0;  // (as above)
+    const int* k = yk + ((long long)f.table * OH + oy) * ksize;
+    resize_v_row(ws + (i * A.ws_rows + y0) * (long long)rowbytes, dst + r * rowbytes, rowbytes, k, n, lane);
   }
 }
 
@@ -308,6 +394,38 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __
 // output is byte for byte that kernel's on the converted frame.  The taps [x0, x0 + n) are walked chroma sample by chroma sample:
 // one chroma read and one set of products for the (up to) two taps that share it.
 template <class Src>
+__device__ __forceinline__ void resize_h_yuv420_row(const Src& S, const YuvRow& in, uint8_t* __restrict__ out, int W, int OW,
+                                                    const int* __restrict__ xb, const int* __restrict__ xk, int ksize, const YuvCoef& k, int lane) {
+  for (int x = lane; x < OW; x += 64) {
+    int x0 = xb[2 * x];
+    int n = min(xb[2 * x + 1], ksize);
+    if (x0 < 0 || x0 + n > W) x0 = 0, n = 0;  // (never for tables from resize.py: a guard against a foreign table)
+    const int xe = x0 + n;
+    const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
+    int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
+    for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
+      int cb, cr;
+      S.chroma_pair(in, xc, cb, cr);
+      const ChromaTerms<Src::BITS> c(cb, cr, k);
+#pragma unroll
+      for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
+        if (xs >= x0 && xs < xe) {
+          int pr, pg, pb;
+          yuv_rgb(S.luma(in, xs), c, k, pr, pg, pb);
+          const int wk = w[xs];
+          s0 += pr * wk;
+          s1 += pg * wk;
+          s2 += pb * wk;
+        }
+      }
+    }
+    out[3 * x] = clip8(s0);
+    out[3 * x + 1] = clip8(s1);
+    out[3 * x + 2] = clip8(s2);
+  }
+}
+
+template <class Src>
 __global__ __launch_bounds__(256) void resize_h_yuv420_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long fpitch,
                                                                 typename Src::Size size, int OW, int row0, int rows, const int* __restrict__ xb,
                                                                 const int* __restrict__ xk, int ksize, typename Src::Arg arg, YuvCoef k,
@@ -319,33 +437,25 @@ __global__ __launch_bounds__(256) void resize_h_yuv420_u8_kernel(const uint8_t* 
     const int y = row0 + (int)(r - f * rows);
     const YuvRow in = S.row(src + f * fpitch, y);
     uint8_t* out = dst + r * OW * 3;
-    for (int x = lane; x < OW; x += 64) {
-      int x0 = xb[2 * x];
-      int n = min(xb[2 * x + 1], ksize);
-      if (x0 < 0 || x0 + n > W) x0 = 0, n = 0;  // (never for tables from resize.py: a guard against a foreign table)
-      const int xe = x0 + n;
-      const int* w = xk + (long long)x * ksize - x0;  // indexed by the source column
-      int s0 = 1 << (RESIZE_BITS - 1), s1 = s0, s2 = s0;
-      for (int xc = x0 >> 1; 2 * xc < xe; ++xc) {
-        int cb, cr;
-        S.chroma_pair(in, xc, cb, cr);
-        const ChromaTerms<Src::BITS> c(cb, cr, k);
-#pragma unroll
-        for (int xs = 2 * xc; xs < 2 * xc + 2; ++xs) {
-          if (xs >= x0 && xs < xe) {
-            int pr, pg, pb;
-            yuv_rgb(S.luma(in, xs), c, k, pr, pg, pb);
-            const int wk = w[xs];
-            s0 += pr * wk;
-            s1 += pg * wk;
-            s2 += pb * wk;
-          }
-        }
-      }
-      out[3 * x] = clip8(s0);
-      out[3 * x + 1] = clip8(s1);
-      out[3 * x + 2] = clip8(s2);
-    }
+    resize_h_yuv420_row(S, in, out, W, OW, xb, xk, ksize, k, lane);
+  }
+}
+
+// resize_h_roi_u8_kernel on 4:2:0 frames, source frame s at byte s * fpitch: the row body above with the lookup of that kernel.
+template <class Src>
+__global__ __launch_bounds__(256) void resize_h_roi_yuv420_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ ws, RoiArgs A,
+                                                                    long long fpitch, typename Src::Size size, int OW, const int* __restrict__ xb,
+                                                                    const int* __restrict__ xk, int ksize, typename Src::Arg arg, YuvCoef k) {
+  const int lane = threadIdx.x & 63, W = size.W;
+  const Src S(arg, size);
+  const long long nrows = A.N * A.ws_rows;
+  for (long long r = wave_row(); r < nrows; r += (long long)gridDim.x * 4) {
+    const long long i = r / A.ws_rows;
+    const int y = (int)(r - i * A.ws_rows);
+    const RoiFrame f = roi_frame(A, i);
+    if (!f.ok || y >= f.rows) continue;
+    const YuvRow in = S.row(src + f.src * fpitch, f.row0 + y);
+    resize_h_yuv420_row(S, in, ws + r * OW * 3, W, OW, xb + (long long)f.table * OW * 2, xk + (long long)f.table * OW * ksize, ksize, k, lane);
   }
 }
 
@@ -638,4 +748,109 @@ extern "C" int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst,
   const Yuv420Source Y{bits, frame_pitch, {y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, shift}};
   return resize_yuv420("resize_yuv420_surface_u8", false, -1, Y, src, dst, ws, F_src, frame_step, H, W,
                        {C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, row0, rows}, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+}
+
+// --- regions of interest: the three entry points (include/advhip.h) ---
+
+// the arguments the three roi entry points share beyond their models'
+struct RoiCall {
+  int64_t F_src, N;
+  const int32_t* src_of;
+  int32_t frame_step;
+  const int32_t* table_of;
+  int32_t n_tables;
+  const int32_t* rowspan;
+  int32_t ws_rows;
+};
+
+// every check of a roi call that does not depend on the source form -> the kernels' argument block
+static int check_roi(const char* who, const uint8_t* src, const uint8_t* dst, const uint8_t* ws, const RoiCall& Q, int32_t H, int32_t W,
+                     const ResizeArgs& R, RoiArgs* A) {
+  ADVHIP_REQUIRE(src && dst, "%s: null frames or output", who);
+  ADVHIP_REQUIRE(ws, "%s: null workspace (both passes always run)", who);
+  ADVHIP_REQUIRE(Q.frame_step >= 1, "%s: frame step %d", who, Q.frame_step);
+  ADVHIP_REQUIRE(Q.F_src >= 1 && Q.N >= 1 && H >= 1 && W >= 1 && R.OH >= 1 && R.OW >= 1,
+                 "%s: sizes must be >= 1 (F_src=%lld, N=%lld, %d x %d -> %d x %d)", who, (long long)Q.F_src, (long long)Q.N, H, W, R.OH, R.OW);
+  ADVHIP_REQUIRE(R.C == 3, "%s: the output has 3 channels (RGB), got C=%d", who, R.C);
+  ADVHIP_REQUIRE(Q.n_tables >= 1, "%s: %d tables", who, Q.n_tables);
+  ADVHIP_REQUIRE(R.xbounds && R.xcoef, "%s: null horizontal tables", who);
+  ADVHIP_REQUIRE(R.ybounds && R.ycoef, "%s: null vertical tables", who);
+  ADVHIP_REQUIRE(R.xksize >= 1, "%s: horizontal ksize %d < 1", who, R.xksize);
+  ADVHIP_REQUIRE(R.yksize >= 1, "%s: vertical ksize %d < 1", who, R.yksize);
+  ADVHIP_REQUIRE(Q.rowspan, "%s: null rowspan", who);
+  ADVHIP_REQUIRE(Q.ws_rows >= 1 && Q.ws_rows <= H, "%s: ws_rows %d outside [1, %d]", who, Q.ws_rows, H);
+  ADVHIP_REQUIRE((long long)W * 3 <= INT32_MAX && (long long)R.OW * 3 <= INT32_MAX, "%s: rows of %d / %d pixels are too long", who, W, R.OW);
+  long long last, out_bytes, ws_bytes, xk_ints, yk_ints;
+  ADVHIP_REQUIRE(mul_ok(Q.N, R.OH, R.OW, R.C, &out_bytes) && mul_ok(Q.N, Q.ws_rows, R.OW, R.C, &ws_bytes) &&
+                     mul_ok(Q.n_tables, R.OW, R.xksize, 1, &xk_ints) && mul_ok(Q.n_tables, R.OH, R.yksize, 1, &yk_ints),
+                 "%s: frame or table sizes overflow int64", who);
+  ADVHIP_REQUIRE(Q.src_of || (mul_ok(Q.N - 1, Q.frame_step, 1, 1, &last) && last < Q.F_src),
+                 "%s: output frame %lld at frame step %d is past the %lld source frames", who, (long long)Q.N - 1, Q.frame_step, (long long)Q.F_src);
+  *A = {Q.src_of, Q.table_of, Q.rowspan, Q.F_src, Q.N, Q.frame_step, Q.n_tables, H, Q.ws_rows};
+  return ADVHIP_OK;
+}
+
+// the vertical pass of a roi call, from the workspace
+static int launch_roi_vertical(const char* what, const RoiArgs& A, const ResizeArgs& R, const uint8_t* ws, uint8_t* dst, hipStream_t s) {
+  hipLaunchKernelGGL(resize_v_roi_u8_kernel, dim3(row_grid(A.N * R.OH)), dim3(256), 0, s, ws, dst, A, R.OH, R.OW * R.C, R.ybounds, R.ycoef, R.yksize);
+  return check_launch(what);
+}
+
+extern "C" int advhip_resize_roi_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of, int32_t frame_step,
+                                    const int32_t* table_of, int32_t n_tables, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
+                                    const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds, const int32_t* ycoef,
+                                    int32_t yksize, const int32_t* rowspan, int32_t ws_rows, void* stream) {
+  const char* who = "resize_roi_u8";
+  const ResizeArgs R{C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, 0, ws_rows};
+  RoiArgs A;
+  if (const int rc = check_roi(who, src, dst, ws, {F_src, N, src_of, frame_step, table_of, n_tables, rowspan, ws_rows}, H, W, R, &A); rc != ADVHIP_OK)
+    return rc;
+  long long in_bytes;
+  ADVHIP_REQUIRE(mul_ok(F_src, H, W, C, &in_bytes), "%s: frame sizes overflow int64", who);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(resize_h_roi_u8_kernel, dim3(row_grid(N * ws_rows)), dim3(256), 0, s, src, ws, A, W, OW, xbounds, xcoef, xksize);
+  if (const int rc = check_launch("resize_roi_u8 horizontal pass"); rc != ADVHIP_OK) return rc;
+  return launch_roi_vertical("resize_roi_u8 vertical pass", A, R, ws, dst, s);
+}
+
+// both 4:2:0 roi entry points
+static int resize_roi_yuv420(const char* who, bool compact, int layout, const Yuv420Source& Y, const uint8_t* src, uint8_t* dst, uint8_t* ws,
+                             const RoiCall& Q, int32_t H, int32_t W, const ResizeArgs& R, const YuvCoef& k, void* stream) {
+  RoiArgs A;
+  if (const int rc = check_roi(who, src, dst, ws, Q, H, W, R, &A); rc != ADVHIP_OK) return rc;
+  if (const int rc = compact ? check_yuv420(who, H, W, layout, k) : check_surface(who, src, H, W, Y, k); rc != ADVHIP_OK) return rc;
+  long long in_bytes;
+  ADVHIP_REQUIRE(mul_ok(Q.F_src, Y.frame_pitch, 1, 1, &in_bytes), "%s: frame sizes overflow int64", who);
+  hipStream_t s = (hipStream_t)stream;
+  auto launch = [&](auto kernel, const auto& size, const auto& arg) {
+    hipLaunchKernelGGL(kernel, dim3(row_grid(Q.N * Q.ws_rows)), dim3(256), 0, s, src, ws, A, Y.frame_pitch, size, R.OW, R.xbounds, R.xcoef, R.xksize, arg, k);
+  };
+  if (compact) launch(resize_h_roi_yuv420_u8_kernel<CompactSource>, CompactSource::Size{H, W}, layout);
+  else if (Y.bits == 8) launch(resize_h_roi_yuv420_u8_kernel<SurfaceSource<8>>, SurfaceSource<8>::Size{W}, Y.S);
+  else launch(resize_h_roi_yuv420_u8_kernel<SurfaceSource<10>>, SurfaceSource<10>::Size{W}, Y.S);
+  if (const int rc = check_launch("resize_roi_yuv420_u8 horizontal pass"); rc != ADVHIP_OK) return rc;
+  return launch_roi_vertical("resize_roi_yuv420_u8 vertical pass", A, R, ws, dst, s);
+}
+
+extern "C" int advhip_resize_roi_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of,
+                                           int32_t frame_step, const int32_t* table_of, int32_t n_tables, int32_t H, int32_t W, int32_t C,
+                                           int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                                           const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, const int32_t* rowspan, int32_t ws_rows,
+                                           int32_t layout, int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu,
+                                           void* stream) {
+  return resize_roi_yuv420("resize_roi_yuv420_u8", true, layout, compact_source(H, W, layout), src, dst, ws,
+                           {F_src, N, src_of, frame_step, table_of, n_tables, rowspan, ws_rows}, H, W,
+                           {C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, 0, ws_rows}, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
+}
+
+extern "C" int advhip_resize_roi_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of,
+                                            int32_t frame_step, const int32_t* table_of, int32_t n_tables, int64_t frame_pitch, int32_t H,
+                                            int32_t W, int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef,
+                                            int32_t xksize, const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, const int32_t* rowspan,
+                                            int32_t ws_rows, int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset,
+                                            int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
+                                            int32_t cgu, int32_t cgv, int32_t cbu, void* stream) {
+  const Yuv420Source Y{bits, frame_pitch, {y_offset, y_pitch, cb_offset, cr_offset, chroma_pitch, chroma_step, shift}};
+  return resize_roi_yuv420("resize_roi_surface_u8", false, -1, Y, src, dst, ws, {F_src, N, src_of, frame_step, table_of, n_tables, rowspan, ws_rows}, H,
+                           W, {C, OH, OW, xbounds, xcoef, xksize, ybounds, ycoef, yksize, 0, ws_rows}, YuvCoef{yoff, cy, crv, cgu, cgv, cbu}, stream);
 }

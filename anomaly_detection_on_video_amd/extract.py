@@ -142,7 +142,7 @@ def extract_video(model, video_clips: torch.Tensor, batch_size: int = 16, **kw) 
 def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRAMES_PER_CLIP, crop: int = 224,
                          clips_per_step: Optional[int] = None, resize=None, resample="bilinear", clip_stride: Optional[int] = None,
                          crops=None, frame_step: Optional[int] = None, normalize=None, pixel_format=None, surface=None,
-                         **kw) -> np.ndarray:
+                         box=None, **kw) -> np.ndarray:
     """One video as resized uint8 frames (F, H, W, 3) -- what the decoder + GroupResize(256) hand over -- to np.float32
     (n_clips, 10, 2048): TenCrop, float conversion, normalisation, LoopPad and both permutes run on the device
     (mil_ops.tencrop_normalize_u8), so only the resized uint8 frames cross PCIe (1/23 of the fp32 ten-crop tensor the
@@ -192,7 +192,13 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
     `surface` (a resize.Surface, e.g. from resize.surface; with `pixel_format`; default None = the compact frames above): `frames`
     are the decoder's surfaces as they are, uint8 (F, frame_bytes) -- a row pitch above W, aligned rows, plane offsets, NV21 / YV12
     order, 10-bit P010 / yuv420p10le -- and the conversion or the fused resize reads them in place by that geometry.  Host frames
-    cross PCIe as they are, padding included.  The features are again those of the converted frames, bit for bit; no file-name tag."""
+    cross PCIe as they are, padding included.  The features are again those of the converted frames, bit for bit; no file-name tag.
+
+    `box` (left, top, right, bottom) in source pixels, floats allowed (with `resize`; default None = the whole frame): a region of
+    interest -- every decoded frame is resized from that box, PIL's `Image.resize(size, resample, box=box)` (resize_u8(box=)), so
+    the features are those of the box-resized frames bit for bit, from any source form.  An int `resize` is the box's short side."""
+    if box is not None and resize is None:
+        raise ValueError("box= names a part of the decoded frames: it needs resize= (the size the box is resized to)")
     s, crops, fstep = resolve_sampling(frames_per_clip, clip_stride, crops, frame_step)
     norm = resolve_normalize(normalize)
     plain = normalize_is_default(norm)
@@ -237,7 +243,10 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
                 (h, w), c = (surface.height, surface.width), 3
             else:
                 (h, w), c = ((fr.shape[1], fr.shape[2]), fr.shape[3]) if pf is None else (resize_mod.frame_hw(fr.shape), 3)
-            oh, ow = (h, w) if resize is None else resize_mod.output_size(h, w, resize)
+            if box is not None:
+                oh, ow = resize_mod.box_output_size(resize_mod.resolve_box("extract_video_frames", box, h, w), resize)
+            else:
+                oh, ow = (h, w) if resize is None else resize_mod.output_size(h, w, resize)
             nf = fr.shape[0] if rstep is None else -(-fr.shape[0] // rstep)
             n = nf * oh * ow * c
             buf = torch.empty((n + 16,), device=dev, dtype=torch.uint8)
@@ -245,9 +254,9 @@ def extract_video_frames(model, frames: torch.Tensor, frames_per_clip: int = FRA
             if resize is None:  # 4:2:0 frames a decoder scaled already: the conversion launch alone
                 fr = resize_mod.yuv420_to_rgb_u8(fr, pf, out=out, frame_step=rstep, surface=surface)
             elif pf is None:
-                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep)
+                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, box=box)
             else:
-                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, pixel_format=pf, surface=surface)
+                fr = resize_mod.resize_u8(fr, resize, resample, out=out, frame_step=rstep, pixel_format=pf, surface=surface, box=box)
         elif direct and not fr.is_cuda:  # a device buffer with a few spare bytes behind the pixels (the stem fetches whole 4-byte pieces)
             buf = torch.empty((fr.numel() + 16,), device=dev, dtype=torch.uint8)
             if fr.is_contiguous():

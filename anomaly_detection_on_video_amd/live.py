@@ -254,13 +254,27 @@ class LiveFrames:
     mil_ops.frame_gate_update in front of the ring push, and a step on which nothing is due still uploads nothing, synchronises
     nothing and dispatches no torch arithmetic; `decide`, called on due steps only, copies gate_state to the host and
     synchronises the stream once.  `last_decision` = (extract, held) of the last decide, `extracted_total` and `held_total`
-    count windows; all three are host values."""
+    count windows; all three are host values.
+
+        lf = LiveFrames(n_cameras, frame_hw=(256, 340), ..., rois=resize.RoiSpec((1080, 1920), {0: (0, 0, 960, 540), 3: (200.5, 100, 1400, 900)}))
+        due = lf.push(cams, frames, pixel_format="nv12")        # each camera's box of its decoded frame -> its ring
+        due = lf.push((4, 5, 6), frames, source_of=(0, 0, 1))   # cameras 4 and 5 are two regions of frames[0], camera 6 one of frames[1]
+
+    `rois` (a resize.RoiSpec; None, the default: nothing is built and `push` is launch for launch what it is without the argument)
+    gives every camera a region of interest of its decoded (H, W) frames -- a (left, top, right, bottom) box as PIL's
+    `Image.resize(box=)` takes it, floats allowed; a camera without one sees the whole frame -- resized to frame_hw.  The tables of
+    all cameras are built and uploaded once, here (resize.roi_tables); `push` then takes decoded frames in any form resize_u8 takes
+    and resizes them into the staging buffer in one pair of launches, camera c with table c (resize.resize_rois_u8 with table_of =
+    the cached id vector), so a steady push still uploads nothing and dispatches no torch arithmetic.  `source_of` (host ints, one
+    per listed camera, cached on the device per tuple like the ids) names the row of `frames` each camera reads: one wide frame
+    in, several virtual cameras' frames out.  The motion gate, the rings and everything behind them see the resized frames."""
 
     MAX_ROWS = 65535  # frame rows of one launch (the grid's second dimension)
 
     def __init__(self, n_cameras: int, frame_hw=(256, 340), frames_per_clip: int = 16, frame_step: Optional[int] = None,
-                 clip_stride: Optional[int] = None, device="cuda:0", motion=None):
+                 clip_stride: Optional[int] = None, device="cuda:0", motion=None, rois=None):
         from . import ops
+        from . import resize as rz
 
         try:
             fh, fw = frame_hw
@@ -292,6 +306,13 @@ class LiveFrames:
         self._clips = torch.empty((self.n_cameras * self.frames_per_clip,) + frame, dtype=torch.uint8, device=self.device)
         self._staging = torch.empty((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
         self.last_decision, self.extracted_total, self.held_total = None, 0, 0
+        self.rois = None
+        if rois is not None:
+            self.rois = self._resolve_rois(rois)
+            with torch.cuda.device(self.device):
+                self._roi_tables = rz.roi_tables(*self.rois.source_hw, self.frame_hw, self.rois.boxes, self.rois.resample, self.device)
+            self._roi_ws = torch.empty((self.n_cameras * self._roi_tables.ws_rows * self.frame_hw[1] * 3,), dtype=torch.uint8, device=self.device)
+            self._sources = _Lru(lambda rows: torch.tensor(rows, dtype=torch.int32).to(self.device))  # (keyed by checked tuples only)
         if self.motion is not None:
             self.gate_limit = self.motion.limit(fb)
             self.anchor = torch.zeros((self.n_cameras,) + frame, dtype=torch.uint8, device=self.device)
@@ -301,6 +322,41 @@ class LiveFrames:
             self._gate_rows = self._gate_host.numpy()  # (the same memory: what `decide` reads behind its synchronisation)
             self._ref_epoch, self._holds = [None] * self.n_cameras, [0] * self.n_cameras
             self._decided_at = [0] * self.n_cameras  # the count at which a camera's window was last decided
+
+    def _resolve_rois(self, rois):
+        """`rois` -> a resize.RoiSpec with (H, W) ints and a list of n_cameras boxes (None: the whole frame); the boxes themselves
+        are checked by resize.roi_tables."""
+        from . import resize as rz
+
+        what = "LiveFrames: rois"
+        if not isinstance(rois, rz.RoiSpec):
+            if not isinstance(rois, (tuple, list)) or not 2 <= len(rois) <= 3:
+                raise HipExtensionError(f"{what} = {rois!r} is not a resize.RoiSpec(source_hw, boxes, resample='bilinear')")
+            rois = rz.RoiSpec(*rois)
+        try:
+            h, w = rois.source_hw
+        except (TypeError, ValueError):
+            raise HipExtensionError(f"{what}: source_hw = {rois.source_hw!r} is not a pair (H, W)") from None
+        if (hh := host_int(h)) is None or (ww := host_int(w)) is None or hh < 1 or ww < 1:
+            raise HipExtensionError(f"{what}: source_hw = {rois.source_hw!r} is not a pair of integers >= 1")
+        boxes = rois.boxes
+        if hasattr(boxes, "keys"):
+            bad = [c for c in boxes.keys() if host_int(c, floats=False) is None or not 0 <= int(c) < self.n_cameras]
+            if bad:
+                raise HipExtensionError(f"{what}: boxes name cameras {bad} outside [0, {self.n_cameras})")
+            by_cam = {int(c): boxes[c] for c in boxes.keys()}
+            boxes = [by_cam.get(c) for c in range(self.n_cameras)]
+        elif isinstance(boxes, (tuple, list)) and len(boxes) == self.n_cameras:
+            boxes = list(boxes)
+        else:
+            raise HipExtensionError(f"{what}: boxes must be a sequence of {self.n_cameras} boxes (one per camera, None: the whole frame) or a "
+                                    f"{{camera: box}} dict, got {boxes!r}")
+        try:
+            for bx in boxes:
+                rz.resolve_box(what, bx, hh, ww)
+            return rz.RoiSpec((hh, ww), boxes, rz.filter_name(rois.resample))
+        except ValueError as e:
+            raise HipExtensionError(str(e)) from None
 
     @property
     def counts(self) -> torch.Tensor:
@@ -330,22 +386,37 @@ class LiveFrames:
             return sf.height, sf.width
         return rz.frame_hw(frames.shape) if frames.dim() == 3 else None
 
-    def push(self, cams: Sequence[int], frames: torch.Tensor, resize=None, resample="bilinear", pixel_format=None, surface=None) -> Tuple[int, ...]:
+    def push(self, cams: Sequence[int], frames: torch.Tensor, resize=None, resample="bilinear", pixel_format=None, surface=None,
+             source_of=None) -> Tuple[int, ...]:
         """One new decoded frame for each camera of `cams` (distinct host ints); `frames` uint8 with len(cams) leading rows, on the
         host (copied non-blocking on the current stream) or on the device.  Without `resize`: (n, FH, FW, 3), already at ring
         size.  With `resize` (resize_u8's `size`): whatever resize_u8 takes -- packed RGB (n, H, W, 3), 4:2:0 (n, 3H/2, W) with
         `pixel_format`, (n, frame_bytes) with `surface` -- resized into the staging buffer; a result of another size than frame_hw
         is refused before anything is launched.  All frames of one call share a geometry.  -> the listed cameras whose clip
-        became due with this push, in `cams` order, decided on the host mirror of the counts."""
+        became due with this push, in `cams` order, decided on the host mirror of the counts.
+        With `rois` (the class docstring): `frames` are decoded frames of the RoiSpec's geometry in any of those forms, `resize` is
+        refused (the boxes and frame_hw say what is resized to what), and `source_of` -- host ints, one per listed camera, each a
+        row of `frames` -- lets several cameras read the same row; without it `frames` has one row per camera."""
         from . import resize as rz
 
         what = "LiveFrames.push"
         cams = self.cameras.check(cams, what)
         n = len(cams)
-        if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 2 or frames.shape[0] != n:
+        if source_of is not None and self.rois is None:
+            raise HipExtensionError(f"{what}: source_of names the decoded frame each camera's region is cut from: this LiveFrames has no rois")
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 2 or (frames.shape[0] != n and source_of is None):
             raise HipExtensionError(f"{what}: frames must be a torch.uint8 tensor with {n} leading rows, one frame per listed camera, got "
                                     f"{getattr(frames, 'dtype', type(frames).__name__)} {tuple(getattr(frames, 'shape', ()))}")
-        if resize is None:
+        if self.rois is not None:
+            if resize is not None:
+                raise HipExtensionError(f"{what}: resize= together with rois: the cameras' boxes are resized to the rings' {self.frame_hw} already")
+            hw = self._source_hw(frames, pixel_format, surface)
+            if hw is not None and tuple(hw) != self.rois.source_hw:
+                raise HipExtensionError(f"{what}: the rois are boxes of {self.rois.source_hw[0]} x {self.rois.source_hw[1]} frames, these are "
+                                        f"{hw[0]} x {hw[1]}")
+            if source_of is not None:
+                source_of = self._check_sources(what, source_of, n, frames.shape[0])
+        elif resize is None:
             if pixel_format is not None or surface is not None:
                 raise HipExtensionError(f"{what}: pixel_format / surface describe frames to be converted: give resize= (the ring's size {self.frame_hw} "
                                         f"for frames already that large)")
@@ -359,7 +430,10 @@ class LiveFrames:
                                         f"hold {self.frame_hw} frames")
         if not frames.is_cuda:
             frames = frames.to(self.device, non_blocking=True)
-        if resize is not None:
+        if self.rois is not None:  # camera c's box with table c: the id vector is the table vector
+            frames = rz.resize_rois_u8(frames, self._roi_tables, table_of=self.cameras.ids(cams), src_of=None if source_of is None else self._sources(source_of),
+                                       out=self._staging[:n], pixel_format=pixel_format, surface=surface, ws=self._roi_ws)
+        elif resize is not None:
             frames = rz.resize_u8(frames, resize, resample, out=self._staging[:n], pixel_format=pixel_format, surface=surface)
         if self.motion is not None:  # on the frames as they enter the ring (its checks of `frames` are the ring push's: refused here, nothing has moved)
             mil_ops.frame_gate_update(frames, self.cameras.ids(cams), self.anchor, self.gate_state, self._gate_scratch, self.motion.pixel_delta,
@@ -367,6 +441,19 @@ class LiveFrames:
         mil_ops.frame_ring_push(frames, self.cameras.ids(cams), self.ring, self._counts)
         self.cameras.bump(cams)
         return tuple(c for c in cams if self.is_due(self.cameras.host[c]))
+
+    def _check_sources(self, what: str, source_of, n: int, n_frames: int) -> Tuple[int, ...]:
+        """`source_of` as a tuple of n host ints in [0, n_frames), or a refusal."""
+        if type(source_of) is tuple and len(source_of) == n and all(type(r) is int and 0 <= r < n_frames for r in source_of):
+            return source_of
+        if torch.is_tensor(source_of) or isinstance(source_of, (np.ndarray, str, bytes)) or not hasattr(source_of, "__len__"):
+            raise HipExtensionError(f"{what}: source_of must be a sequence of host integers, got a {type(source_of).__name__}")
+        if len(source_of) != n:
+            raise HipExtensionError(f"{what}: source_of has {len(source_of)} entries for {n} listed cameras")
+        for r in source_of:
+            if host_int(r) is None or not 0 <= int(r) < n_frames:
+                raise HipExtensionError(f"{what}: source_of entry {r!r} is not a row of the {n_frames} frames")
+        return tuple(int(r) for r in source_of)
 
     def decide(self, due: Sequence[int]) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
         """The motion gate's decision for the cameras whose clip the last push made due -> (extract, held), both in `due` order:
@@ -595,13 +682,13 @@ class LiveScorer:
             raise HipExtensionError(f"{what}: the backbone's features are {tuple(feats.shape)}, the rings hold {self.channels} channels")
         self.push(cams, feats.reshape(len(cams), self.ncrops, self.channels))
 
-    _PUSH_KW, _FORWARD_KW = ("resize", "resample", "pixel_format", "surface"), ("crop", "crops", "normalize")
+    _PUSH_KW, _FORWARD_KW = ("resize", "resample", "pixel_format", "surface", "source_of"), ("crop", "crops", "normalize")
 
     def step_camera_frames(self, backbone, live_frames: LiveFrames, cams: Sequence[int], frames: torch.Tensor, **kw) -> Optional[LiveScores]:
         """One new decoded frame per listed camera, through to the scores: `live_frames.push(cams, frames, ...)`; when no clip
         became due, None, with nothing else launched; else `live_frames.windows(due)`, backbone.forward_frames on those
         back-to-back clips (the gather has applied clip_stride and frame_step already), `push(due, feats)` and `score(due)`.
-        `kw`: push's resize / resample / pixel_format / surface and forward_frames' crop / crops / normalize, with len(crops) =
+        `kw`: push's resize / resample / pixel_format / surface / source_of and forward_frames' crop / crops / normalize, with len(crops) =
         ncrops; frames_per_clip, frame_step and clip_stride are the LiveFrames' own and refused here.  The features and scores of
         a camera are those of its frames as an offline video, window by window.  With `events=` every due window is one sample
         of the camera's series: a sample is then clip_stride frames, not span frames, and EventSpec's lengths (smooth, merge_gap,

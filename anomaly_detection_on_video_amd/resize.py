@@ -14,6 +14,11 @@ available to pin against): packed RGB frames remain the reference-parity path.
 A decoder's surface as it is -- a row pitch above W, aligned rows, plane offsets, NV21 / YV12 chroma order, 10-bit samples (P010,
 yuv420p10le) -- goes in through `surface=` (Surface, surface, resolve_surface) next to `pixel_format`: the frames are then uint8
 (F, frame_bytes) and the same kernels read them in place by byte geometry.
+
+A part of the picture -- PIL's `Image.resize(size, resample, box=(left, top, right, bottom))`, float boxes -- goes through
+`box_coefficients` (Pillow's `precompute_coeffs` with the box held as C floats), `roi_tables` (K stacked table sets on the device)
+and `resize_rois_u8` (a source frame and a table per output frame, two launches: advhip_resize_roi_u8 and its 4:2:0 forms);
+`resize_u8(box=)` is the one-box case.
 """
 from __future__ import annotations
 
@@ -275,10 +280,30 @@ def output_size(h: int, w: int, size: Union[int, Tuple[int, int]]) -> Tuple[int,
 def coefficients(in_size: int, out_size: int, resample: Union[int, str] = "bilinear") -> Tuple[np.ndarray, np.ndarray]:
     """Pillow's tables for one axis: bounds int32 (out, 2) = (first source index, tap count) and the 2**22 fixed-point
     coefficients int32 (out, ksize), zero past each output's tap count."""
-    support0, filt = FILTERS[filter_name(resample)]
     if in_size < 1 or out_size < 1:
         raise ValueError(f"resize: sizes must be >= 1 (in {in_size}, out {out_size})")
-    scale = float(in_size) / out_size
+    return _coefficients(in_size, 0.0, float(in_size) / out_size, out_size, resample)
+
+
+def box_coefficients(in_size: int, in0: float, in1: float, out_size: int,
+                     resample: Union[int, str] = "bilinear") -> Tuple[np.ndarray, np.ndarray]:
+    """`coefficients` for the source interval [in0, in1) of an axis of `in_size` samples: Pillow's `precompute_coeffs` with a
+    box (`Image.resize(..., box=)`), in the shape `coefficients` returns.  Pillow holds the box as C floats, so the order of the
+    roundings is part of the rule: in0 and in1 are rounded to float32 first, the extent in1 - in0 is subtracted IN float32, and
+    only then scale = double(extent) / out_size; everything behind that is `coefficients`' double arithmetic with the centres
+    moved by in0.  box_coefficients(n, 0, n, m) is coefficients(n, m)."""
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resize: sizes must be >= 1 (in {in_size}, out {out_size})")
+    lo, hi = np.float32(in0), np.float32(in1)
+    extent = np.float32(hi - lo)
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo < 0 or hi > in_size or not extent > 0:
+        raise ValueError(f"resize: the interval [{in0!r}, {in1!r}) is not a non-empty part of [0, {in_size}] (as float32: [{lo!r}, {hi!r}))")
+    return _coefficients(in_size, float(lo), float(extent) / out_size, out_size, resample)
+
+
+def _coefficients(in_size: int, in0: float, scale: float, out_size: int, resample) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc in double: output i is centred at in0 + (i + 0.5) * scale."""
+    support0, filt = FILTERS[filter_name(resample)]
     fs = max(scale, 1.0)
     support = support0 * fs
     ksize = int(math.ceil(support)) * 2 + 1
@@ -287,7 +312,7 @@ def coefficients(in_size: int, out_size: int, resample: Union[int, str] = "bilin
     coef = np.zeros((out_size, ksize), dtype=np.int32)
     one = float(1 << PRECISION_BITS)
     for i in range(out_size):
-        center = (i + 0.5) * scale
+        center = in0 + (i + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         n = min(int(center + support + 0.5), in_size) - xmin
         w = [filt((j + xmin - center + 0.5) * ss) for j in range(n)]
@@ -350,6 +375,209 @@ def tables(in_h: int, in_w: int, out_h: int, out_w: int, resample: Union[int, st
     return t
 
 
+# ---- regions of interest: a source box per frame (PIL Image.resize(size, resample, box=(l, t, r, b))) ---------------------------
+
+def resolve_box(who: str, box, in_h: int, in_w: int) -> Tuple[float, float, float, float]:
+    """`box` = (left, top, right, bottom) in source pixels, as Pillow's `box=` -> the four numbers as Pillow holds them (float32
+    values, as Python floats); None is the whole frame.  Refused by name: anything but four finite host numbers, a box that
+    leaves the frame (Pillow raises too) and an extent that is not positive after the float32 rounding."""
+    if box is None:
+        return 0.0, 0.0, float(in_w), float(in_h)
+    if torch.is_tensor(box) or isinstance(box, (str, bytes)) or not hasattr(box, "__len__") or len(box) != 4:
+        raise ValueError(f"{who}: box {box!r} is not (left, top, right, bottom): four host numbers")
+    for v in box:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError(f"{who}: box {tuple(box)!r}: {v!r} is not a finite host number")
+    l, t, r, b = (np.float32(v) for v in box)
+    if l < 0 or t < 0 or r > in_w or b > in_h:
+        raise ValueError(f"{who}: box {tuple(box)!r} leaves the {in_h} x {in_w} frame (left, top >= 0, right <= {in_w}, bottom <= {in_h})")
+    if not np.float32(r - l) > 0 or not np.float32(b - t) > 0:
+        raise ValueError(f"{who}: box {tuple(box)!r} is empty: right - left and bottom - top must be positive in float32")
+    return float(l), float(t), float(r), float(b)
+
+
+def box_output_size(box, size: Union[int, Tuple[int, int]]) -> Tuple[int, int]:
+    """`output_size`'s rule on a box: an (h, w) pair is used as given; an int sets the short side of the box's extents (bottom -
+    top, right - left; float32 values subtracted in float32, as the tables see them) and scales the long side to int(size * long /
+    short)."""
+    if isinstance(size, (tuple, list)):
+        return output_size(1, 1, size)
+    l, t, r, b = (np.float32(v) for v in box)
+    h, w = float(np.float32(b - t)), float(np.float32(r - l))
+    if not (h > 0 and w > 0):
+        raise ValueError(f"resize: box {tuple(box)!r} is empty")
+    size = int(size)
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(size * long / short)
+    oh, ow = (new_long, size) if w <= h else (size, new_long)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"resize: output size ({oh}, {ow}) must be at least 1 x 1")
+    return oh, ow
+
+
+def _identity(n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The table of an axis Pillow does not resample: output i is source i, with the coefficient 1."""
+    return (np.stack([np.arange(n), np.ones(n, dtype=np.int64)], axis=1).astype(np.int32),
+            np.full((n, 1), 1 << PRECISION_BITS, dtype=np.int32))
+
+
+def box_plan(in_h: int, in_w: int, out_h: int, out_w: int, box=None, resample: Union[int, str] = "bilinear") -> Plan:
+    """`plan` with a box: Pillow's pass rule (the horizontal pass iff out_w != in_w or left != 0 or right != in_w, the vertical
+    one iff out_h != in_h or top != 0 or bottom != in_h), box_coefficients for an axis that is resampled and the explicit
+    identity table for one that is not.  row0 / rows: the source rows the vertical table reads."""
+    l, t, r, b = resolve_box("resize", box, in_h, in_w)
+    if out_h < 1 or out_w < 1:
+        raise ValueError(f"resize: output size ({out_h}, {out_w}) must be at least 1 x 1")
+    horizontal = out_w != in_w or l != 0 or r != in_w
+    vertical = out_h != in_h or t != 0 or b != in_h
+    xb, xk = box_coefficients(in_w, l, r, out_w, resample) if horizontal else _identity(in_w)
+    yb, yk = box_coefficients(in_h, t, b, out_h, resample) if vertical else _identity(in_h)
+    filter_name(resample)  # (refused even where both tables are identities)
+    row0 = int(yb[0, 0])
+    return Plan(out_h, out_w, horizontal, vertical, xb, xk, yb, yk, row0, int(yb[-1, 0] + yb[-1, 1]) - row0)
+
+
+class RoiTables(NamedTuple):
+    """K stacked table sets for frames of one geometry and one output size, one per box, on the device (roi_tables).  Every set
+    has both axes (box_plan's identity where Pillow skips a pass), each axis padded with zero coefficients to the largest ksize
+    of that axis over the K boxes.  The host arrays are kept for whoever wants to look: xbounds (K, OW, 2), xcoef (K, OW,
+    xksize), ybounds (K, OH, 2), ycoef (K, OH, yksize), rowspan (K, 2) = (row0, rows) of each set's horizontal pass."""
+    in_h: int
+    in_w: int
+    out_h: int
+    out_w: int
+    boxes: Tuple[Tuple[float, float, float, float], ...]
+    resample: str
+    xbounds: np.ndarray
+    xcoef: np.ndarray
+    ybounds: np.ndarray
+    ycoef: np.ndarray
+    rowspan: np.ndarray
+    ws_rows: int  # max rows: the rows per frame of the workspace between the passes
+    buf: torch.Tensor  # int32 [xbounds | xcoef | ybounds | ycoef | rowspan] on the device
+    offsets: Tuple[int, int, int, int, int]
+
+    @property
+    def n_tables(self) -> int:
+        return len(self.boxes)
+
+
+def roi_tables(in_h: int, in_w: int, out_hw, boxes, resample: Union[int, str] = "bilinear", device="cuda") -> RoiTables:
+    """The stacked device tables of K >= 1 boxes of (in_h, in_w) frames, all resized to `out_hw` = (h, w) (box_output_size gives
+    the pair of an int size): one upload on the current stream, from pinned memory, as `tables` does.  `boxes`: a sequence of
+    (left, top, right, bottom) boxes; None stands for the whole frame."""
+    in_h, in_w = int(in_h), int(in_w)
+    if in_h < 1 or in_w < 1:
+        raise ValueError(f"roi_tables: frames of {in_h} x {in_w}")
+    if not isinstance(out_hw, (tuple, list)) or len(out_hw) != 2:
+        raise ValueError(f"roi_tables: out_hw {out_hw!r} is not an (h, w) pair (box_output_size gives the pair of an int size)")
+    oh, ow = output_size(in_h, in_w, tuple(out_hw))
+    name = filter_name(resample)
+    if boxes is None or isinstance(boxes, (str, bytes)) or torch.is_tensor(boxes) or not hasattr(boxes, "__len__") or len(boxes) < 1:
+        raise ValueError(f"roi_tables: boxes must be a sequence of at least one box (None: the whole frame), got {boxes!r}")
+    resolved = tuple(resolve_box("roi_tables", bx, in_h, in_w) for bx in boxes)  # (every refusal before any table is built)
+    distinct = {bx: box_plan(in_h, in_w, oh, ow, bx, name) for bx in dict.fromkeys(resolved)}  # (many cameras often share a few boxes)
+    plans = [distinct[bx] for bx in resolved]
+    kx, ky = max(p.xcoef.shape[1] for p in plans), max(p.ycoef.shape[1] for p in plans)
+    pad = lambda k, n: np.pad(k, ((0, 0), (0, n - k.shape[1])))  # noqa: E731
+    xb, yb = np.stack([p.xbounds for p in plans]), np.stack([p.ybounds for p in plans])
+    xk, yk = np.stack([pad(p.xcoef, kx) for p in plans]), np.stack([pad(p.ycoef, ky) for p in plans])
+    rowspan = np.array([(p.row0, p.rows) for p in plans], dtype=np.int32)
+    parts = [xb, xk, yb, yk, rowspan]
+    offsets = tuple(int(o) for o in np.cumsum([0] + [a.size for a in parts[:-1]]))
+    host = torch.from_numpy(np.concatenate([a.reshape(-1) for a in parts]).astype(np.int32))
+    if torch.cuda.is_available():
+        host = host.pin_memory()  # an asynchronous copy on the current stream (the pinned block outlives it)
+    return RoiTables(in_h, in_w, oh, ow, resolved, name, xb, xk, yb, yk, rowspan, int(rowspan[:, 1].max()), host.to(device, non_blocking=True), offsets)
+
+
+class RoiSpec(NamedTuple):
+    """What LiveFrames(rois=) takes: the geometry (H, W) of the cameras' decoded frames and a box per camera -- a sequence of
+    n_cameras boxes or a {camera: box} dict; a camera without one (None, or absent from the dict) gets the whole frame."""
+    source_hw: Tuple[int, int]
+    boxes: object
+    resample: Union[int, str] = "bilinear"
+
+
+_ROI_TABLES: Dict[tuple, RoiTables] = {}
+
+
+def _box_tables(in_h: int, in_w: int, oh: int, ow: int, box, name: str, device: torch.device) -> RoiTables:
+    """The one-box RoiTables of resize_u8(box=), cached per (geometry, box, filter, device) as `tables` caches."""
+    key = (in_h, in_w, oh, ow, box, name, torch.device(device))
+    t = _ROI_TABLES.get(key)
+    if t is None:
+        t = _ROI_TABLES[key] = roi_tables(in_h, in_w, (oh, ow), [box], name, device)
+    return t
+
+
+def _index_vector(who: str, name: str, v, device) -> Optional[torch.Tensor]:
+    """`table_of` / `src_of`: None, an int32 device vector, or a host sequence of ints (uploaded once, here)."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        if v.dtype != torch.int32 or v.dim() != 1 or not v.is_contiguous() or v.device != device or v.numel() < 1:
+            raise HipExtensionError(f"{who}: {name} must be a contiguous int32 vector on {device}, got {v.dtype} {tuple(v.shape)} on {v.device}")
+        return v
+    try:
+        host = [int(i) for i in v if not isinstance(i, bool) and float(i).is_integer()]
+        ok = len(host) == len(v) >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or any(not -(1 << 31) <= i < 1 << 31 for i in host):
+        raise HipExtensionError(f"{who}: {name} must be a non-empty sequence of host integers or an int32 device vector, got {v!r}")
+    return torch.tensor(host, dtype=torch.int32).to(device, non_blocking=True)
+
+
+def resize_rois_u8(frames: torch.Tensor, rois: RoiTables, table_of=None, src_of=None, frame_step: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None, pixel_format=None, surface: Optional[Surface] = None,
+                   ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frames on the GPU in any form resize_u8 takes -> uint8 (N, OH, OW, 3): output frame i is PIL's
+    `Image.resize((OW, OH), resample, box=rois.boxes[table_of[i]])` of source frame src_of[i], bit for bit, in two launches on
+    the current stream whatever the boxes are (advhip_resize_roi_u8 and its 4:2:0 forms).  `table_of` / `src_of`: int32 device
+    vectors, or host sequences (uploaded here, once); without `table_of` every frame uses table 0, without `src_of` output i reads
+    source frame i * frame_step.  N is their length, else the sampled frame count ceil(F / frame_step).  An output frame whose
+    source or table index is out of range is left as it is.  `out` as in resize_u8; `ws`: a caller-owned uint8 workspace of at
+    least N * rois.ws_rows * OW * 3 bytes (default: allocated here)."""
+    who = "resize_rois_u8"
+    if not isinstance(rois, RoiTables):
+        raise HipExtensionError(f"{who}: rois must be a RoiTables (resize.roi_tables), got {type(rois).__name__}")
+    d = _frame_step(who, frame_step)
+    pf = resolve_pixel_format(pixel_format)
+    if pf is None and surface is not None:
+        raise ValueError(f"{who}: surface= describes 4:2:0 frames and needs a pixel_format")
+    src = _source(who, frames, pf, surface)
+    if (src.H, src.W) != (rois.in_h, rois.in_w):
+        raise HipExtensionError(f"{who}: the tables are for {rois.in_h} x {rois.in_w} frames, these are {src.H} x {src.W}")
+    if rois.buf.device != frames.device:
+        raise HipExtensionError(f"{who}: the tables are on {rois.buf.device}, the frames on {frames.device}")
+    table_of = _index_vector(who, "table_of", table_of, frames.device)
+    src_of = _index_vector(who, "src_of", src_of, frames.device)
+    if src_of is not None and frame_step is not None:
+        raise ValueError(f"{who}: src_of names every source frame itself: frame_step has no meaning next to it")
+    if table_of is not None and src_of is not None and table_of.numel() != src_of.numel():
+        raise HipExtensionError(f"{who}: table_of has {table_of.numel()} entries, src_of {src_of.numel()}")
+    N = src_of.numel() if src_of is not None else table_of.numel() if table_of is not None else -(-src.F_src // d)
+    if src_of is None and (N - 1) * d >= src.F_src:
+        raise HipExtensionError(f"{who}: table_of has {N} entries, but {src.F_src} frames at frame_step {d} are {-(-src.F_src // d)}")
+    oh, ow = rois.out_h, rois.out_w
+    if out is None:
+        out = torch.empty((N, oh, ow, 3), device=frames.device, dtype=torch.uint8)
+    else:
+        _check_out(who, frames, out, (N, oh, ow, 3))
+    ws_bytes = N * rois.ws_rows * ow * 3
+    if ws is None:
+        ws = torch.empty((ws_bytes,), device=frames.device, dtype=torch.uint8)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < ws_bytes or ws.device != frames.device:
+        raise HipExtensionError(f"{who}: ws must be a contiguous uint8 tensor of at least {ws_bytes} bytes on {frames.device}")
+    b, (o_xb, o_xk, o_yb, o_yk, o_rs) = rois.buf, rois.offsets
+    fn = getattr(_lib.load(), src.resize_roi)
+    check(fn(ptr(frames), ptr(out), ptr(ws), src.F_src, N, ptr(src_of), d, ptr(table_of), rois.n_tables, *src.before, src.H, src.W, 3, oh, ow,
+             ptr(b[o_xb:]), ptr(b[o_xk:]), rois.xcoef.shape[2], ptr(b[o_yb:]), ptr(b[o_yk:]), rois.ycoef.shape[2], ptr(b[o_rs:]), rois.ws_rows,
+             *src.after, stream(frames)), who)
+    return out
+
+
 def _check_out(who: str, frames: torch.Tensor, out: torch.Tensor, shape: tuple) -> None:
     require_gpu(frames, out)
     if out.dtype != torch.uint8 or tuple(out.shape) != shape:
@@ -374,6 +602,7 @@ class _Source(NamedTuple):
     W: int
     convert: Optional[str]
     resize: str
+    resize_roi: str
     before: tuple
     after: tuple
 
@@ -384,17 +613,19 @@ def _source(who: str, frames: torch.Tensor, pf: Optional[PixelFormat], surface) 
     if pf is None:
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise HipExtensionError(f"{who} wants uint8 (F,H,W,3) RGB frames, got {frames.dtype} {tuple(frames.shape)}")
-        return _Source(*frames.shape[:3], None, "advhip_resize_u8_sampled", (), ())
+        return _Source(*frames.shape[:3], None, "advhip_resize_u8_sampled", "advhip_resize_roi_u8", (), ())
     if surface is None:
         if frames.dtype != torch.uint8 or frames.dim() != 3:
             raise HipExtensionError(f"{who} wants uint8 (F, 3H/2, W) {pf.layout} frames, got {frames.dtype} {tuple(frames.shape)}")
         h, w = frame_hw(frames.shape)
-        return _Source(frames.shape[0], h, w, "advhip_yuv420_to_rgb_u8", "advhip_resize_yuv420_u8", (), (LAYOUTS[pf.layout],) + yuv_coefficients(pf))
+        return _Source(frames.shape[0], h, w, "advhip_yuv420_to_rgb_u8", "advhip_resize_yuv420_u8", "advhip_resize_roi_yuv420_u8", (),
+                       (LAYOUTS[pf.layout],) + yuv_coefficients(pf))
     if frames.dtype != torch.uint8 or frames.dim() != 2:
         raise HipExtensionError(f"{who} with surface= wants uint8 (F, frame_bytes) frames, got {frames.dtype} {tuple(frames.shape)}")
     sf = resolve_surface(surface, pf, frames.shape[1])
     geometry = (sf.bits, sf.shift, sf.y_offset, sf.y_pitch, sf.cb_offset, sf.cr_offset, sf.chroma_pitch, sf.chroma_step)
-    return _Source(frames.shape[0], sf.height, sf.width, "advhip_yuv420_surface_to_rgb_u8", "advhip_resize_yuv420_surface_u8", (frames.shape[1],),
+    return _Source(frames.shape[0], sf.height, sf.width, "advhip_yuv420_surface_to_rgb_u8", "advhip_resize_yuv420_surface_u8", "advhip_resize_roi_surface_u8",
+                   (frames.shape[1],),
                    geometry + yuv_coefficients(pf, sf.bits))
 
 
@@ -423,7 +654,7 @@ def yuv420_to_rgb_u8(frames: torch.Tensor, pixel_format, out: Optional[torch.Ten
 
 def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, resample: Union[int, str] = "bilinear",
               out: Optional[torch.Tensor] = None, frame_step: Optional[int] = None, pixel_format=None,
-              surface: Optional[Surface] = None) -> torch.Tensor:
+              surface: Optional[Surface] = None, box=None) -> torch.Tensor:
     """uint8 (F, H, W, 3) frames on the GPU -> (F, OH, OW, 3), what `GroupResize(size, resample)` gives frame by frame (PIL
     `Image.resize`, bit for bit), on the current stream with no host synchronisation.  `out` places the result in a
     caller-owned contiguous (F, OH, OW, 3) uint8 tensor (e.g. a view of a larger buffer).  Without `out`, frames already at
@@ -435,7 +666,11 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     resize_u8(yuv420_to_rgb_u8(frames, pixel_format), ...) byte for byte without the full-size RGB frames: the horizontal pass
     converts each tap's pixel as it reads it.  Frames already at the output size come back converted.
     `surface` (with `pixel_format`; default None = the compact frames): `frames` are uint8 (F, frame_bytes) decoder surfaces, as
-    in yuv420_to_rgb_u8, and the result is again resize_u8(yuv420_to_rgb_u8(frames, pixel_format, surface=surface), ...)."""
+    in yuv420_to_rgb_u8, and the result is again resize_u8(yuv420_to_rgb_u8(frames, pixel_format, surface=surface), ...).
+    `box` (left, top, right, bottom) in source pixels, floats allowed (default None = this call as it always was): every frame is
+    PIL's `Image.resize(size, resample, box=box)` bit for bit, taps at the box's edge reading the pixels beside it, from any of
+    the source forms above and with `frame_step`.  An int `size` is the short side of the box (box_output_size).  One table set
+    through resize_rois_u8's entry points, cached per (geometry, box, filter, device); always a new tensor (or `out`)."""
     d = _frame_step("resize_u8", frame_step)
     pf = resolve_pixel_format(pixel_format)
     if pf is None and surface is not None:
@@ -443,6 +678,10 @@ def resize_u8(frames: torch.Tensor, size: Union[int, Tuple[int, int]] = 256, res
     src = _source("resize_u8", frames, pf, surface)
     F, H, W, yuv = -(-src.F_src // d), src.H, src.W, pf is not None
     name = filter_name(resample)
+    if box is not None:
+        box = resolve_box("resize_u8", box, H, W)
+        oh, ow = box_output_size(box, size)
+        return resize_rois_u8(frames, _box_tables(H, W, oh, ow, box, name, frames.device), frame_step=d, out=out, pixel_format=pf, surface=surface)
     oh, ow = output_size(H, W, size)
     if out is None:
         if not yuv and (oh, ow) == (H, W):  # (4:2:0 frames always come back converted)

@@ -1078,6 +1078,40 @@ int advhip_resize_yuv420_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* w
                                     int64_t cr_offset, int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv,
                                     int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
 
+/* --- regions of interest: a source box per output frame (PIL Image.resize(size, resample, box=)) ----------------------------
+ * The three resize entry points above with a table set per output frame.  resize.py (box_coefficients, roi_tables) builds one
+ * set per box -- Pillow's precompute_coeffs with the box held as C floats -- and stacks n_tables of them, every axis padded with
+ * zero coefficients to the largest ksize of that axis:
+ *   xbounds int32 (n_tables, OW, 2), xcoef int32 (n_tables, OW, xksize), ybounds int32 (n_tables, OH, 2), ycoef int32 (n_tables,
+ *   OH, yksize);  rowspan int32 (n_tables, 2) ON THE DEVICE = (row0, rows): the source rows table t's vertical pass reads, i.e.
+ *   the rows its horizontal pass computes;  ws_rows = the largest `rows`, 1 <= ws_rows <= H.
+ * Output frame i < N reads source frame src_of[i] (src_of int32 (N,) on the device; null: frame i * frame_step, and then
+ * (N - 1) * frame_step < F_src) with table table_of[i] (int32 (N,) on the device; null: table 0 for every frame).  Both passes
+ * always run (an axis Pillow would skip carries the identity table: bounds (i, 1), coefficient 2^22), so there are exactly two
+ * launches: the horizontal pass writes rows [0, rows) of frame i's slab of ws, uint8 (N, ws_rows, OW, 3), the vertical pass reads
+ * them.  dst uint8 (N, OH, OW, C), C == 3, frame i byte for byte Pillow's box resize of its source frame.
+ * An output frame whose source index is outside [0, F_src) or whose table index is outside [0, n_tables) is not written and
+ * nothing is read for it.  Every argument the host can see is checked before the first launch; a rowspan entry outside the frame
+ * or above ws_rows cannot be (it is device memory): the kernels then count no taps for that table, as for a foreign bounds entry. */
+int advhip_resize_roi_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of, int32_t frame_step,
+                         const int32_t* table_of, int32_t n_tables, int32_t H, int32_t W, int32_t C, int32_t OH, int32_t OW,
+                         const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds, const int32_t* ycoef,
+                         int32_t yksize, const int32_t* rowspan, int32_t ws_rows, void* stream);
+/* The same from compact 4:2:0 frames (F_src, 3H/2, W), converted tap by tap as in advhip_resize_yuv420_u8. */
+int advhip_resize_roi_yuv420_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of,
+                                int32_t frame_step, const int32_t* table_of, int32_t n_tables, int32_t H, int32_t W, int32_t C, int32_t OH,
+                                int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize, const int32_t* ybounds,
+                                const int32_t* ycoef, int32_t yksize, const int32_t* rowspan, int32_t ws_rows, int32_t layout, int32_t yoff,
+                                int32_t cy, int32_t crv, int32_t cgu, int32_t cgv, int32_t cbu, void* stream);
+/* The same from decoder surfaces, with the geometry and the rules of advhip_resize_yuv420_surface_u8. */
+int advhip_resize_roi_surface_u8(const uint8_t* src, uint8_t* dst, uint8_t* ws, int64_t F_src, int64_t N, const int32_t* src_of,
+                                 int32_t frame_step, const int32_t* table_of, int32_t n_tables, int64_t frame_pitch, int32_t H, int32_t W,
+                                 int32_t C, int32_t OH, int32_t OW, const int32_t* xbounds, const int32_t* xcoef, int32_t xksize,
+                                 const int32_t* ybounds, const int32_t* ycoef, int32_t yksize, const int32_t* rowspan, int32_t ws_rows,
+                                 int32_t bits, int32_t shift, int64_t y_offset, int64_t y_pitch, int64_t cb_offset, int64_t cr_offset,
+                                 int64_t chroma_pitch, int32_t chroma_step, int32_t yoff, int32_t cy, int32_t crv, int32_t cgu, int32_t cgv,
+                                 int32_t cbu, void* stream);
+
 /* Weighted ROC counts: what the frame-level ROC / PR curves of src/runner.py:62-79 are made of, from one item per clip.
  *   scores fp32 (M,), pos / neg int32 (M,) non-negative weights (the positive / negative frames an item stands for), 1 <= M < 2^31.
  *   thresholds fp32 (M,), tps / fps int64 (M,), meta int64 (4,) = {G, non-finite scores, sum of pos, sum of neg}.
